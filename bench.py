@@ -18,7 +18,14 @@ device in the timed steps — over frames rendered one at a time right after it
 come from one extra counting frame after the timed region
 (RR_FLAG_COUNT_TRAVERSAL).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line
+(headline figures only). --full adds everything else the benchmark measures,
+each in runs of its own after the timed region: the kernels timed one frame at
+a time, the counting frame, the roofline and PMC blocks, the CPU baselines.
+--dump-outputs DIR writes what the last timed step handed its caller (the
+image file the frame was written to) as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   N > 1 without a launcher: bench.py starts N worker processes itself, one per
   GPU (HIP_VISIBLE_DEVICES=i, before any GPU call in this process), as the
   reference starts one worker per node (scripts/arnes/
@@ -112,7 +119,16 @@ def parse_args():
                          "profiles/r<N>_pmc.json for 04vs, profiles/r<N>_pmc_<workload>.json otherwise)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch, partition and reduce without rendering (no GPU needed; value is null)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: kernels timed "
+                         "one frame at a time, the counting frame, roofline / PMC blocks, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup is not None and a.warmup < 0:
+        ap.error("--warmup must not be negative")
     wl = WORKLOADS[a.workload]
     if a.steps is None:
         a.steps = wl["steps"]
@@ -728,6 +744,96 @@ def roofline_line(args, cls, cstats, kernel_ms, launches, names, steps, timed=No
     return out
 
 
+# --dump-outputs: counters of FrameStats that depend on the frame alone (not on
+# timing or on how frames overlapped), in the order of frame_counters.npy
+DUMP_COUNTERS = ("width", "height", "spp", "n_triangles", "camera_rays", "camera_rays_traced", "extension_rays",
+                 "shadow_rays", "extension_rays_escaped", "shadow_rays_escaped", "output_bytes")
+DUMP_BUDGET = {"frame_file_bytes": 8 << 20, "frame_rgb": 48 << 20}  # bytes on disk; 64 MB in all
+
+
+def capped_sample(a, max_bytes: int, seed: int = 0):
+    """`a` itself when it fits in max_bytes, else a fixed sample of its rows
+    (first axis): the same seeded choice for the same shape, in index order."""
+    import numpy as np
+    row = a[0].nbytes if a.ndim > 1 else a.itemsize
+    n = max_bytes // row
+    if len(a) <= n:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(len(a), size=n, replace=False))
+    return a[idx]
+
+
+def dump_outputs(directory: str, image_path: str, stats) -> list:
+    """What the last timed step handed its caller, as <directory>/<name>.npy:
+      frame_file_bytes  the bytes of the image file the frame was written to
+                        (JPEG / PNG as the job asks), one float32 per byte;
+      frame_rgb         that file decoded to H*W x 3 float32 in 0..255 (only
+                        where Pillow can be imported);
+      frame_counters    DUMP_COUNTERS of the frame's FrameStats, float64.
+    Arrays above their DUMP_BUDGET are a seeded sample of their rows
+    (capped_sample). Returns the names written."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    out = {"frame_file_bytes": np.fromfile(image_path, dtype=np.uint8).astype(np.float32),
+           "frame_counters": np.array([float(getattr(stats, k)) for k in DUMP_COUNTERS], np.float64)}
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    if Image is not None:
+        with Image.open(image_path) as im:
+            out["frame_rgb"] = np.asarray(im.convert("RGB"), dtype=np.float32).reshape(-1, 3)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), capped_sample(a, DUMP_BUDGET.get(name, 1 << 20)))
+    return sorted(out)
+
+
+def traversed_rays(rays: dict) -> tuple[int, int]:
+    """(traversed, spawned) of the timed region's ray totals: escaped
+    continuations / shadow rays (k_tiles' hull rule) are spawned and counted,
+    but never walk a node."""
+    traced = (rays["camera_traced"] + rays["extension"] - rays["extension_escaped"] + rays["shadow"]
+              - rays["shadow_escaped"])
+    return traced, rays["camera_traced"] + rays["extension"] + rays["shadow"]
+
+
+def headline(args, wl, job, world, t_max, elapsed, last_stats, device_warmup, substituted, tile_modes, places, rays,
+             dumped) -> dict:
+    """The result line of a plain run: the timed region's own figures (--full
+    adds the blocks measured in runs of their own)."""
+    traced, spawned = traversed_rays(rays)
+    result = {
+        "metric": wl["metric"], "value": round(args.steps * world / t_max, 4), "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(t_max / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": wl["data"], "full": bool(args.full),
+        "device_warmup": {**device_warmup, "note": "the timed steps' frames rendered before the W warmup steps "
+                          "so the timed region starts at the engine clock it keeps (GPU clock ramp); not timed"},
+        "config": {"workload": wl["workload"], "job": os.path.basename(wl["job"]),
+                   "resolution": f"{int(last_stats.width)}x{int(last_stats.height)}", "spp": int(last_stats.spp),
+                   "parallelism": f"frame-parallel x{world} (one worker per GPU, no collective)",
+                   "pipelining": "serial (rr_render_frame per frame)" if args.serial else
+                                 "3 frames in flight: frame N encoded + written while N+1 renders and N+2 waits on its stream",
+                   "view_transform_substituted": int(any(substituted)),
+                   "k_tiles_units": tile_modes,
+                   "placement_by_rank": places},
+        "mrays_per_s_per_gpu": round(traced / elapsed / 1e6, 1),
+        "mrays_spawned_per_s_per_gpu": round(spawned / elapsed / 1e6, 1),
+        "rays_per_frame": {**{k: v // max(args.steps, 1) for k, v in rays.items()},
+                           "traversed": traced // max(args.steps, 1)},
+        "rays_note": "camera = W x H x spp samples; camera_traced = those tested against a triangle (the rest "
+                     "lie outside the scene's screen rectangle or meet no triangle of their tile and are "
+                     "resolved as background without a ray); extension / shadow = continuation / NEE shadow "
+                     "rays spawned, of which *_escaped left a hull side of their triangle (every vertex of the "
+                     "scene behind that side's plane: they meet nothing) and were resolved without a traversal; "
+                     "traversed = camera_traced + extension + shadow - the escaped ones. mrays_per_s_per_gpu "
+                     "counts traversed rays only; mrays_spawned_per_s_per_gpu counts the escaped ones too",
+    }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
+    return result
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -876,6 +982,25 @@ def main():
         places = [None] * world
         dist.all_gather_object(places, placement)
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        f_last = frame_of(args.warmup + args.steps - 1)
+        dumped = dump_outputs(args.dump_outputs, rr.output_file_path(outdir, job.output_file_name_format, f_last,
+                                                                     job.output_file_format), last_stats)
+
+    if not args.full:
+        # a plain run: the headline figures of the timed region and nothing that
+        # takes a run of its own
+        if rank == 0:
+            print(json.dumps(headline(args, wl, job, world, t_max, elapsed, last_stats, device_warmup, substituted,
+                                      tile_modes, places, rays, dumped)), flush=True)
+        runner.close()
+        shutil.rmtree(outdir, ignore_errors=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # Per-launch kernel times for the roofline. When consecutive k_tiles frames
     # overlap on the device (the two frame slots' streams, rr_api.cpp
     # enqueue_frame), an event pair around a launch also spans the wait for the
@@ -945,48 +1070,21 @@ def main():
                                 f"{os.environ.get('OMP_NUM_THREADS')} of {usable} usable"}
             except Exception as e:  # baseline is reported, never the target
                 cpu = {"value": None, "unit": "frames/s", "error": str(e)}
-        # rays that entered a traversal: escaped continuations / shadow rays
-        # (k_tiles' hull rule) are spawned and counted, but never walk a node
-        traced = (rays["camera_traced"] + rays["extension"] - rays["extension_escaped"] + rays["shadow"]
-                  - rays["shadow_escaped"])
-        spawned = rays["camera_traced"] + rays["extension"] + rays["shadow"]
         wl_key = "" if args.workload == "04vs" else f"_{args.workload}"
         pmc_path = args.pmc_summary or newest_profile("%s_pmc" + wl_key + ".json")
         kc = float(getattr(cstats, "kernel_clock_ghz", 0.0) or 0.0) if cstats is not None else 0.0
         kernels_pmc = pmc_kernel_block(pmc_kernels(pmc_path),
                                        os.path.relpath(pmc_path, ROOT) if pmc_path else None,
                                        kc if 1.0 < kc <= PEAK_CLOCK_GHZ * 1.05 else PEAK_CLOCK_GHZ)
-        result = {
-            "metric": wl["metric"], "value": round(value, 4), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(t_max / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": wl["data"],
-            "device_warmup": {**device_warmup, "note": "the timed steps' frames rendered before the W warmup steps "
-                              "so the timed region starts at the engine clock it keeps (GPU clock ramp); not timed"},
-            "config": {"workload": wl["workload"], "job": os.path.basename(wl["job"]),
-                       "resolution": f"{int(last_stats.width)}x{int(last_stats.height)}", "spp": int(last_stats.spp),
-                       "parallelism": f"frame-parallel x{world} (one worker per GPU, no collective)",
-                       "pipelining": "serial (rr_render_frame per frame)" if args.serial else
-                                     "3 frames in flight: frame N encoded + written while N+1 renders and N+2 waits on its stream",
-                       "view_transform_substituted": int(any(substituted)),
-                       "k_tiles_units": tile_modes,
-                       "placement_by_rank": places},
-            "mrays_per_s_per_gpu": round(traced / elapsed / 1e6, 1),
+        result = headline(args, wl, job, world, t_max, elapsed, last_stats, device_warmup, substituted, tile_modes,
+                          places, rays, dumped)
+        traced, _ = traversed_rays(rays)
+        result.update({
             # SURVEY 8(d)'s form: rays traced over the summed render-kernel time
             # (kernels timed alone, see roofline.launch_timing)
             "mrays_per_s_per_gpu_kernel_time": (
                 round(traced / args.steps / (sum(roof_ms) / max(roof_steps, 1) * 1e-3) / 1e6, 1)
                 if sum(roof_ms) > 0 else None),
-            "mrays_spawned_per_s_per_gpu": round(spawned / elapsed / 1e6, 1),
-            "rays_per_frame": {**{k: v // max(args.steps, 1) for k, v in rays.items()},
-                               "traversed": traced // max(args.steps, 1)},
-            "rays_note": "camera = W x H x spp samples; camera_traced = those tested against a triangle (the rest "
-                         "lie outside the scene's screen rectangle or meet no triangle of their tile and are "
-                         "resolved as background without a ray); extension / shadow = continuation / NEE shadow "
-                         "rays spawned, of which *_escaped left a hull side of their triangle (every vertex of the "
-                         "scene behind that side's plane: they meet nothing) and were resolved without a traversal; "
-                         "traversed = camera_traced + extension + shadow - the escaped ones. mrays_per_s_per_gpu "
-                         "counts traversed rays only; mrays_spawned_per_s_per_gpu counts the escaped ones too",
             "kernels_pmc": kernels_pmc,
             "whole_job_ceiling_frames_s": dispatch_ceiling(job.to_dict(), world),
             "value_under_reference_master_max": round(min(value, dispatch_ceiling(job.to_dict(), world)["value"]), 4),
@@ -994,7 +1092,7 @@ def main():
             "kernels": per_class,
             "roofline": roofline,
             "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(result), flush=True)
     runner.close()
     shutil.rmtree(outdir, ignore_errors=True)

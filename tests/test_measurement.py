@@ -154,3 +154,50 @@ def test_occupancy_ignores_an_overstated_grbm_span():
     row = bench.pmc_kernel_block({"k_tiles<false,false>": e}, "x", clock)["kernels"]["k_tiles<false,false>"]
     assert row["occupancy_waves_per_simd"] == 3.2  # the GRBM span would have said 0.94
     assert bench.occupancy_figures({"pmc_pass_avg_ms": 1.0}) == {}
+
+
+def test_capped_sample_is_fixed_and_within_budget():
+    """--dump-outputs: an array under its budget is written whole; a larger one
+    is the same seeded choice of rows every time, in index order."""
+    a = np.arange(30, dtype=np.float32).reshape(10, 3)
+    assert bench.capped_sample(a, a.nbytes) is a
+    s = bench.capped_sample(a, 4 * a[0].nbytes)
+    assert s.shape == (4, 3) and s.nbytes <= 4 * a[0].nbytes
+    assert np.array_equal(s, bench.capped_sample(a.copy(), 4 * a[0].nbytes))
+    rows = (s[:, 0] // 3).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s, a[rows])
+    flat = bench.capped_sample(np.arange(100, dtype=np.float32), 40)
+    assert flat.shape == (10,) and np.all(np.diff(flat) > 0)
+
+
+def test_dump_outputs_writes_the_frame_file(tmp_path):
+    """dump_outputs on a frame file the host encoder wrote (PNG: lossless):
+    its bytes as float32, the pixels where Pillow is there to decode them, the
+    counters in DUMP_COUNTERS order as float64."""
+    import importlib
+    rr = importlib.import_module("diploma_thesis-distributed_rendering_of_cgi_using_a_render_cluster_amd")
+    rgba = np.random.default_rng(3).integers(0, 256, (8, 16, 4), dtype=np.uint8)
+    rgba[..., 3] = 255
+    rr.encode_image(rgba, str(tmp_path / "frame_0001"), "PNG")
+    img = tmp_path / "frame_0001.png"
+    stats = types.SimpleNamespace(**{k: i + 1 for i, k in enumerate(bench.DUMP_COUNTERS)})
+    names = bench.dump_outputs(str(tmp_path / "dump"), str(img), stats)
+    assert {"frame_file_bytes", "frame_counters"} <= set(names)
+    assert sorted(names) == sorted(f[:-4] for f in os.listdir(tmp_path / "dump"))
+    b = np.load(tmp_path / "dump" / "frame_file_bytes.npy")
+    assert b.dtype == np.float32 and np.array_equal(b, np.frombuffer(img.read_bytes(), np.uint8))
+    c = np.load(tmp_path / "dump" / "frame_counters.npy")
+    assert c.dtype == np.float64 and c.tolist() == [float(i + 1) for i in range(len(bench.DUMP_COUNTERS))]
+    if "frame_rgb" in names:
+        px = np.load(tmp_path / "dump" / "frame_rgb.npy")
+        assert px.dtype == np.float32 and np.array_equal(px, rgba[..., :3].reshape(-1, 3))
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """--full and --dump-outputs are off unless asked for; --steps is taken as given."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse_args()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "d"

@@ -810,13 +810,13 @@ def _render_scene_view(name, view):
         OO.render = orig
 
 
-def test_log2_fixed_accuracy():
+def test_log2_fixed_accuracy(tmp_path):
     """The libm-free log2 of the Filmic shaper (view.hip log2_fixed) is within
     3e-7 of log2 over the normal range: checked through the shaper's
     allocation a = (log2 x + 12.47) / 25 on a 1x1x1 identity cube + identity
     curve, where one 8-bit step is 25/255 stops."""
     import os
-    d = "/tmp/rr_identity_luts"
+    d = str(tmp_path / "rr_identity_luts")
     os.makedirs(os.path.join(d, "luts"), exist_ok=True)
     with open(os.path.join(d, "luts", HO.FILMIC_LUT_FILES[0]), "w") as fh:
         fh.write("SPILUT 1.0\n3 3\n2 2 2\n")

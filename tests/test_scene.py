@@ -9,12 +9,12 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, have_reference, scene_path
+from conftest import GOLDEN, ROOT, scene_path
 from oracle import host_oracle as HO
 
 S01 = scene_path("01_simple-animation.rrscene")
 S04 = scene_path("04_very-simple-standin.rrscene")
-BLEND = "/root/reference/blender-projects/01_simple-animation/01_simple-animation.blend"
+BLEND = os.path.join(ROOT, "blender-projects", "01_simple-animation", "01_simple-animation.blend")
 
 
 def test_fcurve_golden_table(rr):
@@ -90,7 +90,6 @@ def test_render_params_override(rr):
     assert st.camera[13] == pytest.approx(0.36) and st.camera[12] == pytest.approx(0.09)
 
 
-@pytest.mark.skipif(not have_reference(), reason="needs the reference .blend")
 def test_exporter_reproduces_committed_scene():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from blend_export import export

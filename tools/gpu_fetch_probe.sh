@@ -2,7 +2,7 @@
 # PMC byte-counter calibration on the GPU box (tools/fetch_probe.hip): one
 # rocprofv3 pass per counter group, then the ratios (tools/fetch_probe.py).
 set -u
-out=gpurun_out/fetch_probe
+out=${RR_OUT:-output}/fetch_probe
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 timeout -s KILL 90 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -o run -- tools/bin/fetch_probe \

@@ -5,7 +5,7 @@
 # signal ends the whole call so nothing else touches a possibly-faulted GPU.
 #   tools/gpu_steps.sh <seconds> <cmd...> ::: <seconds> <cmd...> ::: ...
 set -u
-mkdir -p gpurun_out
+mkdir -p ${RR_OUT:-output}
 step=()
 run_step() {
     local secs=$1; shift

@@ -3,7 +3,7 @@
 #   TAG=x SCENE=scenes/... FRAME=90 SPP=16 tools/prof_scene.sh
 set -e
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-O=gpurun_out/prof_${TAG:-scene}
+O=${RR_OUT:-output}/prof_${TAG:-scene}
 mkdir -p $O
 timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 tools/diag_traversal.py ${SCENE:-scenes/02_physics-standin.rrscene} ${FRAME:-90} ${SPP:-16} > $O/diag.json
 timeout -s KILL 90 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O/sq1 -o run -- python3 tools/diag_traversal.py ${SCENE:-scenes/02_physics-standin.rrscene} ${FRAME:-90} ${SPP:-16} > /dev/null

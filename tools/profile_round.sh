@@ -5,12 +5,12 @@
 #   tools/profile_round.sh <tag> [workload] [extra bench args]
 #   tools/profile_round.sh r1                 # 04vs, the headline config
 #   tools/profile_round.sh r1_c5 c5 "--spp 64" # C5 (same per-launch sizes: 32-spp chunks)
-# Outputs under gpurun_out/prof_<tag>/; copy the summaries into profiles/.
+# Outputs under ${RR_OUT:-output}/prof_<tag>/; copy the summaries into profiles/.
 set -euo pipefail
 tag=${1:-r1}
 wl=${2:-04vs}
 extra=${3:-}
-out=gpurun_out/prof_$tag
+out=${RR_OUT:-output}/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 
@@ -27,14 +27,14 @@ if [ "$wl" == "c5" ]; then steps="--steps 2 --warmup 1"; psteps="--steps 1 --war
 ser=""
 if [ "$wl" == "04vs" ] || [ "$wl" == "01" ]; then ser="--serial"; fi
 if [ "$wl" == "c5" ]; then psteps="--steps 1 --warmup 1"; else psteps="--steps 6 --warmup 1"; fi
-B="bench.py --workload $wl $psteps --no-cpu-baseline --no-profile $extra"
+B="bench.py --full --workload $wl $psteps --no-cpu-baseline --no-profile $extra"
 
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run \
-    -- python3 bench.py --workload $wl $steps --no-cpu-baseline $extra > "$out/trace_bench.json"
+    -- python3 bench.py --full --workload $wl $steps --no-cpu-baseline $extra > "$out/trace_bench.json"
 echo "trace done"
 if [ -n "$ser" ]; then
     timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_serial" -o run \
-        -- python3 bench.py --workload $wl $steps --no-cpu-baseline --serial $extra > "$out/trace_serial_bench.json"
+        -- python3 bench.py --full --workload $wl $steps --no-cpu-baseline --serial $extra > "$out/trace_serial_bench.json"
     echo "serial trace done"
 fi
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -o run -- python3 $B > /dev/null
