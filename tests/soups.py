@@ -89,19 +89,30 @@ def padded_soup(seed: int, n: int) -> np.ndarray:
     return np.concatenate([tris, np.array(extra, np.float32).reshape(-1, 3, 3)]).astype(np.float32)
 
 
-def soup_scene(base_scene_path: str, seed: int, out_path: str, n: int | None = None) -> np.ndarray:
-    """Writes the soup of `seed` (padded_soup(seed, n) when n is given) as a
-    copy of the scene at base_scene_path (the 04vs stand-in) with its mesh
-    replaced; returns the triangles."""
+def soup_scene(base_scene_path: str, seed: int, out_path: str, n: int | None = None,
+               tris: np.ndarray | None = None) -> np.ndarray:
+    """Writes the soup of `seed` (padded_soup(seed, n) when n is given; the
+    (n, 3, 3) float32 array `tris` itself when that is given) as a copy of the
+    scene at base_scene_path (the 04vs stand-in) with its mesh replaced;
+    returns the triangles."""
+    scene = soup_scene_dict(base_scene_path, seed, n, tris)
+    with open(out_path, "w") as f:
+        json.dump(scene, f)
+    mesh = scene["meshes"][0]
+    return np.array(mesh["vertices"], np.float32).reshape(-1, 3, 3)
+
+
+def soup_scene_dict(base_scene_path: str, seed: int, n: int | None = None, tris: np.ndarray | None = None) -> dict:
+    """The scene soup_scene writes, as the parsed JSON."""
     with open(base_scene_path) as f:
         scene = json.load(f)
-    tris = random_soup(seed) if n is None else padded_soup(seed, n)
+    if tris is None:
+        tris = random_soup(seed) if n is None else padded_soup(seed, n)
+    assert tris.dtype == np.float32 and tris.shape[1:] == (3, 3)
     mesh = scene["meshes"][0]
     mesh["vertices"] = [float(x) for x in tris.reshape(-1)]
     mesh["triangles"] = list(range(3 * len(tris)))
     mesh["material_indices"] = [0] * len(tris)
     mesh["smooth"] = [0] * len(tris)
     scene["name"] = f"soup-{seed}"
-    with open(out_path, "w") as f:
-        json.dump(scene, f)
-    return tris
+    return scene

@@ -291,6 +291,57 @@ def test_lbvh_degenerate_inputs():
     assert prims[0] == 0  # equal t: the smallest original id wins
 
 
+def degenerate_world_tris(name):
+    """World triangles at frame 1 of a tests/degenerate.py case, from the scene
+    the device tests load (the device's frame_state(...).tris equal these)."""
+    import degenerate
+    tris, _ = world_tris(degenerate.scene_dict(scene_path("04_very-simple-standin.rrscene"), name), 1)
+    return tris
+
+
+def _degenerate_cases():
+    import degenerate
+    return degenerate.TRACE_CASES
+
+
+@pytest.mark.parametrize("name", _degenerate_cases())
+def test_degenerate_cases_walks_equal_brute_force(name):
+    """Every degenerate / boundary-size case of tests/degenerate.py on the ray
+    batches the device tests use (test_gpu_degenerate.py): the oracle's walks
+    of the LBVH, PLOC and the 6-wide collapse find the brute-force closest hits
+    (ids and t) without dropping a stack push, and the batches are not vacuous:
+    more than a tenth of the rays hit wherever a triangle has area, none where
+    none has, and identical triangles answer with the smallest id."""
+    import degenerate
+    tris = degenerate_world_tris(name)
+    degenerate.check_property(name, tris)
+    for kind, rays in (("rays", degenerate.rays(name, tris)), ("packets", degenerate.packet_rays(name, tris))):
+        bh, bp = O.trace_brute(tris, rays)
+        O.stack_drops(reset=True)
+        for width in (2, 3, 4):
+            h, p, occ = O.trace(tris, rays, width=width)
+            assert np.array_equal(p, bp), (kind, width, int(np.count_nonzero(p != bp)))
+            assert np.array_equal(h[:, 0], bh[:, 0]), (kind, width)
+            assert np.array_equal(occ.astype(bool), bp >= 0), (kind, width)
+        assert O.stack_drops() == 0
+        frac = float((bp >= 0).mean())
+        print(f"{name}: {kind} hit fraction {frac:.3f}")
+        if name in degenerate.NO_AREA:
+            assert frac == 0.0
+        elif kind == "rays":
+            assert frac > 0.10
+        else:  # a sparse soup fills little of the packets' frustum: more than a stray ray must hit
+            assert np.count_nonzero(bp >= 0) >= 32
+        if name.startswith("same"):
+            assert np.all(bp[bp >= 0] == 0)
+    if name in ("rand64", "coplanar40"):
+        edge = degenerate.edge_rays(name, tris, O.trace_brute)
+        for width in (2, 4):
+            h, p, occ = O.trace(tris, edge, width=width)
+            print(f"{name}: {len(edge)} edge rays, width {width}: {int((p >= 0).sum())} hits")
+        assert O.stack_drops() == 0
+
+
 def test_lambert_and_principled_bsdf():
     n = [0, 0, 1]
     wo = [0, 0.6, 0.8]
