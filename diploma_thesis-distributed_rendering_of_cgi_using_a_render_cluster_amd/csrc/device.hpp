@@ -268,6 +268,29 @@ size_t jpeg_stream_max_bytes(int W, int H);
 void jpeg_encode_device(const uint8_t* d_rgba, int W, int H, const float* d_tab, const uint32_t* d_huff,
                         int16_t* d_coeffs, JpegDevBufs& b, uint8_t* host_out, hipStream_t st);
 
+// Device PNG encode (png.hip): Sub filter, LZ77 and dynamic-Huffman deflate of
+// an RGBA8 frame in bands of kPngBandRows rows, written to pinned host memory
+// as [uint64 length][8 B pad][78 01 + deflate data]; host_tab receives
+// {Adler-32, filtered bytes} per band for the host to combine (image_io
+// png_wrap_stream). The band height is fixed, so a frame's bytes depend on
+// the image alone.
+constexpr int kPngBandRows = 16;
+struct PngPlan {
+    int W, H, nbands;
+    uint32_t stride;     // filtered bytes per row, 4W + 1
+    uint32_t row_dist;   // stride when it fits the 32 KB window (the row-above distance), else 0
+    uint32_t band_full;  // filtered bytes of a full band
+    uint32_t band_pos;   // positions reserved per band (whole parse tiles)
+    uint32_t nsub, nseg; // per band: 4096-position chunks, 512-position parse segments
+    uint32_t band_cap;   // bytes reserved per band's deflate piece (>= its stored form)
+};
+// false: the size is outside what the device encoder takes (W > 2^20, or a stream of 2 GB and more).
+bool png_plan(int W, int H, PngPlan& p);
+size_t png_scratch_words(const PngPlan& p);
+size_t png_stream_max_bytes(const PngPlan& p);  // zlib stream with every band stored
+void png_encode_device(const uint8_t* d_rgba, const PngPlan& p, uint32_t* scratch, uint8_t* host_out,
+                       uint32_t* host_tab, hipStream_t st);
+
 // Per chunk: one pair per bounce b = 0..max_bounces {paths entering b+1,
 // shadow rays of b}, one pair of slack, then the words below.
 int counters_per_chunk(int max_bounces);

@@ -482,6 +482,24 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
     return true;
 }
 
+void png_wrap_stream(int W, int H, const uint8_t* zs, size_t n, const uint32_t* band_tab, int nbands,
+                     std::vector<uint8_t>& out) {
+    uLong a = adler32(0L, Z_NULL, 0);
+    for (int b = 0; b < nbands; ++b) a = adler32_combine(a, band_tab[2 * b], (z_off_t)band_tab[2 * b + 1]);
+    std::vector<uint8_t> z(zs, zs + n);
+    for (int k = 3; k >= 0; --k) z.push_back((uint8_t)(a >> (8 * k)));
+    out.clear();
+    out.reserve(z.size() + 64);
+    const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+    out.insert(out.end(), sig, sig + 8);
+    uint8_t ihdr[13] = {(uint8_t)(W >> 24), (uint8_t)(W >> 16), (uint8_t)(W >> 8), (uint8_t)W,
+                        (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H,
+                        8, 6, 0, 0, 0};
+    png_chunk(out, "IHDR", ihdr, 13);
+    png_chunk(out, "IDAT", z.data(), z.size());
+    png_chunk(out, "IEND", nullptr, 0);
+}
+
 bool write_file(const std::string& path, const std::vector<uint8_t>& data) {
     FILE* f = std::fopen(path.c_str(), "wb");
     if (!f) return false;

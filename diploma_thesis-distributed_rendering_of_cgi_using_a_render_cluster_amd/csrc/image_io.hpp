@@ -29,6 +29,11 @@ void jpeg_header_bytes(int W, int H, int quality, std::vector<uint8_t>& out);
 void jpeg_huff_tables(uint32_t out[4 * 256]);
 bool encode_jpeg(const uint8_t* rgba, int W, int H, int quality, std::vector<uint8_t>& out, int threads = 0);
 bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, int level = 1, int threads = 0);
+// The PNG file around a zlib stream coded on the device (png.hip): z = 78 01 +
+// the bands' deflate pieces; band_tab = {Adler-32, filtered bytes} per band,
+// combined here into the stream's Adler-32. Signature, IHDR, one IDAT, IEND.
+void png_wrap_stream(int W, int H, const uint8_t* z, size_t n, const uint32_t* band_tab, int nbands,
+                     std::vector<uint8_t>& out);
 bool write_file(const std::string& path, const std::vector<uint8_t>& data);
 
 }  // namespace rr

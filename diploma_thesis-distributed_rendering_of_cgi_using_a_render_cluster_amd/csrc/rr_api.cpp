@@ -91,8 +91,9 @@ struct FrameSlot {
     bool busy = false;
     uint64_t ticket = 0;
     // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
-    // work done, 3 outputs on the host (after their copies)
-    hipEvent_t ev[5] = {};
+    // work done, 3 outputs on the host (after their copies), 5 (device PNG
+    // frames) before the PNG coder: the state shared between frames is free
+    hipEvent_t ev[6] = {};
     DevBuf<int32_t> counters;  // this frame's ray counters (swapped into DevPaths while enqueuing)
     // this frame's device outputs (swapped into DevPaths / rr_ctx while enqueuing):
     // their copies to the host run while the next frames' kernels write the other
@@ -103,6 +104,9 @@ struct FrameSlot {
     KernelProfiler prof;
     PinnedBuf host_rgba, host_counters, host_upload;
     PinnedBuf host_jpeg;   // device-coded JPEG stream: [uint64 length][pad][bytes]
+    PinnedBuf host_png;    // device-coded zlib stream of a PNG frame, same layout (png.hip)
+    PinnedBuf host_png_tab;  // its bands' {Adler-32, filtered bytes}
+    PngPlan png_plan{};
     FrameSetup fs;
     bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
     std::string view_warning;
@@ -111,7 +115,7 @@ struct FrameSlot {
     rr_scene* scene = nullptr;
     std::string out_path, format;
     int quality = 0;
-    bool jpeg = false, want_rgba = false, count = false;
+    bool jpeg = false, png = false, want_rgba = false, count = false;  // png: coded on the device (rr_set_device_png)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log into trav_counts (rr_debug_tile_costs)
     float* film_out = nullptr;
     FrameRun r{};
@@ -136,6 +140,7 @@ struct FrameSlot {
     DevBuf<int32_t> tile_order, spill;
     DevBuf<unsigned long long> trav_counts;
     DevBuf<uint32_t> jpeg_blk, jpeg_scratch;
+    DevBuf<uint32_t> png_scratch;
     DevScene alt;
     const rr_scene* alt_scene = nullptr;
     void release_private() {
@@ -151,6 +156,7 @@ struct FrameSlot {
         trav_counts.release();
         jpeg_blk.release();
         jpeg_scratch.release();
+        png_scratch.release();
         alt.release();
         alt = DevScene{};
         alt_scene = nullptr;
@@ -171,6 +177,9 @@ struct rr_ctx {
     // device entropy coder (jpeg.hip): Huffman tables, per-row scratch, stream
     DevBuf<uint32_t> jpeg_huff;
     DevBuf<uint32_t> jpeg_scratch, jpeg_blk;
+    // device PNG encoder (png.hip): on for "PNG" frames (rr_set_device_png / RR_DEVICE_PNG), its scratch
+    bool device_png = false;
+    DevBuf<uint32_t> png_scratch;
     std::vector<float> filter_cache;
     float filter_width_cached = -1.f;
     bool srgb_uploaded = false;
@@ -488,6 +497,41 @@ bool write_device_jpeg(const FrameSlot& sl, const std::string& path, uint64_t* b
     return write_file(path, data);
 }
 
+// Device PNG encode of an RGBA8 frame (png.hip) into the slot's pinned stream
+// buffer and band table, on the context stream.
+void enqueue_png_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W, int H) {
+    PngPlan p;
+    if (!png_plan(W, H, p)) throw std::runtime_error("image size outside the device PNG encoder's range");
+    sl.png_plan = p;
+    c->png_scratch.ensure(png_scratch_words(p));
+    sl.host_png.ensure(png_stream_max_bytes(p) + 32);
+    sl.host_png_tab.ensure((size_t)p.nbands * 2 * sizeof(uint32_t));
+    void *dev_host = nullptr, *dev_tab = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_png.ptr, 0));
+    RR_HIP(hipHostGetDevicePointer(&dev_tab, sl.host_png_tab.ptr, 0));
+    c->paths.prof.begin(c->stream, RR_K_PNG);
+    png_encode_device(d_rgba, p, c->png_scratch.ptr, static_cast<uint8_t*>(dev_host), static_cast<uint32_t*>(dev_tab),
+                      c->stream);
+    c->paths.prof.end(c->stream);
+}
+
+// The bytes of a device-coded PNG frame: host-built chunks around the device stream.
+void device_png_bytes(const FrameSlot& sl, std::vector<uint8_t>& data) {
+    uint64_t len = 0;
+    std::memcpy(&len, sl.host_png.ptr, sizeof len);
+    if (len + 16 + 4 > sl.host_png.cap) throw std::runtime_error("device PNG stream overflow");
+    const PngPlan& p = sl.png_plan;
+    png_wrap_stream(p.W, p.H, sl.host_png.ptr + 16, (size_t)len, reinterpret_cast<const uint32_t*>(sl.host_png_tab.ptr),
+                    p.nbands, data);
+}
+
+bool write_device_png(const FrameSlot& sl, const std::string& path, uint64_t* bytes) {
+    std::vector<uint8_t> data;
+    device_png_bytes(sl, data);
+    *bytes = data.size();
+    return write_file(path, data);
+}
+
 // Enqueue the device part of one frame on the context stream (no host
 // synchronisation): LBVH (if needed), wavefront, tonemap, optionally the JPEG
 // transform, and the asynchronous copies of the slot's outputs.
@@ -531,6 +575,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
             std::swap(p.trav_counts, sl.trav_counts);
             std::swap(c->jpeg_blk, sl.jpeg_blk);
             std::swap(c->jpeg_scratch, sl.jpeg_scratch);
+            std::swap(c->png_scratch, sl.png_scratch);
             if (sl.tiles) swap_products(sl.scene->dev, sl.alt);
             c->in_slot = !c->in_slot;
         }
@@ -541,8 +586,10 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     SlotSwap slot_swap(c, sl);
     hipStream_t st = c->stream;
     FrameSlot* prev = c->last_enqueued;
+    // (the device PNG coder reads its slot's rgba8 and writes slot buffers
+    // only, so the next frame waits for the image, not for the coder)
     if (prev && prev != &sl && !(sl.tiles && prev->tiles))
-        RR_HIP(hipStreamWaitEvent(st, prev->ev[2], 0));
+        RR_HIP(hipStreamWaitEvent(st, prev->png ? prev->ev[5] : prev->ev[2], 0));
     c->last_enqueued = &sl;
     // a k_tiles frame enqueued while another k_tiles frame is pending overlaps
     // it: whole-tile work units (render_frame_device); a frame rendered alone
@@ -614,6 +661,10 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
             c->jpeg_tab_quality = sl.quality;
         }
         enqueue_jpeg_device(c, sl, c->paths.rgba8.ptr, fs.W, fs.H, c->jpeg_tab.ptr);
+    }
+    if (sl.png) {
+        RR_HIP(hipEventRecord(sl.ev[5], st));
+        enqueue_png_device(c, sl, c->paths.rgba8.ptr, fs.W, fs.H);
     }
     RR_HIP(hipEventRecord(sl.ev[2], st));
     // the outputs' device-to-host copies follow on the slot's own stream: the
@@ -829,6 +880,7 @@ int rr_create(int device_ordinal, rr_ctx** out) {
             if (*d && load_filmic_luts(d, l, err)) c->filmic.upload(l, d);
             else if (*d) c->ctx_warning = "RR_OCIO_DIR: " + err;
         }
+        if (const char* d = getenv("RR_DEVICE_PNG")) c->device_png = std::string(d) == "1";
         *out = c.release();
         return RR_OK;
     });
@@ -847,6 +899,7 @@ void rr_destroy(rr_ctx* c) {
     c->jpeg_huff.release();
     c->jpeg_scratch.release();
     c->jpeg_blk.release();
+    c->png_scratch.release();
     for (auto& sl : c->slots) {
         for (auto& e : sl.ev)
             if (e) (void)hipEventDestroy(e);
@@ -947,7 +1000,8 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->format = (out_path && format) ? format : "";
         sl->quality = jpeg_quality;
         sl->jpeg = jpeg;
-        sl->want_rgba = out_path && !jpeg;
+        sl->png = out_path && !jpeg && c->device_png;  // format is "PNG"
+        sl->want_rgba = out_path && !jpeg && !sl->png;
         sl->film_out = nullptr;
         sl->anchor = idle(c);
         sl->submit_at = unix_now();
@@ -1008,6 +1062,10 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
             const std::string path = sl->out_path + ".jpg";
             if (!write_device_jpeg(*sl, path, &bytes))
                 return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
+        } else if (sl->png) {  // PNG chunks + the device-coded zlib stream
+            const std::string path = sl->out_path + ".png";
+            if (!write_device_png(*sl, path, &bytes))
+                return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
         } else if (!sl->out_path.empty()) {
             const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), sl->format.c_str(),
                                     sl->quality, &bytes);
@@ -1065,6 +1123,7 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         sl->out_path.clear();
         sl->format.clear();
         sl->jpeg = false;
+        sl->png = false;
         sl->want_rgba = true;
         sl->film_out = film;
         sl->ticket = c->next_ticket;
@@ -1127,6 +1186,33 @@ int rr_debug_jpeg_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, 
         }
         img.release();
         dtab.release();
+        return RR_OK;
+    });
+}
+
+int rr_set_device_png(rr_ctx* c, int32_t on) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    c->device_png = on != 0;  // read when a frame is submitted; frames in flight keep their choice
+    return RR_OK;
+}
+
+int rr_debug_png_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
+                        uint64_t* len) {
+    if (!c || !rgba8 || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    return guarded([&] {
+        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
+        set_device(c);
+        DevBuf<uint8_t> img;
+        img.ensure((size_t)w * h * 4);
+        RR_HIP(hipMemcpy(img.ptr, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice));
+        FrameSlot& sl = c->slots[0];
+        enqueue_png_device(c, sl, img.ptr, w, h);
+        RR_HIP(hipStreamSynchronize(c->stream));
+        img.release();
+        std::vector<uint8_t> data;
+        device_png_bytes(sl, data);
+        *len = data.size();
+        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
         return RR_OK;
     });
 }

@@ -75,6 +75,7 @@ class FrameStats(ctypes.Structure):
 
 RR_FLAG_PROFILE_KERNELS, RR_FLAG_COUNT_TRAVERSAL, RR_FLAG_WAVEFRONT = 1, 2, 4
 KERNEL_CLASSES = ["build", "primary", "extend", "shadow", "accumulate", "shade", "tiles"]
+RR_K_PNG = 7  # FrameStats.kernel_ms index of the device PNG encoder (rr_set_device_png)
 
 
 # Every symbol include/rr.h declares (checked by tests/test_abi.py).
@@ -86,6 +87,7 @@ EXPORTS = [
     "rr_scene_free", "rr_destroy", "rr_debug_counts", "rr_debug_scene_mesh", "rr_debug_frame_state", "rr_debug_bvh",
     "rr_debug_trace", "rr_debug_object_matrix", "rr_debug_qbvh", "rr_debug_bvh_hier", "rr_debug_jpeg_device",
     "rr_debug_bsdf_sample", "rr_debug_fastmath_check", "rr_debug_tile_costs",
+    "rr_set_device_png", "rr_debug_png_device",
 ]
 
 _lib = None
@@ -139,6 +141,8 @@ def lib() -> ctypes.CDLL:
         "rr_debug_bvh_hier": (c_int, [P, P, i32, i32, u32p, u32p, i32p, f32p]),
         "rr_debug_jpeg_device": (c_int, [P, u8p, i32, i32, i32, u8p, ctypes.c_uint64,
                                          ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_set_device_png": (c_int, [P, i32]),
+        "rr_debug_png_device": (c_int, [P, u8p, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -395,6 +399,25 @@ class RenderContext:
         _check(lib().rr_debug_jpeg_device(self.handle, _ptr(rgba, ctypes.c_uint8), w, h, int(quality),
                                           _ptr(out, ctypes.c_uint8), n.value, ctypes.byref(n)), self.handle)
         return out.tobytes()
+
+    def set_device_png(self, on: bool = True):
+        """rr_set_device_png: code "PNG" frames of this context on the device
+        (png.hip) instead of reading the image back for the host's zlib threads."""
+        _check(lib().rr_set_device_png(self.handle, 1 if on else 0), self.handle)
+
+    def png_device(self, rgba: np.ndarray) -> bytes:
+        """rr_debug_png_device: the PNG file bytes of an (H, W, 4) uint8 image
+        encoded on the device (Sub filter, LZ77, dynamic Huffman)."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+        h, w = rgba.shape[:2]
+        raw = (4 * w + 1) * h
+        out = np.zeros(raw + raw // 8 + 4096, np.uint8)  # above the all-stored worst case
+        n = ctypes.c_uint64()
+        _check(lib().rr_debug_png_device(self.handle, _ptr(rgba, ctypes.c_uint8), w, h,
+                                         _ptr(out, ctypes.c_uint8), out.size, ctypes.byref(n)), self.handle)
+        if n.value > out.size:
+            raise RRError(RR_EINVAL, f"device PNG of {n.value} bytes exceeds the {out.size}-byte buffer")
+        return out[:n.value].tobytes()
 
     def bsdf_sample(self, mat12, n, wo, u):
         """rr_debug_bsdf_sample: (wi [k,3], f [k,3], pdf [k], ok [k]: 0 end, 1 diffuse, 2 glossy)."""

@@ -40,9 +40,10 @@ class RenderError(RuntimeError):
 
 class BackendRunner:
     def __init__(self, base_directory_path: str | os.PathLike, tracer: WorkerTraceBuilder | None = None,
-                 device: int = 0, params: RenderParams | None = None, ctx=None):
+                 device: int = 0, params: RenderParams | None = None, ctx=None, device_png: bool = False):
         """ctx: a RenderContext on `device` is created here; tests of the host
-        logic alone pass a stand-in with the same methods (no rendering)."""
+        logic alone pass a stand-in with the same methods (no rendering).
+        device_png: "PNG" jobs are coded on the device (rr_set_device_png)."""
         base = Path(base_directory_path)
         if not base.is_dir():
             raise RenderError("Provided base directory path is not a directory.")
@@ -50,6 +51,8 @@ class BackendRunner:
         self.tracer = tracer if tracer is not None else WorkerTraceBuilder()
         self.params = params
         self.ctx = ctx if ctx is not None else RenderContext(device)
+        if device_png:
+            self.ctx.set_device_png(True)
         self._scenes: dict[str, Scene] = {}
         self._lock = threading.Lock()  # one caller at a time per context (queue.rs:79-118)
         self.last_stats = None

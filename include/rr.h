@@ -89,6 +89,7 @@ typedef struct rr_render_params {
 #define RR_K_ACCUM 4     /* film accumulate + tonemap */
 #define RR_K_SHADE 5     /* split path (large scenes): shading kernels; PRIMARY/EXTEND then time traversal only */
 #define RR_K_TILES 6     /* LDS-resident scenes: k_tiles, every sample of an 8x8 pixel tile run to completion + film + tonemap */
+#define RR_K_PNG 7       /* device PNG encoder (rr_set_device_png): all its kernels, one event pair per frame */
 #define RR_K_CLASSES 8
 
 /* The five timestamps the reference recovers from Blender's stdout
@@ -118,7 +119,7 @@ typedef struct rr_frame_stats {
     double anim_ms;          /* host animation eval + upload */
     double build_ms;         /* device: world transform + LBVH build (0 if cached) */
     double trace_ms;         /* device: wavefront kernels (raygen .. accumulate) */
-    double readback_ms;      /* device->host of the 8-bit image */
+    double readback_ms;      /* device->host of the 8-bit image (device JPEG / PNG: the coder + its stream) */
     double encode_ms;        /* host: JPEG/PNG encode + write */
     double total_ms;         /* whole call */
     int32_t bvh_rebuilt;     /* 1 if the LBVH was rebuilt for this frame */
@@ -253,6 +254,24 @@ int rr_encode_image(const uint8_t* rgba8, int32_t width, int32_t height,
  * Exported for parity tests against rr_encode_image. */
 int rr_debug_jpeg_device(rr_ctx* ctx, const uint8_t* rgba8, int32_t width, int32_t height,
                          int32_t jpeg_quality, uint8_t* out, uint64_t cap, uint64_t* len);
+
+/* Select the device PNG encoder for "PNG" frames of ctx (on != 0): Sub filter,
+ * LZ77 and dynamic-Huffman deflate run on the GPU after the view transform
+ * (png.hip), only the zlib stream crosses PCIe and the host writes the chunk
+ * framing — instead of the 8-bit image's readback and the zlib threads of
+ * rr_encode_image. Replaces the PNG side of Blender's write_still
+ * (render-timing-script.py:83-92). Off by default; rr_create reads
+ * RR_DEVICE_PNG=1 from the environment the same way. The files decode to the
+ * same pixels either way; their bytes differ. Applies to frames submitted
+ * after the call. RR_EINVAL for a NULL ctx. */
+int rr_set_device_png(rr_ctx* ctx, int32_t on);
+
+/* Encode an RGBA8 image with the device PNG path (the one rr_set_device_png
+ * selects for rendered frames; write_still, render-timing-script.py:83-92).
+ * *len receives the file size; the bytes are copied to out if cap >= *len.
+ * Exported for round-trip tests. */
+int rr_debug_png_device(rr_ctx* ctx, const uint8_t* rgba8, int32_t width, int32_t height,
+                        uint8_t* out, uint64_t cap, uint64_t* len);
 
 /* Thread-local message of the last failure on this thread (ctx may be NULL). */
 const char* rr_last_error(rr_ctx* ctx);
