@@ -3,7 +3,9 @@ row above, one dynamic-Huffman block per 16-row band with a stored fallback)
 writes files that decode to exactly the input pixels, deterministically, within
 size conditions that only real dynamic codes and working matches meet; rendered
 frames take it when rr_set_device_png is on and keep the host encoder's bytes
-when it is off; frames in flight do not share its buffers."""
+when it is off; frames in flight do not share its buffers. What the files
+contain — tokens, code lengths, stored or dynamic per band — is pinned to
+oracle/png_oracle.py in tests/test_gpu_png_tokens.py."""
 import zlib
 
 import numpy as np
