@@ -277,12 +277,19 @@ void jpeg_encode_device(const uint8_t* d_rgba, int W, int H, const float* d_tab,
 constexpr int kPngBandRows = 16;
 struct PngPlan {
     int W, H, nbands;
-    uint32_t stride;     // filtered bytes per row, 4W + 1
-    uint32_t row_dist;   // stride when it fits the 32 KB window (the row-above distance), else 0
-    uint32_t band_full;  // filtered bytes of a full band
+    uint32_t stride;     // front-end bytes per row (PNG: filtered, 4W + 1; EXR: 8W)
+    uint32_t band_full;  // front-end bytes of a full band
     uint32_t band_pos;   // positions reserved per band (whole parse tiles)
     uint32_t nsub, nseg; // per band: 4096-position chunks, 512-position parse segments
     uint32_t band_cap;   // bytes reserved per band's deflate piece (>= its stored form)
+    // the three match distances tried at every position, 0 = none (beyond the 32 KB window).
+    // PNG: 1, 4 (pixel period), 4W + 1 (the filtered row above)
+    uint32_t dist[3];
+    // every band is a deflate stream of its own (EXR chunks): its dynamic block is
+    // final and ends the piece; the alternative is not the stored form but the
+    // band's raw bytes, written by the front end's owner, and the host table
+    // holds {mode (0 dynamic, 1 raw), bytes, Adler-32, front-end bytes} per band
+    int own_stream;
 };
 // false: the size is outside what the device encoder takes (W > 2^20, or a stream of 2 GB and more).
 bool png_plan(int W, int H, PngPlan& p);
@@ -290,6 +297,36 @@ size_t png_scratch_words(const PngPlan& p);
 size_t png_stream_max_bytes(const PngPlan& p);  // zlib stream with every band stored
 void png_encode_device(const uint8_t* d_rgba, const PngPlan& p, uint32_t* scratch, uint8_t* host_out,
                        uint32_t* host_tab, hipStream_t st);
+
+// The deflate stages of png.hip behind another front end (exr.hip). The front
+// end fills `filt` (band b at b * band_pos) and `adler_part` ({sum of bytes,
+// sum of (m - k) * byte k} per 4096-byte chunk, at 2 * (b * nsub + chunk)).
+struct DeflateBufs {
+    uint8_t *filt, *out;  // out: band b's piece at b * band_cap
+    uint16_t *cand, *exits, *entry;
+    uint32_t *adler_part, *subhist, *codes, *sub_off, *rec, *prefix;  // rec: 4 words per band (k_png_codes)
+    size_t words;
+};
+constexpr uint32_t kDeflateSub = 4096;  // positions per Adler chunk
+// Everything of the plan but dist and own_stream; false: a stream of 2 GB and more.
+bool deflate_plan(int W, int H, uint32_t stride, PngPlan& p);
+DeflateBufs deflate_carve(const PngPlan& p, uint32_t* base);  // base nullptr: only `words`
+void deflate_bands_device(const PngPlan& p, const DeflateBufs& c, hipStream_t st);  // match ... emit
+void deflate_gather_device(const PngPlan& p, const DeflateBufs& c, uint8_t* host_out, uint32_t* host_tab,
+                           hipStream_t st);
+
+// Device OpenEXR encode (exr.hip): the film's means as half-float A, B, G, R
+// planes in ZIP chunks of kPngBandRows scanlines. Front end (half conversion,
+// plane split, byte reorder, predictor, Adler sums) + the deflate stages
+// above; host_out = [uint64 length][8 B pad][the chunks' pieces: deflate data
+// without zlib framing, or the raw chunk bytes], host_tab = {mode, bytes,
+// Adler-32, chunk bytes} per chunk (image_io exr_wrap_stream).
+// false: W > 2^19 (band positions in 32-bit counters), or a stream of 2 GB and more.
+bool exr_plan(int W, int H, PngPlan& p);
+size_t exr_stream_max_bytes(const PngPlan& p);  // every chunk raw
+// film: W x H float4 sums, scaled by inv_spp; alpha_one: A = 1.0 (rendered frames), else film.w * inv_spp.
+void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const PngPlan& p, uint32_t* scratch,
+                       uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 // Per chunk: one pair per bounce b = 0..max_bounces {paths entering b+1,
 // shadow rays of b}, one pair of slack, then the words below.

@@ -500,6 +500,76 @@ void png_wrap_stream(int W, int H, const uint8_t* zs, size_t n, const uint32_t* 
     png_chunk(out, "IEND", nullptr, 0);
 }
 
+// --------------------------------------------------------------- EXR ------
+namespace {
+void put_le(std::vector<uint8_t>& o, uint64_t v, int bytes) {
+    for (int k = 0; k < bytes; ++k) o.push_back((uint8_t)(v >> (8 * k)));
+}
+void put_str(std::vector<uint8_t>& o, const char* s) {
+    for (; *s; ++s) o.push_back((uint8_t)*s);
+    o.push_back(0);
+}
+void exr_attr(std::vector<uint8_t>& o, const char* name, const char* type, const std::vector<uint8_t>& value) {
+    put_str(o, name);
+    put_str(o, type);
+    put_le(o, value.size(), 4);
+    o.insert(o.end(), value.begin(), value.end());
+}
+}  // namespace
+
+bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
+                     std::vector<uint8_t>& out) {
+    out.clear();
+    out.reserve(n + 512 + (size_t)nchunks * 22);
+    const uint8_t start[8] = {0x76, 0x2F, 0x31, 0x01, 2, 0, 0, 0};
+    out.insert(out.end(), start, start + 8);
+    std::vector<uint8_t> v;
+    for (const char* ch : {"A", "B", "G", "R"}) {
+        put_str(v, ch);
+        put_le(v, 1, 4);  // HALF
+        put_le(v, 0, 4);  // pLinear, 3 reserved bytes
+        put_le(v, 1, 4);  // xSampling
+        put_le(v, 1, 4);  // ySampling
+    }
+    v.push_back(0);
+    exr_attr(out, "channels", "chlist", v);
+    exr_attr(out, "compression", "compression", {3});  // ZIP, 16 scanlines
+    v.clear();
+    put_le(v, 0, 4);
+    put_le(v, 0, 4);
+    put_le(v, (uint32_t)(W - 1), 4);
+    put_le(v, (uint32_t)(H - 1), 4);
+    exr_attr(out, "dataWindow", "box2i", v);
+    exr_attr(out, "displayWindow", "box2i", v);
+    exr_attr(out, "lineOrder", "lineOrder", {0});
+    const std::vector<uint8_t> one = {0, 0, 0x80, 0x3F};  // 1.0f
+    exr_attr(out, "pixelAspectRatio", "float", one);
+    exr_attr(out, "screenWindowCenter", "v2f", std::vector<uint8_t>(8, 0));
+    exr_attr(out, "screenWindowWidth", "float", one);
+    out.push_back(0);
+    uint64_t at = out.size() + 8ull * (uint64_t)nchunks;
+    for (int b = 0; b < nchunks; ++b) {
+        put_le(out, at, 8);
+        at += 8 + chunk_tab[4 * b + 1] + (chunk_tab[4 * b] == 0 ? 6 : 0);
+    }
+    size_t src = 0;
+    for (int b = 0; b < nchunks; ++b) {
+        const uint32_t mode = chunk_tab[4 * b], len = chunk_tab[4 * b + 1], adler = chunk_tab[4 * b + 2];
+        if (src + len > n) return false;
+        put_le(out, (uint32_t)(b * 16), 4);
+        put_le(out, mode == 0 ? len + 6 : len, 4);
+        if (mode == 0) {
+            out.push_back(0x78);
+            out.push_back(0x01);
+        }
+        out.insert(out.end(), data + src, data + src + len);
+        if (mode == 0)
+            for (int k = 3; k >= 0; --k) out.push_back((uint8_t)(adler >> (8 * k)));
+        src += len;
+    }
+    return src == n;
+}
+
 bool write_file(const std::string& path, const std::vector<uint8_t>& data) {
     FILE* f = std::fopen(path.c_str(), "wb");
     if (!f) return false;

@@ -34,6 +34,13 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
 // combined here into the stream's Adler-32. Signature, IHDR, one IDAT, IEND.
 void png_wrap_stream(int W, int H, const uint8_t* z, size_t n, const uint32_t* band_tab, int nbands,
                      std::vector<uint8_t>& out);
+// The OpenEXR file (single-part scanline, version 2; half A, B, G, R; ZIP,
+// chunks of 16 scanlines) around chunks coded on the device (exr.hip): data =
+// the chunks' pieces back to back, chunk_tab = {mode, bytes, Adler-32, chunk
+// bytes} per chunk. Mode 0: deflate data, wrapped here in 78 01 ... Adler-32;
+// mode 1: the raw chunk. false: the pieces do not add up to n.
+bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
+                     std::vector<uint8_t>& out);
 bool write_file(const std::string& path, const std::vector<uint8_t>& data);
 
 }  // namespace rr

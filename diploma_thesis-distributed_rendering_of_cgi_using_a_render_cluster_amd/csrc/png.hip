@@ -35,6 +35,12 @@
 //    host memory, 16-byte stores; total length; per-band Adler / length table.
 // Same image -> same bytes: integer counts and ORs only, nothing depends on
 // the order of arrival.
+//
+// The stages from k_png_match on take a band description (PngPlan: bytes per
+// row, three candidate distances, own_stream), not PNG's geometry, and also
+// run behind exr.hip's front end (deflate_bands_device, deflate_gather_device):
+// there every band is a final stream of its own, and a band that would not
+// shrink is left to that front end's owner to write raw.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -68,7 +74,7 @@ __device__ __forceinline__ Band band_of(const PngPlan& p, int b) {
     r.row0 = b * kPngBandRows;
     r.rows = min(kPngBandRows, p.H - r.row0);
     r.n = p.stride * (uint32_t)r.rows;
-    r.last = b + 1 == p.nbands;
+    r.last = p.own_stream || b + 1 == p.nbands;
     return r;
 }
 
@@ -125,7 +131,7 @@ __device__ __forceinline__ int extra_bits(int s) {  // of symbol s in the kSyms 
     return (s >= 265 && s < 285) ? (s - 261) >> 2 : 0;
 }
 __device__ __forceinline__ uint32_t dist_of(const PngPlan& p, uint32_t dsel) {
-    return dsel == 0 ? 1u : dsel == 1 ? 4u : p.stride;
+    return dsel == 0 ? p.dist[0] : dsel == 1 ? p.dist[1] : p.dist[2];
 }
 
 // ------------------------------------------------------------ filter ------
@@ -196,13 +202,13 @@ __global__ __launch_bounds__(kThreads) void k_png_match(const uint8_t* __restric
     if (c0 >= bd.n) return;
     const uint8_t* f = filt + (size_t)b * p.band_pos;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t rd = p.row_dist;  // 0: the row above is beyond the window
+    const uint32_t d0 = p.dist[0], d1 = p.dist[1], rd = p.dist[2];  // 0: not a candidate (beyond the window)
     for (int g = wv; g < kMaskWords; g += kThreads / 64) {
         const uint32_t j = c0 + (uint32_t)g * 64u + (uint32_t)lane;
         const bool in = j < bd.n;  // a match never runs past the band's end
         const uint32_t v = in ? f[j] : 0u;
-        const bool e1 = in && j >= 1 && f[j - 1] == v;  // ... nor starts before the band
-        const bool e4 = in && j >= 4 && f[j - 4] == v;
+        const bool e1 = in && d0 && j >= d0 && f[j - d0] == v;  // ... nor starts before the band
+        const bool e4 = in && d1 && j >= d1 && f[j - d1] == v;
         const bool er = in && rd && j >= rd && f[j - rd] == v;
         const uint64_t m1 = __ballot(e1), m4 = __ballot(e4), mr = __ballot(er);
         if (lane == 0) {
@@ -213,15 +219,16 @@ __global__ __launch_bounds__(kThreads) void k_png_match(const uint8_t* __restric
     }
     __syncthreads();
     uint16_t* c = cand + (size_t)b * p.band_pos;
-    const int far_min = rd > 4096 ? 4 : 3;  // a 3-byte match that far costs more than its literals (zlib TOO_FAR)
+    // a 3-byte match further than 4096 costs more than its literals (zlib TOO_FAR)
+    const int min0 = d0 > 4096 ? 4 : 3, min1 = d1 > 4096 ? 4 : 3, far_min = rd > 4096 ? 4 : 3;
     for (uint32_t k = threadIdx.x; k < kSub; k += kThreads) {
         const uint32_t j = c0 + k;
         if (j >= bd.n) break;
         const int g = (int)(k >> 6), l = (int)(k & 63);
         const int l1 = run_from(mask[0], g, l), l4 = run_from(mask[1], g, l), lr = run_from(mask[2], g, l);
         int best = 0, sel = 0;
-        if (l1 >= 3) best = l1;
-        if (l4 >= 3 && l4 > best) best = l4, sel = 1;
+        if (l1 >= min0) best = l1;
+        if (l4 >= min1 && l4 > best) best = l4, sel = 1;
         if (lr >= far_min && lr > best) best = lr, sel = 2;
         c[j] = (uint16_t)(best | (sel << 9));
     }
@@ -566,7 +573,8 @@ __global__ __launch_bounds__(kThreads) void k_png_codes(PngPlan p, const uint32_
         const uint32_t eob = pos;
         const uint32_t total = eob + lens[256];
         const uint32_t dyn = bd.last ? (total + 7) / 8 : (total + 3 + 7) / 8 + 4;
-        const uint32_t sto = stored_bytes(bd.n);
+        // own streams: against the band's raw bytes, less the 6 bytes of zlib framing the host adds
+        const uint32_t sto = p.own_stream ? (bd.n > 6u ? bd.n - 6u : 0u) : stored_bytes(bd.n);
         const uint32_t mode = dyn < sto ? 0u : 1u;
         uint32_t s1 = 1, s2 = 0;  // Adler-32 of the band from the chunk sums
         for (uint32_t q = 0; q < nsub; ++q) {
@@ -577,7 +585,7 @@ __global__ __launch_bounds__(kThreads) void k_png_codes(PngPlan p, const uint32_
         }
         uint32_t* r = rec + 4 * (size_t)b;
         r[0] = mode;
-        r[1] = mode ? sto : dyn;
+        r[1] = mode ? (p.own_stream ? bd.n : sto) : dyn;
         r[2] = (s2 << 16) | s1;
         r[3] = bd.n;
         if (mode == 0) {  // block header, end of block and trailer; the tokens come from k_png_emit
@@ -624,6 +632,7 @@ __global__ __launch_bounds__(kThreads) void k_png_emit(const uint8_t* __restrict
     const uint8_t* f = filt + (size_t)b * p.band_pos;
     uint8_t* ob = out + (size_t)b * p.band_cap;
     if (rec[4 * (size_t)b] != 0u) {  // stored: pieces of at most 65,535 bytes behind 5-byte headers
+        if (p.own_stream) return;  // raw band: the front end's owner writes the unprocessed bytes (exr.hip)
         const uint32_t end = min(bd.n, t0 + kTile);
         for (uint32_t j = t0 + threadIdx.x; j < end; j += kThreads) {
             const uint32_t piece = j / 65535u;
@@ -709,6 +718,7 @@ __global__ __launch_bounds__(kThreads) void k_png_emit(const uint8_t* __restrict
 
 // ------------------------------------------------------------ gather ------
 // host: [uint64 length][8 B pad][78 01][deflate data]; tab: {Adler-32, raw bytes} per band.
+// Own streams: [uint64 length][8 B pad][the bands' pieces]; tab: rec (4 words) per band.
 __global__ __launch_bounds__(kThreads) void k_png_scan(PngPlan p, const uint32_t* __restrict__ rec,
                                                        uint32_t* __restrict__ prefix, uint8_t* __restrict__ host,
                                                        uint32_t* __restrict__ tab) {
@@ -720,12 +730,20 @@ __global__ __launch_bounds__(kThreads) void k_png_scan(PngPlan p, const uint32_t
         const uint32_t total = wg_scan(v, ws);
         if (b < p.nbands) {
             prefix[b] = base + v;
-            tab[2 * (size_t)b] = rec[4 * (size_t)b + 2];
-            tab[2 * (size_t)b + 1] = rec[4 * (size_t)b + 3];
+            if (p.own_stream) {
+                for (int k = 0; k < 4; ++k) tab[4 * (size_t)b + k] = rec[4 * (size_t)b + k];
+            } else {
+                tab[2 * (size_t)b] = rec[4 * (size_t)b + 2];
+                tab[2 * (size_t)b + 1] = rec[4 * (size_t)b + 3];
+            }
         }
         base += total;
     }
     if (threadIdx.x == 0) {
+        if (p.own_stream) {
+            *reinterpret_cast<uint64_t*>(host) = (uint64_t)base;
+            return;
+        }
         *reinterpret_cast<uint64_t*>(host) = (uint64_t)base + 2u;
         host[16] = 0x78;
         host[17] = 0x01;  // deflate, 32 KB window, no dictionary (as the host encoder)
@@ -738,7 +756,7 @@ __global__ __launch_bounds__(kThreads) void k_png_gather(PngPlan p, const uint32
     const int b = blockIdx.y;
     const uint32_t len = rec[4 * (size_t)b + 1];
     const uint8_t* src = out + (size_t)b * p.band_cap;  // 16-byte aligned
-    const size_t dst0 = 18 + (size_t)prefix[b];
+    const size_t dst0 = (p.own_stream ? 16 : 18) + (size_t)prefix[b];
     const uint32_t head = min(len, (uint32_t)((16u - (dst0 & 15u)) & 15u));  // bytes before the first aligned chunk
     const uint32_t q = blockIdx.x * kThreads + threadIdx.x;
     if (q == 0)
@@ -765,13 +783,11 @@ inline uint32_t host_stored_bytes(uint32_t n) { return n + 5u * ((n + 65534u) / 
 
 }  // namespace
 
-bool png_plan(int W, int H, PngPlan& p) {
-    // a band's bit offsets (at most 16 bits a byte) stay below 2^32
-    if (W <= 0 || H <= 0 || W > (1 << 20)) return false;
+bool deflate_plan(int W, int H, uint32_t stride, PngPlan& p) {
+    p = PngPlan{};
     p.W = W;
     p.H = H;
-    p.stride = 4u * (uint32_t)W + 1u;
-    p.row_dist = p.stride <= 32768u ? p.stride : 0u;
+    p.stride = stride;
     p.nbands = (H + kPngBandRows - 1) / kPngBandRows;
     p.band_full = p.stride * (uint32_t)std::min(H, kPngBandRows);
     p.band_pos = (p.band_full + kTile - 1) / kTile * kTile;
@@ -781,20 +797,23 @@ bool png_plan(int W, int H, PngPlan& p) {
     return (uint64_t)p.nbands * p.band_cap < (1ull << 31);  // band offsets in the stream are 32-bit
 }
 
+bool png_plan(int W, int H, PngPlan& p) {
+    // a band's bit offsets (at most 16 bits a byte) stay below 2^32
+    if (W <= 0 || H <= 0 || W > (1 << 20)) return false;
+    const bool ok = deflate_plan(W, H, 4u * (uint32_t)W + 1u, p);
+    p.dist[0] = 1u;
+    p.dist[1] = 4u;
+    p.dist[2] = p.stride <= 32768u ? p.stride : 0u;
+    return ok;
+}
+
 size_t png_stream_max_bytes(const PngPlan& p) {
     const uint32_t last = p.stride * (uint32_t)(p.H - (p.nbands - 1) * kPngBandRows);
     return 2 + (size_t)(p.nbands - 1) * host_stored_bytes(p.band_full) + host_stored_bytes(last) + 4;
 }
 
-namespace {
-struct PngCarve {
-    uint8_t *filt, *out;
-    uint16_t *cand, *exits, *entry;
-    uint32_t *adler_part, *subhist, *codes, *sub_off, *rec, *prefix;
-    size_t words;
-};
-PngCarve png_carve(const PngPlan& p, uint32_t* base) {
-    PngCarve c{};
+DeflateBufs deflate_carve(const PngPlan& p, uint32_t* base) {
+    DeflateBufs c{};
     size_t at = 0;  // in 32-bit words; every part starts 16-byte aligned
     auto take = [&](size_t bytes) {
         uint32_t* r = base ? base + at : nullptr;
@@ -816,16 +835,12 @@ PngCarve png_carve(const PngPlan& p, uint32_t* base) {
     c.words = at;
     return c;
 }
-}  // namespace
 
-size_t png_scratch_words(const PngPlan& p) { return png_carve(p, nullptr).words; }
+size_t png_scratch_words(const PngPlan& p) { return deflate_carve(p, nullptr).words; }
 
-void png_encode_device(const uint8_t* d_rgba, const PngPlan& p, uint32_t* scratch, uint8_t* host_out,
-                       uint32_t* host_tab, hipStream_t st) {
-    const PngCarve c = png_carve(p, scratch);
+void deflate_bands_device(const PngPlan& p, const DeflateBufs& c, hipStream_t st) {
     const dim3 subs(p.nsub, p.nbands), tiles(p.band_pos / kTile, p.nbands);
     RR_HIP(hipMemsetAsync(c.out, 0, (size_t)p.nbands * p.band_cap, st));
-    k_png_filter<<<subs, kThreads, 0, st>>>(d_rgba, p, c.filt, c.adler_part);
     k_png_match<<<subs, kThreads, 0, st>>>(c.filt, p, c.cand);
     k_png_exits<<<tiles, kThreads, 0, st>>>(c.cand, p, c.exits);
     k_png_entries<<<p.nbands, 64, 0, st>>>(c.exits, p, c.entry);
@@ -833,10 +848,23 @@ void png_encode_device(const uint8_t* d_rgba, const PngPlan& p, uint32_t* scratc
     k_png_codes<<<p.nbands, kThreads, 0, st>>>(p, c.subhist, c.adler_part, c.codes, c.sub_off, c.rec,
                                                reinterpret_cast<uint32_t*>(c.out));
     k_png_emit<<<tiles, kThreads, 0, st>>>(c.filt, p, c.cand, c.codes, c.sub_off, c.rec, c.out);
+    RR_HIP(hipGetLastError());
+}
+
+void deflate_gather_device(const PngPlan& p, const DeflateBufs& c, uint8_t* host_out, uint32_t* host_tab,
+                           hipStream_t st) {
     k_png_scan<<<1, kThreads, 0, st>>>(p, c.rec, c.prefix, host_out, host_tab);
     k_png_gather<<<dim3((p.band_cap / 16 + 1 + kThreads - 1) / kThreads, p.nbands), kThreads, 0, st>>>(
         p, c.rec, c.prefix, c.out, host_out);
     RR_HIP(hipGetLastError());
+}
+
+void png_encode_device(const uint8_t* d_rgba, const PngPlan& p, uint32_t* scratch, uint8_t* host_out,
+                       uint32_t* host_tab, hipStream_t st) {
+    const DeflateBufs c = deflate_carve(p, scratch);
+    k_png_filter<<<dim3(p.nsub, p.nbands), kThreads, 0, st>>>(d_rgba, p, c.filt, c.adler_part);
+    deflate_bands_device(p, c, st);
+    deflate_gather_device(p, c, host_out, host_tab, st);
 }
 
 }  // namespace rr

@@ -92,7 +92,7 @@ struct FrameSlot {
     uint64_t ticket = 0;
     // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
     // work done, 3 outputs on the host (after their copies), 5 (device PNG
-    // frames) before the PNG coder: the state shared between frames is free
+    // and EXR frames) before the deflate coder: the state shared between frames is free
     hipEvent_t ev[6] = {};
     DevBuf<int32_t> counters;  // this frame's ray counters (swapped into DevPaths while enqueuing)
     // this frame's device outputs (swapped into DevPaths / rr_ctx while enqueuing):
@@ -107,6 +107,9 @@ struct FrameSlot {
     PinnedBuf host_png;    // device-coded zlib stream of a PNG frame, same layout (png.hip)
     PinnedBuf host_png_tab;  // its bands' {Adler-32, filtered bytes}
     PngPlan png_plan{};
+    PinnedBuf host_exr;      // device-coded chunks of an OPEN_EXR frame: [uint64 length][pad][pieces] (exr.hip)
+    PinnedBuf host_exr_tab;  // its chunks' {mode, bytes, Adler-32, chunk bytes}
+    PngPlan exr_plan{};
     FrameSetup fs;
     bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
     std::string view_warning;
@@ -116,6 +119,7 @@ struct FrameSlot {
     std::string out_path, format;
     int quality = 0;
     bool jpeg = false, png = false, want_rgba = false, count = false;  // png: coded on the device (rr_set_device_png)
+    bool exr = false;  // an OPEN_EXR frame: the film coded on the device (exr.hip)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log into trav_counts (rr_debug_tile_costs)
     float* film_out = nullptr;
     FrameRun r{};
@@ -532,6 +536,43 @@ bool write_device_png(const FrameSlot& sl, const std::string& path, uint64_t* by
     return write_file(path, data);
 }
 
+// Device OpenEXR encode of a film of sums (exr.hip) into the slot's pinned
+// chunk buffer and chunk table, on the context stream. The scratch is the
+// deflate coder's (a frame has one format).
+void enqueue_exr_device(rr_ctx* c, FrameSlot& sl, const float4* d_film, float inv_spp, bool alpha_one, int W, int H) {
+    PngPlan p;
+    if (!exr_plan(W, H, p)) throw std::runtime_error("image size outside the device EXR encoder's range");
+    sl.exr_plan = p;
+    c->png_scratch.ensure(png_scratch_words(p));
+    sl.host_exr.ensure(exr_stream_max_bytes(p) + 32);
+    sl.host_exr_tab.ensure((size_t)p.nbands * 4 * sizeof(uint32_t));
+    void *dev_host = nullptr, *dev_tab = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_exr.ptr, 0));
+    RR_HIP(hipHostGetDevicePointer(&dev_tab, sl.host_exr_tab.ptr, 0));
+    c->paths.prof.begin(c->stream, RR_K_PNG);
+    exr_encode_device(d_film, inv_spp, alpha_one, p, c->png_scratch.ptr, static_cast<uint8_t*>(dev_host),
+                      static_cast<uint32_t*>(dev_tab), c->stream);
+    c->paths.prof.end(c->stream);
+}
+
+// The bytes of a device-coded EXR frame: host-built header and offset table around the device chunks.
+void device_exr_bytes(const FrameSlot& sl, std::vector<uint8_t>& data) {
+    uint64_t len = 0;
+    std::memcpy(&len, sl.host_exr.ptr, sizeof len);
+    if (len + 16 > sl.host_exr.cap) throw std::runtime_error("device EXR stream overflow");
+    const PngPlan& p = sl.exr_plan;
+    if (!exr_wrap_stream(p.W, p.H, sl.host_exr.ptr + 16, (size_t)len,
+                         reinterpret_cast<const uint32_t*>(sl.host_exr_tab.ptr), p.nbands, data))
+        throw std::runtime_error("device EXR chunk table does not match its stream");
+}
+
+bool write_device_exr(const FrameSlot& sl, const std::string& path, uint64_t* bytes) {
+    std::vector<uint8_t> data;
+    device_exr_bytes(sl, data);
+    *bytes = data.size();
+    return write_file(path, data);
+}
+
 // Enqueue the device part of one frame on the context stream (no host
 // synchronisation): LBVH (if needed), wavefront, tonemap, optionally the JPEG
 // transform, and the asynchronous copies of the slot's outputs.
@@ -586,10 +627,10 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     SlotSwap slot_swap(c, sl);
     hipStream_t st = c->stream;
     FrameSlot* prev = c->last_enqueued;
-    // (the device PNG coder reads its slot's rgba8 and writes slot buffers
-    // only, so the next frame waits for the image, not for the coder)
+    // (the device PNG / EXR coder reads its slot's rgba8 / film and writes slot
+    // buffers only, so the next frame waits for the image, not for the coder)
     if (prev && prev != &sl && !(sl.tiles && prev->tiles))
-        RR_HIP(hipStreamWaitEvent(st, prev->png ? prev->ev[5] : prev->ev[2], 0));
+        RR_HIP(hipStreamWaitEvent(st, (prev->png || prev->exr) ? prev->ev[5] : prev->ev[2], 0));
     c->last_enqueued = &sl;
     // a k_tiles frame enqueued while another k_tiles frame is pending overlaps
     // it: whole-tile work units (render_frame_device); a frame rendered alone
@@ -665,6 +706,10 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     if (sl.png) {
         RR_HIP(hipEventRecord(sl.ev[5], st));
         enqueue_png_device(c, sl, c->paths.rgba8.ptr, fs.W, fs.H);
+    }
+    if (sl.exr) {  // the film's means: the product finish_frame forms, no view transform
+        RR_HIP(hipEventRecord(sl.ev[5], st));
+        enqueue_exr_device(c, sl, c->paths.film.ptr, 1.0f / (float)fs.spp, true, fs.W, fs.H);
     }
     RR_HIP(hipEventRecord(sl.ev[2], st));
     // the outputs' device-to-host copies follow on the slot's own stream: the
@@ -979,9 +1024,11 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
     if (!c || !s || !ticket) return fail(RR_EINVAL, "NULL ctx, scene or ticket");
     if (s->ctx && s->ctx != c) return fail(RR_EINVAL, "scene belongs to another context");
     if (out_path && !format) return fail(RR_EINVAL, "format is required when out_path is given");
-    if (format && std::string(format) != "JPEG" && std::string(format) != "PNG")
+    if (format && std::string(format) != "JPEG" && std::string(format) != "PNG" &&
+        std::string(format) != "OPEN_EXR")
         return fail(RR_ENOTSUP, std::string("unsupported output format '") + format + "'");
     const bool jpeg = out_path && std::string(format) == "JPEG";
+    const bool exr = out_path && std::string(format) == "OPEN_EXR";
     if (jpeg && (jpeg_quality < 1 || jpeg_quality > 100)) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
     FrameSlot* sl = slot_for(c, c->next_ticket);
     if (sl->busy) return fail(RR_EBUSY, "too many frames in flight (complete the oldest first)");
@@ -1000,8 +1047,14 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->format = (out_path && format) ? format : "";
         sl->quality = jpeg_quality;
         sl->jpeg = jpeg;
-        sl->png = out_path && !jpeg && c->device_png;  // format is "PNG"
-        sl->want_rgba = out_path && !jpeg && !sl->png;
+        sl->exr = exr;
+        sl->png = out_path && !jpeg && !exr && c->device_png;  // format is "PNG"
+        sl->want_rgba = out_path && !jpeg && !exr && !sl->png;
+        if (exr) {  // refused, never rerouted
+            PngPlan plan;
+            if (!exr_plan(sl->fs.W, sl->fs.H, plan))
+                return fail(RR_EINVAL, "image size outside the device EXR encoder's range");
+        }
         sl->film_out = nullptr;
         sl->anchor = idle(c);
         sl->submit_at = unix_now();
@@ -1066,6 +1119,10 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
             const std::string path = sl->out_path + ".png";
             if (!write_device_png(*sl, path, &bytes))
                 return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
+        } else if (sl->exr) {  // header and offset table + the device-coded chunks
+            const std::string path = sl->out_path + ".exr";
+            if (!write_device_exr(*sl, path, &bytes))
+                return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
         } else if (!sl->out_path.empty()) {
             const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), sl->format.c_str(),
                                     sl->quality, &bytes);
@@ -1124,6 +1181,7 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         sl->format.clear();
         sl->jpeg = false;
         sl->png = false;
+        sl->exr = false;
         sl->want_rgba = true;
         sl->film_out = film;
         sl->ticket = c->next_ticket;
@@ -1211,6 +1269,29 @@ int rr_debug_png_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, u
         img.release();
         std::vector<uint8_t> data;
         device_png_bytes(sl, data);
+        *len = data.size();
+        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
+        return RR_OK;
+    });
+}
+
+int rr_debug_exr_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
+                        uint64_t* len) {
+    if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    PngPlan plan;
+    if (!exr_plan(w, h, plan)) return fail(RR_EINVAL, "image size outside the device EXR encoder's range");
+    return guarded([&] {
+        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
+        set_device(c);
+        DevBuf<float4> img;
+        img.ensure((size_t)w * h);
+        RR_HIP(hipMemcpy(img.ptr, rgba, (size_t)w * h * sizeof(float4), hipMemcpyHostToDevice));
+        FrameSlot& sl = c->slots[0];
+        enqueue_exr_device(c, sl, img.ptr, 1.0f, false, w, h);
+        RR_HIP(hipStreamSynchronize(c->stream));
+        img.release();
+        std::vector<uint8_t> data;
+        device_exr_bytes(sl, data);
         *len = data.size();
         if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
         return RR_OK;

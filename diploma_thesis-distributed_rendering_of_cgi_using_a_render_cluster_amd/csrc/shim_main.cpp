@@ -149,7 +149,7 @@ int main(int argc, char** argv) {
         rr_destroy(ctx);
         return 1;
     }
-    const std::string ext = fmt == "PNG" ? ".png" : ".jpg";
+    const std::string ext = fmt == "PNG" ? ".png" : fmt == "OPEN_EXR" ? ".exr" : ".jpg";
     std::printf("Fra:%ld Mem:0M | Rendered %d x %d, %d spp, %.3f ms device\n", frame, st.width, st.height, st.spp,
                 st.build_ms + st.trace_ms);
     std::printf("Saved: '%s%s'\n", out_path.c_str(), ext.c_str());

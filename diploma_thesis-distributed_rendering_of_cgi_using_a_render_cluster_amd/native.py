@@ -75,7 +75,7 @@ class FrameStats(ctypes.Structure):
 
 RR_FLAG_PROFILE_KERNELS, RR_FLAG_COUNT_TRAVERSAL, RR_FLAG_WAVEFRONT = 1, 2, 4
 KERNEL_CLASSES = ["build", "primary", "extend", "shadow", "accumulate", "shade", "tiles"]
-RR_K_PNG = 7  # FrameStats.kernel_ms index of the device PNG encoder (rr_set_device_png)
+RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, or OPEN_EXR)
 
 
 # Every symbol include/rr.h declares (checked by tests/test_abi.py).
@@ -87,7 +87,7 @@ EXPORTS = [
     "rr_scene_free", "rr_destroy", "rr_debug_counts", "rr_debug_scene_mesh", "rr_debug_frame_state", "rr_debug_bvh",
     "rr_debug_trace", "rr_debug_object_matrix", "rr_debug_qbvh", "rr_debug_bvh_hier", "rr_debug_jpeg_device",
     "rr_debug_bsdf_sample", "rr_debug_fastmath_check", "rr_debug_tile_costs",
-    "rr_set_device_png", "rr_debug_png_device",
+    "rr_set_device_png", "rr_debug_png_device", "rr_debug_exr_device",
 ]
 
 _lib = None
@@ -143,6 +143,7 @@ def lib() -> ctypes.CDLL:
                                          ctypes.POINTER(ctypes.c_uint64)]),
         "rr_set_device_png": (c_int, [P, i32]),
         "rr_debug_png_device": (c_int, [P, u8p, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_debug_exr_device": (c_int, [P, f32p, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -417,6 +418,19 @@ class RenderContext:
                                          _ptr(out, ctypes.c_uint8), out.size, ctypes.byref(n)), self.handle)
         if n.value > out.size:
             raise RRError(RR_EINVAL, f"device PNG of {n.value} bytes exceeds the {out.size}-byte buffer")
+        return out[:n.value].tobytes()
+
+    def exr_device(self, rgba: np.ndarray) -> bytes:
+        """rr_debug_exr_device: the OpenEXR file bytes (half A, B, G, R; ZIP) of an
+        (H, W, 4) float32 image of means, encoded on the device (exr.hip)."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+        h, w = rgba.shape[:2]
+        out = np.zeros(8 * w * h + 16 * ((h + 15) // 16) + 1024, np.uint8)  # above the all-raw worst case
+        n = ctypes.c_uint64()
+        _check(lib().rr_debug_exr_device(self.handle, _ptr(rgba, ctypes.c_float), w, h,
+                                         _ptr(out, ctypes.c_uint8), out.size, ctypes.byref(n)), self.handle)
+        if n.value > out.size:
+            raise RRError(RR_EINVAL, f"device EXR of {n.value} bytes exceeds the {out.size}-byte buffer")
         return out[:n.value].tobytes()
 
     def bsdf_sample(self, mat12, n, wo, u):

@@ -43,7 +43,8 @@ class BackendRunner:
                  device: int = 0, params: RenderParams | None = None, ctx=None, device_png: bool = False):
         """ctx: a RenderContext on `device` is created here; tests of the host
         logic alone pass a stand-in with the same methods (no rendering).
-        device_png: "PNG" jobs are coded on the device (rr_set_device_png)."""
+        device_png: "PNG" jobs are coded on the device (rr_set_device_png).
+        "OPEN_EXR" jobs (half-float ZIP files of the linear film) always are."""
         base = Path(base_directory_path)
         if not base.is_dir():
             raise RenderError("Provided base directory path is not a directory.")

@@ -89,7 +89,7 @@ typedef struct rr_render_params {
 #define RR_K_ACCUM 4     /* film accumulate + tonemap */
 #define RR_K_SHADE 5     /* split path (large scenes): shading kernels; PRIMARY/EXTEND then time traversal only */
 #define RR_K_TILES 6     /* LDS-resident scenes: k_tiles, every sample of an 8x8 pixel tile run to completion + film + tonemap */
-#define RR_K_PNG 7       /* device PNG encoder (rr_set_device_png): all its kernels, one event pair per frame */
+#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, or OPEN_EXR): all its kernels, one event pair per frame */
 #define RR_K_CLASSES 8
 
 /* The five timestamps the reference recovers from Blender's stdout
@@ -119,8 +119,8 @@ typedef struct rr_frame_stats {
     double anim_ms;          /* host animation eval + upload */
     double build_ms;         /* device: world transform + LBVH build (0 if cached) */
     double trace_ms;         /* device: wavefront kernels (raygen .. accumulate) */
-    double readback_ms;      /* device->host of the 8-bit image (device JPEG / PNG: the coder + its stream) */
-    double encode_ms;        /* host: JPEG/PNG encode + write */
+    double readback_ms;      /* device->host of the 8-bit image (device JPEG / PNG / EXR: the coder + its stream) */
+    double encode_ms;        /* host: JPEG/PNG encode (EXR: container) + write */
     double total_ms;         /* whole call */
     int32_t bvh_rebuilt;     /* 1 if the LBVH was rebuilt for this frame */
     int32_t n_triangles;
@@ -195,9 +195,17 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *  - frame_index: the frame to evaluate (Blender frame number, scene.frame_set).
  *  - out_path: output path WITHOUT extension, '#' runs already substituted
  *    (render-timing-script.py:69-78,82); the library appends ".jpg" / ".png"
- *    as Blender's write_still does with R_EXTENSION. NULL: render only.
- *  - format: "JPEG" or "PNG" (job output_file_format, shared/src/jobs/mod.rs:80).
- *  - jpeg_quality: 1..100 (the reference script forces 90, :84).
+ *    / ".exr" as Blender's write_still does with R_EXTENSION. NULL: render only.
+ *  - format: "JPEG", "PNG" or "OPEN_EXR" (job output_file_format,
+ *    shared/src/jobs/mod.rs:80, handed to image_settings.file_format,
+ *    render-timing-script.py:83-92). "OPEN_EXR": the film's mean linear
+ *    radiance before any view transform (alpha = 1) as half-float A, B, G, R
+ *    channels, ZIP compression in chunks of 16 scanlines, single-part scanline
+ *    file; halfs are the means clamped to +-65504 and rounded to nearest even.
+ *    Coded on the GPU (exr.hip); there is no host EXR encoder. RR_EINVAL for a
+ *    width above 2^19 or a frame of 2 GB and more.
+ *  - jpeg_quality: 1..100 (the reference script forces 90, :84); ignored for
+ *    "PNG" and "OPEN_EXR".
  *  - timing / stats: optional outputs (may be NULL). */
 int rr_render_frame(rr_ctx* ctx, rr_scene* scene, int32_t frame_index,
                     const rr_render_params* params, const char* out_path,
@@ -243,7 +251,8 @@ int rr_scene_resolution(rr_scene* scene, const rr_render_params* params,
                         int32_t* width, int32_t* height);
 
 /* Encode an RGBA8 image (rows top to bottom) to `path` + extension.
- * Host encoder used by rr_render_frame; exported for tests. */
+ * Host encoder used by rr_render_frame; exported for tests. "JPEG" and "PNG"
+ * only: "OPEN_EXR" needs the float film and is RR_ENOTSUP here. */
 int rr_encode_image(const uint8_t* rgba8, int32_t width, int32_t height,
                     const char* out_path_no_ext, const char* format,
                     int32_t jpeg_quality, uint64_t* bytes_written);
@@ -271,6 +280,14 @@ int rr_set_device_png(rr_ctx* ctx, int32_t on);
  * *len receives the file size; the bytes are copied to out if cap >= *len.
  * Exported for round-trip tests. */
 int rr_debug_png_device(rr_ctx* ctx, const uint8_t* rgba8, int32_t width, int32_t height,
+                        uint8_t* out, uint64_t cap, uint64_t* len);
+
+/* Encode a float RGBA image (rows top to bottom, width * height * 4 floats,
+ * taken as means: spp = 1, alpha from the image) with the device OpenEXR path
+ * (the one "OPEN_EXR" frames take; write_still, render-timing-script.py:83-92).
+ * *len receives the file size; the bytes are copied to out if cap >= *len.
+ * Exported for round-trip tests. */
+int rr_debug_exr_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
                         uint8_t* out, uint64_t cap, uint64_t* len);
 
 /* Thread-local message of the last failure on this thread (ctx may be NULL). */
