@@ -328,6 +328,31 @@ size_t exr_stream_max_bytes(const PngPlan& p);  // every chunk raw
 void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const PngPlan& p, uint32_t* scratch,
                        uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
+// The Filmic LUTs of one device as kernel arguments (view.hpp FilmicDev::args).
+struct FilmicArgs {
+    const float4* cube;
+    const float* lut1;
+    int n3, n1, comps;
+    float lo1, hi1;
+};
+
+// Device 16-bit PNG encode (png16.hip): the film's display-referred image as
+// RGBA with 16-bit big-endian samples, A = 65535. Front end (mean, exposure,
+// clamp, view transform, quantize16, Sub filter over 8-byte pixels, Adler
+// sums) + the deflate stages above as one zlib stream; host_out and host_tab
+// as png_encode_device writes them (image_io png16_wrap_stream).
+// false: W > 2^19 (band positions in 32-bit counters), or a stream of 2 GB and more.
+bool png16_plan(int W, int H, PngPlan& p);
+struct Png16Front {
+    const float4* film;  // W x H sums
+    float inv_spp, exposure_scale;
+    int view_transform;  // RR_VIEW_STANDARD / RAW / FILMIC (FILMIC: `filmic` holds the LUTs)
+    const float* srgb16;  // kSrgb16LutSize + 2 floats (scene.hpp build_srgb16_lut)
+    FilmicArgs filmic;
+};
+void png16_encode_device(const Png16Front& f, const PngPlan& p, uint32_t* scratch, uint8_t* host_out,
+                         uint32_t* host_tab, hipStream_t st);
+
 // Per chunk: one pair per bounce b = 0..max_bounces {paths entering b+1,
 // shadow rays of b}, one pair of slack, then the words below.
 int counters_per_chunk(int max_bounces);

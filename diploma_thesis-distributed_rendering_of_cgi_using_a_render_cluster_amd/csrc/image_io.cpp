@@ -483,7 +483,7 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
 }
 
 void png_wrap_stream(int W, int H, const uint8_t* zs, size_t n, const uint32_t* band_tab, int nbands,
-                     std::vector<uint8_t>& out) {
+                     std::vector<uint8_t>& out, int depth) {
     uLong a = adler32(0L, Z_NULL, 0);
     for (int b = 0; b < nbands; ++b) a = adler32_combine(a, band_tab[2 * b], (z_off_t)band_tab[2 * b + 1]);
     std::vector<uint8_t> z(zs, zs + n);
@@ -494,7 +494,7 @@ void png_wrap_stream(int W, int H, const uint8_t* zs, size_t n, const uint32_t* 
     out.insert(out.end(), sig, sig + 8);
     uint8_t ihdr[13] = {(uint8_t)(W >> 24), (uint8_t)(W >> 16), (uint8_t)(W >> 8), (uint8_t)W,
                         (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H,
-                        8, 6, 0, 0, 0};
+                        (uint8_t)depth, 6, 0, 0, 0};
     png_chunk(out, "IHDR", ihdr, 13);
     png_chunk(out, "IDAT", z.data(), z.size());
     png_chunk(out, "IEND", nullptr, 0);

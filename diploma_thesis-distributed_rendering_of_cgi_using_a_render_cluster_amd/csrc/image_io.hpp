@@ -32,8 +32,10 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
 // The PNG file around a zlib stream coded on the device (png.hip): z = 78 01 +
 // the bands' deflate pieces; band_tab = {Adler-32, filtered bytes} per band,
 // combined here into the stream's Adler-32. Signature, IHDR, one IDAT, IEND.
+// depth: bits per sample of the RGBA image the stream holds, 8 (png.hip) or 16
+// (png16.hip: big-endian samples, rows of 8W + 1 filtered bytes).
 void png_wrap_stream(int W, int H, const uint8_t* z, size_t n, const uint32_t* band_tab, int nbands,
-                     std::vector<uint8_t>& out);
+                     std::vector<uint8_t>& out, int depth = 8);
 // The OpenEXR file (single-part scanline, version 2; half A, B, G, R; ZIP,
 // chunks of 16 scanlines) around chunks coded on the device (exr.hip): data =
 // the chunks' pieces back to back, chunk_tab = {mode, bytes, Adler-32, chunk

@@ -40,7 +40,8 @@
 // row, three candidate distances, own_stream), not PNG's geometry, and also
 // run behind exr.hip's front end (deflate_bands_device, deflate_gather_device):
 // there every band is a final stream of its own, and a band that would not
-// shrink is left to that front end's owner to write raw.
+// shrink is left to that front end's owner to write raw. png16.hip's front end
+// (16-bit samples, rows of 8W + 1 bytes) keeps this file's one-stream scheme.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

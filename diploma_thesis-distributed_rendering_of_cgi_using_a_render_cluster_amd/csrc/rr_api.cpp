@@ -120,6 +120,10 @@ struct FrameSlot {
     int quality = 0;
     bool jpeg = false, png = false, want_rgba = false, count = false;  // png: coded on the device (rr_set_device_png)
     bool exr = false;  // an OPEN_EXR frame: the film coded on the device (exr.hip)
+    // a "PNG" frame of 16 bits per sample: the film coded on the device (png16.hip)
+    // into host_png / host_png_tab; png is false
+    bool png16 = false;
+    int png_bits = 8;  // of the stream in host_png
     bool unit_logged = false;  // its k_tiles launch wrote the unit log into trav_counts (rr_debug_tile_costs)
     float* film_out = nullptr;
     FrameRun r{};
@@ -184,6 +188,9 @@ struct rr_ctx {
     // device PNG encoder (png.hip): on for "PNG" frames (rr_set_device_png / RR_DEVICE_PNG), its scratch
     bool device_png = false;
     DevBuf<uint32_t> png_scratch;
+    // bit depth of "PNG" frames (rr_set_png_depth / RR_PNG_DEPTH): 0 the scene's, 8, 16
+    int png_depth = 0;
+    DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
     std::vector<float> filter_cache;
     float filter_width_cached = -1.f;
     bool srgb_uploaded = false;
@@ -507,6 +514,7 @@ void enqueue_png_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W, 
     PngPlan p;
     if (!png_plan(W, H, p)) throw std::runtime_error("image size outside the device PNG encoder's range");
     sl.png_plan = p;
+    sl.png_bits = 8;
     c->png_scratch.ensure(png_scratch_words(p));
     sl.host_png.ensure(png_stream_max_bytes(p) + 32);
     sl.host_png_tab.ensure((size_t)p.nbands * 2 * sizeof(uint32_t));
@@ -526,7 +534,7 @@ void device_png_bytes(const FrameSlot& sl, std::vector<uint8_t>& data) {
     if (len + 16 + 4 > sl.host_png.cap) throw std::runtime_error("device PNG stream overflow");
     const PngPlan& p = sl.png_plan;
     png_wrap_stream(p.W, p.H, sl.host_png.ptr + 16, (size_t)len, reinterpret_cast<const uint32_t*>(sl.host_png_tab.ptr),
-                    p.nbands, data);
+                    p.nbands, data, sl.png_bits);
 }
 
 bool write_device_png(const FrameSlot& sl, const std::string& path, uint64_t* bytes) {
@@ -534,6 +542,43 @@ bool write_device_png(const FrameSlot& sl, const std::string& path, uint64_t* by
     device_png_bytes(sl, data);
     *bytes = data.size();
     return write_file(path, data);
+}
+
+// The 16-bit path's sRGB table on the device. Written once, before the first
+// kernel that reads it is enqueued, and never again.
+static_assert(kSrgb16LutSize == kSrgb16N, "host table and device read agree on the interval count");
+void ensure_srgb16(rr_ctx* c) {
+    if (c->srgb16_lut.ptr) return;
+    std::vector<float> lut(kSrgb16LutSize + 2);
+    build_srgb16_lut(lut.data());
+    c->srgb16_lut.ensure(lut.size());
+    RR_HIP(hipMemcpy(c->srgb16_lut.ptr, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
+}
+
+// Device 16-bit PNG encode of a film of sums (png16.hip) into the slot's pinned
+// PNG stream buffer and band table, on the context stream. view_transform is
+// the resolved one (Filmic only with the context's LUTs). The scratch is the
+// deflate coder's (a frame has one format).
+void enqueue_png16_device(rr_ctx* c, FrameSlot& sl, const float4* d_film, float inv_spp, float exposure_scale,
+                          int view_transform, int W, int H) {
+    PngPlan p;
+    if (!png16_plan(W, H, p)) throw std::runtime_error("image size outside the device 16-bit PNG encoder's range");
+    if (view_transform == VIEW_FILMIC && !c->filmic.ready) throw std::runtime_error("Filmic view transform without LUTs");
+    ensure_srgb16(c);
+    sl.png_plan = p;
+    sl.png_bits = 16;
+    c->png_scratch.ensure(png_scratch_words(p));
+    sl.host_png.ensure(png_stream_max_bytes(p) + 32);
+    sl.host_png_tab.ensure((size_t)p.nbands * 2 * sizeof(uint32_t));
+    void *dev_host = nullptr, *dev_tab = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_png.ptr, 0));
+    RR_HIP(hipHostGetDevicePointer(&dev_tab, sl.host_png_tab.ptr, 0));
+    const Png16Front f{d_film, inv_spp, exposure_scale, view_transform, c->srgb16_lut.ptr,
+                       view_transform == VIEW_FILMIC ? c->filmic.args() : FilmicArgs{}};
+    c->paths.prof.begin(c->stream, RR_K_PNG);
+    png16_encode_device(f, p, c->png_scratch.ptr, static_cast<uint8_t*>(dev_host), static_cast<uint32_t*>(dev_tab),
+                        c->stream);
+    c->paths.prof.end(c->stream);
 }
 
 // Device OpenEXR encode of a film of sums (exr.hip) into the slot's pinned
@@ -630,7 +675,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     // (the device PNG / EXR coder reads its slot's rgba8 / film and writes slot
     // buffers only, so the next frame waits for the image, not for the coder)
     if (prev && prev != &sl && !(sl.tiles && prev->tiles))
-        RR_HIP(hipStreamWaitEvent(st, (prev->png || prev->exr) ? prev->ev[5] : prev->ev[2], 0));
+        RR_HIP(hipStreamWaitEvent(st, (prev->png || prev->exr || prev->png16) ? prev->ev[5] : prev->ev[2], 0));
     c->last_enqueued = &sl;
     // a k_tiles frame enqueued while another k_tiles frame is pending overlaps
     // it: whole-tile work units (render_frame_device); a frame rendered alone
@@ -710,6 +755,10 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     if (sl.exr) {  // the film's means: the product finish_frame forms, no view transform
         RR_HIP(hipEventRecord(sl.ev[5], st));
         enqueue_exr_device(c, sl, c->paths.film.ptr, 1.0f / (float)fs.spp, true, fs.W, fs.H);
+    }
+    if (sl.png16) {  // the film again, through exposure and view transform, at 16 bits
+        RR_HIP(hipEventRecord(sl.ev[5], st));
+        enqueue_png16_device(c, sl, c->paths.film.ptr, k.inv_spp, k.exposure_scale, fs.view_transform, fs.W, fs.H);
     }
     RR_HIP(hipEventRecord(sl.ev[2], st));
     // the outputs' device-to-host copies follow on the slot's own stream: the
@@ -905,6 +954,13 @@ int rr_create(int device_ordinal, rr_ctx** out) {
         if (device_ordinal < 0 || device_ordinal >= n)
             return fail(RR_ENODEV, "device ordinal " + std::to_string(device_ordinal) + " out of range (" +
                                        std::to_string(n) + " visible)");
+        int png_depth = 0;
+        if (const char* d = getenv("RR_PNG_DEPTH")) {  // as rr_set_png_depth
+            const std::string v(d);
+            if (v == "8") png_depth = 8;
+            else if (v == "16") png_depth = 16;
+            else if (!v.empty() && v != "0") return fail(RR_EINVAL, "RR_PNG_DEPTH must be 0, 8 or 16, got '" + v + "'");
+        }
         std::unique_ptr<rr_ctx> c(new rr_ctx());
         c->device = device_ordinal;
         set_device(c.get());
@@ -926,6 +982,7 @@ int rr_create(int device_ordinal, rr_ctx** out) {
             else if (*d) c->ctx_warning = "RR_OCIO_DIR: " + err;
         }
         if (const char* d = getenv("RR_DEVICE_PNG")) c->device_png = std::string(d) == "1";
+        c->png_depth = png_depth;
         *out = c.release();
         return RR_OK;
     });
@@ -945,6 +1002,7 @@ void rr_destroy(rr_ctx* c) {
     c->jpeg_scratch.release();
     c->jpeg_blk.release();
     c->png_scratch.release();
+    c->srgb16_lut.release();
     for (auto& sl : c->slots) {
         for (auto& e : sl.ev)
             if (e) (void)hipEventDestroy(e);
@@ -1048,8 +1106,18 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->quality = jpeg_quality;
         sl->jpeg = jpeg;
         sl->exr = exr;
-        sl->png = out_path && !jpeg && !exr && c->device_png;  // format is "PNG"
-        sl->want_rgba = out_path && !jpeg && !exr && !sl->png;
+        const bool png = out_path && !jpeg && !exr;  // format is "PNG"
+        // 16 bits per sample: always the device coder (there is no host one)
+        sl->png16 = png && (c->png_depth ? c->png_depth : s->desc.render.color_depth) == 16;
+        sl->png = png && !sl->png16 && c->device_png;
+        sl->want_rgba = png && !sl->png16 && !sl->png;
+        if (sl->png16) {  // refused, never rerouted
+            PngPlan plan;
+            if (!png16_plan(sl->fs.W, sl->fs.H, plan))
+                return fail(RR_EINVAL, "image size outside the device 16-bit PNG encoder's range");
+            set_device(c);
+            ensure_srgb16(c);
+        }
         if (exr) {  // refused, never rerouted
             PngPlan plan;
             if (!exr_plan(sl->fs.W, sl->fs.H, plan))
@@ -1115,7 +1183,7 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
             const std::string path = sl->out_path + ".jpg";
             if (!write_device_jpeg(*sl, path, &bytes))
                 return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
-        } else if (sl->png) {  // PNG chunks + the device-coded zlib stream
+        } else if (sl->png || sl->png16) {  // PNG chunks + the device-coded zlib stream
             const std::string path = sl->out_path + ".png";
             if (!write_device_png(*sl, path, &bytes))
                 return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
@@ -1181,6 +1249,7 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         sl->format.clear();
         sl->jpeg = false;
         sl->png = false;
+        sl->png16 = false;
         sl->exr = false;
         sl->want_rgba = true;
         sl->film_out = film;
@@ -1296,6 +1365,51 @@ int rr_debug_exr_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint
         if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
         return RR_OK;
     });
+}
+
+int rr_set_png_depth(rr_ctx* c, int32_t depth) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    if (depth != 0 && depth != 8 && depth != 16) return fail(RR_EINVAL, "PNG depth must be 0 (the scene's), 8 or 16");
+    c->png_depth = depth;  // read when a frame is submitted; frames in flight keep their choice
+    return RR_OK;
+}
+
+int rr_debug_png16_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int32_t view_transform,
+                          float exposure_scale, uint8_t* out, uint64_t cap, uint64_t* len) {
+    if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    if (view_transform != VIEW_STANDARD && view_transform != VIEW_RAW && view_transform != VIEW_FILMIC)
+        return fail(RR_EINVAL, "unsupported view transform");
+    if (view_transform == VIEW_FILMIC && !c->filmic.ready)
+        return fail(RR_EINVAL, "Filmic view transform without LUTs (rr_set_ocio_config / RR_OCIO_DIR)");
+    PngPlan plan;
+    if (!png16_plan(w, h, plan)) return fail(RR_EINVAL, "image size outside the device 16-bit PNG encoder's range");
+    return guarded([&] {
+        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
+        set_device(c);
+        DevBuf<float4> img;
+        img.ensure((size_t)w * h);
+        RR_HIP(hipMemcpy(img.ptr, rgba, (size_t)w * h * sizeof(float4), hipMemcpyHostToDevice));
+        FrameSlot& sl = c->slots[0];
+        enqueue_png16_device(c, sl, img.ptr, 1.0f, exposure_scale, view_transform, w, h);
+        RR_HIP(hipStreamSynchronize(c->stream));
+        img.release();
+        std::vector<uint8_t> data;
+        device_png_bytes(sl, data);
+        *len = data.size();
+        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
+        return RR_OK;
+    });
+}
+
+int rr_debug_srgb16_table(float* table, int32_t cap, int32_t* n) {
+    if (!n) return fail(RR_EINVAL, "n is NULL");
+    *n = kSrgb16LutSize + 1;
+    if (table && cap >= *n) {
+        std::vector<float> lut(kSrgb16LutSize + 2);
+        build_srgb16_lut(lut.data());
+        std::memcpy(table, lut.data(), (size_t)*n * sizeof(float));
+    }
+    return RR_OK;
 }
 
 int rr_debug_scene_mesh(rr_scene* s, float* tri_local9, int32_t* tri_object) {

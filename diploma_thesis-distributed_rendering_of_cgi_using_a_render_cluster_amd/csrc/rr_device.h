@@ -1369,4 +1369,27 @@ RR_HD uint8_t quantize8(float f) {
     return (uint8_t)(f * 255.0f + 0.5f);
 }
 
+// The 16-bit PNG path (png16.hip). The 8-bit table is too coarse for 65535
+// codes, so this path reads a finer one of its own: kSrgb16N
+// intervals (a power of two: u * kSrgb16N is exact) and an entry [kSrgb16N + 1]
+// that repeats [kSrgb16N], for u in [0, 1]. Separately rounded multiply and
+// add, no fmaf, so numpy's float32 restates the read bit for bit
+// (tests/png16_reader.py).
+constexpr int kSrgb16N = 16384;
+RR_HD float srgb_oetf16(float x, const float* lut) {
+    if (x <= 0.0031308f) return x * 12.92f;
+    const float f = x * (float)kSrgb16N;
+    const int i = (int)f;
+    const float fr = f - (float)i;
+    const float d = lut[i + 1] - lut[i];
+    const float m = d * fr;
+    return lut[i] + m;
+}
+RR_HD uint16_t quantize16(float f) {
+    if (f <= 0.0f) return 0;
+    if (f >= 1.0f) return 65535;
+    const float s = f * 65535.0f;
+    return (uint16_t)(s + 0.5f);
+}
+
 }  // namespace rr

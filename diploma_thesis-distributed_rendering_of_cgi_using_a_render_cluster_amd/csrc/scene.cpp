@@ -618,6 +618,12 @@ void build_srgb_lut(float* lut) {
         lut[i] = (float)(1.055 * std::pow((double)i / kSrgbLutSize, 1.0 / 2.4) - 0.055);
 }
 
+void build_srgb16_lut(float* lut) {
+    for (int i = 0; i <= kSrgb16LutSize; ++i)
+        lut[i] = (float)(1.055 * std::pow((double)i / kSrgb16LutSize, 1.0 / 2.4) - 0.055);
+    lut[kSrgb16LutSize + 1] = lut[kSrgb16LutSize];
+}
+
 SceneDesc load_scene(const std::string& path) {
     SceneDesc s;
     s.path = path;
@@ -643,6 +649,11 @@ SceneDesc load_scene(const std::string& path) {
         d.exposure = r.get_num("exposure", d.exposure);
         d.seed = (uint32_t)r.get_num("seed", d.seed);
         d.spp_per_chunk = (int)r.get_num("spp_per_chunk", 0);
+        // Blender's image_settings.color_depth for PNG output ('8' or '16')
+        const double depth = r.get_num("color_depth", 8);
+        if (depth != 8.0 && depth != 16.0)
+            throw std::runtime_error("render.color_depth must be 8 or 16, got " + std::to_string(depth));
+        d.color_depth = (int)depth;
         d.view_transform_name = r.get_str("view_transform", "Standard");
         // "Filmic" is applied through Blender's OCIO LUTs when the context has
         // them (rr_set_ocio_config); otherwise the frame falls back to Standard

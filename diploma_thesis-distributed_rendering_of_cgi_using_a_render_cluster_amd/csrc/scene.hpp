@@ -110,6 +110,7 @@ struct RenderDesc {
     // Cycles 3.6 defaults (scene.cycles): max_bounces 12, diffuse 4, glossy 4
     int samples = 128, max_bounces = 12, max_diffuse_bounces = 4, max_glossy_bounces = 4;
     double clamp_indirect = 10.0, filter_width = 1.5, exposure = 0.0;
+    int color_depth = 8;  // PNG output: 8 or 16 bits per sample (rr_set_png_depth 0 takes it)
     int view_transform = VIEW_STANDARD;
     std::string view_transform_name = "Standard";
     // What of the scene's colour management a frame does not apply, for the
@@ -177,5 +178,9 @@ constexpr int kMatLutFloatsPerMat = 260;
 constexpr int kMatLutPsOffset = 130;
 void build_material_lut(const float* mat12, float* out /* kMatLutFloatsPerMat */);
 void build_srgb_lut(float* lut /* kSrgbLutSize + 1 */);
+// The 16-bit PNG path's finer table (rr_device.h srgb_oetf16, kSrgb16N
+// intervals): entries [0, kSrgb16LutSize] and a repeat of the last.
+constexpr int kSrgb16LutSize = 16384;
+void build_srgb16_lut(float* lut /* kSrgb16LutSize + 2 */);
 
 }  // namespace rr

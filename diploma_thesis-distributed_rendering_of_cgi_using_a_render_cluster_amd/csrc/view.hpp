@@ -54,6 +54,7 @@ struct FilmicDev {
     std::string dir;
     void upload(const FilmicLuts& l, const std::string& from);
     void release();
+    FilmicArgs args() const { return FilmicArgs{cube.ptr, lut1.ptr, n3, n1, comps, lo1, hi1}; }
 };
 
 // rgba8 = Filmic(film sums * inv_spp * exposure_scale) for every pixel.

@@ -75,7 +75,7 @@ class FrameStats(ctypes.Structure):
 
 RR_FLAG_PROFILE_KERNELS, RR_FLAG_COUNT_TRAVERSAL, RR_FLAG_WAVEFRONT = 1, 2, 4
 KERNEL_CLASSES = ["build", "primary", "extend", "shadow", "accumulate", "shade", "tiles"]
-RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, or OPEN_EXR)
+RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR)
 
 
 # Every symbol include/rr.h declares (checked by tests/test_abi.py).
@@ -88,6 +88,7 @@ EXPORTS = [
     "rr_debug_trace", "rr_debug_object_matrix", "rr_debug_qbvh", "rr_debug_bvh_hier", "rr_debug_jpeg_device",
     "rr_debug_bsdf_sample", "rr_debug_fastmath_check", "rr_debug_tile_costs",
     "rr_set_device_png", "rr_debug_png_device", "rr_debug_exr_device",
+    "rr_set_png_depth", "rr_debug_png16_device", "rr_debug_srgb16_table",
 ]
 
 _lib = None
@@ -144,6 +145,10 @@ def lib() -> ctypes.CDLL:
         "rr_set_device_png": (c_int, [P, i32]),
         "rr_debug_png_device": (c_int, [P, u8p, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_exr_device": (c_int, [P, f32p, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_set_png_depth": (c_int, [P, i32]),
+        "rr_debug_png16_device": (c_int, [P, f32p, i32, i32, i32, ctypes.c_float, u8p, ctypes.c_uint64,
+                                          ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_debug_srgb16_table": (c_int, [f32p, i32, i32p]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -265,10 +270,13 @@ class Scene:
 class RenderContext:
     """One HIP device (rr_ctx). Not thread-safe; one frame in flight at a time."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, png_depth: int = 0):
+        """png_depth: bits per sample of "PNG" frames (set_png_depth; 0: the scene's)."""
         h = ctypes.c_void_p()
         _check(lib().rr_create(int(device), ctypes.byref(h)))
         self.handle = h
+        if png_depth:
+            self.set_png_depth(png_depth)
         self.device = device
 
     def close(self):
@@ -420,6 +428,28 @@ class RenderContext:
             raise RRError(RR_EINVAL, f"device PNG of {n.value} bytes exceeds the {out.size}-byte buffer")
         return out[:n.value].tobytes()
 
+    def set_png_depth(self, depth: int = 0):
+        """rr_set_png_depth: bits per sample of "PNG" frames of this context, 0
+        (the scene's render.color_depth), 8 or 16. 16-bit frames are always coded
+        on the device (png16.hip)."""
+        _check(lib().rr_set_png_depth(self.handle, int(depth)), self.handle)
+
+    def png16_device(self, rgba: np.ndarray, view_transform: int = 0, exposure_scale: float = 1.0) -> bytes:
+        """rr_debug_png16_device: the 16-bit RGBA PNG file bytes of an (H, W, 4)
+        float32 image of means, taken through exposure, clamp, view transform and
+        quantize16 and encoded on the device (png16.hip). Alpha is forced to 1."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+        h, w = rgba.shape[:2]
+        raw = (8 * w + 1) * h
+        out = np.zeros(raw + 5 * (raw // 65535 + (h + 15) // 16 + 1) + 1024, np.uint8)  # above the all-stored worst case
+        n = ctypes.c_uint64()
+        _check(lib().rr_debug_png16_device(self.handle, _ptr(rgba, ctypes.c_float), w, h, int(view_transform),
+                                           ctypes.c_float(exposure_scale), _ptr(out, ctypes.c_uint8), out.size,
+                                           ctypes.byref(n)), self.handle)
+        if n.value > out.size:
+            raise RRError(RR_EINVAL, f"device PNG of {n.value} bytes exceeds the {out.size}-byte buffer")
+        return out[:n.value].tobytes()
+
     def exr_device(self, rgba: np.ndarray) -> bytes:
         """rr_debug_exr_device: the OpenEXR file bytes (half A, B, G, R; ZIP) of an
         (H, W, 4) float32 image of means, encoded on the device (exr.hip)."""
@@ -479,6 +509,16 @@ class RenderContext:
                                     _ptr(hits, ctypes.c_float), _ptr(prims, ctypes.c_int32),
                                     _ptr(occ, ctypes.c_uint8)), self.handle)
         return hits[:n], prims[:n], occ[:n]
+
+
+def srgb16_table() -> np.ndarray:
+    """rr_debug_srgb16_table: the float32 sRGB table of the 16-bit PNG path
+    (intervals + 1 entries; host only, no device needed)."""
+    n = ctypes.c_int32()
+    _check(lib().rr_debug_srgb16_table(None, 0, ctypes.byref(n)))
+    t = np.zeros(n.value, np.float32)
+    _check(lib().rr_debug_srgb16_table(_ptr(t, ctypes.c_float), t.size, ctypes.byref(n)))
+    return t
 
 
 def encode_image(rgba: np.ndarray, out_path_no_ext: str, fmt: str, quality: int = 90) -> int:

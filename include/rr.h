@@ -89,7 +89,7 @@ typedef struct rr_render_params {
 #define RR_K_ACCUM 4     /* film accumulate + tonemap */
 #define RR_K_SHADE 5     /* split path (large scenes): shading kernels; PRIMARY/EXTEND then time traversal only */
 #define RR_K_TILES 6     /* LDS-resident scenes: k_tiles, every sample of an 8x8 pixel tile run to completion + film + tonemap */
-#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, or OPEN_EXR): all its kernels, one event pair per frame */
+#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR): all its kernels, one event pair per frame */
 #define RR_K_CLASSES 8
 
 /* The five timestamps the reference recovers from Blender's stdout
@@ -289,6 +289,38 @@ int rr_debug_png_device(rr_ctx* ctx, const uint8_t* rgba8, int32_t width, int32_
  * Exported for round-trip tests. */
 int rr_debug_exr_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
                         uint8_t* out, uint64_t cap, uint64_t* len);
+
+/* Bit depth of "PNG" frames of ctx: 0 = the scene's render.color_depth (8 when
+ * the scene has none; the default), 8 or 16 = that depth. Replaces Blender's
+ * image_settings.color_depth behind write_still (render-timing-script.py:83-92).
+ * A 16-bit frame is RGBA with 16-bit samples, quantised from the float film
+ * after exposure and view transform (not from the 8-bit image), and is always
+ * coded on the device (png16.hip), whatever rr_set_device_png says: there is no
+ * host 16-bit encoder, and rr_encode_image stays 8-bit. 8-bit PNG, JPEG and
+ * OPEN_EXR frames are unaffected. rr_create reads RR_PNG_DEPTH (0, 8 or 16)
+ * from the environment the same way. Applies to frames submitted after the
+ * call. A 16-bit frame wider than 2^19 pixels, or with a stream of 2 GB and
+ * more, is refused with RR_EINVAL when submitted. RR_EINVAL for a NULL ctx or
+ * another depth. */
+int rr_set_png_depth(rr_ctx* ctx, int32_t depth);
+
+/* Encode a float RGBA image (rows top to bottom, width * height * 4 floats,
+ * taken as means: spp = 1; alpha is forced to 1) with the device 16-bit PNG
+ * path (the one 16-bit "PNG" frames take; write_still,
+ * render-timing-script.py:83-92): value * exposure_scale, clamp to [0, 1],
+ * view_transform (RR_VIEW_STANDARD, RR_VIEW_RAW, or RR_VIEW_FILMIC with the
+ * context's LUTs; Filmic without LUTs is RR_EINVAL here), 16-bit quantisation,
+ * Sub filter, deflate. *len receives the file size; the bytes are copied to out
+ * if cap >= *len. Exported for round-trip tests. */
+int rr_debug_png16_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
+                          int32_t view_transform, float exposure_scale, uint8_t* out, uint64_t cap,
+                          uint64_t* len);
+
+/* The sRGB table of the 16-bit PNG path (host only, no device needed): *n
+ * receives the number of floats (intervals + 1), which are copied to table if
+ * cap >= *n. Entry i = 1.055 (i / (n - 1))^(1 / 2.4) - 0.055, computed in
+ * double. Exported so that tests restate the table read, not the table. */
+int rr_debug_srgb16_table(float* table, int32_t cap, int32_t* n);
 
 /* Thread-local message of the last failure on this thread (ctx may be NULL). */
 const char* rr_last_error(rr_ctx* ctx);

@@ -182,6 +182,11 @@ def export(path: str, args) -> dict:
 
     vs = bf.get(sc, "view_settings")
     view_transform = bf.read_struct_at(vs, "ColorManagedViewSettings", "view_transform")
+    # image_settings.color_depth: ImageFormatData.depth holds R_IMF_CHAN_DEPTH_*
+    # (8 bits = 1 << 1, 16 bits = 1 << 4); the renderer writes PNG at 8 or 16
+    # bits per sample, any other depth (EXR's 32, DPX's 10 / 12) exports as 8
+    imf_depth = bf.read_struct_at(rd("im_format"), "ImageFormatData", "depth")
+    color_depth = 16 if imf_depth == (1 << 4) else 8
     out = {
         "format": "rrscene", "version": 1, "name": idname(bf, sc),
         "source": {"file": os.path.basename(path), "blender_version": bf.version,
@@ -200,6 +205,8 @@ def export(path: str, args) -> dict:
             "clamp_indirect": args.clamp_indirect, "seed": args.seed,
         },
     }
+    if color_depth != 8:  # 8 is what a scene without the field means: such exports stay as they were
+        out["render"]["color_depth"] = color_depth
     # ID blocks, indexed by old pointer
     mats = bf.blocks_with_code(b"MA")
     mat_index = {b.old_ptr: i for i, b in enumerate(mats)}
