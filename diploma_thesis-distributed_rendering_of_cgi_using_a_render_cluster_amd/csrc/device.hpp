@@ -268,64 +268,29 @@ size_t jpeg_stream_max_bytes(int W, int H);
 void jpeg_encode_device(const uint8_t* d_rgba, int W, int H, const float* d_tab, const uint32_t* d_huff,
                         int16_t* d_coeffs, JpegDevBufs& b, uint8_t* host_out, hipStream_t st);
 
-// Device PNG encode (png.hip): Sub filter, LZ77 and dynamic-Huffman deflate of
-// an RGBA8 frame in bands of kPngBandRows rows, written to pinned host memory
-// as [uint64 length][8 B pad][78 01 + deflate data]; host_tab receives
-// {Adler-32, filtered bytes} per band for the host to combine (image_io
-// png_wrap_stream). The band height is fixed, so a frame's bytes depend on
-// the image alone.
-constexpr int kPngBandRows = 16;
-struct PngPlan {
-    int W, H, nbands;
-    uint32_t stride;     // front-end bytes per row (PNG: filtered, 4W + 1; EXR: 8W)
-    uint32_t band_full;  // front-end bytes of a full band
-    uint32_t band_pos;   // positions reserved per band (whole parse tiles)
-    uint32_t nsub, nseg; // per band: 4096-position chunks, 512-position parse segments
-    uint32_t band_cap;   // bytes reserved per band's deflate piece (>= its stored form)
-    // the three match distances tried at every position, 0 = none (beyond the 32 KB window).
-    // PNG: 1, 4 (pixel period), 4W + 1 (the filtered row above)
-    uint32_t dist[3];
-    // every band is a deflate stream of its own (EXR chunks): its dynamic block is
-    // final and ends the piece; the alternative is not the stored form but the
-    // band's raw bytes, written by the front end's owner, and the host table
-    // holds {mode (0 dynamic, 1 raw), bytes, Adler-32, front-end bytes} per band
-    int own_stream;
-};
-// false: the size is outside what the device encoder takes (W > 2^20, or a stream of 2 GB and more).
-bool png_plan(int W, int H, PngPlan& p);
-size_t png_scratch_words(const PngPlan& p);
-size_t png_stream_max_bytes(const PngPlan& p);  // zlib stream with every band stored
-void png_encode_device(const uint8_t* d_rgba, const PngPlan& p, uint32_t* scratch, uint8_t* host_out,
+// The three formats coded by the device deflate coder (deflate.hpp): each has
+// a plan (false: the size is outside what the encoder takes, W above the bound
+// named below or a stream of 2 GB and more) and an encode call that runs its
+// front end, the coder's stages and the gather into pinned host memory:
+// host_out = [uint64 length][8 B pad][bytes], host_tab = the bands' table
+// (DeflatePlan::own_stream). scratch: deflate_scratch_words(p) words.
+struct DeflatePlan;
+
+// 8-bit PNG (png.hip): the Sub-filtered RGBA8 frame as one zlib stream, 78 01 +
+// deflate data (image_io png_wrap_stream). W <= 2^20.
+bool png_plan(int W, int H, DeflatePlan& p);
+void png_encode_device(const uint8_t* d_rgba, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                        uint32_t* host_tab, hipStream_t st);
 
-// The deflate stages of png.hip behind another front end (exr.hip). The front
-// end fills `filt` (band b at b * band_pos) and `adler_part` ({sum of bytes,
-// sum of (m - k) * byte k} per 4096-byte chunk, at 2 * (b * nsub + chunk)).
-struct DeflateBufs {
-    uint8_t *filt, *out;  // out: band b's piece at b * band_cap
-    uint16_t *cand, *exits, *entry;
-    uint32_t *adler_part, *subhist, *codes, *sub_off, *rec, *prefix;  // rec: 4 words per band (k_png_codes)
-    size_t words;
-};
-constexpr uint32_t kDeflateSub = 4096;  // positions per Adler chunk
-// Everything of the plan but dist and own_stream; false: a stream of 2 GB and more.
-bool deflate_plan(int W, int H, uint32_t stride, PngPlan& p);
-DeflateBufs deflate_carve(const PngPlan& p, uint32_t* base);  // base nullptr: only `words`
-void deflate_bands_device(const PngPlan& p, const DeflateBufs& c, hipStream_t st);  // match ... emit
-void deflate_gather_device(const PngPlan& p, const DeflateBufs& c, uint8_t* host_out, uint32_t* host_tab,
-                           hipStream_t st);
-
-// Device OpenEXR encode (exr.hip): the film's means as half-float A, B, G, R
-// planes in ZIP chunks of kPngBandRows scanlines. Front end (half conversion,
-// plane split, byte reorder, predictor, Adler sums) + the deflate stages
-// above; host_out = [uint64 length][8 B pad][the chunks' pieces: deflate data
-// without zlib framing, or the raw chunk bytes], host_tab = {mode, bytes,
-// Adler-32, chunk bytes} per chunk (image_io exr_wrap_stream).
-// false: W > 2^19 (band positions in 32-bit counters), or a stream of 2 GB and more.
-bool exr_plan(int W, int H, PngPlan& p);
-size_t exr_stream_max_bytes(const PngPlan& p);  // every chunk raw
+// OpenEXR (exr.hip): the film's means as half-float A, B, G, R planes in ZIP
+// chunks of kDeflateBandRows scanlines (half conversion, plane split, byte
+// reorder, predictor); the bytes are the chunks' pieces: deflate data without
+// zlib framing, or the raw chunk bytes (image_io exr_wrap_stream). W <= 2^19
+// (band positions in 32-bit counters).
+bool exr_plan(int W, int H, DeflatePlan& p);
+size_t exr_stream_max_bytes(const DeflatePlan& p);  // every chunk raw
 // film: W x H float4 sums, scaled by inv_spp; alpha_one: A = 1.0 (rendered frames), else film.w * inv_spp.
-void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const PngPlan& p, uint32_t* scratch,
+void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
                        uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 // The Filmic LUTs of one device as kernel arguments (view.hpp FilmicDev::args).
@@ -339,10 +304,10 @@ struct FilmicArgs {
 // Device 16-bit PNG encode (png16.hip): the film's display-referred image as
 // RGBA with 16-bit big-endian samples, A = 65535. Front end (mean, exposure,
 // clamp, view transform, quantize16, Sub filter over 8-byte pixels, Adler
-// sums) + the deflate stages above as one zlib stream; host_out and host_tab
-// as png_encode_device writes them (image_io png16_wrap_stream).
-// false: W > 2^19 (band positions in 32-bit counters), or a stream of 2 GB and more.
-bool png16_plan(int W, int H, PngPlan& p);
+// sums) as one zlib stream; host_out and host_tab as png_encode_device writes
+// them (image_io png_wrap_stream, depth 16). W <= 2^19 (band positions in
+// 32-bit counters).
+bool png16_plan(int W, int H, DeflatePlan& p);
 struct Png16Front {
     const float4* film;  // W x H sums
     float inv_spp, exposure_scale;
@@ -350,7 +315,7 @@ struct Png16Front {
     const float* srgb16;  // kSrgb16LutSize + 2 floats (scene.hpp build_srgb16_lut)
     FilmicArgs filmic;
 };
-void png16_encode_device(const Png16Front& f, const PngPlan& p, uint32_t* scratch, uint8_t* host_out,
+void png16_encode_device(const Png16Front& f, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                          uint32_t* host_tab, hipStream_t st);
 
 // Per chunk: one pair per bounce b = 0..max_bounces {paths entering b+1,

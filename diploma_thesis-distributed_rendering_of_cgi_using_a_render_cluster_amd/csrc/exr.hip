@@ -11,22 +11,22 @@
 // difference to its predecessor + 128. Within a half of the reordered bytes,
 // position k is the sample (row k / 4W, plane k % 4W / W, x k % W).
 //
-//  - k_exr_front: the preprocessed bytes of every chunk and their Adler
-//    partial sums per 4096 bytes — the part k_png_filter plays for PNG. A pure
-//    function of the film: a position converts its own sample and its
-//    predecessor's, no lane waits for another.
-//  - png.hip's deflate stages (match, exits, entries, mark, codes, emit) over
-//    bands = chunks, every band a stream of its own, with the distances 1, W
-//    (the same pixel in the neighbouring plane: grey pixels give equal planes)
-//    and 4W (the scanline above within a half).
+//  - ExrFront: the preprocessed byte at a position, the front end of the
+//    deflate coder (deflate.hpp k_deflate_front). A position converts its own
+//    sample and its predecessor's.
+//  - deflate.hip's stages over bands = chunks, every band a stream of its own
+//    (own_stream), with the distances 1, W (the same pixel in the neighbouring
+//    plane: grey pixels give equal planes) and 4W (the scanline above within a
+//    half).
 //  - k_exr_raw: a chunk whose zlib stream would not be smaller than n carries
 //    its n unprocessed bytes; the codes stage decides, this kernel writes them.
-//  - png.hip's scan + gather into pinned host memory.
+//  - deflate.hip's scan + gather into pinned host memory.
 // Same film -> same bytes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "deflate.hpp"
 #include "device.hpp"
 
 namespace rr {
@@ -64,7 +64,7 @@ struct Film {
 };
 
 // Half of sample k of a band: k counts scanline by scanline, plane by plane (A, B, G, R).
-__device__ __forceinline__ uint32_t sample_half(const Film& fm, const PngPlan& p, int row0, uint32_t k) {
+__device__ __forceinline__ uint32_t sample_half(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
     const uint32_t W = (uint32_t)p.W, row_samples = 4u * W;
     const uint32_t row = k / row_samples, rem = k - row * row_samples;
     const uint32_t ch = rem / W, x = rem - ch * W;
@@ -75,60 +75,30 @@ __device__ __forceinline__ uint32_t sample_half(const Film& fm, const PngPlan& p
 }
 
 // Byte j of a band after the reorder (before the predictor).
-__device__ __forceinline__ uint32_t reordered_byte(const Film& fm, const PngPlan& p, int row0, uint32_t half_n,
+__device__ __forceinline__ uint32_t reordered_byte(const Film& fm, const DeflatePlan& p, int row0, uint32_t half_n,
                                                    uint32_t j) {
     const bool hi = j >= half_n;
     const uint32_t h = sample_half(fm, p, row0, hi ? j - half_n : j);
     return hi ? h >> 8 : h & 0xFFu;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
-__global__ __launch_bounds__(kThreads) void k_exr_front(Film fm, PngPlan p, uint8_t* __restrict__ filt,
-                                                        uint32_t* __restrict__ adler_part) {
-    __shared__ uint32_t red[2][kThreads / 64];
-    const int b = blockIdx.y;
-    const int row0 = b * kPngBandRows;
-    const uint32_t n = p.stride * (uint32_t)min(kPngBandRows, p.H - row0);
-    const uint32_t c0 = blockIdx.x * kDeflateSub;
-    if (c0 >= n) return;
-    const uint32_t m = min(kDeflateSub, n - c0);
-    uint8_t* out = filt + (size_t)b * p.band_pos;
-    uint32_t s1 = 0, s2 = 0;
-    for (uint32_t k = threadIdx.x; k < m; k += kThreads) {
-        const uint32_t j = c0 + k;
+// Byte j of a chunk as the coder sees it: reordered, less its predecessor + 128.
+struct ExrFront {
+    Film fm;
+    __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t n, uint32_t j) const {
         uint32_t v = reordered_byte(fm, p, row0, n / 2, j);
         if (j > 0) v = (v - reordered_byte(fm, p, row0, n / 2, j - 1) + 128u) & 0xFFu;
-        out[j] = (uint8_t)v;
-        s1 += v;
-        s2 += (m - k) * v;
+        return v;
     }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = s1;
-        red[1][threadIdx.x >> 6] = s2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0, c = 0;
-        for (int w = 0; w < kThreads / 64; ++w) a += red[0][w], c += red[1][w];
-        uint32_t* o = adler_part + 2 * ((size_t)b * p.nsub + blockIdx.x);
-        o[0] = a;  // < 2^32: <= 4096 * 255
-        o[1] = c;  // < 2^32: <= 255 * 4096 * 4097 / 2
-    }
-}
+};
 
 // Raw chunks (rec mode 1): the n bytes as the file's reader expects them, unprocessed.
-__global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, PngPlan p, const uint32_t* __restrict__ rec,
+__global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, DeflatePlan p, const uint32_t* __restrict__ rec,
                                                       uint8_t* __restrict__ out) {
     const int b = blockIdx.y;
     if (rec[4 * (size_t)b] == 0u) return;
-    const int row0 = b * kPngBandRows;
-    const uint32_t n = p.stride * (uint32_t)min(kPngBandRows, p.H - row0);
+    const int row0 = b * kDeflateBandRows;
+    const uint32_t n = p.stride * (uint32_t)min(kDeflateBandRows, p.H - row0);
     const uint32_t k = blockIdx.x * kThreads + threadIdx.x;  // sample
     if (2u * k >= n) return;
     const uint32_t h = sample_half(fm, p, row0, k);
@@ -138,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, PngPlan p, const 
 
 }  // namespace
 
-bool exr_plan(int W, int H, PngPlan& p) {
+bool exr_plan(int W, int H, DeflatePlan& p) {
     // a band's bit offsets (at most 16 bits a byte, 128 W bytes) stay below 2^32
     if (W <= 0 || H <= 0 || W > (1 << 19)) return false;
     const bool ok = deflate_plan(W, H, 8u * (uint32_t)W, p);
@@ -150,13 +120,13 @@ bool exr_plan(int W, int H, PngPlan& p) {
     return ok;
 }
 
-size_t exr_stream_max_bytes(const PngPlan& p) { return (size_t)p.stride * (size_t)p.H; }
+size_t exr_stream_max_bytes(const DeflatePlan& p) { return (size_t)p.stride * (size_t)p.H; }
 
-void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const PngPlan& p, uint32_t* scratch,
+void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
                        uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
     const DeflateBufs c = deflate_carve(p, scratch);
     const Film fm{d_film, inv_spp, alpha_one ? 1 : 0};
-    k_exr_front<<<dim3(p.nsub, p.nbands), kThreads, 0, st>>>(fm, p, c.filt, c.adler_part);
+    k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFront{fm}, p, c.filt, c.adler_part);
     deflate_bands_device(p, c, st);
     k_exr_raw<<<dim3((p.band_full / 2 + kThreads - 1) / kThreads, p.nbands), kThreads, 0, st>>>(fm, p, c.rec, c.out);
     deflate_gather_device(p, c, host_out, host_tab, st);

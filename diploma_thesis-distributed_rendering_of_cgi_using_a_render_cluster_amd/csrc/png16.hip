@@ -1,6 +1,6 @@
 // 16-bit PNG encode on the device: the film's display-referred image as RGBA
 // with 16-bit samples, quantised from the float values after exposure and view
-// transform (the 8-bit image is not involved), deflated by png.hip's stages, so
+// transform (the 8-bit image is not involved), deflated by deflate.hip, so
 // only the zlib stream crosses PCIe and the host writes the chunk framing
 // (image_io png_wrap_stream, depth 16). Replaces Blender's
 // image_settings.color_depth = '16' behind write_still
@@ -10,10 +10,9 @@
 // A as big-endian 16-bit samples, each byte less the byte 8 positions (one
 // pixel) before it. A = 65535.
 //
-//  - k_png16_front: the filtered bytes of every band of kPngBandRows rows and
-//    their Adler partial sums per 4096 bytes — the part k_png_filter plays at
-//    8 bits. A pure function of the film: a position computes its own sample
-//    and its left neighbour's, no lane waits for another. Per sample, in the
+//  - Png16Sub: the filtered byte at a position, the front end of the deflate
+//    coder (deflate.hpp k_deflate_front). A position computes its own sample
+//    and its left neighbour's. Per sample, in the
 //    operation order of wavefront.hip tonemap / view.hip k_view_filmic:
 //    c = sum * inv_spp * exposure_scale, then
 //      Standard: quantize16(srgb_oetf16(clamp(c, 0, 1)))
@@ -22,24 +21,23 @@
 //                at 8 bits)
 //    with contraction off, so a host restatement gives the same bits
 //    (tests/png16_reader.py).
-//  - png.hip's deflate stages (match, exits, entries, mark, codes, emit) over
-//    the bands of one zlib stream with the stored fallback, with the distances
+//  - deflate.hip's stages over the bands of one zlib stream with the stored
+//    fallback, with the distances
 //    2 (equal neighbouring samples: grey pixels, and every zero run), 8 (the
 //    pixel period) and 8W + 1 (the filtered row above).
-//  - png.hip's scan + gather into pinned host memory.
+//  - deflate.hip's scan + gather into pinned host memory.
 // Same film -> same bytes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "deflate.hpp"
 #include "device.hpp"
 #include "view_filmic.h"
 
 namespace rr {
 
 namespace {
-
-constexpr int kThreads = 256;
 
 // The third match distance, 1 or 2 (profiles/png16_device.md).
 #ifndef RR_PNG16_DIST3
@@ -70,54 +68,22 @@ __device__ __forceinline__ uint32_t row_byte(const Png16Front& f, const float4* 
     return (q & 1u) ? s & 0xFFu : s >> 8;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
-__global__ __launch_bounds__(kThreads) void k_png16_front(Png16Front f, PngPlan p, uint8_t* __restrict__ filt,
-                                                          uint32_t* __restrict__ adler_part) {
-    __shared__ uint32_t red[2][kThreads / 64];
-    const int b = blockIdx.y;
-    const int row0 = b * kPngBandRows;
-    const uint32_t n = p.stride * (uint32_t)min(kPngBandRows, p.H - row0);
-    const uint32_t c0 = blockIdx.x * kDeflateSub;
-    if (c0 >= n) return;
-    const uint32_t m = min(kDeflateSub, n - c0);
-    uint8_t* out = filt + (size_t)b * p.band_pos;
-    uint32_t s1 = 0, s2 = 0;
-    for (uint32_t k = threadIdx.x; k < m; k += kThreads) {
-        const uint32_t j = c0 + k;
+// Byte j of a band: filter type 1 (Sub) in front of every row of differences.
+struct Png16Sub {
+    Png16Front f;
+    __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t, uint32_t j) const {
         const uint32_t row = j / p.stride, x = j - row * p.stride;
-        uint32_t v = 1u;  // filter type Sub
-        if (x > 0) {
-            const float4* src = f.film + (size_t)(row0 + (int)row) * (size_t)p.W;
-            v = row_byte(f, src, x - 1u);
-            if (x > 8u) v = (v - row_byte(f, src, x - 9u)) & 0xFFu;
-        }
-        out[j] = (uint8_t)v;
-        s1 += v;
-        s2 += (m - k) * v;
+        if (x == 0) return 1u;
+        const float4* src = f.film + (size_t)(row0 + (int)row) * (size_t)p.W;
+        uint32_t v = row_byte(f, src, x - 1u);
+        if (x > 8u) v = (v - row_byte(f, src, x - 9u)) & 0xFFu;
+        return v;
     }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = s1;
-        red[1][threadIdx.x >> 6] = s2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0, c = 0;
-        for (int w = 0; w < kThreads / 64; ++w) a += red[0][w], c += red[1][w];
-        uint32_t* o = adler_part + 2 * ((size_t)b * p.nsub + blockIdx.x);
-        o[0] = a;  // < 2^32: <= 4096 * 255
-        o[1] = c;  // < 2^32: <= 255 * 4096 * 4097 / 2
-    }
-}
+};
 
 }  // namespace
 
-bool png16_plan(int W, int H, PngPlan& p) {
+bool png16_plan(int W, int H, DeflatePlan& p) {
     // a band's bit offsets (at most 16 bits a byte, 128 W + 16 bytes) stay below 2^32
     if (W <= 0 || H <= 0 || W > (1 << 19)) return false;
     const bool ok = deflate_plan(W, H, 8u * (uint32_t)W + 1u, p);
@@ -128,10 +94,10 @@ bool png16_plan(int W, int H, PngPlan& p) {
     return ok;
 }
 
-void png16_encode_device(const Png16Front& f, const PngPlan& p, uint32_t* scratch, uint8_t* host_out,
+void png16_encode_device(const Png16Front& f, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                          uint32_t* host_tab, hipStream_t st) {
     const DeflateBufs c = deflate_carve(p, scratch);
-    k_png16_front<<<dim3(p.nsub, p.nbands), kThreads, 0, st>>>(f, p, c.filt, c.adler_part);
+    k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(Png16Sub{f}, p, c.filt, c.adler_part);
     deflate_bands_device(p, c, st);
     deflate_gather_device(p, c, host_out, host_tab, st);
 }

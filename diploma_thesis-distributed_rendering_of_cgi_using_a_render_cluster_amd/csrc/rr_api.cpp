@@ -25,6 +25,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "deflate.hpp"
 #include "device.hpp"
 #include "image_io.hpp"
 #include "rr.h"
@@ -70,6 +71,27 @@ struct PinnedBuf {
     }
 };
 
+// Who codes a frame's output. HostRgba: the 8-bit image comes back to the host
+// (rr_render_frame_to_memory; a "PNG" file from the host's zlib threads where a
+// path is given). Jpeg ... Exr: coded on the device, the file written from the
+// slot's pinned stream. Png8: "PNG" with rr_set_device_png; Png16: "PNG" at 16
+// bits per sample, for which there is no host coder.
+enum class Coder { None, HostRgba, Jpeg, Png8, Png16, Exr };
+
+// The formats behind the deflate coder (deflate.hip): their coder reads only
+// its slot's rgba8 / film and writes slot buffers only.
+bool device_deflate(Coder k) { return k == Coder::Png8 || k == Coder::Png16 || k == Coder::Exr; }
+
+const char* coder_ext(Coder k) { return k == Coder::Jpeg ? ".jpg" : k == Coder::Exr ? ".exr" : ".png"; }
+
+// The pinned outputs of a deflate-coded frame (deflate.hpp): the stream
+// [uint64 length][pad][bytes] and the bands' table, 2 or 4 words per band by
+// the plan's own_stream.
+struct DeflateOut {
+    PinnedBuf stream, tab;
+    DeflatePlan plan{};
+};
+
 }  // namespace
 
 struct FrameRun {
@@ -104,26 +126,17 @@ struct FrameSlot {
     KernelProfiler prof;
     PinnedBuf host_rgba, host_counters, host_upload;
     PinnedBuf host_jpeg;   // device-coded JPEG stream: [uint64 length][pad][bytes]
-    PinnedBuf host_png;    // device-coded zlib stream of a PNG frame, same layout (png.hip)
-    PinnedBuf host_png_tab;  // its bands' {Adler-32, filtered bytes}
-    PngPlan png_plan{};
-    PinnedBuf host_exr;      // device-coded chunks of an OPEN_EXR frame: [uint64 length][pad][pieces] (exr.hip)
-    PinnedBuf host_exr_tab;  // its chunks' {mode, bytes, Adler-32, chunk bytes}
-    PngPlan exr_plan{};
+    DeflateOut deflate;    // device-coded PNG / OPEN_EXR frame; the plan is made when the frame is submitted
     FrameSetup fs;
     bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
     std::string view_warning;
     double submit_at = 0.0;         // UNIX time when the device work was enqueued
     bool anchor = false;            // submitted to an idle context: its device start is submit_at
     rr_scene* scene = nullptr;
-    std::string out_path, format;
+    std::string out_path;
     int quality = 0;
-    bool jpeg = false, png = false, want_rgba = false, count = false;  // png: coded on the device (rr_set_device_png)
-    bool exr = false;  // an OPEN_EXR frame: the film coded on the device (exr.hip)
-    // a "PNG" frame of 16 bits per sample: the film coded on the device (png16.hip)
-    // into host_png / host_png_tab; png is false
-    bool png16 = false;
-    int png_bits = 8;  // of the stream in host_png
+    Coder coder = Coder::None;
+    bool count = false;
     bool unit_logged = false;  // its k_tiles launch wrote the unit log into trav_counts (rr_debug_tile_costs)
     float* film_out = nullptr;
     FrameRun r{};
@@ -148,7 +161,7 @@ struct FrameSlot {
     DevBuf<int32_t> tile_order, spill;
     DevBuf<unsigned long long> trav_counts;
     DevBuf<uint32_t> jpeg_blk, jpeg_scratch;
-    DevBuf<uint32_t> png_scratch;
+    DevBuf<uint32_t> deflate_scratch;
     DevScene alt;
     const rr_scene* alt_scene = nullptr;
     void release_private() {
@@ -164,7 +177,7 @@ struct FrameSlot {
         trav_counts.release();
         jpeg_blk.release();
         jpeg_scratch.release();
-        png_scratch.release();
+        deflate_scratch.release();
         alt.release();
         alt = DevScene{};
         alt_scene = nullptr;
@@ -185,9 +198,9 @@ struct rr_ctx {
     // device entropy coder (jpeg.hip): Huffman tables, per-row scratch, stream
     DevBuf<uint32_t> jpeg_huff;
     DevBuf<uint32_t> jpeg_scratch, jpeg_blk;
-    // device PNG encoder (png.hip): on for "PNG" frames (rr_set_device_png / RR_DEVICE_PNG), its scratch
+    // 8-bit "PNG" frames are coded on the device (rr_set_device_png / RR_DEVICE_PNG)
     bool device_png = false;
-    DevBuf<uint32_t> png_scratch;
+    DevBuf<uint32_t> deflate_scratch;  // the deflate coder's (a frame has one format)
     // bit depth of "PNG" frames (rr_set_png_depth / RR_PNG_DEPTH): 0 the scene's, 8, 16
     int png_depth = 0;
     DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
@@ -472,6 +485,15 @@ int fit_spp_chunk(const FrameSetup& fs, const DevPaths& p) {
     return (int)std::max<long>(1, std::min<long>(c, fit));
 }
 
+// The device JPEG transform's table: dct | qinv luma | qinv chroma.
+void jpeg_device_table(int quality, float out[192]) {
+    JpegTables t;
+    jpeg_tables(quality, t);
+    std::memcpy(out, t.dct, sizeof t.dct);
+    std::memcpy(out + 64, t.qinv_l, sizeof t.qinv_l);
+    std::memcpy(out + 128, t.qinv_c, sizeof t.qinv_c);
+}
+
 // Device JPEG encode of an RGBA8 frame (transform into c->jpeg_coeffs +
 // Huffman coding) into the slot's pinned stream buffer, on the context stream.
 void enqueue_jpeg_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W, int H, const float* d_tab) {
@@ -496,52 +518,13 @@ void enqueue_jpeg_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W,
                        c->stream);
 }
 
-// The file of a device-coded frame: host-built header + the device stream.
-bool write_device_jpeg(const FrameSlot& sl, const std::string& path, uint64_t* bytes) {
+// The file of a device-coded JPEG frame: host-built header + the device stream.
+void jpeg_file_bytes(const FrameSlot& sl, std::vector<uint8_t>& data) {
     uint64_t len = 0;
     std::memcpy(&len, sl.host_jpeg.ptr, sizeof len);
     if (len + 16 > sl.host_jpeg.cap) throw std::runtime_error("device JPEG stream overflow");
-    std::vector<uint8_t> data;
     jpeg_header_bytes(sl.fs.W, sl.fs.H, sl.quality, data);
     data.insert(data.end(), sl.host_jpeg.ptr + 16, sl.host_jpeg.ptr + 16 + len);
-    *bytes = data.size();
-    return write_file(path, data);
-}
-
-// Device PNG encode of an RGBA8 frame (png.hip) into the slot's pinned stream
-// buffer and band table, on the context stream.
-void enqueue_png_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W, int H) {
-    PngPlan p;
-    if (!png_plan(W, H, p)) throw std::runtime_error("image size outside the device PNG encoder's range");
-    sl.png_plan = p;
-    sl.png_bits = 8;
-    c->png_scratch.ensure(png_scratch_words(p));
-    sl.host_png.ensure(png_stream_max_bytes(p) + 32);
-    sl.host_png_tab.ensure((size_t)p.nbands * 2 * sizeof(uint32_t));
-    void *dev_host = nullptr, *dev_tab = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_png.ptr, 0));
-    RR_HIP(hipHostGetDevicePointer(&dev_tab, sl.host_png_tab.ptr, 0));
-    c->paths.prof.begin(c->stream, RR_K_PNG);
-    png_encode_device(d_rgba, p, c->png_scratch.ptr, static_cast<uint8_t*>(dev_host), static_cast<uint32_t*>(dev_tab),
-                      c->stream);
-    c->paths.prof.end(c->stream);
-}
-
-// The bytes of a device-coded PNG frame: host-built chunks around the device stream.
-void device_png_bytes(const FrameSlot& sl, std::vector<uint8_t>& data) {
-    uint64_t len = 0;
-    std::memcpy(&len, sl.host_png.ptr, sizeof len);
-    if (len + 16 + 4 > sl.host_png.cap) throw std::runtime_error("device PNG stream overflow");
-    const PngPlan& p = sl.png_plan;
-    png_wrap_stream(p.W, p.H, sl.host_png.ptr + 16, (size_t)len, reinterpret_cast<const uint32_t*>(sl.host_png_tab.ptr),
-                    p.nbands, data, sl.png_bits);
-}
-
-bool write_device_png(const FrameSlot& sl, const std::string& path, uint64_t* bytes) {
-    std::vector<uint8_t> data;
-    device_png_bytes(sl, data);
-    *bytes = data.size();
-    return write_file(path, data);
 }
 
 // The 16-bit path's sRGB table on the device. Written once, before the first
@@ -555,67 +538,77 @@ void ensure_srgb16(rr_ctx* c) {
     RR_HIP(hipMemcpy(c->srgb16_lut.ptr, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
-// Device 16-bit PNG encode of a film of sums (png16.hip) into the slot's pinned
-// PNG stream buffer and band table, on the context stream. view_transform is
-// the resolved one (Filmic only with the context's LUTs). The scratch is the
-// deflate coder's (a frame has one format).
-void enqueue_png16_device(rr_ctx* c, FrameSlot& sl, const float4* d_film, float inv_spp, float exposure_scale,
-                          int view_transform, int W, int H) {
-    PngPlan p;
-    if (!png16_plan(W, H, p)) throw std::runtime_error("image size outside the device 16-bit PNG encoder's range");
+// The plan of a deflate-coded frame. A size outside the coder's range is
+// refused, never rerouted: there is no other coder that writes the same file.
+int plan_or_refuse(Coder k, int W, int H, DeflatePlan& p) {
+    const bool ok = k == Coder::Png8 ? png_plan(W, H, p) : k == Coder::Png16 ? png16_plan(W, H, p) : exr_plan(W, H, p);
+    if (ok) return RR_OK;
+    const char* name = k == Coder::Png8 ? "PNG" : k == Coder::Png16 ? "16-bit PNG" : "EXR";
+    return fail(RR_EINVAL, std::string("image size outside the device ") + name + " encoder's range");
+}
+
+// The formats' encode calls as enqueue_deflate's `launch`. film: sums, scaled
+// by inv_spp.
+auto launch_png8(const uint8_t* d_rgba) {
+    return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
+        png_encode_device(d_rgba, p, scratch, out, tab, st);
+    };
+}
+// view_transform is the resolved one (Filmic only with the context's LUTs).
+auto launch_png16(rr_ctx* c, const float4* d_film, float inv_spp, float exposure_scale, int view_transform) {
     if (view_transform == VIEW_FILMIC && !c->filmic.ready) throw std::runtime_error("Filmic view transform without LUTs");
     ensure_srgb16(c);
-    sl.png_plan = p;
-    sl.png_bits = 16;
-    c->png_scratch.ensure(png_scratch_words(p));
-    sl.host_png.ensure(png_stream_max_bytes(p) + 32);
-    sl.host_png_tab.ensure((size_t)p.nbands * 2 * sizeof(uint32_t));
-    void *dev_host = nullptr, *dev_tab = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_png.ptr, 0));
-    RR_HIP(hipHostGetDevicePointer(&dev_tab, sl.host_png_tab.ptr, 0));
     const Png16Front f{d_film, inv_spp, exposure_scale, view_transform, c->srgb16_lut.ptr,
                        view_transform == VIEW_FILMIC ? c->filmic.args() : FilmicArgs{}};
-    c->paths.prof.begin(c->stream, RR_K_PNG);
-    png16_encode_device(f, p, c->png_scratch.ptr, static_cast<uint8_t*>(dev_host), static_cast<uint32_t*>(dev_tab),
-                        c->stream);
-    c->paths.prof.end(c->stream);
+    return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
+        png16_encode_device(f, p, scratch, out, tab, st);
+    };
+}
+auto launch_exr(const float4* d_film, float inv_spp, bool alpha_one) {
+    return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
+        exr_encode_device(d_film, inv_spp, alpha_one, p, scratch, out, tab, st);
+    };
 }
 
-// Device OpenEXR encode of a film of sums (exr.hip) into the slot's pinned
-// chunk buffer and chunk table, on the context stream. The scratch is the
-// deflate coder's (a frame has one format).
-void enqueue_exr_device(rr_ctx* c, FrameSlot& sl, const float4* d_film, float inv_spp, bool alpha_one, int W, int H) {
-    PngPlan p;
-    if (!exr_plan(W, H, p)) throw std::runtime_error("image size outside the device EXR encoder's range");
-    sl.exr_plan = p;
-    c->png_scratch.ensure(png_scratch_words(p));
-    sl.host_exr.ensure(exr_stream_max_bytes(p) + 32);
-    sl.host_exr_tab.ensure((size_t)p.nbands * 4 * sizeof(uint32_t));
+// Device deflate of one frame into the slot's pinned stream buffer and band
+// table, on the context stream.
+template <class Launch>
+void enqueue_deflate(rr_ctx* c, FrameSlot& sl, const DeflatePlan& p, Launch launch) {
+    DeflateOut& o = sl.deflate;
+    o.plan = p;
+    c->deflate_scratch.ensure(deflate_scratch_words(p));
+    o.stream.ensure((p.own_stream ? exr_stream_max_bytes(p) : deflate_stream_max_bytes(p)) + 32);
+    o.tab.ensure((size_t)p.nbands * (p.own_stream ? 4 : 2) * sizeof(uint32_t));
     void *dev_host = nullptr, *dev_tab = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_exr.ptr, 0));
-    RR_HIP(hipHostGetDevicePointer(&dev_tab, sl.host_exr_tab.ptr, 0));
+    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
+    RR_HIP(hipHostGetDevicePointer(&dev_tab, o.tab.ptr, 0));
     c->paths.prof.begin(c->stream, RR_K_PNG);
-    exr_encode_device(d_film, inv_spp, alpha_one, p, c->png_scratch.ptr, static_cast<uint8_t*>(dev_host),
-                      static_cast<uint32_t*>(dev_tab), c->stream);
+    launch(p, c->deflate_scratch.ptr, static_cast<uint8_t*>(dev_host), static_cast<uint32_t*>(dev_tab), c->stream);
     c->paths.prof.end(c->stream);
 }
 
-// The bytes of a device-coded EXR frame: host-built header and offset table around the device chunks.
-void device_exr_bytes(const FrameSlot& sl, std::vector<uint8_t>& data) {
+// The file of a deflate-coded frame: the host-built container of format k
+// around the device stream.
+void deflate_file_bytes(const DeflateOut& o, Coder k, std::vector<uint8_t>& data) {
+    const DeflatePlan& p = o.plan;
+    const uint32_t* tab = reinterpret_cast<const uint32_t*>(o.tab.ptr);
     uint64_t len = 0;
-    std::memcpy(&len, sl.host_exr.ptr, sizeof len);
-    if (len + 16 > sl.host_exr.cap) throw std::runtime_error("device EXR stream overflow");
-    const PngPlan& p = sl.exr_plan;
-    if (!exr_wrap_stream(p.W, p.H, sl.host_exr.ptr + 16, (size_t)len,
-                         reinterpret_cast<const uint32_t*>(sl.host_exr_tab.ptr), p.nbands, data))
-        throw std::runtime_error("device EXR chunk table does not match its stream");
-}
-
-bool write_device_exr(const FrameSlot& sl, const std::string& path, uint64_t* bytes) {
-    std::vector<uint8_t> data;
-    device_exr_bytes(sl, data);
-    *bytes = data.size();
-    return write_file(path, data);
+    std::memcpy(&len, o.stream.ptr, sizeof len);
+    // one stream: its bound counts the 4 bytes of Adler-32 the host adds
+    if (len > o.stream.cap || len + 16 + (p.own_stream ? 0 : 4) > o.stream.cap)
+        throw std::runtime_error("device deflate stream overflow");
+    switch (k) {
+    case Coder::Png8:
+    case Coder::Png16:
+        png_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Png16 ? 16 : 8);
+        break;
+    case Coder::Exr:
+        if (!exr_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data))
+            throw std::runtime_error("device EXR chunk table does not match its stream");
+        break;
+    default:
+        throw std::runtime_error("not a deflate-coded frame");
+    }
 }
 
 // Enqueue the device part of one frame on the context stream (no host
@@ -661,7 +654,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
             std::swap(p.trav_counts, sl.trav_counts);
             std::swap(c->jpeg_blk, sl.jpeg_blk);
             std::swap(c->jpeg_scratch, sl.jpeg_scratch);
-            std::swap(c->png_scratch, sl.png_scratch);
+            std::swap(c->deflate_scratch, sl.deflate_scratch);
             if (sl.tiles) swap_products(sl.scene->dev, sl.alt);
             c->in_slot = !c->in_slot;
         }
@@ -672,10 +665,10 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     SlotSwap slot_swap(c, sl);
     hipStream_t st = c->stream;
     FrameSlot* prev = c->last_enqueued;
-    // (the device PNG / EXR coder reads its slot's rgba8 / film and writes slot
-    // buffers only, so the next frame waits for the image, not for the coder)
+    // (the deflate coder reads its slot's rgba8 / film and writes slot buffers
+    // only, so the next frame waits for the image, ev[5], not for the coder)
     if (prev && prev != &sl && !(sl.tiles && prev->tiles))
-        RR_HIP(hipStreamWaitEvent(st, (prev->png || prev->exr || prev->png16) ? prev->ev[5] : prev->ev[2], 0));
+        RR_HIP(hipStreamWaitEvent(st, device_deflate(prev->coder) ? prev->ev[5] : prev->ev[2], 0));
     c->last_enqueued = &sl;
     // a k_tiles frame enqueued while another k_tiles frame is pending overlaps
     // it: whole-tile work units (render_frame_device); a frame rendered alone
@@ -733,38 +726,33 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     }
     RR_HIP(hipEventRecord(sl.ev[4], st));
     const size_t npix = (size_t)fs.W * fs.H;
-    if (sl.jpeg) {
+    if (sl.coder == Coder::Jpeg) {
         if (c->jpeg_tab_quality != sl.quality) {
             quiesce(c);
-            JpegTables t;
-            jpeg_tables(sl.quality, t);
             float tab[192];
-            std::memcpy(tab, t.dct, sizeof t.dct);
-            std::memcpy(tab + 64, t.qinv_l, sizeof t.qinv_l);
-            std::memcpy(tab + 128, t.qinv_c, sizeof t.qinv_c);
+            jpeg_device_table(sl.quality, tab);
             c->jpeg_tab.ensure(192);
             RR_HIP(hipMemcpy(c->jpeg_tab.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
             c->jpeg_tab_quality = sl.quality;
         }
         enqueue_jpeg_device(c, sl, c->paths.rgba8.ptr, fs.W, fs.H, c->jpeg_tab.ptr);
     }
-    if (sl.png) {
+    if (device_deflate(sl.coder)) {
         RR_HIP(hipEventRecord(sl.ev[5], st));
-        enqueue_png_device(c, sl, c->paths.rgba8.ptr, fs.W, fs.H);
-    }
-    if (sl.exr) {  // the film's means: the product finish_frame forms, no view transform
-        RR_HIP(hipEventRecord(sl.ev[5], st));
-        enqueue_exr_device(c, sl, c->paths.film.ptr, 1.0f / (float)fs.spp, true, fs.W, fs.H);
-    }
-    if (sl.png16) {  // the film again, through exposure and view transform, at 16 bits
-        RR_HIP(hipEventRecord(sl.ev[5], st));
-        enqueue_png16_device(c, sl, c->paths.film.ptr, k.inv_spp, k.exposure_scale, fs.view_transform, fs.W, fs.H);
+        const DeflatePlan& plan = sl.deflate.plan;  // rr_frame_submit's
+        const float4* film = c->paths.film.ptr;
+        if (sl.coder == Coder::Png8)
+            enqueue_deflate(c, sl, plan, launch_png8(c->paths.rgba8.ptr));
+        else if (sl.coder == Coder::Png16)  // the film again, through exposure and view transform, at 16 bits
+            enqueue_deflate(c, sl, plan, launch_png16(c, film, k.inv_spp, k.exposure_scale, fs.view_transform));
+        else  // the film's means: the product finish_frame forms, no view transform
+            enqueue_deflate(c, sl, plan, launch_exr(film, 1.0f / (float)fs.spp, true));
     }
     RR_HIP(hipEventRecord(sl.ev[2], st));
     // the outputs' device-to-host copies follow on the slot's own stream: the
     // next frames run on the other slots' streams, so nothing waits for them
     hipStream_t cs = st;
-    if (sl.want_rgba) {
+    if (sl.coder == Coder::HostRgba) {
         sl.host_rgba.ensure(npix * 4);
         RR_HIP(hipMemcpyAsync(sl.host_rgba.ptr, c->paths.rgba8.ptr, npix * 4, hipMemcpyDeviceToHost, cs));
     }
@@ -898,6 +886,33 @@ FrameSlot* slot_for(rr_ctx* c, uint64_t ticket) { return &c->slots[ticket % RR_M
 
 bool idle(rr_ctx* c) { return c->next_complete == c->next_ticket; }
 
+// The body of the deflate formats' inspection entry points: an image of the
+// caller's through format k's coder on slot 0, the file's bytes to `out` if
+// `cap` suffices. make(device image) gives enqueue_deflate's launch.
+template <class Make>
+int debug_deflate_device(rr_ctx* c, Coder k, int w, int h, const void* pixels, size_t bytes, uint8_t* out, uint64_t cap,
+                         uint64_t* len, Make make) {
+    DeflatePlan plan;
+    const int rc = plan_or_refuse(k, w, h, plan);
+    if (rc != RR_OK) return rc;
+    return guarded([&] {
+        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
+        set_device(c);
+        DevBuf<uint8_t> img;
+        img.ensure(bytes);
+        RR_HIP(hipMemcpy(img.ptr, pixels, bytes, hipMemcpyHostToDevice));
+        FrameSlot& sl = c->slots[0];
+        enqueue_deflate(c, sl, plan, make(img.ptr));
+        RR_HIP(hipStreamSynchronize(c->stream));
+        img.release();
+        std::vector<uint8_t> data;
+        deflate_file_bytes(sl.deflate, k, data);
+        *len = data.size();
+        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
+        return RR_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1001,7 +1016,7 @@ void rr_destroy(rr_ctx* c) {
     c->jpeg_huff.release();
     c->jpeg_scratch.release();
     c->jpeg_blk.release();
-    c->png_scratch.release();
+    c->deflate_scratch.release();
     c->srgb16_lut.release();
     for (auto& sl : c->slots) {
         for (auto& e : sl.ev)
@@ -1102,26 +1117,20 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->tm.started_rendering_at = unix_now();
         sl->scene = s;
         sl->out_path = out_path ? out_path : "";
-        sl->format = (out_path && format) ? format : "";
         sl->quality = jpeg_quality;
-        sl->jpeg = jpeg;
-        sl->exr = exr;
-        const bool png = out_path && !jpeg && !exr;  // format is "PNG"
-        // 16 bits per sample: always the device coder (there is no host one)
-        sl->png16 = png && (c->png_depth ? c->png_depth : s->desc.render.color_depth) == 16;
-        sl->png = png && !sl->png16 && c->device_png;
-        sl->want_rgba = png && !sl->png16 && !sl->png;
-        if (sl->png16) {  // refused, never rerouted
-            PngPlan plan;
-            if (!png16_plan(sl->fs.W, sl->fs.H, plan))
-                return fail(RR_EINVAL, "image size outside the device 16-bit PNG encoder's range");
+        if (!out_path) sl->coder = Coder::None;
+        else if (jpeg) sl->coder = Coder::Jpeg;
+        else if (exr) sl->coder = Coder::Exr;
+        // "PNG". 16 bits per sample: always the device coder (there is no host one)
+        else if ((c->png_depth ? c->png_depth : s->desc.render.color_depth) == 16) sl->coder = Coder::Png16;
+        else sl->coder = c->device_png ? Coder::Png8 : Coder::HostRgba;
+        if (device_deflate(sl->coder)) {
+            const int rc = plan_or_refuse(sl->coder, sl->fs.W, sl->fs.H, sl->deflate.plan);
+            if (rc != RR_OK) return rc;
+        }
+        if (sl->coder == Coder::Png16) {
             set_device(c);
             ensure_srgb16(c);
-        }
-        if (exr) {  // refused, never rerouted
-            PngPlan plan;
-            if (!exr_plan(sl->fs.W, sl->fs.H, plan))
-                return fail(RR_EINVAL, "image size outside the device EXR encoder's range");
         }
         sl->film_out = nullptr;
         sl->anchor = idle(c);
@@ -1179,21 +1188,15 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
         c->gpu_free_at = std::min(dev_start + r.device_ms * 1e-3, t_sync);
         uint64_t bytes = 0;
         const auto t_enc = std::chrono::steady_clock::now();
-        if (sl->jpeg) {  // JFIF headers + the device-coded stream
-            const std::string path = sl->out_path + ".jpg";
-            if (!write_device_jpeg(*sl, path, &bytes))
-                return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
-        } else if (sl->png || sl->png16) {  // PNG chunks + the device-coded zlib stream
-            const std::string path = sl->out_path + ".png";
-            if (!write_device_png(*sl, path, &bytes))
-                return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
-        } else if (sl->exr) {  // header and offset table + the device-coded chunks
-            const std::string path = sl->out_path + ".exr";
-            if (!write_device_exr(*sl, path, &bytes))
-                return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
-        } else if (!sl->out_path.empty()) {
-            const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), sl->format.c_str(),
-                                    sl->quality, &bytes);
+        if (sl->coder == Coder::Jpeg || device_deflate(sl->coder)) {  // the host's container + the device-coded stream
+            std::vector<uint8_t> data;
+            if (sl->coder == Coder::Jpeg) jpeg_file_bytes(*sl, data);
+            else deflate_file_bytes(sl->deflate, sl->coder, data);
+            const std::string path = sl->out_path + coder_ext(sl->coder);
+            bytes = data.size();
+            if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
+        } else if (sl->coder == Coder::HostRgba) {  // a submitted frame's: "PNG" by the host coder
+            const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), "PNG", sl->quality, &bytes);
             if (e != RR_OK) return e;
         }
         const double enc_ms = ms_since(t_enc);
@@ -1246,12 +1249,7 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         sl->view_substituted = !sl->view_warning.empty();
         sl->scene = s;
         sl->out_path.clear();
-        sl->format.clear();
-        sl->jpeg = false;
-        sl->png = false;
-        sl->png16 = false;
-        sl->exr = false;
-        sl->want_rgba = true;
+        sl->coder = Coder::HostRgba;
         sl->film_out = film;
         sl->ticket = c->next_ticket;
         enqueue_frame(c, *sl);
@@ -1286,12 +1284,8 @@ int rr_debug_jpeg_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, 
         DevBuf<uint8_t> img;
         img.ensure((size_t)w * h * 4);
         RR_HIP(hipMemcpy(img.ptr, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice));
-        JpegTables t;
-        jpeg_tables(quality, t);
         float tab[192];
-        std::memcpy(tab, t.dct, sizeof t.dct);
-        std::memcpy(tab + 64, t.qinv_l, sizeof t.qinv_l);
-        std::memcpy(tab + 128, t.qinv_c, sizeof t.qinv_c);
+        jpeg_device_table(quality, tab);
         DevBuf<float> dtab;
         dtab.ensure(192);
         RR_HIP(hipMemcpy(dtab.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
@@ -1302,15 +1296,10 @@ int rr_debug_jpeg_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, 
         sl.quality = quality;
         enqueue_jpeg_device(c, sl, img.ptr, w, h, dtab.ptr);
         RR_HIP(hipStreamSynchronize(st));
-        uint64_t n = 0;
-        std::memcpy(&n, sl.host_jpeg.ptr, sizeof n);
-        std::vector<uint8_t> hdr;
-        jpeg_header_bytes(w, h, quality, hdr);
-        *len = hdr.size() + n;
-        if (out && cap >= *len) {
-            std::memcpy(out, hdr.data(), hdr.size());
-            std::memcpy(out + hdr.size(), sl.host_jpeg.ptr + 16, n);
-        }
+        std::vector<uint8_t> data;
+        jpeg_file_bytes(sl, data);
+        *len = data.size();
+        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
         img.release();
         dtab.release();
         return RR_OK;
@@ -1326,45 +1315,16 @@ int rr_set_device_png(rr_ctx* c, int32_t on) {
 int rr_debug_png_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
                         uint64_t* len) {
     if (!c || !rgba8 || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        DevBuf<uint8_t> img;
-        img.ensure((size_t)w * h * 4);
-        RR_HIP(hipMemcpy(img.ptr, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice));
-        FrameSlot& sl = c->slots[0];
-        enqueue_png_device(c, sl, img.ptr, w, h);
-        RR_HIP(hipStreamSynchronize(c->stream));
-        img.release();
-        std::vector<uint8_t> data;
-        device_png_bytes(sl, data);
-        *len = data.size();
-        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
-        return RR_OK;
+    return debug_deflate_device(c, Coder::Png8, w, h, rgba8, (size_t)w * h * 4, out, cap, len, [](const void* img) {
+        return launch_png8(static_cast<const uint8_t*>(img));
     });
 }
 
 int rr_debug_exr_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
                         uint64_t* len) {
     if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    PngPlan plan;
-    if (!exr_plan(w, h, plan)) return fail(RR_EINVAL, "image size outside the device EXR encoder's range");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        DevBuf<float4> img;
-        img.ensure((size_t)w * h);
-        RR_HIP(hipMemcpy(img.ptr, rgba, (size_t)w * h * sizeof(float4), hipMemcpyHostToDevice));
-        FrameSlot& sl = c->slots[0];
-        enqueue_exr_device(c, sl, img.ptr, 1.0f, false, w, h);
-        RR_HIP(hipStreamSynchronize(c->stream));
-        img.release();
-        std::vector<uint8_t> data;
-        device_exr_bytes(sl, data);
-        *len = data.size();
-        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
-        return RR_OK;
-    });
+    return debug_deflate_device(c, Coder::Exr, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
+                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false); });
 }
 
 int rr_set_png_depth(rr_ctx* c, int32_t depth) {
@@ -1381,24 +1341,11 @@ int rr_debug_png16_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, in
         return fail(RR_EINVAL, "unsupported view transform");
     if (view_transform == VIEW_FILMIC && !c->filmic.ready)
         return fail(RR_EINVAL, "Filmic view transform without LUTs (rr_set_ocio_config / RR_OCIO_DIR)");
-    PngPlan plan;
-    if (!png16_plan(w, h, plan)) return fail(RR_EINVAL, "image size outside the device 16-bit PNG encoder's range");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        DevBuf<float4> img;
-        img.ensure((size_t)w * h);
-        RR_HIP(hipMemcpy(img.ptr, rgba, (size_t)w * h * sizeof(float4), hipMemcpyHostToDevice));
-        FrameSlot& sl = c->slots[0];
-        enqueue_png16_device(c, sl, img.ptr, 1.0f, exposure_scale, view_transform, w, h);
-        RR_HIP(hipStreamSynchronize(c->stream));
-        img.release();
-        std::vector<uint8_t> data;
-        device_png_bytes(sl, data);
-        *len = data.size();
-        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
-        return RR_OK;
-    });
+    return debug_deflate_device(c, Coder::Png16, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
+                                [&](const void* img) {
+                                    return launch_png16(c, static_cast<const float4*>(img), 1.0f, exposure_scale,
+                                                        view_transform);
+                                });
 }
 
 int rr_debug_srgb16_table(float* table, int32_t cap, int32_t* n) {

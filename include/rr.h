@@ -266,7 +266,7 @@ int rr_debug_jpeg_device(rr_ctx* ctx, const uint8_t* rgba8, int32_t width, int32
 
 /* Select the device PNG encoder for "PNG" frames of ctx (on != 0): Sub filter,
  * LZ77 and dynamic-Huffman deflate run on the GPU after the view transform
- * (png.hip), only the zlib stream crosses PCIe and the host writes the chunk
+ * (png.hip, deflate.hip), only the zlib stream crosses PCIe and the host writes the chunk
  * framing — instead of the 8-bit image's readback and the zlib threads of
  * rr_encode_image. Replaces the PNG side of Blender's write_still
  * (render-timing-script.py:83-92). Off by default; rr_create reads

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY — the checker of the device PNG encoder (png.hip).
+"""TEST INFRASTRUCTURE ONLY — the checker of the device PNG encoder (png.hip, deflate.hip).
 
 Pure Python and numpy; imports neither the package nor a GPU library. Two halves:
 
@@ -9,7 +9,7 @@ Pure Python and numpy; imports neither the package nor a GPU library. Two halves
     the container scheme (independent byte-aligned pieces).
     zlib is never asked to decode; tests/test_png_oracle.py cross-checks this
     inflate against it.
-  * A plain serial reference of what png.hip and DESIGN.md §4 say the encoder
+  * A plain serial reference of what deflate.hip and DESIGN.md §4 say the encoder
     computes: the Sub filter, the greedy parse over the distances 1 / 4 / row
     above, the RFC's length and distance symbols as tables, and the cost and
     depth of an optimal (heap-built) Huffman code to judge the emitted codes
@@ -23,7 +23,7 @@ import heapq
 
 import numpy as np
 
-BAND_ROWS = 16      # kPngBandRows
+BAND_ROWS = 16      # kDeflateBandRows
 WINDOW = 32768
 MAX_MATCH = 258
 MIN_MATCH = 3
@@ -508,7 +508,7 @@ def _huffman(freq):
 
 def at_least_two_codes(freq):
     """The encoder gives every alphabet at least two codes, so that each is a
-    complete prefix code (png.hip k_png_codes, as zlib does): unused symbols
+    complete prefix code (deflate.hip k_deflate_codes, as zlib does): unused symbols
     from the lowest index on count once until two are in use."""
     f = list(freq)
     for s in range(len(f)):

@@ -1,5 +1,5 @@
 """The device OPEN_EXR path (exr.hip: half conversion, plane split, byte
-reorder and predictor in front of png.hip's deflate stages, every 16-row chunk
+reorder and predictor in front of deflate.hip's stages, every 16-row chunk
 a zlib stream of its own with a raw fallback) writes files that the strict
 reader of tests/exr_reader.py decodes to exactly float16(clip(film)),
 deterministically, within size conditions that only working matches over the

@@ -1,4 +1,4 @@
-"""The device PNG path (png.hip: Sub filter, LZ77 over the distances 1 / 4 /
+"""The device PNG path (png.hip + deflate.hip: Sub filter, LZ77 over the distances 1 / 4 /
 row above, one dynamic-Huffman block per 16-row band with a stored fallback)
 writes files that decode to exactly the input pixels, deterministically, within
 size conditions that only real dynamic codes and working matches meet; rendered

@@ -1,5 +1,5 @@
 """The device 16-bit PNG path (png16.hip: mean, exposure, clamp, view transform,
-quantize16, Sub filter over 8-byte pixels in front of png.hip's deflate stages,
+quantize16, Sub filter over 8-byte pixels in front of deflate.hip's stages,
 one zlib stream) writes files that the strict reader of tests/png16_reader.py
 decodes to exactly the samples its numpy float32 restatement of the front end
 gives, deterministically; the Filmic view agrees with the 8-bit path within

@@ -1,4 +1,4 @@
-"""The device PNG encoder (png.hip) against oracle/png_oracle.py, token for
+"""The device PNG encoder (png.hip, deflate.hip) against oracle/png_oracle.py, token for
 token and code for code. For every band of every case: the file passes the
 strict inflate and the container checks (complete codes, no match before its
 band, byte-aligned bands, BFINAL last only); a dynamic band's tokens equal the
