@@ -1,6 +1,7 @@
 // Host-side interface of the device module: buffers in HBM and the launch
-// sequences of the LBVH build (bvh.hip) and the wavefront integrator
-// (wavefront.hip). DESIGN.md §4 describes the layout.
+// sequences of the LBVH build (bvh.hip) and the path integrator (wavefront.hip:
+// the split path and the frame dispatcher; tiles.hip: the tile path).
+// DESIGN.md §4 describes the layout.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -164,8 +165,8 @@ struct DevPaths {
     int last_tile_slices = 0;      // render_frame_device: k_tiles units per box tile of the last frame (0: not k_tiles)
     bool last_unit_logged = false; // render_frame_device: the last k_tiles launch wrote its unit log (trav_counts)
     int grid_blocks = 0;  // persistent grid for path kernels
-    void ensure_paths(size_t n);
-    void ensure_tiles();  // k_tiles: only the traversal stack spill area
+    void ensure_paths(size_t n);  // wavefront.hip
+    void ensure_tiles();  // tiles.hip; k_tiles: only the traversal stack spill area
     void release();
 };
 
@@ -234,6 +235,10 @@ bool frame_uses_tiles(const FrameConsts& base, bool force_wavefront);
 // Render all chunks of one frame: film accumulate + tonemap to rgba8.
 // counters_per_chunk receives the device counter layout for stats.
 void render_frame_device(DevScene& s, DevPaths& p, const FrameConsts& base, int n_chunks,
+                         hipStream_t st);
+// The k_tiles frame of render_frame_device (frame_uses_tiles holds; tiles.hip):
+// k_tile_order, k_tiles over all samples, k_tiles_fold when tiles are sliced.
+void render_tiles_device(DevScene& s, DevPaths& p, const FrameConsts& base, int n_chunks,
                          hipStream_t st);
 
 // Trace a batch of rays (debug / parity entry point).

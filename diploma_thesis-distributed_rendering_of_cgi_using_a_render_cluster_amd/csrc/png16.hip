@@ -13,7 +13,7 @@
 //  - Png16Sub: the filtered byte at a position, the front end of the deflate
 //    coder (deflate.hpp k_deflate_front). A position computes its own sample
 //    and its left neighbour's. Per sample, in the
-//    operation order of wavefront.hip tonemap / view.hip k_view_filmic:
+//    operation order of paths.hpp tonemap / view.hip k_view_filmic:
 //    c = sum * inv_spp * exposure_scale, then
 //      Standard: quantize16(srgb_oetf16(clamp(c, 0, 1)))
 //      Raw:      quantize16(clamp(c, 0, 1))

@@ -812,7 +812,7 @@ void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int
     const int cpc = counters_per_chunk(fs.max_bounces);
     uint64_t drops = 0, ext_traced = 0, sh_traced = 0;
     for (int c = 0; c < r.chunks; ++c) {
-        // pair b: {paths entering bounce b+1, shadow rays of bounce b} (wavefront.hip)
+        // pair b: {paths entering bounce b+1, shadow rays of bounce b} (wavefront.hip, tiles.hip)
         const int32_t* q = &r.counters[(size_t)cpc * c];
         st->camera_rays_traced += (uint64_t)(uint32_t)q[camera_traced_slot(fs.max_bounces)];
         drops += (uint64_t)(uint32_t)q[drops_slot(fs.max_bounces)];

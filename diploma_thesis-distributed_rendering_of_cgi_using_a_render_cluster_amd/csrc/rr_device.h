@@ -583,7 +583,7 @@ RR_HD void leaf_test(const TriPack& tp, int idx, const Shear& s, float3 o, float
 // ds_write/ds_read (a generic pointer would become flat_* accesses).
 typedef __attribute__((address_space(3))) int lds_int;
 typedef __attribute__((address_space(3))) uint32_t lds_uint;
-// LDS-staged scene data (wavefront.hip stage_scene): HIP's float4 has no
+// LDS-staged scene data (tiles.hip stage_scene): HIP's float4 has no
 // address-space-3 copy, so 16-byte moves use a clang vector type.
 typedef float rr_f4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) rr_f4v lds_f4w;
@@ -709,7 +709,7 @@ struct TravCount {
 // (traverse() below); the split trace kernels of large scenes interleave
 // step() with lane refill (wavefront.hip trace_refill), which changes only the
 // schedule, never the visited nodes, so the hits are identical.
-// nodes / tris: global or LDS pointers (wavefront.hip SceneView).
+// nodes / tris: global or LDS pointers (paths.hpp SceneView).
 // The largest |coordinate| of a BVH2's scene box (its root's two child boxes).
 RR_D float scene_radius(const BvhNode& r) {
     const float a = fmaxf(fmaxf(fmaxf(fabsf(r.a.x), fabsf(r.a.y)), fmaxf(fabsf(r.a.z), fabsf(r.a.w))),
@@ -1309,7 +1309,7 @@ RR_HD float3 sample_vndf(float3 v, float alpha, float dx, float dy) {
 // bsdf_eval_v. glossy: the specular lobe was picked (Cycles LABEL_GLOSSY;
 // else LABEL_DIFFUSE), which decides the bounce counter the scatter advances.
 // (T, B): make_onb(N), which LDS-resident scenes stage per triangle side
-// (wavefront.hip stage_scene) instead of computing it per sample.
+// (tiles.hip stage_scene) instead of computing it per sample.
 template <typename FloatP>
 RR_HD bool bsdf_sample_onb(const Mat& m, FloatP lut, const BsdfView& vw, float3 N, float3 T, float3 B, float3 wo,
                            float ul, float u1, float u2, float3& wi, float3& f, float& pdf, bool& glossy) {

@@ -21,43 +21,22 @@
 // uncontracted, libm-free form of rr_device.h and matches oracle/rr_oracle.c
 // bit for bit.
 //
+// This file is the split path of large scenes, the debug kernels and the
+// frame dispatcher; LDS-resident scenes render through the tile path
+// (tiles.hip, render_tiles_device), and what both share is in paths.hpp.
+//
 // Replaces the per-pixel, per-sample path integration of Cycles behind
 // bpy.ops.render.render (/root/reference/scripts/render-timing-script.py:90).
 #pragma clang fp contract(off)
 
-#include <hip/hip_runtime.h>
-
 #include <cstdlib>
-#include <map>
-#include <type_traits>
 #include <string>
 
-#include "device.hpp"
-
-#if RR_TILES_TU  // tiles.hip builds only k_tiles from this file: the other kernels go unused there
-#pragma clang diagnostic ignored "-Wunused-function"
-#else            // and k_tiles' helpers go unused here
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
-#endif
+#include "paths.hpp"
 
 namespace rr {
 
 namespace {
-
-constexpr int kFilterN = 1024;
-// Film sum order (every path, and oracle/rr_oracle.c): samples are summed in
-// order within groups of kFilmGroup, and the group sums in order into the
-// film (sum = 0; per group: sum += group). Frames of <= kFilmGroup samples
-// are the plain in-order sum. Groups let k_tiles split a tile's samples
-// across waves without changing a bit.
-#ifndef RR_FILM_GROUP
-#define RR_FILM_GROUP 32
-#endif
-constexpr int kFilmGroup = RR_FILM_GROUP;
-constexpr int kSrgbN = 4096;
-constexpr int kLightF = 12;
-constexpr int kMatF = 12;
-constexpr float kFltMax = 3.402823466e+38f;
 
 // Radiance record per path, 3 floats (12 B: dwordx3 loads/stores; a float4
 // record moved 33 % more bytes through the primary / accumulate stream).
@@ -87,135 +66,6 @@ struct ShadowQueue {
     float4* c;  // contribution.xyz, hull escape flag as in PathQueue::t
 };
 
-// Read-only scene data of the path kernels: in HBM (GlobalView) or, for
-// scenes small enough, staged once per block into LDS (LdsView), which turns
-// every node / triangle / material / filter fetch of the traversal and shading
-// chains into a ds_read (~64-cycle latency instead of an L1/L2 round trip).
-template <typename NodeP, typename TriP, typename FloatP>
-struct SceneView {
-    NodeP nodes;
-    TriP tris;
-    FloatP mats, lights, filter;
-    FloatP lut;  // material tables (kMatLutStride floats per material, build_material_lut)
-    lds_f4w* cam = nullptr;  // LDS scenes, camera kernels: 3 float4 per triangle (stage_camera)
-    // unit geometric normal + material per triangle: LDS scenes' staged copy
-    // (shading kernels), HBM scenes' DevScene::tnrm (RR_SHADE_NRM) — one
-    // member for both, so the LDS view passed to k_tiles' out-of-line calls
-    // stays the size it was
-    typename std::conditional<std::is_same<FloatP, lds_float*>::value, lds_f4w*, const float4*>::type nrm = nullptr;
-    lds_f4w* matd = nullptr;  // LDS scenes, shading kernels: each material with its derived terms (kMatDF4)
-    lds_f4w* onb = nullptr;   // LDS scenes, shading kernels: make_onb of both sides' normals (kOnbF4 per triangle)
-};
-// RR_SHADE_NRM (default): the split path's shading reads each hit triangle's
-// normal and material from DevScene::tnrm (16 B) instead of its 48 B record
-// and a cross product: shading per 02 / 03 / C5 frame slice 11.34 / 11.49 /
-// 9.18 -> 10.77 / 10.85 / 8.61 ms (profiles/r5_ab_spec.txt).
-#ifndef RR_SHADE_NRM
-#define RR_SHADE_NRM 1
-#endif
-using GlobalView = SceneView<const BvhNode*, const TriPack*, const float*>;
-using LdsView = SceneView<lds_node*, lds_tri*, lds_float*>;
-
-template <typename FloatP>
-__device__ __forceinline__ Mat load_mat(FloatP mats, int id) {
-    const FloatP m = mats + kMatF * id;
-    Mat r;
-    r.base = mk3(m[0], m[1], m[2]);
-    r.metallic = m[3];
-    r.specular = m[4];
-    r.roughness = m[5];
-    r.ior = m[6];
-    r.emission = mk3(m[7], m[8], m[9]);
-    r.model = (int)m[10];
-    return r;
-}
-
-// Material `id` with its derived BSDF terms: LDS-resident scenes stage them
-// per material (stage_scene: load_mat + mat_derive once per block, the same
-// operations, so the same bits), 4 float4 a shading point reads instead of
-// deriving them per sample; scenes in HBM derive at load.
-constexpr int kMatDF4 = 4;
-//   [0] base.xyz, roughness  [1] emission.xyz, model  [2] alpha, a2, kd0, spec_on  [3] cspec0.xyz, 0
-template <typename View>
-RR_D Mat view_mat(const View& v, int id) {
-    Mat m;
-    if constexpr (std::is_same<View, LdsView>::value) {
-        const lds_f4w* q = v.matd + kMatDF4 * id;
-        const float4 a = lds_ld4(q), b = lds_ld4(q + 1), c = lds_ld4(q + 2), d = lds_ld4(q + 3);
-        m.base = xyz(a);
-        m.roughness = a.w;
-        m.emission = xyz(b);
-        m.model = f2i(b.w);
-        m.alpha = c.x;
-        m.a2 = c.y;
-        m.kd0 = c.z;
-        m.spec_on = f2i(c.w);
-        m.cspec0 = xyz(d);
-        m.metallic = m.specular = m.ior = 0.0f;  // used by mat_derive only
-    } else {
-        m = load_mat(v.mats, id);
-        mat_derive(m);
-    }
-    return m;
-}
-
-// Camera ray for (pixel, sample): filter-importance-sampled subpixel position,
-// pinhole through the sensor plane at unit distance, z-depth clipping.
-// Screen rectangle of the scene box (screen_rect), or disabled.
-struct ScreenCull {
-    bool on = false;
-    float r[4];
-    RR_D bool outside(float fx, float fy) const {
-        return on && (fx < r[0] || fx > r[1] || fy < r[2] || fy > r[3]);
-    }
-};
-// From the root node's two child boxes (global or LDS nodes).
-template <typename NodeP>
-RR_D ScreenCull screen_cull(const FrameConsts& fc, NodeP nodes) {
-    ScreenCull sc;
-    if (fc.n_tris <= 0) return sc;
-    const BvhNode nd = load_node(nodes, 0);
-    const float lo[3] = {fminf(nd.a.x, nd.b.z), fminf(nd.a.y, nd.b.w), fminf(nd.a.z, nd.c.x)};
-    const float hi[3] = {fmaxf(nd.a.w, nd.c.y), fmaxf(nd.b.x, nd.c.z), fmaxf(nd.b.y, nd.c.w)};
-    sc.on = screen_rect(fc.cam_pos, fc.cam_right, fc.cam_up, fc.cam_back, fc.half_w, fc.half_h, (float)fc.W,
-                        (float)fc.H, lo, hi, sc.r);
-    return sc;
-}
-
-// culled (optional): set when the ray's subpixel position is outside the
-// scene's screen rectangle (the ray misses everything).
-template <typename FloatP>
-__device__ __forceinline__ void camera_ray_xy(const FrameConsts& fc, FloatP filt, int px, int py,
-                                              uint32_t key, float3& o, float3& d, float& tmin, float& tmax,
-                                              const ScreenCull* cull = nullptr, bool* culled = nullptr) {
-    // the subpixel pair: the 16-bit halves of the path key itself (a hash
-    // output, so no hash of its own; the other dimensions hash key + offset);
-    // both < 1: the filter table is read without its range branches
-    const float ux = (float)(key >> 16) * 1.52587890625e-05f, uy = (float)(key & 0xffffu) * 1.52587890625e-05f;
-    const float fx = (float)px + 0.5f + table_lerp_padded(filt, kFilterN, ux);
-    const float fy = (float)py + 0.5f + table_lerp_padded(filt, kFilterN, uy);
-    if (cull) {
-        *culled = cull->outside(fx, fy);
-        if (*culled) {  // a miss: no direction needed (shade() of a miss reads only T and the world)
-            o = fc.cam_pos;
-            d = mk3(0.0f, 0.0f, 1.0f);
-            tmin = 0.0f;
-            tmax = -1.0f;
-            return;
-        }
-    }
-    const float sx = fmaf(fx, fc.inv_w2, -1.0f) * fc.half_w;
-    const float sy = fmaf(-fy, fc.inv_h2, 1.0f) * fc.half_h;
-    const float len = sqrt_rn(fmaf(sy, sy, fmaf(sx, sx, 1.0f)));  // >= 1
-    const float3 dw = mk3(fmaf(fc.cam_up.x, sy, fmaf(fc.cam_right.x, sx, -fc.cam_back.x)),
-                          fmaf(fc.cam_up.y, sy, fmaf(fc.cam_right.y, sx, -fc.cam_back.y)),
-                          fmaf(fc.cam_up.z, sy, fmaf(fc.cam_right.z, sx, -fc.cam_back.z)));
-    const float il = rcp_rn(len);  // len in [1, 2^60]: the camera's half extents are finite
-    d = scl3(dw, il);
-    o = fc.cam_pos;
-    tmin = fc.clip_start * len;
-    tmax = fc.clip_end * len;
-}
 template <typename FloatP>
 __device__ __forceinline__ void camera_ray(const FrameConsts& fc, FloatP filt, int pix,
                                            uint32_t key, float3& o, float3& d, float& tmin, float& tmax,
@@ -224,559 +74,9 @@ __device__ __forceinline__ void camera_ray(const FrameConsts& fc, FloatP filt, i
     camera_ray_xy(fc, filt, pix - py * fc.W, py, key, o, d, tmin, tmax, cull, culled);
 }
 
-// Staged material word of LDS-resident scenes: material id | hull_flags << kHullShift.
-constexpr int kHullShift = 30;
-constexpr int kOnbF4 = 4;  // staged shading frames per triangle (stage_scene)
-
-struct ShadeOut {
-    bool cont, shadow;
-    bool esc;                // the rays leave a hull side of the hit triangle (hull_flags): they meet nothing
-    float3 o, d, T;          // continuation ray + throughput
-    uint32_t lob;            // continuation's lobe bounce counters (lobe_counts)
-    float3 so, sd, sc;       // shadow ray + pending contribution
-    float sdist;
-};
-
-// Per-lobe bounce counters of a path (Cycles path state diffuse_bounce /
-// glossy_bounce, intern/cycles/kernel/integrator/path_state.h path_state_next),
-// packed: diffuse scatters in bits 0..15, glossy scatters in bits 16..31.
-constexpr uint32_t kGlossyOne = 0x10000u;
-// Whether the path ends at this hit (emission only, no NEE, no scatter): the
-// scatter that brought it here advanced a counter to its cap. Cycles marks the
-// path PATH_RAY_TERMINATE_AFTER_TRANSPARENT when bounce >= max_bounce,
-// diffuse_bounce >= max_diffuse_bounce or glossy_bounce >= max_glossy_bounce
-// after the increment; the caps here are >= 1 (setup_frame), so a cap of 0
-// ("direct light only") behaves as Cycles': the camera hit still scatters once.
-template <typename FC>
-RR_D bool path_capped(const FC& fc, int bounce, uint32_t lob) {
-    return bounce >= fc.max_bounces || (int)(lob & 0xffffu) >= fc.max_diffuse || (int)(lob >> 16) >= fc.max_glossy;
-}
-
-RR_D void add_to(float3& L, float3 c) {
-    L.x = L.x + c.x;
-    L.y = L.y + c.y;
-    L.z = L.z + c.z;
-}
-
-// Shadow rays of shade(): handed back in ShadeOut (queue kernels) ...
-struct EmitShadow {
-    static constexpr bool kInline = false;
-    RR_D bool operator()(float3, float3, float) const { return false; }
-};
-
-// K9: shade one path at `bounce` given its closest hit; L updated in place.
-// With an inline shadow tracer (Shadow::kInline: a functor returning whether
-// the ray (origin, direction, distance) is occluded) the NEE ray is traced as
-// soon as it exists and its contribution added, before the continuation is
-// sampled: the same radiance additions in the same order as emitting it
-// (emission, then NEE, then the next bounce), with the shadow-ray state dead
-// before the continuation's registers are needed. out.shadow still reports
-// that a shadow ray was traced.
-// ... and the continuation: handed back in ShadeOut (out.o / d / T / lob), or,
-// with an in-place handler (Cont::kInline: called as on_cont(origin,
-// direction, throughput, lobe counters, leaves a hull side, L)), taken over at
-// the point it is sampled, so that its ray is never held past shade() (k_tiles:
-// held to the sample loop's join, the compiler spilled it to scratch in every
-// sample, most of that kernel's HBM write traffic).
-struct EmitCont {
-    static constexpr bool kInline = false;
-    RR_D void operator()(float3, float3, float3, uint32_t, bool, float3&) const {}
-};
-
-// FC: FrameConsts or ShadeConsts (the fields shade() reads: world,
-// clamp_indirect, the bounce caps, n_lights).
-template <typename View, typename Shadow = EmitShadow, typename FC = FrameConsts, typename Cont = EmitCont>
-__device__ __forceinline__ void shade(const FC& fc, int bounce, const View& v, float3 o, float3 d,
-                                      float3 T, uint32_t lob, const Hit& h, uint32_t key, float3& L, ShadeOut& out,
-                                      const Shadow& trace_shadow = Shadow{}, const Cont& on_cont = Cont{}) {
-    out.cont = false;
-    out.shadow = false;
-    out.esc = false;
-    if (h.idx < 0) {
-        float3 c = mul3(T, fc.world);
-        if (bounce > 0) c = clamp_contrib(c, fc.clamp_indirect);
-        add_to(L, c);
-        return;
-    }
-    int mid;
-    float3 N;
-    uint32_t hull = 0;  // hull_flags of the hit triangle (LDS-resident scenes)
-    if constexpr (std::is_same<View, LdsView>::value) {
-        const float4 nm = lds_ld4(v.nrm + h.idx);  // staged: norm3(cross3(e1, e2)), material id | hull flags
-        N = xyz(nm);
-        mid = f2i(nm.w) & ((1 << kHullShift) - 1);
-        hull = (uint32_t)f2i(nm.w) >> kHullShift;
-        // an LDS-resident scene holds a handful of materials (scene_lds_f4): the
-        // table offsets become 24-bit multiplies (full rate) instead of
-        // v_mul_lo_u32 / v_mad_u64_u32
-        __builtin_assume(mid >= 0 && mid < 4096);
-    } else if (RR_SHADE_NRM && v.nrm) {
-        const float4 nm = v.nrm[h.idx];  // k_tri_nrm: the same normal, precomputed
-        N = xyz(nm);
-        mid = f2i(nm.w);
-    } else {
-        const TriPack tp = load_tri(v.tris, h.idx);
-        mid = f2i(tp.p1.w);
-        N = norm3(cross3(sub3(xyz(tp.p1), xyz(tp.p0)), sub3(xyz(tp.p2), xyz(tp.p0))));
-    }
-    const Mat m = view_mat(v, mid);
-    const auto lut = v.lut + kMatLutStride * mid;
-    const float t = h.t;
-    const float3 P = madd3(o, d, t);
-    const bool flip = dot3(N, d) > 0.0f;
-    if (flip) N = mk3(-N.x, -N.y, -N.z);
-    // shadow and continuation rays leave on N's side: the front side unless flipped
-    const bool esc = ((hull >> (flip ? 1 : 0)) & 1u) != 0u;
-    out.esc = esc;
-    const float3 wo = mk3(-d.x, -d.y, -d.z);
-    if (m.emission.x != 0.0f || m.emission.y != 0.0f || m.emission.z != 0.0f) {
-        float3 c = mul3(T, m.emission);
-        if (bounce > 0) c = clamp_contrib(c, fc.clamp_indirect);
-        add_to(L, c);
-    }
-    if (path_capped(fc, bounce, lob)) return;
-    const BsdfView vw = bsdf_view(m, lut, N, wo);
-    const uint32_t dim0 = 2u + (uint32_t)(kDimsPerBounce * bounce);
-    // dimension pairs of this bounce (rng2): (light pick, lobe choice) at
-    // dim0, the disk point at dim0 + 1, the BSDF direction at dim0 + 4;
-    // Russian roulette keeps dim0 + 6 (oracle/rr_oracle.c radiance)
-    float u_light, u_lobe;
-    rng2(key, dim0, u_light, u_lobe);
-    const float3 Po = offset_ray(P, N);
-    // next-event estimation toward one uniformly chosen light
-    if (fc.n_lights > 0) {
-        int li = (int)(u_light * (float)fc.n_lights);
-        if (li > fc.n_lights - 1) li = fc.n_lights - 1;
-        __builtin_assume(li >= 0 && li < kMaxLights);  // rng >= 0, n_lights <= kMaxLights (setup_frame)
-        const auto lt = v.lights + kLightF * li;
-        float3 wi, Li;  // Li: radiance x cos_light / pdf (solid angle), i.e. I*cos/d^2
-        float dist;
-        if (lt[0] == 0.0f) {  // point / disk light
-            const float3 lp = mk3(lt[1], lt[2], lt[3]);
-            const float radius = lt[7];
-            const float3 I = mk3(lt[8], lt[9], lt[10]);
-            const float3 tl = sub3(lp, P);
-            const float dl2 = dot3(tl, tl);
-            if (radius > 0.0f) {
-                float sl, rl;
-                sqrt_rcp_any(dl2, sl, rl);
-                const float3 wl = scl3(tl, rl);
-                float3 b1, b2;
-                make_onb(wl, b1, b2);
-                float dx, dy;
-                float u1, u2;
-                rng2(key, dim0 + 1u, u1, u2);
-                concentric_disk(u1, u2, dx, dy);
-                dx = dx * radius;
-                dy = dy * radius;
-                const float3 sp = madd3(madd3(lp, b1, dx), b2, dy);
-                const float3 ts = sub3(sp, P);
-                const float ds2 = dot3(ts, ts);
-                float id;
-                sqrt_rcp_any(ds2, dist, id);
-                wi = scl3(ts, id);
-                const float cl = fabsf(dot3(wl, wi));
-                Li = scl3(I, cl * id * id);
-            } else {
-                float id;
-                sqrt_rcp_any(dl2, dist, id);
-                wi = scl3(tl, id);
-                Li = scl3(I, 1.0f / dl2);
-            }
-        } else {  // sun: delta direction, irradiance
-            wi = mk3(-lt[4], -lt[5], -lt[6]);
-            dist = kFltMax;
-            Li = mk3(lt[8], lt[9], lt[10]);
-        }
-        const float cosN = dot3(N, wi);
-        if (cosN > 0.0f) {
-            float pdf;
-            const float3 f = bsdf_eval_v(m, lut, vw, N, wo, wi, pdf);  // f * cosN
-            const float k = (float)fc.n_lights;
-            float3 c = mk3(T.x * f.x * k * Li.x, T.y * f.y * k * Li.y, T.z * f.z * k * Li.z);
-            if (bounce > 0) c = clamp_contrib(c, fc.clamp_indirect);
-            if (max3f(c) > 0.0f) {
-                out.shadow = true;
-                if constexpr (Shadow::kInline) {
-                    if (esc || !trace_shadow(Po, wi, dist)) add_to(L, c);
-                } else {
-                    out.so = Po;
-                    out.sd = wi;
-                    out.sdist = dist;
-                    out.sc = c;
-                }
-            }
-        }
-    }
-    // continue the path
-    float3 wi, f;
-    float pdf;
-    bool glossy;
-    float u_b1, u_b2;
-    rng2(key, dim0 + 4u, u_b1, u_b2);
-    bool sampled;
-    if constexpr (std::is_same<View, LdsView>::value) {  // the staged frame of the hit side
-        const lds_f4w* fr = v.onb + kOnbF4 * h.idx + (flip ? 2 : 0);
-        const float4 tb = lds_ld4(fr), bb = lds_ld4(fr + 1);
-        sampled = bsdf_sample_onb(m, lut, vw, N, xyz(tb), mk3(tb.w, bb.x, bb.y), wo, u_lobe, u_b1, u_b2, wi, f, pdf,
-                                  glossy);
-    } else {
-        sampled = bsdf_sample(m, lut, vw, N, wo, u_lobe, u_b1, u_b2, wi, f, pdf, glossy);
-    }
-    if (!sampled) return;
-    const float k = 1.0f / pdf;  // f = f * cosL already
-    T = mk3(T.x * f.x * k, T.y * f.y * k, T.z * f.z * k);
-    if (!(max3f(T) > 0.0f)) return;
-    if (bounce >= kRrStartBounce) {
-        const float q = fminf(max3f(T), 1.0f);
-        if (rng(key, dim0 + 6u) >= q) return;
-        const float iq = 1.0f / q;
-        T = mk3(T.x * iq, T.y * iq, T.z * iq);
-    }
-    out.cont = true;
-    if constexpr (Cont::kInline) {
-        on_cont(Po, wi, T, lob + (glossy ? kGlossyOne : 1u), esc, L);
-        return;
-    }
-    out.o = Po;
-    out.d = wi;
-    out.T = T;
-    out.lob = lob + (glossy ? kGlossyOne : 1u);
-}
-
-// The frame constants shade() reads, for the out-of-line continuation of the
-// tile kernel's paths (tiles_continue): passed by value, because a reference
-// to the kernel's FrameConsts argument would put the whole struct in scratch.
-struct ShadeConsts {
-    float3 world;
-    float clamp_indirect;
-    int max_bounces, max_diffuse, max_glossy, n_lights, n_tris;
-};
-
-constexpr int kWavesPerBlock = kBlock / 64;
-constexpr int kMaxBlocksPerCu = 8;  // grid cap per CU
-
 RR_D uint32_t wave_id() { return blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); }
 
-// Traversal-count reduction (RR_FLAG_COUNT_TRAVERSAL only).
-__device__ __forceinline__ void flush_counts(unsigned long long* __restrict__ tc, int slot, uint32_t nv,
-                                             uint32_t nt) {
-    unsigned long long a = nv, b = nt;
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off);
-        b += __shfl_xor(b, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&tc[slot], a);
-        atomicAdd(&tc[slot + 1], b);
-    }
-}
-
-}  // namespace
-struct SceneArgs {
-    const BvhNode* nodes;
-    const QNode6* qnodes;    // quantised 6-wide hierarchy (split path)
-    const TriPack* tris;
-    const float* mats;
-    const float* lights;
-    const float* filter;
-    const float* mat_lut;    // kMatLutStride floats per material
-    int n_nodes, n_tris, n_mats, n_lights;
-    int n_qnodes;            // its node count
-};
-
-namespace {
 RR_D GlobalView global_view(const SceneArgs& a) { return {a.nodes, a.tris, a.mats, a.lights, a.filter, a.mat_lut}; }
-
-RR_D void lds_copy(lds_f4w* dst, const float4* __restrict__ src, int n4) {
-    const rr_f4v* s = reinterpret_cast<const rr_f4v*>(src);
-    for (int i = threadIdx.x; i < n4; i += kBlock) dst[i] = s[i];
-}
-// Hull flags of an LDS-resident scene's triangle i (oracle/rr_oracle.c
-// tri_hull, the same float operations): bit 0 when every vertex of every
-// triangle lies behind triangle i's plane on its front side (the cross(e1, e2)
-// direction, e1 = v1 - v0, e2 = v2 - v0), up to 2^-12 of the vertex's distance
-// from v0 times |n|_1; bit 1
-// the same for the back side. A ray leaving the triangle on a side whose bit is
-// set moves away from a plane the whole scene lies behind: it meets nothing, so
-// its continuation misses and its shadow ray is unoccluded without a traversal
-// (the tests skipped could only report rounding-level grazing hits). On 04vs /
-// 01 (a cube) every face is such a side: no secondary ray is traversed. Kept in
-// bits kHullShift.. of the staged material word (shade() reads that word anyway).
-RR_D uint32_t hull_flags(lds_tri* tris, int n_tris, int i) {
-    const TriPack s = load_tri(tris, i);
-    const float3 v0 = xyz(s.p0), n = cross3(sub3(xyz(s.p1), v0), sub3(xyz(s.p2), v0));
-    const float an = fabsf(n.x) + fabsf(n.y) + fabsf(n.z);
-    bool front = true, back = true;
-    for (int j = 0; j < n_tris; ++j) {
-        const TriPack e = load_tri(tris, j);
-        const float3 w[3] = {xyz(e.p0), xyz(e.p1), xyz(e.p2)};
-        for (int k = 0; k < 3; ++k) {
-            const float3 r = sub3(w[k], v0);
-            const float h = dot3(n, r);
-            const float lim = an * (fabsf(r.x) + fabsf(r.y) + fabsf(r.z)) * 0x1p-12f;
-            front = front && h <= lim;
-            back = back && -h <= lim;
-        }
-    }
-    return (front ? 1u : 0u) | (back ? 2u : 0u);
-}
-
-// Stages the scene at the start of dynamic LDS (all threads call; ends with a
-// barrier). `shading`: also materials, lights and the filter table. Returns the
-// view; `used` receives the float4 slots taken (LDS layout: scene_lds_f4()).
-// Camera-ray data of one triangle (sorted index i), staged next to the scene
-// by the kernels that trace camera rays of LDS-resident scenes: every camera
-// ray starts at the camera, so woop_test's vertices relative to the origin,
-// v - o, are computed once per block (the same float operations, so
-// camera_hit's t / u / v are bit-identical to woop_test's) — in each of the
-// three axis permutations of rot3, so that a ray reads its own (kz) with a
-// per-lane LDS address instead of permuting per test (18 selects per triangle
-// test) — and the triangle's screen rectangle (tri_screen_rect) bins it to the
-// 8x8 tiles whose samples can hit it.
-//   [13i + 3kz + k] = (rot3(v_k - o, kz), orig id for k = 0, else 0), kz, k = 0..2
-//   [13i + 9] = (x0, x1, y0, y1), [13i + 10..12] = the screen edge lines
-// Screen rectangle of a triangle (pixels, one pixel of slack) and its three
-// edge lines e[k] = (nx, ny, c): nx*x + ny*y + c >= 0 inside, |n| = 1, so the
-// value is a signed distance in pixels. A triangle at or behind the camera
-// plane, or degenerate on screen, keeps the unbounded rectangle / edges that
-// every point satisfies.
-RR_D void tri_screen_rect(const FrameConsts& fc, const float3 p[3], float r[4], float e[3][3]) {
-    float x0 = kFltMax, x1 = -kFltMax, y0 = kFltMax, y1 = -kFltMax;
-    float fx[3], fy[3];
-    for (int k = 0; k < 3; ++k) e[k][0] = e[k][1] = 0.0f, e[k][2] = 1.0f;
-    for (int k = 0; k < 3; ++k) {
-        const float3 v = sub3(p[k], fc.cam_pos);
-        const float depth = -dot3(v, fc.cam_back);
-        if (!(depth > 1.0e-4f)) {  // at or behind the camera plane: no bound, every tile keeps it
-            r[0] = r[2] = -kFltMax;
-            r[1] = r[3] = kFltMax;
-            return;
-        }
-        const float sx = dot3(v, fc.cam_right) / depth;
-        const float sy = dot3(v, fc.cam_up) / depth;
-        fx[k] = (sx / fc.half_w + 1.0f) * ((float)fc.W * 0.5f);
-        fy[k] = (1.0f - sy / fc.half_h) * ((float)fc.H * 0.5f);
-        x0 = fminf(x0, fx[k]);
-        x1 = fmaxf(x1, fx[k]);
-        y0 = fminf(y0, fy[k]);
-        y1 = fmaxf(y1, fy[k]);
-    }
-    r[0] = x0 - 1.0f;  // a pixel of slack covers rounding, as screen_rect's
-    r[1] = x1 + 1.0f;
-    r[2] = y0 - 1.0f;
-    r[3] = y1 + 1.0f;
-    const float area = (fx[1] - fx[0]) * (fy[2] - fy[0]) - (fy[1] - fy[0]) * (fx[2] - fx[0]);
-    if (!(fabsf(area) > 1.0e-3f)) return;  // (near-)degenerate on screen: edges stay open
-    const float sgn = area > 0.0f ? 1.0f : -1.0f;
-    for (int k = 0; k < 3; ++k) {
-        const int a = k, b = (k + 1) % 3;
-        float nx = -(fy[b] - fy[a]) * sgn, ny = (fx[b] - fx[a]) * sgn;  // towards the third vertex
-        const float len = sqrtf(nx * nx + ny * ny);
-        nx = nx / len;
-        ny = ny / len;
-        e[k][0] = nx;
-        e[k][1] = ny;
-        e[k][2] = -(nx * fx[a] + ny * fy[a]);
-    }
-}
-
-// Camera-ray data per triangle in LDS: the vertices relative to the camera in
-// the three permutations (9 float4), the screen rectangle, the three screen
-// edge lines.
-constexpr int kCamF4 = 13;
-constexpr int kCamRect = 9;  // float4 offset of the screen rectangle, the edge lines follow
-RR_D void stage_camera(lds_f4w* q, lds_tri* tris, int n_tris, const FrameConsts& fc) {
-    for (int i = threadIdx.x; i < n_tris; i += kBlock) {
-        const TriPack tp = load_tri(tris, i);
-        const float3 pts[3] = {xyz(tp.p0), xyz(tp.p1), xyz(tp.p2)};
-        float r[4], e[3][3];
-        tri_screen_rect(fc, pts, r, e);
-        for (int k = 0; k < 3; ++k) {
-            const float3 a = sub3(pts[k], fc.cam_pos);
-            for (int kz = 0; kz < 3; ++kz) {
-                const float3 r = rot3(a, kz);
-                rr_f4v x;
-                x.x = r.x; x.y = r.y; x.z = r.z; x.w = k == 0 ? tp.p0.w : 0.0f;
-                q[kCamF4 * i + 3 * kz + k] = x;
-            }
-        }
-        rr_f4v c;
-        c.x = r[0]; c.y = r[1]; c.z = r[2]; c.w = r[3];
-        q[kCamF4 * i + kCamRect] = c;
-        for (int k = 0; k < 3; ++k) {
-            rr_f4v l;
-            l.x = e[k][0]; l.y = e[k][1]; l.z = e[k][2]; l.w = 0.0f;
-            q[kCamF4 * i + kCamRect + 1 + k] = l;
-        }
-    }
-}
-
-// kCam: also stage the camera-ray data (stage_camera, from *cam_fc) after the
-// scene. A compile-time switch, not a null test on cam_fc: comparing the
-// address of the kernel's FrameConsts argument with null kept the whole
-// struct in scratch (180 B per lane, every field read with a scratch load).
-template <bool kCam = false>
-RR_D LdsView stage_scene(lds_f4w* base, const SceneArgs& a, bool shading, int& used,
-                         const FrameConsts* cam_fc = nullptr) {
-    lds_f4w* q = base;
-    LdsView v;
-    v.nodes = (lds_node*)q;
-    lds_copy(q, reinterpret_cast<const float4*>(a.nodes), 4 * a.n_nodes);
-    q += 4 * a.n_nodes;
-    v.tris = (lds_tri*)q;
-    lds_copy(q, reinterpret_cast<const float4*>(a.tris), kTriF4 * a.n_tris);
-    q += kTriF4 * a.n_tris;
-    v.mats = v.lights = v.filter = v.lut = nullptr;
-    if (shading) {
-        v.mats = (lds_float*)q;
-        lds_copy(q, reinterpret_cast<const float4*>(a.mats), 3 * a.n_mats);
-        q += 3 * a.n_mats;
-        v.lights = (lds_float*)q;
-        lds_copy(q, reinterpret_cast<const float4*>(a.lights), 3 * a.n_lights);
-        q += 3 * a.n_lights;
-        v.filter = (lds_float*)q;
-        lds_copy(q, reinterpret_cast<const float4*>(a.filter), kFilterN / 4);
-        q += kFilterN / 4;
-        v.lut = (lds_float*)q;
-        lds_copy(q, reinterpret_cast<const float4*>(a.mat_lut), kMatLutStride / 4 * a.n_mats);
-        q += kMatLutStride / 4 * a.n_mats;
-    }
-    if (shading || kCam) __syncthreads();  // the copies above are visible
-    if (shading) {  // per-triangle unit normals, material ids and hull flags (shade() reads no TriPack)
-        v.nrm = q;
-        for (int i = threadIdx.x; i < a.n_tris; i += kBlock) {
-            const TriPack tp = load_tri(v.tris, i);
-            const float3 n = norm3(cross3(sub3(xyz(tp.p1), xyz(tp.p0)), sub3(xyz(tp.p2), xyz(tp.p0))));
-            rr_f4v x;
-            x.x = n.x; x.y = n.y; x.z = n.z;
-            x.w = i2f(f2i(tp.p1.w) | (int)(hull_flags(v.tris, a.n_tris, i) << kHullShift));
-            q[i] = x;
-        }
-        q += a.n_tris;
-        v.matd = q;  // derived material records (view_mat)
-        for (int i = threadIdx.x; i < a.n_mats; i += kBlock) {
-            Mat m = load_mat(v.mats, i);
-            mat_derive(m);
-            rr_f4v r0, r1, r2, r3;
-            r0.x = m.base.x; r0.y = m.base.y; r0.z = m.base.z; r0.w = m.roughness;
-            r1.x = m.emission.x; r1.y = m.emission.y; r1.z = m.emission.z; r1.w = i2f(m.model);
-            r2.x = m.alpha; r2.y = m.a2; r2.z = m.kd0; r2.w = i2f(m.spec_on);
-            r3.x = m.cspec0.x; r3.y = m.cspec0.y; r3.z = m.cspec0.z; r3.w = 0.0f;
-            q[kMatDF4 * i] = r0;
-            q[kMatDF4 * i + 1] = r1;
-            q[kMatDF4 * i + 2] = r2;
-            q[kMatDF4 * i + 3] = r3;
-        }
-        q += kMatDF4 * a.n_mats;
-        // the shading frame (T, B) = make_onb(N) of both sides of each
-        // triangle, computed here once instead of per sample (the same
-        // operations, so the same bits): side s at [kOnbF4 i + 2 s] = (T, B.x),
-        // [kOnbF4 i + 2 s + 1] = (B.y, B.z, -, -)
-        v.onb = q;
-        __syncthreads();  // the normals above are visible
-        for (int j = threadIdx.x; j < 2 * a.n_tris; j += kBlock) {
-            const int i = j >> 1, side = j & 1;
-            const float4 nm = lds_ld4(v.nrm + i);
-            const float3 n = side ? mk3(-nm.x, -nm.y, -nm.z) : xyz(nm);
-            float3 t, b;
-            make_onb(n, t, b);
-            rr_f4v x, y;
-            x.x = t.x; x.y = t.y; x.z = t.z; x.w = b.x;
-            y.x = b.y; y.y = b.z; y.z = 0.0f; y.w = 0.0f;
-            q[kOnbF4 * i + 2 * side] = x;
-            q[kOnbF4 * i + 2 * side + 1] = y;
-        }
-        q += kOnbF4 * a.n_tris;
-    }
-    if constexpr (kCam) {
-        v.cam = q;
-        stage_camera(q, v.tris, a.n_tris, *cam_fc);
-        q += kCamF4 * a.n_tris;
-    }
-    used = (int)(q - base);
-    __syncthreads();
-    return v;
-}
-
-// Closest hit of a camera ray (origin fc.cam_pos) over the triangles whose bits
-// are set in the wave-uniform mask {m0, m1} (sorted indices 0..127): woop_test
-// with the staged vertices relative to the camera, closest_tri's accept rule. The
-// rule is order-independent (smaller t, then smaller original id), so the
-// result equals testing every triangle whenever the mask holds every triangle
-// the ray can hit (tile_mask). LDS-resident scenes trace camera rays this way
-// instead of walking the LBVH; oracle/rr_oracle.c brute-forces them the same.
-RR_D void set_miss(Hit& h, float tmax) {
-    h.t = tmax;
-    h.u = h.v = 0.0f;
-    h.idx = -1;
-    h.orig = -1;
-}
-template <bool kCount>
-RR_D void camera_tris(const LdsView& v, uint64_t m0, uint64_t m1, const Shear& sh, int kz, float tmin, Hit& h,
-                      TravCount& cnt) {
-    for (int w = 0; w < 2; ++w) {
-        uint64_t m = w ? m1 : m0;
-        while (m) {
-            const int i = (int)__builtin_ctzll(m) + 64 * w;
-            m &= m - 1;
-            if (kCount) ++cnt.tris;
-            const lds_f4w* q = v.cam + kCamF4 * i + 3 * kz;  // this ray's permutation
-            const float4 ca = lds_ld4(q), cb = lds_ld4(q + 1), cc = lds_ld4(q + 2);
-            float t, u, vv;
-            if (woop_core(sh, xyz(ca), xyz(cb), xyz(cc), t, u, vv)) {
-                const int orig = f2i(ca.w);
-                if (closer(t, orig, tmin, h)) {
-                    h.t = t;
-                    h.u = u;
-                    h.v = vv;
-                    h.idx = i;
-                    h.orig = orig;
-                }
-            }
-        }
-    }
-}
-// The closest hit of a camera ray over the tile's mask (camera_tris with the
-// ray's own shear axis). A wave-uniform axis (a scalar kz, no per-lane
-// permutation or address offset; the camera rays of a tile nearly always share
-// it) measured no faster (04vs / 01 pipelined 946 / 965 against 953 / 972
-// frames/s) and is not kept.
-template <bool kCount>
-RR_D void camera_hit(const LdsView& v, uint64_t m0, uint64_t m1, float3 d, float tmin, float tmax, Hit& h,
-                     TravCount& cnt) {
-    set_miss(h, tmax);
-    // camera_ray_xy: d = dw / |dw|
-    const Shear sh = make_shear_unit(d);
-    camera_tris<kCount>(v, m0, m1, sh, sh.kz, tmin, h, cnt);
-}
-
-// Triangles whose screen rectangle meets the sample positions of pixels
-// [x0, x1] x [y0, y1] (centres + filter offsets below fc.filter_reach), as a
-// wave-uniform 128-bit mask; n_tris <= 128 (every LDS-resident scene).
-RR_D void tile_mask(const FrameConsts& fc, const LdsView& v, int n_tris, float x0, float x1, float y0, float y1,
-                    uint64_t& m0, uint64_t& m1) {
-    const float r = fc.filter_reach;
-    const float X0 = x0 + 0.5f - r, X1 = x1 + 0.5f + r, Y0 = y0 + 0.5f - r, Y1 = y1 + 0.5f + r;
-    uint64_t a = 0, b = 0;
-    for (int i = 0; i < n_tris; ++i) {
-        const float4 q = lds_ld4(v.cam + kCamF4 * i + kCamRect);
-        bool in = !(q.y < X0 || q.x > X1 || q.w < Y0 || q.z > Y1);
-        for (int k = 0; k < 3 && in; ++k) {  // the expanded tile wholly outside an edge (+1 px of slack)
-            const float4 l = lds_ld4(v.cam + kCamF4 * i + kCamRect + 1 + k);
-            const float m = l.x * (l.x > 0.0f ? X1 : X0) + l.y * (l.y > 0.0f ? Y1 : Y0) + l.z;
-            in = m >= -1.0f;
-        }
-        if (in) {
-            if (i < 64) a |= 1ull << i;
-            else b |= 1ull << (i - 64);
-        }
-    }
-    m0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32) |
-         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-    m1 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
-         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-}
 
 // ------------------------------------------------------------------------
 // Split path for scenes that do not fit in LDS (C4/C5-sized BVHs): traversal
@@ -1719,18 +1019,6 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_shadow_refill(Scen
 
 // K11 (+K12 on the last chunk): film += radiance of this chunk's samples in
 // sample order; then mean -> exposure -> view transform -> 8-bit.
-RR_D uchar4 tonemap(const FrameConsts& fc, float4 acc, const float* __restrict__ srgb) {
-    float c[3] = {acc.x * fc.inv_spp * fc.exposure_scale, acc.y * fc.inv_spp * fc.exposure_scale,
-                  acc.z * fc.inv_spp * fc.exposure_scale};
-    uint8_t q[3];
-    for (int k = 0; k < 3; ++k) {
-        float v = fminf(fmaxf(c[k], 0.0f), 1.0f);
-        if (fc.view_transform == 0) v = srgb_oetf(v, srgb, kSrgbN);
-        q[k] = quantize8(v);
-    }
-    return make_uchar4(q[0], q[1], q[2], 255);
-}
-
 // Film sum in the grouped order (kFilmGroup, rr_device.h): the open group's
 // partial sum crosses chunk boundaries in `part` (touched only by frames of
 // several chunks).
@@ -1806,619 +1094,6 @@ __global__ __launch_bounds__(kBlock) void k_world(FrameConsts fc, float4* __rest
     for (int pix = blockIdx.x * kBlock + threadIdx.x; pix < fc.npix; pix += gridDim.x * kBlock) {
         film[pix] = acc;
         out[pix] = px;
-    }
-}
-
-// K-tiles (LDS-resident scenes): one wave per 8x8 pixel tile
-// runs every sample of its 64 pixels to completion — raygen, closest hit,
-// shade, the NEE shadow ray traced inline, continuation — adds each path's
-// radiance to its pixel's film sum in registers in sample order, then writes
-// the film and the tonemapped pixel once. No radiance records, no queues, no
-// accumulate pass: the per-path HBM stream of the wavefront kernels (12 B
-// record written + read, 48 B per queued ray) disappears. A path's radiance
-// additions keep their order (emission(0), NEE(0), emission(1), ...) and the
-// film sum runs over samples 0..spp-1 like k_accumulate's, so the result is
-// bit-identical to the wavefront kernels and to the oracle.
-// Tiles come from an atomic counter (one atomic per wave per tile), those
-// overlapping the scene's screen rectangle first: they carry the traversal
-// and shading work, so the long tiles start early and the background tiles,
-// whose samples are all culled camera rays, fill the tail.
-constexpr int kTile = 8;  // 8x8 pixels = one wave
-#ifndef RR_TILE_SHARDS
-#define RR_TILE_SHARDS 8
-#endif
-constexpr int kTileShards = RR_TILE_SHARDS;  // k_tiles unit counters (one per block % 8)
-constexpr int kTileCtrStride = 32;  // words between them (128 B)
-
-struct TileOrder {
-    int tx, n;               // tiles per row, tiles in the frame
-    int bx0, by0, bw, bh;    // tile box over the screen rectangle (bw = bh = 0: none)
-    // i-th tile: first the box row-major, then the rest row-major (wave-uniform).
-    RR_D void at(int i, int& x, int& y) const {
-        const int nb = bw * bh;
-        if (i < nb) {
-            y = i / bw;
-            x = bx0 + (i - y * bw);
-            y += by0;
-            return;
-        }
-        int j = i - nb;
-        const int ntop = by0 * tx;
-        if (j < ntop) {
-            y = j / tx;
-            x = j - y * tx;
-            return;
-        }
-        j -= ntop;
-        const int rw = tx - bw, nmid = bh * rw;
-        if (j < nmid) {
-            const int r = j / rw, cx = j - r * rw;
-            y = by0 + r;
-            x = cx < bx0 ? cx : cx + bw;
-            return;
-        }
-        j -= nmid;
-        y = j / tx;
-        x = j - y * tx;
-        y += by0 + bh;
-    }
-};
-
-// Tile box of the pixels whose samples can fall inside the screen rectangle
-// (filter offsets are below 2 px). Scheduling only: every sample still takes
-// its own culling test, so the box never changes a result.
-RR_D TileOrder tile_order(const FrameConsts& fc, const ScreenCull& sc) {
-    TileOrder to;
-    to.tx = (fc.W + kTile - 1) / kTile;
-    const int ty = (fc.H + kTile - 1) / kTile;
-    to.n = to.tx * ty;
-    to.bx0 = to.by0 = 0;
-    to.bw = to.tx;
-    to.bh = ty;
-    if (!sc.on) return to;  // no rectangle: every tile may carry work
-    const float m = fc.filter_reach + 1.0f;
-    const float x0 = fmaxf(sc.r[0] - m, 0.0f), x1 = fminf(sc.r[1] + m, (float)fc.W - 1.0f);
-    const float y0 = fmaxf(sc.r[2] - m, 0.0f), y1 = fminf(sc.r[3] + m, (float)fc.H - 1.0f);
-    if (!(x0 <= x1 && y0 <= y1)) {
-        to.bw = to.bh = 0;
-        return to;
-    }
-    to.bx0 = (int)x0 / kTile;
-    to.by0 = (int)y0 / kTile;
-    to.bw = (int)x1 / kTile - to.bx0 + 1;
-    to.bh = (int)y1 / kTile - to.by0 + 1;
-    return to;
-}
-
-// Whether no sample of tile (tx, ty) can land inside the screen rectangle:
-// every subpixel position is px + 0.5 + offset with |offset| < filter_reach
-// (which includes a pixel of rounding slack), so each sample's own test in
-// camera_ray_xy would cull it. Then every sample's radiance is exactly the
-// world term (T = 1 at bounce 0, no clamp).
-RR_D bool tile_culled(const FrameConsts& fc, const ScreenCull& sc, int tx, int ty) {
-    if (!sc.on) return false;
-    const float x0 = (float)(tx * kTile) + 0.5f, y0 = (float)(ty * kTile) + 0.5f;
-    const float x1 = x0 + (float)(kTile - 1), y1 = y0 + (float)(kTile - 1);
-    const float r = fc.filter_reach;
-    return x1 + r < sc.r[0] || x0 - r > sc.r[1] || y1 + r < sc.r[2] || y0 - r > sc.r[3];
-}
-
-RR_D int uniform_i(int x) { return __builtin_amdgcn_readfirstlane(x); }
-RR_D float uniform_f(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
-RR_D ScreenCull uniform_cull(ScreenCull c) {
-    c.on = uniform_i(c.on ? 1 : 0) != 0;
-    for (int k = 0; k < 4; ++k) c.r[k] = uniform_f(c.r[k]);
-    return c;
-}
-RR_D TileOrder uniform_order(TileOrder t) {
-    t.tx = uniform_i(t.tx);
-    t.n = uniform_i(t.n);
-    t.bx0 = uniform_i(t.bx0);
-    t.by0 = uniform_i(t.by0);
-    t.bw = uniform_i(t.bw);
-    t.bh = uniform_i(t.bh);
-    return t;
-}
-
-// Per-lane ray counts of the tile kernel, reduced once per wave at exit into
-// the chunk-0 counter pairs: {0, 1} = bounce 0, {2, 3} = all later bounces
-// (rr_api.cpp fill_stats sums the pairs); tail = the chunk's words from
-// camera_traced_slot on: [0] camera rays traced, [2] / [3] continuations /
-// shadow rays traversed (the out-of-line traversals; the other continuations
-// and shadow rays left a hull side and were resolved without a traversal,
-// rr_frame_stats *_escaped).
-RR_D void flush_rays(uint32_t* __restrict__ tot, uint32_t c0, uint32_t s0, uint32_t c1, uint32_t s1,
-                     uint32_t* __restrict__ tail, uint32_t t0, uint32_t ext_traced, uint32_t sh_traced) {
-    // the counts are wave totals (wave_count, TileTrav::wctr): lane 0 adds them
-    const uint32_t v[4] = {c0, s0, c1, s1};
-    if ((threadIdx.x & 63) == 0) {
-        for (int k = 0; k < 4; ++k)
-            if (v[k]) atomicAdd(&tot[k], v[k]);
-        if (t0) atomicAdd(&tail[0], t0);
-        if (ext_traced) atomicAdd(&tail[2], ext_traced);
-        if (sh_traced) atomicAdd(&tail[3], sh_traced);
-    }
-}
-
-// The tile kernel's secondary traversals as out-of-line functions: on the
-// scenes it renders they are rare (04vs / 01: a cube, every face a hull side,
-// so no shadow or continuation ray is traversed but for the odd path through
-// an edge crack), and inlined, their registers and control flow weighed on the
-// whole sample loop (A/B, 40 pipelined frames: 04vs 886 -> 907, 01 901 -> 923
-// frames/s; solo launches -1 %). Their state goes through the call's stack
-// frame; the register budget stays at 4 waves per SIMD (5 measured slower
-// solo, +-0 pipelined).
-// Everything the out-of-line traversals need, passed by value: the traversal
-// stack's LDS and HBM parts (the TravStack is built in the callee), the frame's
-// drop counter, this wave's LDS counters (wctr: [0] continuations and [1]
-// shadow rays of bounces >= 1, tiles_continue; [2] continuation and [3] shadow
-// rays traversed, rr_frame_stats *_escaped) and the counting pass's totals
-// (tc, null otherwise). Round 4 passed the stack and the counters by
-// reference, which put them (and the LdsView) in scratch: written by every
-// wave at launch, and every wave's scratch lines went back to HBM — most of
-// k_tiles' 124-140 MB of PMC traffic per launch against 41 MB compulsory.
-constexpr int kWctr = 8;  // LDS counter words per wave of k_tiles (TileTrav::wctr)
-#ifndef RR_TILES_LOG_ALWAYS
-#define RR_TILES_LOG_ALWAYS 0  // diagnostic builds: the unit log in every k_tiles launch, not only counting ones
-#endif
-struct TileTrav {
-    lds_int* lds;
-    int* spill;
-    int stride;
-    uint32_t* drops;
-    lds_uint* wctr;  // this wave's kWctr LDS words: [0] / [1] bounce-1.. continuation / shadow rays, [2] / [3]
-                     // traversed extension / shadow rays, counting launches: [4..7] their nodes / triangles
-    unsigned long long* tc;
-};
-// Active lanes of the wave whose predicate holds: the tile kernel's ray
-// counters are wave totals kept in scalar registers (no per-lane VGPRs live
-// across the unit loop).
-RR_D uint32_t wave_count(bool p) { return (uint32_t)__popcll(__ballot(p)); }
-// *p += n by the first active lane (n: a wave total).
-RR_D void wave_add(lds_uint* p, uint32_t n) {
-    if ((int)(threadIdx.x & 63) == (int)__builtin_ctzll(__ballot(true))) *p += n;
-}
-template <bool kCount>
-__device__ __noinline__ bool shadow_trace(LdsView v, int n_tris, float3 so, float3 sd, float dist, TileTrav tt) {
-    wave_add(tt.wctr + 3, wave_count(true));
-    TravStack st{tt.lds, tt.spill, tt.stride, 0, tt.drops};
-    TravCount cnt;
-    Hit hs;
-    const bool occ = traverse<true, kCount>(v.nodes, v.tris, n_tris, so, sd, 0.0f, dist, st, hs, cnt);
-    if (kCount) {  // the wave's LDS words, flushed once per wave (a global atomic per lane and call
-                   // serialised the counting launch on one address)
-        __hip_atomic_fetch_add(tt.wctr + 6, cnt.nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(tt.wctr + 7, cnt.tris, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return occ;
-}
-template <bool kCount>
-__device__ __noinline__ Hit ext_trace(LdsView v, int n_tris, float3 o, float3 d, TileTrav tt) {
-    wave_add(tt.wctr + 2, wave_count(true));
-    TravStack st{tt.lds, tt.spill, tt.stride, 0, tt.drops};
-    TravCount cnt;
-    Hit h;
-    traverse<false, kCount>(v.nodes, v.tris, n_tris, o, d, 0.0f, kFltMax, st, h, cnt);
-    if (kCount) {
-        __hip_atomic_fetch_add(tt.wctr + 4, cnt.nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(tt.wctr + 5, cnt.tris, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return h;
-}
-// The tile kernel's shadow rays, traced inside shade() (any hit over the
-// LDS-resident LBVH).
-template <bool kCount>
-struct InlineShadow {
-    static constexpr bool kInline = true;
-    LdsView v;
-    int n_tris;
-    TileTrav tt;
-    RR_D bool operator()(float3 so, float3 sd, float dist) const {
-        return shadow_trace<kCount>(v, n_tris, so, sd, dist, tt);
-    }
-};
-
-// Bounces 1 .. max_bounces of the tile kernel's paths whose camera hit
-// continues into the scene (the continuation does not leave a hull side):
-// out of line, so that the sample loop holds one shading point, bounce 0,
-// with its bounce-dependent terms folded (dimensions, clamp, Russian
-// roulette), and carries no bounce loop. On 04vs / 01 (a cube) no path gets
-// here but for a camera ray through an edge crack. The same shade() calls in
-// the same order as the loop it replaces, so the same bits. Measured against
-// the loop (three interleaved rounds, 04vs / 01 frame 5 / 20 at 128 spp):
-// solo 1.150 / 1.104 -> 1.068 / 1.021 ms, pipelined 995 / 1,030 -> 1,108 /
-// 1,167 frames/s. Returns L; the wave totals of its continuations and shadow
-// rays go to this wave's LDS counters tt.wctr[0..1]. (Built without
-// -amdgpu-prealloc-sgpr-spill-vgprs, which makes hipcc 7.2 crash on the call.)
-template <bool kCount>
-__device__ __noinline__ float3 tiles_continue(ShadeConsts sc, LdsView v, float3 o, float3 d, float3 T, uint32_t lob,
-                                              uint32_t key, float3 L, TileTrav tt) {
-    uint32_t nc = 0, ns = 0;
-    bool live = true;
-    for (int b = 1; b <= sc.max_bounces; ++b) {
-        if (!__any(live)) break;
-        bool cont = false, shadow = false;
-        if (live) {
-            ShadeOut so;
-            const Hit h = ext_trace<kCount>(v, sc.n_tris, o, d, tt);
-            shade(sc, b, v, o, d, T, lob, h, key, L, so, InlineShadow<kCount>{v, sc.n_tris, tt});
-            cont = so.cont;
-            shadow = so.shadow;
-            if (so.cont && so.esc) {  // leaves a hull side: the world term, as in tiles_body
-                add_to(L, clamp_contrib(mul3(so.T, sc.world), sc.clamp_indirect));
-                live = false;
-            } else if (so.cont) {
-                o = so.o;
-                d = so.d;
-                T = so.T;
-                lob = so.lob;
-            } else {
-                live = false;
-            }
-        }
-        nc += wave_count(cont);
-        ns += wave_count(shadow);
-    }
-    wave_add(tt.wctr, nc);
-    wave_add(tt.wctr + 1, ns);
-    return L;
-}
-
-// RR_TILES_CONT_INPLACE: bit 0 the whole-tile variant, bit 1 the sample-group
-// variant take the continuation inside shade() (else after it, from ShadeOut).
-#ifndef RR_TILES_CONT_INPLACE
-#define RR_TILES_CONT_INPLACE 1
-#endif
-// The bounce-0 continuation of k_tiles, taken over inside shade(): a ray that
-// leaves a hull side of its triangle meets the world (T x world, clamped, as
-// bounce 1's shade() would add it, and the path ends); any other goes on out
-// of line (tiles_continue).
-template <bool kCount>
-struct TileCont {
-    static constexpr bool kInline = true;
-    ShadeConsts sc;
-    LdsView v;
-    TileTrav tt;
-    uint32_t key;
-    RR_D void operator()(float3 o, float3 d, float3 T, uint32_t lob, bool esc, float3& L) const {
-        if (esc)
-            add_to(L, clamp_contrib(mul3(T, sc.world), sc.clamp_indirect));
-        else
-            L = tiles_continue<kCount>(sc, v, o, d, T, lob, key, L, tt);
-    }
-};
-
-// Sample-group slices of the box tiles (load balance: a heavy tile does not
-// run as one wave's unit at the end of the launch). Slab of tile t: one plane
-// per sample group g (group sum, 3 x 64 floats: x, y, z per lane), folded in
-// group order by k_tiles_fold after the launch. (An in-launch hand-off — sc1
-// stores, a ticket per tile, the last slice folding — measured 0.5 ms slower
-// per 04vs frame than this second launch.)
-}  // namespace
-struct TileSlices {
-    int n;             // slices per box tile = sample groups (1: no slicing)
-    size_t floats;     // slab floats per tile: 192 * groups
-    float* slab;
-    const int32_t* order;  // box tiles in hand-out order (k_tile_order)
-    uint32_t* cost;        // per screen tile: real-time ticks of its units, for the next launch's order
-};
-using TilesFn = void (*)(FrameConsts, SceneArgs, uint32_t*, float4*, const float*, uchar4*, uint32_t*, int32_t*,
-                         unsigned long long*, TileSlices);
-// k_tiles<count, whole> of tiles.hip: this file compiled again with
-// RR_TILES_TU and without SLP vectorisation (see the Makefile). whole: one
-// work unit per box tile (the frame overlaps a pending k_tiles frame,
-// TileSlices.n == 1), a variant of its own so that the slab code is compiled
-// out and a counter pass tells its launches from the sliced ones by name.
-TilesFn tiles_kernel(bool count, bool whole);
-namespace {
-
-template <bool kCount, bool kWhole>
-RR_D void tiles_body(const FrameConsts& fc, const LdsView& v, uint32_t* __restrict__ tile_ctr, float4* __restrict__ film,
-                     const float* __restrict__ srgb, uchar4* __restrict__ out, uint32_t* __restrict__ tot,
-                     int32_t* __restrict__ spill, unsigned long long* __restrict__ tc, lds_int* stack,
-                     const TileSlices sl, unsigned long long rt_entry, lds_uint* cont_ctr) {
-    const int stride = gridDim.x * kBlock;
-    // counting instantiation only: the wave's shader-clock and real-time
-    // counters at start and end give the clock the kernel ran at (read-only
-    // counters; the timed instantiation executes none of this)
-    unsigned long long clk0 = 0, rt0 = 0;
-    if (kCount) {
-        clk0 = __builtin_amdgcn_s_memtime();
-        rt0 = __builtin_amdgcn_s_memrealtime();
-    }
-    const TileTrav tt{stack, spill, stride, tot + drops_slot(fc.max_bounces), cont_ctr + kWctr * (threadIdx.x >> 6), tc};
-    TravCount cp;
-    uint32_t n_c0 = 0, n_s0 = 0, n_c1 = 0, n_s1 = 0, n_t0 = 0;
-    // The screen rectangle and the tile order come from the root node in LDS,
-    // so the compiler cannot tell they are wave-uniform and would keep (and
-    // spill) them in VGPRs for the whole kernel: every lane holds the same
-    // values, lane 0's copy goes to SGPRs.
-    const ScreenCull cull = uniform_cull(screen_cull(fc, v.nodes));
-    const TileOrder to = uniform_order(tile_order(fc, cull));
-    const int lane = threadIdx.x & 63;
-    // Work units: each tile of the screen-rectangle box is cut into sl.n slices,
-    // one per sample group; every other tile is one unit whose samples are all
-    // culled (the world term). Those are dealt statically (wave w takes the
-    // tiles nb + w, nb + w + waves, ...: no atomics for the cheap units); the
-    // box slices come from n_shards = min(grid, kTileShards) counters, one per
-    // group of blocks with equal blockIdx % n_shards (blocks are dealt
-    // round-robin over the 8 XCDs, so a shard's atomics stay in one XCD's L2),
-    // shard g handing out slices g, g + n_shards, ... One counter for every
-    // unit serialised ~35k device-scope atomics on one address per 04vs frame.
-    const int ng = (fc.spp_total + kFilmGroup - 1) / kFilmGroup;
-    const int nb = to.bw * to.bh;
-    const int n_slices = kWhole ? 1 : sl.n;
-    const int n_sliced = nb * n_slices;
-    const int n_units = n_sliced + (to.n - nb);  // box slices, then one unit per background tile
-    const int n_shards = min((int)gridDim.x, kTileShards);  // small frames launch fewer blocks than shards
-    const int shard = (int)blockIdx.x % n_shards;
-    // Film value and 8-bit pixel of a background tile: every sample is the
-    // world term, summed in the grouped order, the same bits for every pixel,
-    // so the wave computes them once (wave-uniform, SGPRs) instead of per tile
-    // (128 x 3 adds and a tonemap with its sRGB table reads per background tile).
-    float4 bg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    for (int g = 0; g < ng; ++g) {
-        float3 P = mk3(0.0f, 0.0f, 0.0f);
-        const int s_end = min(fc.spp_total, (g + 1) * kFilmGroup);
-        for (int s = g * kFilmGroup; s < s_end; ++s) add_to(P, fc.world);
-        bg.x = bg.x + P.x;
-        bg.y = bg.y + P.y;
-        bg.z = bg.z + P.z;
-    }
-    bg = make_float4(uniform_f(bg.x), uniform_f(bg.y), uniform_f(bg.z), 0.0f);
-    const uchar4 bg_px = __builtin_bit_cast(uchar4, uniform_i(__builtin_bit_cast(int, tonemap(fc, bg, srgb))));
-    for (;;) {
-        int t, k = 0, nk = 1;  // tile, slice, slices of this tile
-        int u = 0;
-        if (lane == 0) u = (int)atomicAdd(tile_ctr + shard * kTileCtrStride, 1u);
-        u = __builtin_amdgcn_readlane(u, 0) * n_shards + shard;
-        if (u >= n_units) break;
-        if (u < n_sliced) {  // box tiles in the order of k_tile_order (the heaviest first)
-            const int j = kWhole ? u : u / n_slices;
-            k = kWhole ? 0 : u - j * n_slices;
-            nk = n_slices;
-            t = uniform_i(sl.order[j]);
-        } else {  // background tiles (the world term) fill the end of the launch
-            t = nb + (u - n_sliced);
-        }
-        const unsigned long long u_start = __builtin_amdgcn_s_memrealtime();
-        int tx, ty;
-        to.at(t, tx, ty);
-        const int px = tx * kTile + (lane & (kTile - 1)), py = ty * kTile + (lane >> 3);
-        const bool valid = px < fc.W && py < fc.H;
-        const int pix = py * fc.W + px;
-        float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (tile_culled(fc, cull, tx, ty)) {  // background tile: film = the world term, grouped sum (bg)
-            if (k != 0) continue;             // (slice 0 does the whole tile)
-            if (valid) {
-                film[pix] = bg;
-                out[pix] = bg_px;
-            }
-            continue;
-        }
-        // samples of this unit: group k of a sliced tile, else all of them
-        const int s_lo = nk > 1 ? k * kFilmGroup : 0;
-        const int s_hi = nk > 1 ? min(fc.spp_total, s_lo + kFilmGroup) : fc.spp_total;
-        uint64_t cm0, cm1;
-        tile_mask(fc, v, fc.n_tris, (float)(tx * kTile), (float)(tx * kTile + kTile - 1), (float)(ty * kTile),
-                  (float)(ty * kTile + kTile - 1), cm0, cm1);
-        const uint32_t pk = pixel_key(fc.seed, (uint32_t)pix);
-        // no triangle can be hit from this tile (wave-uniform): every sample is
-        // the world term, summed as the sample loop would (0 + world + ...)
-        const int s_run = (cm0 | cm1) != 0 ? s_hi : s_lo;
-        // film sum order: in order within groups of kFilmGroup samples, the
-        // group sums in order (one group per unit when tiles are sliced)
-        float3 P = mk3(0.0f, 0.0f, 0.0f);
-        auto group_end = [&](int s) {
-            if ((s + 1) % kFilmGroup == 0 || s + 1 == s_hi) {
-                acc.x = acc.x + P.x;
-                acc.y = acc.y + P.y;
-                acc.z = acc.z + P.z;
-                P = mk3(0.0f, 0.0f, 0.0f);
-            }
-        };
-        for (int s = s_run; s < s_hi; ++s) {
-            add_to(P, fc.world);
-            group_end(s);
-        }
-        for (int s = s_lo; s < s_run; ++s) {
-            const uint32_t key = sample_key(pk, (uint32_t)s);
-            float3 o = mk3(0.0f, 0.0f, 0.0f), d = o, L = o;
-            float tmin = 0.0f, tmax = -1.0f;
-            bool culled = true;
-            if (valid) camera_ray_xy(fc, v.filter, px, py, key, o, d, tmin, tmax, &cull, &culled);
-            n_t0 += wave_count(!culled);
-            bool cont = false, shadow = false;
-            if (valid) {  // bounce 0: the camera ray against the tile's triangles (wave-uniform masks)
-                Hit h;
-                set_miss(h, tmax);
-                if (!culled) camera_hit<kCount>(v, cm0, cm1, d, tmin, tmax, h, cp);
-                ShadeOut so;
-                const ShadeConsts sc{fc.world, fc.clamp_indirect, fc.max_bounces, fc.max_diffuse, fc.max_glossy,
-                                     fc.n_lights, fc.n_tris};
-                if constexpr ((RR_TILES_CONT_INPLACE & (kWhole ? 1 : 2)) != 0) {
-                    // the continuation (escape to the world, or bounces 1.. out of line) is taken inside
-                    shade(fc, 0, v, o, d, mk3(1.0f, 1.0f, 1.0f), 0u, h, key, L, so,
-                          InlineShadow<kCount>{v, fc.n_tris, tt}, TileCont<kCount>{sc, v, tt, key});
-                } else {
-                    shade(fc, 0, v, o, d, mk3(1.0f, 1.0f, 1.0f), 0u, h, key, L, so,
-                          InlineShadow<kCount>{v, fc.n_tris, tt});
-                    if (so.cont) TileCont<kCount>{sc, v, tt, key}(so.o, so.d, so.T, so.lob, so.esc, L);
-                }
-                cont = so.cont;
-                shadow = so.shadow;
-            }
-            // counted with the whole wave active: a ballot inside `if (valid)`
-            // would land in the counters of valid lanes only, and lane 0 (the
-            // one flush_rays reads) may lie outside the image
-            n_c0 += wave_count(cont);
-            n_s0 += wave_count(shadow);
-            add_to(P, L);
-            group_end(s);
-        }
-        if (!kWhole && nk > 1) {  // one group of a sliced tile: its sum goes to the slab, k_tiles_fold adds them up
-            float* const slab = sl.slab + (size_t)t * sl.floats + (size_t)k * 192;
-            slab[lane] = acc.x;
-            slab[64 + lane] = acc.y;
-            slab[128 + lane] = acc.z;
-        } else if (valid) {
-            film[pix] = acc;
-            out[pix] = tonemap(fc, acc, srgb);
-        }
-        if (lane == 0) {  // this unit's time, for the next launch's hand-out order (k_tile_order)
-            const unsigned long long u_end = __builtin_amdgcn_s_memrealtime();
-            atomicAdd(&sl.cost[ty * to.tx + tx], (uint32_t)(u_end - u_start));
-            if ((kCount || RR_TILES_LOG_ALWAYS) && u < kUnitLog) {  // the counting launch's unit log (device.hpp kUnitLog)
-                tc[kTravWords + 2 * u] = u_start;
-                tc[kTravWords + 2 * u + 1] = u_end;
-            }
-        }
-    }
-    uint32_t* const tail = tot + camera_traced_slot(fc.max_bounces);
-    n_c1 = tt.wctr[0];  // the later bounces (tiles_continue)
-    n_s1 = tt.wctr[1];
-    flush_rays(tot, n_c0, n_s0, n_c1, n_s1, tail, n_t0, tt.wctr[2], tt.wctr[3]);
-    if (kCount && lane == 0) {  // the secondary walks' node / triangle counts of this wave
-        atomicAdd(&tc[2], (unsigned long long)tt.wctr[4]);
-        atomicAdd(&tc[3], (unsigned long long)tt.wctr[5]);
-        atomicAdd(&tc[4], (unsigned long long)tt.wctr[6]);
-        atomicAdd(&tc[5], (unsigned long long)tt.wctr[7]);
-    }
-    if (kCount) {
-        flush_counts(tc, 0, cp.nodes, cp.tris);
-        const unsigned long long clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
-        if ((threadIdx.x & 63) == 0) {  // device.hpp kTravWords
-            atomicAdd(&tc[6], clk1 - clk0);
-            atomicAdd(&tc[7], rt1 - rt0);
-            atomicAdd(&tc[8], 1ull);
-            atomicAdd(&tc[9], rt1 - rt_entry);
-            atomicMax(&tc[10], ~rt_entry);  // the first entry, complemented (the words start at 0)
-            atomicMax(&tc[11], rt1);
-            atomicMax(&tc[12], rt_entry);  // the last entry
-            atomicMax(&tc[13], ~rt1);      // the first end, complemented
-        }
-    }
-}
-
-#if RR_TILES_TU
-// Waves per SIMD the register budget must admit: 4 (<= 128 VGPRs) for the
-// sample-group slices of a frame rendered alone, 5 (<= 96 VGPRs, 42 spill
-// slots) for the whole-tile units of frames that overlap a pending one — the
-// bench's pipelined frames: 04vs / 01 992 / 1,026 against 953 / 970 frames/s
-// at 4 (3 interleaved rounds of 40 frames), while a lone frame's slices ran
-// 1.181 / 1.151 against 1.144 / 1.140 ms; 6 waves (80 VGPRs) 710 frames/s,
-// 3 (137 VGPRs, no spill) 860.
-#ifndef RR_TILES_WAVES
-#define RR_TILES_WAVES 4
-#endif
-#ifndef RR_TILES_WAVES_WHOLE
-#define RR_TILES_WAVES_WHOLE 5
-#endif
-template <bool kCount, bool kWhole>
-__global__ __launch_bounds__(kBlock, kWhole ? RR_TILES_WAVES_WHOLE : RR_TILES_WAVES) void k_tiles(FrameConsts fc,
-                                                                                                 SceneArgs sa,
-                                                                  uint32_t* __restrict__ tile_ctr,
-                                                                  float4* __restrict__ film,
-                                                                  const float* __restrict__ srgb,
-                                                                  uchar4* __restrict__ out, uint32_t* __restrict__ tot,
-                                                                  int32_t* __restrict__ spill,
-                                                                  unsigned long long* __restrict__ tc,
-                                                                  TileSlices sl) {
-    const unsigned long long rt_entry = kCount ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    __shared__ int lds_stack[kLdsStack * kBlock];
-    __shared__ uint32_t cont_ctr[kWctr * kWavesPerBlock];  // per wave: TileTrav::wctr
-    extern __shared__ float4 dyn4[];
-    lds_int* stack = lds_slot(lds_stack);
-    if (threadIdx.x < kWctr * kWavesPerBlock) cont_ctr[threadIdx.x] = 0u;  // stage_scene ends with a barrier
-    int used;
-    const LdsView v = stage_scene<true>((lds_f4w*)dyn4, sa, true, used, &fc);
-    tiles_body<kCount, kWhole>(fc, v, tile_ctr, film, srgb, out, tot, spill, tc, stack, sl, rt_entry,
-                               (lds_uint*)cont_ctr);
-}
-
-#endif  // RR_TILES_TU
-
-// Hand-out order of k_tiles' box tiles (longest processing time first): the
-// tiles of this frame's box sorted by the time their units took in the
-// previous launch at the same screen tile (descending, over 128 log-spaced
-// buckets; the order inside a bucket is arbitrary), so the heaviest units start
-// first and the light rim and background units fill the end of the launch. On
-// 04vs the heaviest tiles lie on the box's rim rows (the lit faces), which the
-// box's row order handed out last, and the launch ended with those units
-// running on a nearly empty chip. Scheduling only: every unit computes the
-// same bits in any order. The same single-workgroup launch zeroes the costs
-// for the coming launch, the unit counters and the ray counters.
-constexpr int kOrderBuckets = 128;
-constexpr int kOrderThreads = 1024;
-RR_D int cost_bucket(uint32_t c) {
-    if (c < 4u) return (int)c;
-    const int e = 31 - __builtin_clz(c);
-    return min(kOrderBuckets - 1, 4 * e + (int)((c >> (e - 2)) & 3u));
-}
-__global__ __launch_bounds__(kOrderThreads) void k_tile_order(FrameConsts fc, const BvhNode* __restrict__ nodes,
-                                                              uint32_t* __restrict__ cost, int32_t* __restrict__ order,
-                                                              uint32_t* __restrict__ tile_ctr,
-                                                              uint32_t* __restrict__ ray_ctr, int n_ray_ctr) {
-    __shared__ uint32_t cnt[kOrderBuckets];
-    const int tid = threadIdx.x;
-    const ScreenCull cull = screen_cull(fc, nodes);
-    const TileOrder to = tile_order(fc, cull);
-    const int nb = to.bw * to.bh;
-    for (int i = tid; i < kOrderBuckets; i += kOrderThreads) cnt[i] = 0u;
-    for (int i = tid; i < kTileShards * kTileCtrStride; i += kOrderThreads) tile_ctr[i] = 0u;
-    for (int i = tid; i < n_ray_ctr; i += kOrderThreads) ray_ctr[i] = 0u;
-    __syncthreads();
-    for (int t = tid; t < nb; t += kOrderThreads) {
-        int x, y;
-        to.at(t, x, y);
-        atomicAdd(&cnt[cost_bucket(cost[y * to.tx + x])], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {  // bucket starts, the heaviest bucket first
-        uint32_t run = 0;
-        for (int b = kOrderBuckets - 1; b >= 0; --b) {
-            const uint32_t c = cnt[b];
-            cnt[b] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-    for (int t = tid; t < nb; t += kOrderThreads) {
-        int x, y;
-        to.at(t, x, y);
-        order[atomicAdd(&cnt[cost_bucket(cost[y * to.tx + x])], 1u)] = t;
-    }
-    __syncthreads();
-    for (int i = tid; i < to.n; i += kOrderThreads) cost[i] = 0u;
-}
-
-// Film of the sliced tiles: the group sums of each box tile that is not
-// culled, added in group order (the same box and culling test as k_tiles,
-// from the same root node), then tonemapped. One wave per tile.
-__global__ __launch_bounds__(kBlock) void k_tiles_fold(FrameConsts fc, const BvhNode* __restrict__ nodes,
-                                                       TileSlices sl, float4* __restrict__ film,
-                                                       const float* __restrict__ srgb, uchar4* __restrict__ out) {
-    const ScreenCull cull = screen_cull(fc, nodes);
-    const TileOrder to = tile_order(fc, cull);
-    const int nb = to.bw * to.bh;
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    for (int t = wave; t < nb; t += gridDim.x * kWavesPerBlock) {
-        int tx, ty;
-        to.at(t, tx, ty);
-        if (tile_culled(fc, cull, tx, ty)) continue;
-        const int px = tx * kTile + (lane & (kTile - 1)), py = ty * kTile + (lane >> 3);
-        if (px >= fc.W || py >= fc.H) continue;
-        const float* slab = sl.slab + (size_t)t * sl.floats;
-        float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        for (int g = 0; g < sl.n; ++g, slab += 192) {
-            acc.x = acc.x + slab[lane];
-            acc.y = acc.y + slab[64 + lane];
-            acc.z = acc.z + slab[128 + lane];
-        }
-        const int pix = py * fc.W + px;
-        film[pix] = acc;
-        out[pix] = tonemap(fc, acc, srgb);
     }
 }
 
@@ -2539,12 +1214,7 @@ __global__ void k_debug_trace4(const QNode6* __restrict__ nodes, const TriPack* 
 
 }  // namespace
 
-#if RR_TILES_TU
-TilesFn tiles_kernel(bool count, bool whole) {
-    return count ? (whole ? k_tiles<true, true> : k_tiles<true, false>)
-                 : (whole ? k_tiles<false, true> : k_tiles<false, false>);
-}
-#else
+#if !RR_TILES_TU  // tiles.hip includes the kernels above (see there); the host side below is this unit's alone
 int device_cu_count() {
     static int cus = 0;
     if (!cus) {
@@ -2564,98 +1234,6 @@ int device_cu_count() {
 int counters_per_chunk(int max_bounces) { return 2 * (max_bounces + 2) + 4; }
 
 namespace {
-// LDS-resident scenes render through k_tiles (RR_FLAG_WAVEFRONT: through the
-// split trace / shade kernels of large scenes, the parity tests' second path).
-// k_tiles slices a box tile into its sample groups: one unit per group, the
-// group sums handed to the slice finishing last through a slab of one plane
-// (3 x 64 floats) per group.
-int film_groups(int spp) { return (spp + kFilmGroup - 1) / kFilmGroup; }
-size_t tile_slab_bytes(int spp, long tiles) {
-    const int ng = film_groups(spp);
-    return ng > 1 ? (size_t)192 * sizeof(float) * ng * (size_t)tiles : 0;
-}
-constexpr size_t kTileSlabMax = (size_t)16 << 30;
-// Persistent grid = resident blocks: CUs x blocks per CU the kernel's register
-// and LDS budget admits (a grid-stride loop over more blocks than fit would
-// only queue the surplus behind the first wave of blocks).
-template <typename K>
-int resident_grid(K kernel, size_t dyn_lds = 0, int block = kBlock) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, dyn_lds) != hipSuccess || per_cu <= 0)
-        per_cu = std::max(1, 1024 / block);
-    return device_cu_count() * std::min(per_cu, kMaxBlocksPerCu * kBlock / block);
-}
-// Resident grid per (kernel, dynamic LDS bytes), cached.
-template <typename K>
-int grid_for(K kernel, size_t dyn_lds, int block = kBlock) {
-    static std::map<std::pair<const void*, size_t>, int> cache;
-    const auto key = std::make_pair(reinterpret_cast<const void*>(kernel), dyn_lds);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    return cache[key] = resident_grid(kernel, dyn_lds, block);
-}
-// What stage_scene stages (without the camera data): the hierarchy and the
-// triangle records, + the normals / shading frames (1 + kOnbF4 float4 per
-// triangle) and the derived material records when shading.
-size_t scene_lds_bytes(const FrameConsts& fc, bool shading) {
-    const int n_nodes = std::max(fc.n_tris - 1, 1);
-    size_t f4 = 4 * (size_t)n_nodes + kTriF4 * (size_t)fc.n_tris;
-    if (shading)
-        f4 += (3 + kMatDF4 + kMatLutStride / 4) * (size_t)fc.n_mats + 3 * (size_t)fc.n_lights + kFilterN / 4 +
-              (size_t)(1 + kOnbF4) * fc.n_tris;
-    return 16 * f4;
-}
-}  // namespace
-
-// k_tiles' LDS per block: its static arrays (the traversal stack of kLdsStack
-// entries per lane, kWctr counter words per wave: 12,416 B, as hipcc reports
-// for every k_tiles instantiation) + the dynamic part TileGrid allocates — the
-// staged scene (stage_scene) and the camera-relative vertices (stage_camera,
-// kCamF4 float4 per triangle). ONE function for both the residency decision
-// and the launch (VERDICT r5 Weak 7: the decision used to count only the
-// hierarchy, triangles, materials, lights and filter table, about half of
-// what the launch then allocated).
-constexpr size_t kTilesStaticLds = sizeof(int) * (size_t)(kLdsStack * kBlock + kWctr * kWavesPerBlock);
-size_t tiles_dyn_lds_bytes(const FrameConsts& fc) {
-    return scene_lds_bytes(fc, true) + 16 * (size_t)kCamF4 * (size_t)fc.n_tris;
-}
-// A scene is LDS-resident (k_tiles) when one block's LDS leaves at least
-// kTilesMinBlocks blocks per CU (160 KB; 3 x 4 waves = 3 waves per SIMD).
-// Measured on dense soups in the 04vs stand-in (tools/lds_residency_study.py,
-// profiles/r5_lds_residency.txt): k_tiles ahead of the split path down to 3
-// blocks per CU (70 triangles: 19.2 against 20.0 ms), level at 2 (90: 20.3
-// against 20.4 ms); below 3 the split path takes the scene. And at most 128
-// triangles (camera_hit's per-tile triangle mask).
-constexpr int kTilesMinBlocks = 3;
-constexpr size_t kCuLds = 160 * 1024;
-bool scene_in_lds(int n_tris, int n_mats, int n_lights) {
-    FrameConsts fc{};
-    fc.n_tris = n_tris;
-    fc.n_mats = n_mats;
-    fc.n_lights = n_lights;
-    return n_tris > 0 && n_tris <= 128 &&
-           kTilesMinBlocks * (kTilesStaticLds + tiles_dyn_lds_bytes(fc)) <= kCuLds;
-}
-
-bool frame_uses_tiles(const FrameConsts& base, bool force_wavefront) {
-    const long n_tiles = (long)((base.W + 7) / 8) * ((base.H + 7) / 8);
-    return scene_in_lds(base.n_tris, base.n_mats, base.n_lights) && !force_wavefront &&
-           tile_slab_bytes(base.spp_total, n_tiles) <= kTileSlabMax;
-}
-
-namespace {
-// Launch geometry of k_tiles: the scene and the camera data staged in dynamic
-// LDS (stage_scene, stage_camera), the resident grid for it.
-struct TileGrid {
-    TilesFn kx;
-    size_t dyn;
-    int grid;
-    TileGrid(const FrameConsts& fc, bool count, bool whole) {
-        dyn = tiles_dyn_lds_bytes(fc);  // what scene_in_lds counted
-        kx = tiles_kernel(count, whole);
-        grid = grid_for(kx, dyn);
-    }
-};
 // Launch geometry of the split (trace / shade) path of large scenes.
 struct SplitGrids {
     int trace_p, trace_e, shadow, shade_p, shade_e, packet, sort;
@@ -2692,10 +1270,6 @@ int accum_grid() {
 // Host side of deal_ctrs: the camera packets deal from word 2 of the bounce-0
 // path queue's counter lines (written by k_shade_primary after them, word 0).
 inline uint32_t* deal_host(uint32_t* q, int word) { return RR_DYN_DEAL ? q + word : nullptr; }
-inline int clamp_grid(long work, int resident, int block = kBlock) {
-    const long g = (work + block - 1) / block;
-    return (int)std::max<long>(1, std::min<long>(g, resident));
-}
 }  // namespace
 
 void DevPaths::ensure_paths(size_t n) {
@@ -2708,11 +1282,6 @@ void DevPaths::ensure_paths(size_t n) {
         hits.ensure(n);
         cap = n;
     }
-    spill.ensure((size_t)kSpillLane * grid_blocks * kBlock);
-}
-
-void DevPaths::ensure_tiles() {
-    if (grid_blocks == 0) grid_blocks = device_cu_count() * kMaxBlocksPerCu;
     spill.ensure((size_t)kSpillLane * grid_blocks * kBlock);
 }
 
@@ -2839,56 +1408,7 @@ void render_frame_device(DevScene& s, DevPaths& p, const FrameConsts& base, int 
     p.last_tile_slices = 0;
     p.last_unit_logged = false;
     if (frame_uses_tiles(base, p.force_wavefront)) {  // one launch: all samples of every tile
-        const TileGrid G(base, p.count_traversal, p.tile_whole);
-        p.ensure_tiles();
-        p.film.ensure((size_t)npix);
-        p.rgba8.ensure((size_t)npix * 4);
-        const int cpc = counters_per_chunk(base.max_bounces);
-        const long tiles = (long)((base.W + 7) / 8) * ((base.H + 7) / 8);
-        const size_t n_ctr = (size_t)cpc * n_chunks;
-        p.counters.ensure(n_ctr);  // zeroed by k_tile_order
-        unsigned long long* tc = nullptr;
-        if (p.count_traversal || RR_TILES_LOG_ALWAYS) {  // (RR_TILES_LOG_ALWAYS: diagnostic builds log every launch's units)
-            p.trav_counts.ensure(kTravWords + 2 * kUnitLog);
-            RR_HIP(hipMemsetAsync(p.trav_counts.ptr, 0, (kTravWords + 2 * kUnitLog) * sizeof(unsigned long long), st));
-            tc = p.trav_counts.ptr;
-            p.last_unit_logged = true;
-        }
-        const SceneArgs sa{s.nodes.ptr, s.qnodes.ptr, s.tris.ptr, p.materials.ptr, p.lights.ptr, p.filter_table.ptr,
-                           p.mat_lut.ptr, std::max(s.n_tris - 1, 1), s.n_tris, base.n_mats, base.n_lights, s.nq};
-        FrameConsts fc = base;
-        fc.first_sample = 0;
-        fc.spp_chunk = base.spp_total;
-        uint32_t* tot = reinterpret_cast<uint32_t*>(p.counters.ptr);
-        if (p.tile_cost.cap < (size_t)tiles) {  // costs of a new size start at 0 (the first order is the box's)
-            p.tile_cost.ensure((size_t)tiles);
-            RR_HIP(hipMemsetAsync(p.tile_cost.ptr, 0, sizeof(uint32_t) * tiles, st));
-        }
-        p.tile_order.ensure((size_t)tiles);
-        // units: one per (box tile, sample group) when the frame runs alone, so
-        // the heaviest tiles do not finish the launch on a nearly empty chip;
-        // one per tile (every group of it, summed in order in the unit) when
-        // the frame overlaps a pending one (p.tile_whole): the other frame's
-        // waves fill the tail, and the slab writes and the fold launch go
-        TileSlices sl{p.tile_whole ? 1 : film_groups(base.spp_total), (size_t)192 * film_groups(base.spp_total), nullptr,
-                      p.tile_order.ptr, p.tile_cost.ptr};
-        p.last_tile_slices = sl.n;
-        if (sl.n > 1) {
-            p.tile_slab.ensure(sl.floats * (size_t)tiles);
-            sl.slab = p.tile_slab.ptr;
-        }
-        const int g = clamp_grid(tiles * 64, G.grid);
-        p.prof.begin(st, RR_K_TILES);
-        p.tile_ctrs.ensure((size_t)kTileShards * kTileCtrStride);
-        k_tile_order<<<1, kOrderThreads, 0, st>>>(fc, s.nodes.ptr, p.tile_cost.ptr, p.tile_order.ptr, p.tile_ctrs.ptr,
-                                                  reinterpret_cast<uint32_t*>(p.counters.ptr), (int)n_ctr);
-        G.kx<<<g, kBlock, G.dyn, st>>>(fc, sa, p.tile_ctrs.ptr, p.film.ptr, p.srgb_lut.ptr,
-                                               reinterpret_cast<uchar4*>(p.rgba8.ptr), tot, p.spill.ptr, tc, sl);
-        if (sl.n > 1)
-            k_tiles_fold<<<(int)std::min<long>((tiles + kWavesPerBlock - 1) / kWavesPerBlock, 2048), kBlock, 0, st>>>(
-                fc, s.nodes.ptr, sl, p.film.ptr, p.srgb_lut.ptr, reinterpret_cast<uchar4*>(p.rgba8.ptr));
-        p.prof.end(st);
-        RR_HIP(hipGetLastError());
+        render_tiles_device(s, p, base, n_chunks, st);
         return;
     }
     p.film.ensure((size_t)npix);
@@ -2994,6 +1514,6 @@ void trace_batch_device(DevScene& s, DevPaths& p, int n, const float4* d_rays, f
                                             p.spill.ptr);
     RR_HIP(hipGetLastError());
 }
+#endif  // !RR_TILES_TU
 
-#endif  // RR_TILES_TU
 }  // namespace rr

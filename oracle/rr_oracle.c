@@ -1280,7 +1280,7 @@ static mat_t load_mat(const float* mats, int id) {
 /* Ray statistics of the last orc_render (orc_ray_counts): continuations and
  * shadow rays created at bounce 0 / at later bounces, as rr_frame_stats counts
  * them, and the first (pixel, sample) pairs whose path continued past bounce 1. */
-/* Hull flags of an LDS-resident scene's triangle (csrc/wavefront.hip
+/* Hull flags of an LDS-resident scene's triangle (csrc/tiles.hip
  * stage_scene, hull_flags; same float operations): bit 0 when every vertex of
  * every triangle lies behind the triangle's plane on its front side (the
  * cross(e1, e2) direction, e1 = v1 - v0, e2 = v2 - v0), up to 2^-12 of the
@@ -1321,7 +1321,7 @@ static double wall_s(void) {
 }
 static int g_late[32], g_n_late;
 
-/* The camera ray of (pix, sample) (csrc/wavefront.hip camera_ray_xy): the
+/* The camera ray of (pix, sample) (csrc/paths.hpp camera_ray_xy): the
  * subpixel pair is the 16-bit halves of the path key itself (a hash output),
  * filter-importance sampled; (fx, fy) its subpixel position. */
 static void camera_ray(const scene_t* S, int pix, int sample, uint32_t* key_out, v3* o, v3* d, float* tmin,
@@ -1361,7 +1361,7 @@ static v3 radiance(const scene_t* S, int pix, int sample, long long rays[4]) {
         if (b == 0 && culled) {
             h.t = tmax; h.u = h.v = 0.0f; h.idx = -1; h.orig = -1;
         } else if (b == 0 && S->cam_all) {
-            /* wavefront.hip camera_hit: LDS-resident scenes test camera rays
+            /* tiles.hip camera_hit: LDS-resident scenes test camera rays
              * against every triangle (the GPU bins them per 8x8 tile, which by
              * construction keeps every triangle a ray can hit; the accept rule
              * is order-independent, so the result is the same) */
@@ -1828,10 +1828,10 @@ double orc_last_build_seconds(void) { return g_build_s; }
 /* The two shortcuts orc_render shares with the product, switchable so the
  * tests can show that neither changes a pixel (tests/test_oracle.py):
  *  cull: camera rays outside the scene's screen rectangle (screen_rect) are
- *        misses without a traversal (csrc/wavefront.hip camera_ray_xy);
+ *        misses without a traversal (csrc/paths.hpp camera_ray_xy);
  *  hull: on LDS-resident scenes (render_ints[7] == 2) a secondary ray leaving
  *        a hull side of its triangle (tri_hull) is a miss / unoccluded without
- *        a traversal (csrc/wavefront.hip hull_flags).
+ *        a traversal (csrc/tiles.hip hull_flags).
  * Both are on by default (what the product does). */
 static int g_rule_cull = 1, g_rule_hull = 1;
 void orc_set_rules(int cull, int hull) { g_rule_cull = cull; g_rule_hull = hull; }
@@ -1910,7 +1910,7 @@ int orc_render(int n_tris, const float* tris9, const int32_t* tri_mat, const flo
         long long rays[4] = {0, 0, 0, 0};
         for (int x = x0; x < x1; ++x) {
             int pix = y * S->W + x;
-            /* film sum order (the product's kFilmGroup, csrc/wavefront.hip): in
+            /* film sum order (the product's kFilmGroup, csrc/paths.hpp): in
              * order within groups of ORC_FILM_GROUP samples, group sums in order */
             v3 acc = V(0.0f, 0.0f, 0.0f);
             for (int g0 = 0; g0 < S->spp; g0 += ORC_FILM_GROUP) {

@@ -204,7 +204,7 @@ def test_c5_scene_size(rr):
 
 
 def tiles_lds_per_block(n_tris: int, n_mats: int, n_lights: int) -> int:
-    """Restatement of k_tiles' LDS per block (wavefront.hip kTilesStaticLds +
+    """Restatement of k_tiles' LDS per block (tiles.hip kTilesStaticLds +
     tiles_dyn_lds_bytes): static traversal stack (12 entries x 256 lanes x 4 B)
     and 8 counter words per wave, + the staged scene in float4s — BVH2 nodes
     (4 per node), triangle records (3), normal + shading frames (1 + 4), camera

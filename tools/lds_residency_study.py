@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """k_tiles against the split path on LDS-resident scenes of growing size (the
-residency cap of wavefront.hip scene_in_lds / the k_tiles LDS footprint).
+residency cap of tiles.hip scene_in_lds / the k_tiles LDS footprint).
 
 Each scene is the 04vs stand-in with its cube replaced by a dense soup of
 n triangles (icosahedral blobs + shards, tests/soups.py style, seeded): k_tiles
@@ -46,7 +46,7 @@ def dense_soup(n: int, seed: int = 1) -> np.ndarray:
 
 
 def lds_bytes(n: int, n_mats: int = 2, n_lights: int = 1) -> int:
-    """k_tiles' LDS per block (wavefront.hip TileGrid: scene_lds_bytes + camera data + the static stack)."""
+    """k_tiles' LDS per block (tiles.hip TileGrid: scene_lds_bytes + camera data + the static stack)."""
     f4 = 4 * max(n - 1, 1) + 3 * n + (3 + 4 + 65) * n_mats + 3 * n_lights + 256 + 5 * n + 13 * n
     return 16 * f4 + 12 * 256 * 4
 

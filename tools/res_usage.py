@@ -4,6 +4,11 @@
 
     python tools/res_usage.py wavefront.hip [tiles.hip ...] [--extra '-DFOO=1']
 
+tiles.hip gets the extra flags of its translation unit (-fno-slp-vectorize);
+the environment variable TILES_TUFLAGS, named as the Makefile's variable,
+replaces them. Its rows for the split path's kernels are the unused copies
+that unit carries (see tiles.hip); the ones that run are wavefront.hip's.
+
 Compiles each file device-only with the Makefile's device flags into /tmp and
 prints one line per kernel: VGPRs, AGPRs, VGPR spills, SGPR spills, scratch
 bytes per lane and waves per SIMD. Build-time inspection only."""
@@ -16,7 +21,7 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                     "diploma_thesis-distributed_rendering_of_cgi_using_a_render_cluster_amd", "csrc")
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-TU_FLAGS = {"tiles.hip": os.environ.get("RR_TILES_TUFLAGS", "-fno-slp-vectorize").split()}
+TU_FLAGS = {"tiles.hip": os.environ.get("TILES_TUFLAGS", "-fno-slp-vectorize").split()}
 
 
 def usage(src, extra):
