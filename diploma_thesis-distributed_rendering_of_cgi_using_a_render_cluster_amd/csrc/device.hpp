@@ -273,7 +273,7 @@ size_t jpeg_stream_max_bytes(int W, int H);
 void jpeg_encode_device(const uint8_t* d_rgba, int W, int H, const float* d_tab, const uint32_t* d_huff,
                         int16_t* d_coeffs, JpegDevBufs& b, uint8_t* host_out, hipStream_t st);
 
-// The three formats coded by the device deflate coder (deflate.hpp): each has
+// The formats coded by the device deflate coder (deflate.hpp): each has
 // a plan (false: the size is outside what the encoder takes, W above the bound
 // named below or a stream of 2 GB and more) and an encode call that runs its
 // front end, the coder's stages and the gather into pinned host memory:
@@ -297,6 +297,12 @@ size_t exr_stream_max_bytes(const DeflatePlan& p);  // every chunk raw
 // film: W x H float4 sums, scaled by inv_spp; alpha_one: A = 1.0 (rendered frames), else film.w * inv_spp.
 void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
                        uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
+// The same file with FLOAT channels: the means' own bits (no clamp, no
+// rounding), chunks of 16W bytes a scanline; exr_stream_max_bytes and the table
+// as above. W <= 2^18 (a band has twice the bytes).
+bool exr32_plan(int W, int H, DeflatePlan& p);
+void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
+                         uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 // The Filmic LUTs of one device as kernel arguments (view.hpp FilmicDev::args).
 struct FilmicArgs {

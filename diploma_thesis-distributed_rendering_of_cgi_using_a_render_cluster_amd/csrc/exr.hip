@@ -22,6 +22,10 @@
 //    its n unprocessed bytes; the codes stage decides, this kernel writes them.
 //  - deflate.hip's scan + gather into pinned host memory.
 // Same film -> same bytes.
+//
+// FLOAT channels (Blender's "Float (Full)", rr_set_exr_depth 32) are a second
+// front end of the same shape: ExrFloatFront, k_exr32_raw and exr32_plan below,
+// n = 16W * rows bytes a chunk, the means' own bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -106,6 +110,55 @@ __global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, DeflatePlan p, co
     *reinterpret_cast<uint16_t*>(o) = (uint16_t)h;
 }
 
+// ---- FLOAT channels (rr_set_exr_depth 32): the film's means as they are ----
+// A chunk of `rows` scanlines holds n = 16W * rows bytes: per scanline the
+// planes A, B, G, R of W little-endian floats each. After the reorder the
+// first n / 2 positions alternate bytes 0 and 2 of consecutive samples, the
+// second n / 2 bytes 1 and 3: position q of a half belongs to sample q / 2.
+
+// Bits of sample k of a band: the mean itself, no clamp and no rounding.
+__device__ __forceinline__ uint32_t sample_float(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
+    const uint32_t W = (uint32_t)p.W, row_samples = 4u * W;
+    const uint32_t row = k / row_samples, rem = k - row * row_samples;
+    const uint32_t ch = rem / W, x = rem - ch * W;
+    const float4 v = fm.px[(size_t)(row0 + (int)row) * W + x];
+    const float c = ch == 0 ? v.w : ch == 1 ? v.z : ch == 2 ? v.y : v.x;
+    const float mean = (ch == 0 && fm.alpha_one) ? 1.0f : __fmul_rn(c, fm.inv_spp);
+    return __float_as_uint(mean);
+}
+
+// Byte j of a band of floats after the reorder (before the predictor).
+__device__ __forceinline__ uint32_t reordered_byte32(const Film& fm, const DeflatePlan& p, int row0, uint32_t half_n,
+                                                     uint32_t j) {
+    const bool hi = j >= half_n;
+    const uint32_t q = hi ? j - half_n : j;
+    const uint32_t bits = sample_float(fm, p, row0, q >> 1);
+    return (bits >> (16u * (q & 1u) + (hi ? 8u : 0u))) & 0xFFu;
+}
+
+// Byte j of a FLOAT chunk as the coder sees it: reordered, less its predecessor + 128.
+struct ExrFloatFront {
+    Film fm;
+    __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t n, uint32_t j) const {
+        uint32_t v = reordered_byte32(fm, p, row0, n / 2, j);
+        if (j > 0) v = (v - reordered_byte32(fm, p, row0, n / 2, j - 1) + 128u) & 0xFFu;
+        return v;
+    }
+};
+
+// Raw FLOAT chunks (rec mode 1): k_exr_raw with 4-byte samples.
+__global__ __launch_bounds__(kThreads) void k_exr32_raw(Film fm, DeflatePlan p, const uint32_t* __restrict__ rec,
+                                                        uint8_t* __restrict__ out) {
+    const int b = blockIdx.y;
+    if (rec[4 * (size_t)b] == 0u) return;
+    const int row0 = b * kDeflateBandRows;
+    const uint32_t n = p.stride * (uint32_t)min(kDeflateBandRows, p.H - row0);
+    const uint32_t k = blockIdx.x * kThreads + threadIdx.x;  // sample
+    if (4u * k >= n) return;                                 // n = 16W * rows: whole samples
+    uint8_t* o = out + (size_t)b * p.band_cap + 4u * k;      // band_cap is a multiple of 16, n <= band_cap
+    *reinterpret_cast<uint32_t*>(o) = sample_float(fm, p, row0, k);
+}
+
 }  // namespace
 
 bool exr_plan(int W, int H, DeflatePlan& p) {
@@ -120,6 +173,28 @@ bool exr_plan(int W, int H, DeflatePlan& p) {
     return ok;
 }
 
+// Which of the four candidate distances of a FLOAT chunk (1, 2, 2W, 8W) the
+// coder's three leave out (profiles/exr32_device.md).
+#ifndef RR_EXR32_DROP
+#define RR_EXR32_DROP 0
+#endif
+
+bool exr32_plan(int W, int H, DeflatePlan& p) {
+    // a band's bit offsets (at most 16 bits a byte, 256 W bytes) stay below 2^30, as exr_plan's
+    if (W <= 0 || H <= 0 || W > (1 << 18)) return false;
+    const bool ok = deflate_plan(W, H, 16u * (uint32_t)W, p);
+    const uint32_t w = (uint32_t)W;
+    // 1; 2: the same byte of the previous sample (a flat area has period 2
+    // after the predictor); 2W: the same pixel in the neighbouring plane; 8W:
+    // the scanline above within a half
+    const uint32_t cand[4] = {1u, 2u, 2u * w, 8u * w};
+    int k = 0;
+    for (int i = 0; i < 4; ++i)
+        if (i != RR_EXR32_DROP) p.dist[k++] = cand[i] <= 32768u ? cand[i] : 0u;
+    p.own_stream = 1;
+    return ok;
+}
+
 size_t exr_stream_max_bytes(const DeflatePlan& p) { return (size_t)p.stride * (size_t)p.H; }
 
 void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
@@ -129,6 +204,16 @@ void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, cons
     k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFront{fm}, p, c.filt, c.adler_part);
     deflate_bands_device(p, c, st);
     k_exr_raw<<<dim3((p.band_full / 2 + kThreads - 1) / kThreads, p.nbands), kThreads, 0, st>>>(fm, p, c.rec, c.out);
+    deflate_gather_device(p, c, host_out, host_tab, st);
+}
+
+void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
+                         uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
+    const DeflateBufs c = deflate_carve(p, scratch);
+    const Film fm{d_film, inv_spp, alpha_one ? 1 : 0};
+    k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFloatFront{fm}, p, c.filt, c.adler_part);
+    deflate_bands_device(p, c, st);
+    k_exr32_raw<<<dim3((p.band_full / 4 + kThreads - 1) / kThreads, p.nbands), kThreads, 0, st>>>(fm, p, c.rec, c.out);
     deflate_gather_device(p, c, host_out, host_tab, st);
 }
 

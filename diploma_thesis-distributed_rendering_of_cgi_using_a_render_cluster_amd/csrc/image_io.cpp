@@ -518,7 +518,8 @@ void exr_attr(std::vector<uint8_t>& o, const char* name, const char* type, const
 }  // namespace
 
 bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
-                     std::vector<uint8_t>& out) {
+                     std::vector<uint8_t>& out, int pixel_type) {
+    const uint32_t row_bytes = (pixel_type == 2 ? 16u : 8u) * (uint32_t)W;  // four planes of FLOAT or HALF
     out.clear();
     out.reserve(n + 512 + (size_t)nchunks * 22);
     const uint8_t start[8] = {0x76, 0x2F, 0x31, 0x01, 2, 0, 0, 0};
@@ -526,8 +527,8 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
     std::vector<uint8_t> v;
     for (const char* ch : {"A", "B", "G", "R"}) {
         put_str(v, ch);
-        put_le(v, 1, 4);  // HALF
-        put_le(v, 0, 4);  // pLinear, 3 reserved bytes
+        put_le(v, (uint32_t)pixel_type, 4);  // 1 HALF, 2 FLOAT
+        put_le(v, 0, 4);                     // pLinear, 3 reserved bytes
         put_le(v, 1, 4);  // xSampling
         put_le(v, 1, 4);  // ySampling
     }
@@ -556,6 +557,9 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
     for (int b = 0; b < nchunks; ++b) {
         const uint32_t mode = chunk_tab[4 * b], len = chunk_tab[4 * b + 1], adler = chunk_tab[4 * b + 2];
         if (src + len > n) return false;
+        // a raw chunk is its scanlines' bytes, a coded one is smaller
+        const uint32_t raw = row_bytes * (uint32_t)std::min(16, H - b * 16);
+        if (chunk_tab[4 * b + 3] != raw || (mode == 0 ? len + 6 >= raw : len != raw)) return false;
         put_le(out, (uint32_t)(b * 16), 4);
         put_le(out, mode == 0 ? len + 6 : len, 4);
         if (mode == 0) {

@@ -40,9 +40,12 @@ void png_wrap_stream(int W, int H, const uint8_t* z, size_t n, const uint32_t* b
 // chunks of 16 scanlines) around chunks coded on the device (exr.hip): data =
 // the chunks' pieces back to back, chunk_tab = {mode, bytes, Adler-32, chunk
 // bytes} per chunk. Mode 0: deflate data, wrapped here in 78 01 ... Adler-32;
-// mode 1: the raw chunk. false: the pieces do not add up to n.
+// mode 1: the raw chunk. pixel_type: 1 HALF (8W bytes a scanline) or 2 FLOAT
+// (16W), the type of all four channels; nothing else in the header depends on
+// it. false: the pieces do not add up to n, or a chunk's size is not what its
+// scanlines allow.
 bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
-                     std::vector<uint8_t>& out);
+                     std::vector<uint8_t>& out, int pixel_type = 1);
 bool write_file(const std::string& path, const std::vector<uint8_t>& data);
 
 }  // namespace rr

@@ -73,16 +73,21 @@ struct PinnedBuf {
 
 // Who codes a frame's output. HostRgba: the 8-bit image comes back to the host
 // (rr_render_frame_to_memory; a "PNG" file from the host's zlib threads where a
-// path is given). Jpeg ... Exr: coded on the device, the file written from the
+// path is given). Jpeg ... Exr32: coded on the device, the file written from the
 // slot's pinned stream. Png8: "PNG" with rr_set_device_png; Png16: "PNG" at 16
-// bits per sample, for which there is no host coder.
-enum class Coder { None, HostRgba, Jpeg, Png8, Png16, Exr };
+// bits per sample, for which there is no host coder. Exr: "OPEN_EXR" with HALF
+// channels; Exr32: with FLOAT channels (rr_set_exr_depth).
+enum class Coder { None, HostRgba, Jpeg, Png8, Png16, Exr, Exr32 };
 
 // The formats behind the deflate coder (deflate.hip): their coder reads only
 // its slot's rgba8 / film and writes slot buffers only.
-bool device_deflate(Coder k) { return k == Coder::Png8 || k == Coder::Png16 || k == Coder::Exr; }
+bool device_deflate(Coder k) {
+    return k == Coder::Png8 || k == Coder::Png16 || k == Coder::Exr || k == Coder::Exr32;
+}
 
-const char* coder_ext(Coder k) { return k == Coder::Jpeg ? ".jpg" : k == Coder::Exr ? ".exr" : ".png"; }
+const char* coder_ext(Coder k) {
+    return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : ".png";
+}
 
 // The pinned outputs of a deflate-coded frame (deflate.hpp): the stream
 // [uint64 length][pad][bytes] and the bands' table, 2 or 4 words per band by
@@ -203,6 +208,8 @@ struct rr_ctx {
     DevBuf<uint32_t> deflate_scratch;  // the deflate coder's (a frame has one format)
     // bit depth of "PNG" frames (rr_set_png_depth / RR_PNG_DEPTH): 0 the scene's, 8, 16
     int png_depth = 0;
+    // channel type of "OPEN_EXR" frames (rr_set_exr_depth / RR_EXR_DEPTH): 0 the scene's, 16 HALF, 32 FLOAT
+    int exr_depth = 0;
     DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
     std::vector<float> filter_cache;
     float filter_width_cached = -1.f;
@@ -541,9 +548,15 @@ void ensure_srgb16(rr_ctx* c) {
 // The plan of a deflate-coded frame. A size outside the coder's range is
 // refused, never rerouted: there is no other coder that writes the same file.
 int plan_or_refuse(Coder k, int W, int H, DeflatePlan& p) {
-    const bool ok = k == Coder::Png8 ? png_plan(W, H, p) : k == Coder::Png16 ? png16_plan(W, H, p) : exr_plan(W, H, p);
+    const bool ok = k == Coder::Png8    ? png_plan(W, H, p)
+                    : k == Coder::Png16 ? png16_plan(W, H, p)
+                    : k == Coder::Exr32 ? exr32_plan(W, H, p)
+                                        : exr_plan(W, H, p);
     if (ok) return RR_OK;
-    const char* name = k == Coder::Png8 ? "PNG" : k == Coder::Png16 ? "16-bit PNG" : "EXR";
+    const char* name = k == Coder::Png8    ? "PNG"
+                       : k == Coder::Png16 ? "16-bit PNG"
+                       : k == Coder::Exr32 ? "32-bit EXR"
+                                           : "EXR";
     return fail(RR_EINVAL, std::string("image size outside the device ") + name + " encoder's range");
 }
 
@@ -564,9 +577,11 @@ auto launch_png16(rr_ctx* c, const float4* d_film, float inv_spp, float exposure
         png16_encode_device(f, p, scratch, out, tab, st);
     };
 }
-auto launch_exr(const float4* d_film, float inv_spp, bool alpha_one) {
+// full: FLOAT channels (Coder::Exr32), else HALF
+auto launch_exr(const float4* d_film, float inv_spp, bool alpha_one, bool full) {
     return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        exr_encode_device(d_film, inv_spp, alpha_one, p, scratch, out, tab, st);
+        if (full) exr32_encode_device(d_film, inv_spp, alpha_one, p, scratch, out, tab, st);
+        else exr_encode_device(d_film, inv_spp, alpha_one, p, scratch, out, tab, st);
     };
 }
 
@@ -603,7 +618,8 @@ void deflate_file_bytes(const DeflateOut& o, Coder k, std::vector<uint8_t>& data
         png_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Png16 ? 16 : 8);
         break;
     case Coder::Exr:
-        if (!exr_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data))
+    case Coder::Exr32:
+        if (!exr_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Exr32 ? 2 : 1))
             throw std::runtime_error("device EXR chunk table does not match its stream");
         break;
     default:
@@ -746,7 +762,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
         else if (sl.coder == Coder::Png16)  // the film again, through exposure and view transform, at 16 bits
             enqueue_deflate(c, sl, plan, launch_png16(c, film, k.inv_spp, k.exposure_scale, fs.view_transform));
         else  // the film's means: the product finish_frame forms, no view transform
-            enqueue_deflate(c, sl, plan, launch_exr(film, 1.0f / (float)fs.spp, true));
+            enqueue_deflate(c, sl, plan, launch_exr(film, 1.0f / (float)fs.spp, true, sl.coder == Coder::Exr32));
     }
     RR_HIP(hipEventRecord(sl.ev[2], st));
     // the outputs' device-to-host copies follow on the slot's own stream: the
@@ -976,6 +992,13 @@ int rr_create(int device_ordinal, rr_ctx** out) {
             else if (v == "16") png_depth = 16;
             else if (!v.empty() && v != "0") return fail(RR_EINVAL, "RR_PNG_DEPTH must be 0, 8 or 16, got '" + v + "'");
         }
+        int exr_depth = 0;
+        if (const char* d = getenv("RR_EXR_DEPTH")) {  // as rr_set_exr_depth
+            const std::string v(d);
+            if (v == "16") exr_depth = 16;
+            else if (v == "32") exr_depth = 32;
+            else if (!v.empty() && v != "0") return fail(RR_EINVAL, "RR_EXR_DEPTH must be 0, 16 or 32, got '" + v + "'");
+        }
         std::unique_ptr<rr_ctx> c(new rr_ctx());
         c->device = device_ordinal;
         set_device(c.get());
@@ -998,6 +1021,7 @@ int rr_create(int device_ordinal, rr_ctx** out) {
         }
         if (const char* d = getenv("RR_DEVICE_PNG")) c->device_png = std::string(d) == "1";
         c->png_depth = png_depth;
+        c->exr_depth = exr_depth;
         *out = c.release();
         return RR_OK;
     });
@@ -1120,7 +1144,8 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->quality = jpeg_quality;
         if (!out_path) sl->coder = Coder::None;
         else if (jpeg) sl->coder = Coder::Jpeg;
-        else if (exr) sl->coder = Coder::Exr;
+        else if (exr)  // HALF unless the context, or at 0 the scene, asks for FLOAT channels
+            sl->coder = (c->exr_depth ? c->exr_depth : s->desc.render.exr_depth) == 32 ? Coder::Exr32 : Coder::Exr;
         // "PNG". 16 bits per sample: always the device coder (there is no host one)
         else if ((c->png_depth ? c->png_depth : s->desc.render.color_depth) == 16) sl->coder = Coder::Png16;
         else sl->coder = c->device_png ? Coder::Png8 : Coder::HostRgba;
@@ -1324,7 +1349,22 @@ int rr_debug_exr_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint
                         uint64_t* len) {
     if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
     return debug_deflate_device(c, Coder::Exr, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
-                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false); });
+                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false, false); });
+}
+
+int rr_set_exr_depth(rr_ctx* c, int32_t depth) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    if (depth != 0 && depth != 16 && depth != 32)
+        return fail(RR_EINVAL, "EXR depth must be 0 (the scene's), 16 or 32");
+    c->exr_depth = depth;  // read when a frame is submitted; frames in flight keep their choice
+    return RR_OK;
+}
+
+int rr_debug_exr32_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
+                          uint64_t* len) {
+    if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    return debug_deflate_device(c, Coder::Exr32, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
+                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false, true); });
 }
 
 int rr_set_png_depth(rr_ctx* c, int32_t depth) {

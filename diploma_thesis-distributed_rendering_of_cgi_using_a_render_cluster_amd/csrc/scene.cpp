@@ -654,6 +654,11 @@ SceneDesc load_scene(const std::string& path) {
         if (depth != 8.0 && depth != 16.0)
             throw std::runtime_error("render.color_depth must be 8 or 16, got " + std::to_string(depth));
         d.color_depth = (int)depth;
+        // the same setting when the format is OPEN_EXR: 'Float (Half)' 16 or 'Float (Full)' 32
+        const double exr_depth = r.get_num("exr_depth", 16);
+        if (exr_depth != 16.0 && exr_depth != 32.0)
+            throw std::runtime_error("render.exr_depth must be 16 or 32, got " + std::to_string(exr_depth));
+        d.exr_depth = (int)exr_depth;
         d.view_transform_name = r.get_str("view_transform", "Standard");
         // "Filmic" is applied through Blender's OCIO LUTs when the context has
         // them (rr_set_ocio_config); otherwise the frame falls back to Standard

@@ -89,6 +89,7 @@ EXPORTS = [
     "rr_debug_bsdf_sample", "rr_debug_fastmath_check", "rr_debug_tile_costs",
     "rr_set_device_png", "rr_debug_png_device", "rr_debug_exr_device",
     "rr_set_png_depth", "rr_debug_png16_device", "rr_debug_srgb16_table",
+    "rr_set_exr_depth", "rr_debug_exr32_device",
 ]
 
 _lib = None
@@ -149,6 +150,8 @@ def lib() -> ctypes.CDLL:
         "rr_debug_png16_device": (c_int, [P, f32p, i32, i32, i32, ctypes.c_float, u8p, ctypes.c_uint64,
                                           ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_srgb16_table": (c_int, [f32p, i32, i32p]),
+        "rr_set_exr_depth": (c_int, [P, i32]),
+        "rr_debug_exr32_device": (c_int, [P, f32p, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -270,13 +273,16 @@ class Scene:
 class RenderContext:
     """One HIP device (rr_ctx). Not thread-safe; one frame in flight at a time."""
 
-    def __init__(self, device: int = 0, png_depth: int = 0):
-        """png_depth: bits per sample of "PNG" frames (set_png_depth; 0: the scene's)."""
+    def __init__(self, device: int = 0, png_depth: int = 0, exr_depth: int = 0):
+        """png_depth: bits per sample of "PNG" frames (set_png_depth; 0: the scene's).
+        exr_depth: channel type of "OPEN_EXR" frames (set_exr_depth; 0: the scene's)."""
         h = ctypes.c_void_p()
         _check(lib().rr_create(int(device), ctypes.byref(h)))
         self.handle = h
         if png_depth:
             self.set_png_depth(png_depth)
+        if exr_depth:
+            self.set_exr_depth(exr_depth)
         self.device = device
 
     def close(self):
@@ -459,6 +465,25 @@ class RenderContext:
         n = ctypes.c_uint64()
         _check(lib().rr_debug_exr_device(self.handle, _ptr(rgba, ctypes.c_float), w, h,
                                          _ptr(out, ctypes.c_uint8), out.size, ctypes.byref(n)), self.handle)
+        if n.value > out.size:
+            raise RRError(RR_EINVAL, f"device EXR of {n.value} bytes exceeds the {out.size}-byte buffer")
+        return out[:n.value].tobytes()
+
+    def set_exr_depth(self, depth: int = 0):
+        """rr_set_exr_depth: channel type of "OPEN_EXR" frames of this context, 0
+        (the scene's render.exr_depth), 16 (HALF) or 32 (FLOAT: the film's means
+        bit for bit)."""
+        _check(lib().rr_set_exr_depth(self.handle, int(depth)), self.handle)
+
+    def exr32_device(self, rgba: np.ndarray) -> bytes:
+        """rr_debug_exr32_device: the OpenEXR file bytes (FLOAT A, B, G, R; ZIP) of
+        an (H, W, 4) float32 image of means, encoded on the device (exr.hip)."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+        h, w = rgba.shape[:2]
+        out = np.zeros(16 * w * h + 16 * ((h + 15) // 16) + 1024, np.uint8)  # above the all-raw worst case
+        n = ctypes.c_uint64()
+        _check(lib().rr_debug_exr32_device(self.handle, _ptr(rgba, ctypes.c_float), w, h,
+                                           _ptr(out, ctypes.c_uint8), out.size, ctypes.byref(n)), self.handle)
         if n.value > out.size:
             raise RRError(RR_EINVAL, f"device EXR of {n.value} bytes exceeds the {out.size}-byte buffer")
         return out[:n.value].tobytes()

@@ -41,14 +41,16 @@ class RenderError(RuntimeError):
 class BackendRunner:
     def __init__(self, base_directory_path: str | os.PathLike, tracer: WorkerTraceBuilder | None = None,
                  device: int = 0, params: RenderParams | None = None, ctx=None, device_png: bool = False,
-                 png_depth: int = 0):
+                 png_depth: int = 0, exr_depth: int = 0):
         """ctx: a RenderContext on `device` is created here; tests of the host
         logic alone pass a stand-in with the same methods (no rendering).
         device_png: "PNG" jobs are coded on the device (rr_set_device_png).
-        "OPEN_EXR" jobs (half-float ZIP files of the linear film) always are.
+        "OPEN_EXR" jobs (ZIP files of the linear film) always are.
         png_depth: bits per sample of "PNG" jobs (rr_set_png_depth): 8, 16, or 0
         for each scene's own render.color_depth; 16-bit frames are always coded
-        on the device."""
+        on the device.
+        exr_depth: channel type of "OPEN_EXR" jobs (rr_set_exr_depth): 16 (HALF),
+        32 (FLOAT), or 0 for each scene's own render.exr_depth (HALF without one)."""
         base = Path(base_directory_path)
         if not base.is_dir():
             raise RenderError("Provided base directory path is not a directory.")
@@ -60,6 +62,8 @@ class BackendRunner:
             self.ctx.set_device_png(True)
         if png_depth:
             self.ctx.set_png_depth(png_depth)
+        if exr_depth:
+            self.ctx.set_exr_depth(exr_depth)
         self._scenes: dict[str, Scene] = {}
         self._lock = threading.Lock()  # one caller at a time per context (queue.rs:79-118)
         self.last_stats = None

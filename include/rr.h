@@ -199,11 +199,14 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *  - format: "JPEG", "PNG" or "OPEN_EXR" (job output_file_format,
  *    shared/src/jobs/mod.rs:80, handed to image_settings.file_format,
  *    render-timing-script.py:83-92). "OPEN_EXR": the film's mean linear
- *    radiance before any view transform (alpha = 1) as half-float A, B, G, R
- *    channels, ZIP compression in chunks of 16 scanlines, single-part scanline
- *    file; halfs are the means clamped to +-65504 and rounded to nearest even.
- *    Coded on the GPU (exr.hip); there is no host EXR encoder. RR_EINVAL for a
- *    width above 2^19 or a frame of 2 GB and more.
+ *    radiance before any view transform (alpha = 1) as A, B, G, R channels,
+ *    ZIP compression in chunks of 16 scanlines, single-part scanline file.
+ *    The channels are HALF by default (the means clamped to +-65504 and
+ *    rounded to nearest even), or FLOAT (the means' own bits, what
+ *    rr_render_frame_to_memory returns) where rr_set_exr_depth or the scene's
+ *    render.exr_depth says 32. Coded on the GPU (exr.hip); there is no host
+ *    EXR encoder. RR_EINVAL for a width above 2^19 (HALF) or 2^18 (FLOAT), or
+ *    a frame of 2 GB and more.
  *  - jpeg_quality: 1..100 (the reference script forces 90, :84); ignored for
  *    "PNG" and "OPEN_EXR".
  *  - timing / stats: optional outputs (may be NULL). */
@@ -315,6 +318,28 @@ int rr_set_png_depth(rr_ctx* ctx, int32_t depth);
 int rr_debug_png16_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
                           int32_t view_transform, float exposure_scale, uint8_t* out, uint64_t cap,
                           uint64_t* len);
+
+/* Channel type of "OPEN_EXR" frames of ctx: 0 = the scene's render.exr_depth
+ * (16 when the scene has none; the default), 16 = HALF, 32 = FLOAT. Replaces
+ * Blender's image_settings.color_depth for OpenEXR, "Float (Half)" / "Float
+ * (Full)", behind write_still (render-timing-script.py:83-92). A FLOAT file
+ * holds the film's means bit for bit: no clamp, no rounding, subnormals kept;
+ * the layout is otherwise the HALF file's (ZIP, 16 scanlines a chunk), coded on
+ * the device (exr.hip) with chunks of twice the bytes. HALF stays the default
+ * although Blender itself picks 32 when a project of another depth is switched
+ * to OpenEXR. PNG and JPEG frames are unaffected. rr_create reads RR_EXR_DEPTH
+ * (0, 16 or 32) from the environment the same way. Applies to frames submitted
+ * after the call. A FLOAT frame wider than 2^18 pixels, or with a stream of
+ * 2 GB and more, is refused with RR_EINVAL when submitted. RR_EINVAL for a
+ * NULL ctx or another depth. */
+int rr_set_exr_depth(rr_ctx* ctx, int32_t depth);
+
+/* rr_debug_exr_device with FLOAT channels (the path rr_set_exr_depth 32
+ * selects): spp = 1, alpha from the image; the file holds the floats given.
+ * *len receives the file size; the bytes are copied to out if cap >= *len.
+ * Exported for round-trip tests. */
+int rr_debug_exr32_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
+                          uint8_t* out, uint64_t cap, uint64_t* len);
 
 /* The sRGB table of the 16-bit PNG path (host only, no device needed): *n
  * receives the number of floats (intervals + 1), which are copied to table if

@@ -184,9 +184,12 @@ def export(path: str, args) -> dict:
     view_transform = bf.read_struct_at(vs, "ColorManagedViewSettings", "view_transform")
     # image_settings.color_depth: ImageFormatData.depth holds R_IMF_CHAN_DEPTH_*
     # (8 bits = 1 << 1, 16 bits = 1 << 4); the renderer writes PNG at 8 or 16
-    # bits per sample, any other depth (EXR's 32, DPX's 10 / 12) exports as 8
+    # bits per sample, any other depth (EXR's 32, DPX's 10 / 12) exports as 8.
+    # 32 bits (1 << 6) is OpenEXR's 'Float (Full)': exr_depth 32, FLOAT channels
+    # for OPEN_EXR jobs; every other depth leaves them HALF
     imf_depth = bf.read_struct_at(rd("im_format"), "ImageFormatData", "depth")
     color_depth = 16 if imf_depth == (1 << 4) else 8
+    exr_depth = 32 if imf_depth == (1 << 6) else 16
     out = {
         "format": "rrscene", "version": 1, "name": idname(bf, sc),
         "source": {"file": os.path.basename(path), "blender_version": bf.version,
@@ -207,6 +210,8 @@ def export(path: str, args) -> dict:
     }
     if color_depth != 8:  # 8 is what a scene without the field means: such exports stay as they were
         out["render"]["color_depth"] = color_depth
+    if exr_depth != 16:  # likewise: 16 is what a scene without the field means
+        out["render"]["exr_depth"] = exr_depth
     # ID blocks, indexed by old pointer
     mats = bf.blocks_with_code(b"MA")
     mat_index = {b.old_ptr: i for i, b in enumerate(mats)}
