@@ -51,6 +51,14 @@ struct DeflateBufs {
     size_t words;
 };
 
+// No distance of the plan twice: a repeated one becomes 0 (none). The plans of
+// the four-channel files keep their lists as they were.
+inline void deflate_distinct(DeflatePlan& p) {
+    for (int a = 1; a < 3; ++a)
+        for (int b = 0; b < a; ++b)
+            if (p.dist[a] == p.dist[b]) p.dist[a] = 0u;
+}
+
 // Everything of the plan but dist and own_stream; false: a stream of 2 GB and more.
 bool deflate_plan(int W, int H, uint32_t stride, DeflatePlan& p);
 DeflateBufs deflate_carve(const DeflatePlan& p, uint32_t* base);  // base nullptr: only `words`

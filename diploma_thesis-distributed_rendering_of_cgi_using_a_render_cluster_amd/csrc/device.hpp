@@ -268,9 +268,13 @@ struct JpegDevBufs {
     uint32_t* ready;     // mcuy: stuffed row length + 1 once counted (k_jpeg_finish)
     uint32_t* scratch;   // mcuy x jpeg_row_scratch_words
 };
-size_t jpeg_row_scratch_words(int W);
-size_t jpeg_stream_max_bytes(int W, int H);
-void jpeg_encode_device(const uint8_t* d_rgba, int W, int H, const float* d_tab, const uint32_t* d_huff,
+// grey: a one-component file (rr_set_color_mode BW): MCUs of one 8x8 block, Y
+// the grey code of grey.h; else six blocks of a 16x16 MCU.
+size_t jpeg_mcu_rows(int H, bool grey);
+size_t jpeg_block_count(int W, int H, bool grey);
+size_t jpeg_row_scratch_words(int W, bool grey);
+size_t jpeg_stream_max_bytes(int W, int H, bool grey);
+void jpeg_encode_device(const uint8_t* d_rgba, int W, int H, bool grey, const float* d_tab, const uint32_t* d_huff,
                         int16_t* d_coeffs, JpegDevBufs& b, uint8_t* host_out, hipStream_t st);
 
 // The formats coded by the device deflate coder (deflate.hpp): each has
@@ -283,8 +287,9 @@ struct DeflatePlan;
 
 // 8-bit PNG (png.hip): the Sub-filtered RGBA8 frame as one zlib stream, 78 01 +
 // deflate data (image_io png_wrap_stream). W <= 2^20.
-bool png_plan(int W, int H, DeflatePlan& p);
-void png_encode_device(const uint8_t* d_rgba, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
+// C: channels of the file (rr_set_color_mode): 4 RGBA, 3 RGB, 1 grey; rows of C W + 1 bytes.
+bool png_plan(int W, int H, int C, DeflatePlan& p);
+void png_encode_device(const uint8_t* d_rgba, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                        uint32_t* host_tab, hipStream_t st);
 
 // OpenEXR (exr.hip): the film's means as half-float A, B, G, R planes in ZIP
@@ -292,17 +297,18 @@ void png_encode_device(const uint8_t* d_rgba, const DeflatePlan& p, uint32_t* sc
 // reorder, predictor); the bytes are the chunks' pieces: deflate data without
 // zlib framing, or the raw chunk bytes (image_io exr_wrap_stream). W <= 2^19
 // (band positions in 32-bit counters).
-bool exr_plan(int W, int H, DeflatePlan& p);
+// C: 4 the planes A, B, G, R; 3: B, G, R; 1: Y, the Rec.709 luma of the means; 2C W bytes a scanline.
+bool exr_plan(int W, int H, int C, DeflatePlan& p);
 size_t exr_stream_max_bytes(const DeflatePlan& p);  // every chunk raw
 // film: W x H float4 sums, scaled by inv_spp; alpha_one: A = 1.0 (rendered frames), else film.w * inv_spp.
-void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
-                       uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
+void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+                       uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 // The same file with FLOAT channels: the means' own bits (no clamp, no
 // rounding), chunks of 16W bytes a scanline; exr_stream_max_bytes and the table
 // as above. W <= 2^18 (a band has twice the bytes).
-bool exr32_plan(int W, int H, DeflatePlan& p);
-void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
-                         uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
+bool exr32_plan(int W, int H, int C, DeflatePlan& p);
+void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+                         uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 // The Filmic LUTs of one device as kernel arguments (view.hpp FilmicDev::args).
 struct FilmicArgs {
@@ -318,7 +324,8 @@ struct FilmicArgs {
 // sums) as one zlib stream; host_out and host_tab as png_encode_device writes
 // them (image_io png_wrap_stream, depth 16). W <= 2^19 (band positions in
 // 32-bit counters).
-bool png16_plan(int W, int H, DeflatePlan& p);
+// C as for png_plan: rows of 2C W + 1 bytes.
+bool png16_plan(int W, int H, int C, DeflatePlan& p);
 struct Png16Front {
     const float4* film;  // W x H sums
     float inv_spp, exposure_scale;
@@ -326,7 +333,7 @@ struct Png16Front {
     const float* srgb16;  // kSrgb16LutSize + 2 floats (scene.hpp build_srgb16_lut)
     FilmicArgs filmic;
 };
-void png16_encode_device(const Png16Front& f, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
+void png16_encode_device(const Png16Front& f, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                          uint32_t* host_tab, hipStream_t st);
 
 // Per chunk: one pair per bounce b = 0..max_bounces {paths entering b+1,

@@ -32,6 +32,7 @@
 
 #include "deflate.hpp"
 #include "device.hpp"
+#include "grey.h"
 
 namespace rr {
 
@@ -67,36 +68,55 @@ struct Film {
     int alpha_one;
 };
 
-// Half of sample k of a band: k counts scanline by scanline, plane by plane (A, B, G, R).
-__device__ __forceinline__ uint32_t sample_half(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
-    const uint32_t W = (uint32_t)p.W, row_samples = 4u * W;
+// Mean of sample k of a band: k counts scanline by scanline, plane by plane.
+// C = 4: planes A, B, G, R; C = 3: B, G, R; C = 1: Y, the Rec.709 luma of the
+// means (products and sums rounded one by one, left to right).
+template <int C>
+__device__ __forceinline__ float sample_mean(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
+    const uint32_t W = (uint32_t)p.W, row_samples = (uint32_t)C * W;
     const uint32_t row = k / row_samples, rem = k - row * row_samples;
     const uint32_t ch = rem / W, x = rem - ch * W;
     const float4 v = fm.px[(size_t)(row0 + (int)row) * W + x];
-    const float c = ch == 0 ? v.w : ch == 1 ? v.z : ch == 2 ? v.y : v.x;
-    const float mean = (ch == 0 && fm.alpha_one) ? 1.0f : __fmul_rn(c, fm.inv_spp);
-    return half_bits(mean);
+    if constexpr (C == 4) {
+        const float c = ch == 0 ? v.w : ch == 1 ? v.z : ch == 2 ? v.y : v.x;
+        return (ch == 0 && fm.alpha_one) ? 1.0f : __fmul_rn(c, fm.inv_spp);
+    } else if constexpr (C == 3) {
+        const float c = ch == 0 ? v.z : ch == 1 ? v.y : v.x;
+        return __fmul_rn(c, fm.inv_spp);
+    } else {
+        const float r = __fmul_rn(v.x, fm.inv_spp), g = __fmul_rn(v.y, fm.inv_spp), b = __fmul_rn(v.z, fm.inv_spp);
+        return luma709(r, g, b);
+    }
+}
+
+// Half of sample k of a band.
+template <int C>
+__device__ __forceinline__ uint32_t sample_half(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
+    return half_bits(sample_mean<C>(fm, p, row0, k));
 }
 
 // Byte j of a band after the reorder (before the predictor).
+template <int C>
 __device__ __forceinline__ uint32_t reordered_byte(const Film& fm, const DeflatePlan& p, int row0, uint32_t half_n,
                                                    uint32_t j) {
     const bool hi = j >= half_n;
-    const uint32_t h = sample_half(fm, p, row0, hi ? j - half_n : j);
+    const uint32_t h = sample_half<C>(fm, p, row0, hi ? j - half_n : j);
     return hi ? h >> 8 : h & 0xFFu;
 }
 
 // Byte j of a chunk as the coder sees it: reordered, less its predecessor + 128.
+template <int C>
 struct ExrFront {
     Film fm;
     __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t n, uint32_t j) const {
-        uint32_t v = reordered_byte(fm, p, row0, n / 2, j);
-        if (j > 0) v = (v - reordered_byte(fm, p, row0, n / 2, j - 1) + 128u) & 0xFFu;
+        uint32_t v = reordered_byte<C>(fm, p, row0, n / 2, j);
+        if (j > 0) v = (v - reordered_byte<C>(fm, p, row0, n / 2, j - 1) + 128u) & 0xFFu;
         return v;
     }
 };
 
 // Raw chunks (rec mode 1): the n bytes as the file's reader expects them, unprocessed.
+template <int C>
 __global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, DeflatePlan p, const uint32_t* __restrict__ rec,
                                                       uint8_t* __restrict__ out) {
     const int b = blockIdx.y;
@@ -105,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, DeflatePlan p, co
     const uint32_t n = p.stride * (uint32_t)min(kDeflateBandRows, p.H - row0);
     const uint32_t k = blockIdx.x * kThreads + threadIdx.x;  // sample
     if (2u * k >= n) return;
-    const uint32_t h = sample_half(fm, p, row0, k);
+    const uint32_t h = sample_half<C>(fm, p, row0, k);
     uint8_t* o = out + (size_t)b * p.band_cap + 2u * k;  // band_cap is a multiple of 16
     *reinterpret_cast<uint16_t*>(o) = (uint16_t)h;
 }
@@ -117,36 +137,34 @@ __global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, DeflatePlan p, co
 // second n / 2 bytes 1 and 3: position q of a half belongs to sample q / 2.
 
 // Bits of sample k of a band: the mean itself, no clamp and no rounding.
+template <int C>
 __device__ __forceinline__ uint32_t sample_float(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
-    const uint32_t W = (uint32_t)p.W, row_samples = 4u * W;
-    const uint32_t row = k / row_samples, rem = k - row * row_samples;
-    const uint32_t ch = rem / W, x = rem - ch * W;
-    const float4 v = fm.px[(size_t)(row0 + (int)row) * W + x];
-    const float c = ch == 0 ? v.w : ch == 1 ? v.z : ch == 2 ? v.y : v.x;
-    const float mean = (ch == 0 && fm.alpha_one) ? 1.0f : __fmul_rn(c, fm.inv_spp);
-    return __float_as_uint(mean);
+    return __float_as_uint(sample_mean<C>(fm, p, row0, k));
 }
 
 // Byte j of a band of floats after the reorder (before the predictor).
+template <int C>
 __device__ __forceinline__ uint32_t reordered_byte32(const Film& fm, const DeflatePlan& p, int row0, uint32_t half_n,
                                                      uint32_t j) {
     const bool hi = j >= half_n;
     const uint32_t q = hi ? j - half_n : j;
-    const uint32_t bits = sample_float(fm, p, row0, q >> 1);
+    const uint32_t bits = sample_float<C>(fm, p, row0, q >> 1);
     return (bits >> (16u * (q & 1u) + (hi ? 8u : 0u))) & 0xFFu;
 }
 
 // Byte j of a FLOAT chunk as the coder sees it: reordered, less its predecessor + 128.
+template <int C>
 struct ExrFloatFront {
     Film fm;
     __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t n, uint32_t j) const {
-        uint32_t v = reordered_byte32(fm, p, row0, n / 2, j);
-        if (j > 0) v = (v - reordered_byte32(fm, p, row0, n / 2, j - 1) + 128u) & 0xFFu;
+        uint32_t v = reordered_byte32<C>(fm, p, row0, n / 2, j);
+        if (j > 0) v = (v - reordered_byte32<C>(fm, p, row0, n / 2, j - 1) + 128u) & 0xFFu;
         return v;
     }
 };
 
 // Raw FLOAT chunks (rec mode 1): k_exr_raw with 4-byte samples.
+template <int C>
 __global__ __launch_bounds__(kThreads) void k_exr32_raw(Film fm, DeflatePlan p, const uint32_t* __restrict__ rec,
                                                         uint8_t* __restrict__ out) {
     const int b = blockIdx.y;
@@ -156,19 +174,32 @@ __global__ __launch_bounds__(kThreads) void k_exr32_raw(Film fm, DeflatePlan p, 
     const uint32_t k = blockIdx.x * kThreads + threadIdx.x;  // sample
     if (4u * k >= n) return;                                 // n = 16W * rows: whole samples
     uint8_t* o = out + (size_t)b * p.band_cap + 4u * k;      // band_cap is a multiple of 16, n <= band_cap
-    *reinterpret_cast<uint32_t*>(o) = sample_float(fm, p, row0, k);
+    *reinterpret_cast<uint32_t*>(o) = sample_float<C>(fm, p, row0, k);
 }
 
 }  // namespace
 
-bool exr_plan(int W, int H, DeflatePlan& p) {
+// The free distance of a one-channel (Y) chunk, where two of the three
+// coincide (profiles/color_modes.md).
+#ifndef RR_EXR_Y_DIST
+#define RR_EXR_Y_DIST 0
+#endif
+#ifndef RR_EXR32_Y_DIST
+#define RR_EXR32_Y_DIST 0
+#endif
+
+bool exr_plan(int W, int H, int C, DeflatePlan& p) {
     // a band's bit offsets (at most 16 bits a byte, 128 W bytes) stay below 2^32
-    if (W <= 0 || H <= 0 || W > (1 << 19)) return false;
-    const bool ok = deflate_plan(W, H, 8u * (uint32_t)W, p);
-    const uint32_t w = (uint32_t)W;
+    if (W <= 0 || H <= 0 || W > (1 << 19) || (C != 1 && C != 3 && C != 4)) return false;
+    const bool ok = deflate_plan(W, H, 2u * (uint32_t)C * (uint32_t)W, p);
+    const uint32_t w = (uint32_t)W, cw = (uint32_t)C * w;
+    // 1; W: the same pixel in the neighbouring plane; C W: the scanline above
+    // within a half. One plane: the last two are one, and no distance is listed twice.
     p.dist[0] = 1u;
     p.dist[1] = w <= 32768u ? w : 0u;
-    p.dist[2] = 4u * w <= 32768u ? 4u * w : 0u;
+    const uint32_t free_y = (uint32_t)(RR_EXR_Y_DIST);  // may name w
+    p.dist[2] = C == 1 ? (free_y <= 32768u ? free_y : 0u) : cw <= 32768u ? cw : 0u;
+    if (C != 4) deflate_distinct(p);  // narrow images: W = 1, 2
     p.own_stream = 1;
     return ok;
 }
@@ -179,42 +210,58 @@ bool exr_plan(int W, int H, DeflatePlan& p) {
 #define RR_EXR32_DROP 0
 #endif
 
-bool exr32_plan(int W, int H, DeflatePlan& p) {
+bool exr32_plan(int W, int H, int C, DeflatePlan& p) {
     // a band's bit offsets (at most 16 bits a byte, 256 W bytes) stay below 2^30, as exr_plan's
-    if (W <= 0 || H <= 0 || W > (1 << 18)) return false;
-    const bool ok = deflate_plan(W, H, 16u * (uint32_t)W, p);
+    if (W <= 0 || H <= 0 || W > (1 << 18) || (C != 1 && C != 3 && C != 4)) return false;
+    const bool ok = deflate_plan(W, H, 4u * (uint32_t)C * (uint32_t)W, p);
     const uint32_t w = (uint32_t)W;
     // 1; 2: the same byte of the previous sample (a flat area has period 2
-    // after the predictor); 2W: the same pixel in the neighbouring plane; 8W:
+    // after the predictor); 2W: the same pixel in the neighbouring plane; 2C W:
     // the scanline above within a half
-    const uint32_t cand[4] = {1u, 2u, 2u * w, 8u * w};
+    const uint32_t cand[4] = {1u, 2u, 2u * w, 2u * (uint32_t)C * w};
     int k = 0;
     for (int i = 0; i < 4; ++i)
         if (i != RR_EXR32_DROP) p.dist[k++] = cand[i] <= 32768u ? cand[i] : 0u;
+    const uint32_t free_y = (uint32_t)(RR_EXR32_Y_DIST);  // may name w
+    if (C == 1) p.dist[2] = free_y <= 32768u ? free_y : 0u;  // 2W twice: the freed slot
+    if (C != 4) deflate_distinct(p);  // narrow images: W = 1
     p.own_stream = 1;
     return ok;
 }
 
 size_t exr_stream_max_bytes(const DeflatePlan& p) { return (size_t)p.stride * (size_t)p.H; }
 
-void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
-                       uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
-    const DeflateBufs c = deflate_carve(p, scratch);
-    const Film fm{d_film, inv_spp, alpha_one ? 1 : 0};
-    k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFront{fm}, p, c.filt, c.adler_part);
+namespace {
+
+template <int C>
+void exr_launch(const Film& fm, bool full, const DeflatePlan& p, const DeflateBufs& c, hipStream_t st) {
+    if (full) k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFloatFront<C>{fm}, p, c.filt, c.adler_part);
+    else k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFront<C>{fm}, p, c.filt, c.adler_part);
     deflate_bands_device(p, c, st);
-    k_exr_raw<<<dim3((p.band_full / 2 + kThreads - 1) / kThreads, p.nbands), kThreads, 0, st>>>(fm, p, c.rec, c.out);
+    const dim3 grid((p.band_full / (full ? 4 : 2) + kThreads - 1) / kThreads, p.nbands);
+    if (full) k_exr32_raw<C><<<grid, kThreads, 0, st>>>(fm, p, c.rec, c.out);
+    else k_exr_raw<C><<<grid, kThreads, 0, st>>>(fm, p, c.rec, c.out);
+}
+
+void exr_encode(const Film& fm, bool full, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
+                uint32_t* host_tab, hipStream_t st) {
+    const DeflateBufs c = deflate_carve(p, scratch);
+    if (C == 1) exr_launch<1>(fm, full, p, c, st);
+    else if (C == 3) exr_launch<3>(fm, full, p, c, st);
+    else exr_launch<4>(fm, full, p, c, st);
     deflate_gather_device(p, c, host_out, host_tab, st);
 }
 
-void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const DeflatePlan& p, uint32_t* scratch,
-                         uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
-    const DeflateBufs c = deflate_carve(p, scratch);
-    const Film fm{d_film, inv_spp, alpha_one ? 1 : 0};
-    k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFloatFront{fm}, p, c.filt, c.adler_part);
-    deflate_bands_device(p, c, st);
-    k_exr32_raw<<<dim3((p.band_full / 4 + kThreads - 1) / kThreads, p.nbands), kThreads, 0, st>>>(fm, p, c.rec, c.out);
-    deflate_gather_device(p, c, host_out, host_tab, st);
+}  // namespace
+
+void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+                       uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
+    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, false, C, p, scratch, host_out, host_tab, st);
+}
+
+void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+                         uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
+    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, true, C, p, scratch, host_out, host_tab, st);
 }
 
 }  // namespace rr

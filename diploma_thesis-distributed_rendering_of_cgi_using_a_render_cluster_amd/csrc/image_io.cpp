@@ -8,6 +8,8 @@
 // encoded on parallel host threads and joined with RSTn markers.
 #include "image_io.hpp"
 
+#include "grey.h"
+
 #include <zlib.h>
 
 #include <algorithm>
@@ -257,11 +259,34 @@ void mcu_row_coeffs(const uint8_t* rgba, int W, int H, int my, const float qy[64
     }
 }
 
+// The same for a grey file's MCU row `my` (8 pixel rows): coefficients
+// [mcux][64], one block an MCU, Y the grey code (grey.h) of the pixel.
+void mcu_row_coeffs_grey(const uint8_t* rgba, int W, int H, int my, const float qy[64], int16_t* out) {
+    const int mcux = (W + 7) / 8;
+    float Y[64];
+    for (int mx = 0; mx < mcux; ++mx) {
+        for (int yy = 0; yy < 8; ++yy) {
+            const int sy = std::min(my * 8 + yy, H - 1);
+            for (int xx = 0; xx < 8; ++xx) {
+                const int sx = std::min(mx * 8 + xx, W - 1);
+                const uint8_t* p = rgba + 4 * ((size_t)sy * W + sx);
+                Y[8 * yy + xx] = (float)grey8(p[0], p[1], p[2]) - 128.0f;
+            }
+        }
+        fdct_quant(Y, qy, out + (size_t)mx * 64);
+    }
+}
+
 // Huffman-code one MCU row (one restart interval) from its coefficients.
-void entropy_mcu_row(const int16_t* coeffs, int mcux, std::vector<uint8_t>& out) {
+void entropy_mcu_row(const int16_t* coeffs, int mcux, std::vector<uint8_t>& out, bool grey = false) {
     const Tables& T = tables();
     BitWriter bw(out);
     int pred[3] = {0, 0, 0};
+    if (grey) {
+        for (int mx = 0; mx < mcux; ++mx) encode_block(bw, coeffs + (size_t)mx * 64, pred[0], T.dc[0], T.ac[0]);
+        bw.flush();
+        return;
+    }
     for (int mx = 0; mx < mcux; ++mx) {
         const int16_t* o = coeffs + (size_t)mx * 6 * 64;
         for (int k = 0; k < 4; ++k) encode_block(bw, o + 64 * k, pred[0], T.dc[0], T.ac[0]);
@@ -271,18 +296,36 @@ void entropy_mcu_row(const int16_t* coeffs, int mcux, std::vector<uint8_t>& out)
     bw.flush();
 }
 
-void jpeg_header(int W, int H, const uint8_t* ql, const uint8_t* qc, std::vector<uint8_t>& out) {
+// grey: one component 1x1 with the luma tables, MCUs of 8x8 pixels.
+void jpeg_header(int W, int H, const uint8_t* ql, const uint8_t* qc, std::vector<uint8_t>& out, bool grey = false) {
     // SOI + APP0 JFIF
     const uint8_t soi_app0[] = {0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00,
                                 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00};
     out.insert(out.end(), soi_app0, soi_app0 + sizeof soi_app0);
     // DQT (tables in zigzag order)
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < (grey ? 1 : 2); ++t) {
         const uint8_t* q = t ? qc : ql;
         out.push_back(0xFF); out.push_back(0xDB);
         put16(out, 67);
         out.push_back((uint8_t)t);
         for (int k = 0; k < 64; ++k) out.push_back(q[kZigzag[k]]);
+    }
+    if (grey) {
+        out.push_back(0xFF); out.push_back(0xC0);
+        put16(out, 11);
+        out.push_back(8);
+        put16(out, H);
+        put16(out, W);
+        const uint8_t comp[4] = {1, 1, 0x11, 0};
+        out.insert(out.end(), comp, comp + 4);
+        write_dht(out, 0, 0, kDcLumBits, kDcLumVal);
+        write_dht(out, 1, 0, kAcLumBits, kAcLumVal);
+        out.push_back(0xFF); out.push_back(0xDD);
+        put16(out, 4);
+        put16(out, (W + 7) / 8);
+        const uint8_t sos[] = {0xFF, 0xDA, 0x00, 0x08, 0x01, 1, 0x00, 0x00, 0x3F, 0x00};
+        out.insert(out.end(), sos, sos + sizeof sos);
+        return;
     }
     // SOF0: 3 components, Y 2x2, Cb/Cr 1x1
     out.push_back(0xFF); out.push_back(0xC0);
@@ -360,11 +403,11 @@ void jpeg_tables(int quality, JpegTables& t) {
     }
 }
 
-void jpeg_header_bytes(int W, int H, int quality, std::vector<uint8_t>& out) {
+void jpeg_header_bytes(int W, int H, int quality, std::vector<uint8_t>& out, bool grey) {
     JpegTables t;
     jpeg_tables(quality, t);
     out.clear();
-    jpeg_header(W, H, t.ql, t.qc, out);
+    jpeg_header(W, H, t.ql, t.qc, out, grey);
 }
 
 void jpeg_huff_tables(uint32_t out[4 * 256]) {
@@ -374,12 +417,29 @@ void jpeg_huff_tables(uint32_t out[4 * 256]) {
         for (int s = 0; s < 256; ++s) out[256 * t + s] = (uint32_t)order[t]->code[s] | ((uint32_t)order[t]->len[s] << 16);
 }
 
-size_t jpeg_coeff_count(int W, int H) { return (size_t)((W + 15) / 16) * ((H + 15) / 16) * 6 * 64; }
+size_t jpeg_coeff_count(int W, int H, bool grey) {
+    return grey ? (size_t)((W + 7) / 8) * ((H + 7) / 8) * 64 : (size_t)((W + 15) / 16) * ((H + 15) / 16) * 6 * 64;
+}
 
-bool encode_jpeg(const uint8_t* rgba, int W, int H, int quality, std::vector<uint8_t>& out, int threads) {
+bool encode_jpeg(const uint8_t* rgba, int W, int H, int quality, std::vector<uint8_t>& out, int threads, bool grey) {
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return false;
     JpegTables t;
     jpeg_tables(quality, t);
+    if (grey) {
+        const int mcux = (W + 7) / 8, mcuy = (H + 7) / 8;
+        out.clear();
+        out.reserve((size_t)W * H / 4);
+        jpeg_header(W, H, t.ql, t.qc, out, true);
+        std::vector<std::vector<uint8_t>> rows((size_t)mcuy);
+        for_rows(mcuy, threads, [&](int my) {
+            std::vector<int16_t> c((size_t)mcux * 64);
+            mcu_row_coeffs_grey(rgba, W, H, my, t.qinv_l, c.data());
+            rows[my].reserve((size_t)mcux * 48);
+            entropy_mcu_row(c.data(), mcux, rows[my], true);
+        });
+        join_rows(rows, out);
+        return true;
+    }
     const int mcux = (W + 15) / 16, mcuy = (H + 15) / 16;
     out.clear();
     out.reserve((size_t)W * H / 2);
@@ -421,9 +481,21 @@ bool encode_jpeg_coeffs(const int16_t* coeffs, int W, int H, int quality, std::v
 // bands'). A band restarts the 32 KB match window, which costs a little ratio
 // and no correctness. A 1080p 02 frame: one thread took most of the frame's
 // time on the host, more than the GPU's.
-bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, int level, int threads) {
-    if (W <= 0 || H <= 0) return false;
-    const size_t stride = (size_t)W * 4;
+// channels: 4 RGBA (colour type 6), 3 RGB (2), 1 grey (0, the grey code of grey.h).
+bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, int level, int threads, int channels) {
+    if (W <= 0 || H <= 0 || (channels != 1 && channels != 3 && channels != 4)) return false;
+    std::vector<uint8_t> packed;  // the image with the file's channels
+    if (channels != 4) {
+        packed.resize((size_t)W * H * channels);
+        for (size_t i = 0, n = (size_t)W * H; i < n; ++i) {
+            const uint8_t* p = rgba + 4 * i;
+            if (channels == 1) packed[i] = (uint8_t)grey8(p[0], p[1], p[2]);
+            else std::memcpy(&packed[3 * i], p, 3);
+        }
+        rgba = packed.data();
+    }
+    const size_t C = (size_t)channels;
+    const size_t stride = (size_t)W * C;
     std::vector<uint8_t> raw((stride + 1) * H);
     if (threads <= 0) threads = encoder_threads();
     const int bands = std::max(1, std::min(threads, H / 16));  // >= 16 rows a band
@@ -436,7 +508,7 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
             uint8_t* dst = &raw[(stride + 1) * y];
             const uint8_t* src = rgba + stride * y;
             dst[0] = 1;
-            for (size_t x = 0; x < stride; ++x) dst[1 + x] = (uint8_t)(src[x] - (x >= 4 ? src[x - 4] : 0));
+            for (size_t x = 0; x < stride; ++x) dst[1 + x] = (uint8_t)(src[x] - (x >= C ? src[x - C] : 0));
         }
         const uint8_t* in = &raw[(stride + 1) * y0];
         const uLong n = (uLong)((stride + 1) * (size_t)(y1 - y0));
@@ -475,7 +547,7 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
     out.insert(out.end(), sig, sig + 8);
     uint8_t ihdr[13] = {(uint8_t)(W >> 24), (uint8_t)(W >> 16), (uint8_t)(W >> 8), (uint8_t)W,
                         (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H,
-                        8, 6, 0, 0, 0};
+                        8, (uint8_t)(channels == 4 ? 6 : channels == 3 ? 2 : 0), 0, 0, 0};
     png_chunk(out, "IHDR", ihdr, 13);
     png_chunk(out, "IDAT", z.data(), z.size());
     png_chunk(out, "IEND", nullptr, 0);
@@ -483,7 +555,7 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
 }
 
 void png_wrap_stream(int W, int H, const uint8_t* zs, size_t n, const uint32_t* band_tab, int nbands,
-                     std::vector<uint8_t>& out, int depth) {
+                     std::vector<uint8_t>& out, int depth, int color_type) {
     uLong a = adler32(0L, Z_NULL, 0);
     for (int b = 0; b < nbands; ++b) a = adler32_combine(a, band_tab[2 * b], (z_off_t)band_tab[2 * b + 1]);
     std::vector<uint8_t> z(zs, zs + n);
@@ -494,7 +566,7 @@ void png_wrap_stream(int W, int H, const uint8_t* zs, size_t n, const uint32_t* 
     out.insert(out.end(), sig, sig + 8);
     uint8_t ihdr[13] = {(uint8_t)(W >> 24), (uint8_t)(W >> 16), (uint8_t)(W >> 8), (uint8_t)W,
                         (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H,
-                        (uint8_t)depth, 6, 0, 0, 0};
+                        (uint8_t)depth, (uint8_t)color_type, 0, 0, 0};
     png_chunk(out, "IHDR", ihdr, 13);
     png_chunk(out, "IDAT", z.data(), z.size());
     png_chunk(out, "IEND", nullptr, 0);
@@ -518,15 +590,17 @@ void exr_attr(std::vector<uint8_t>& o, const char* name, const char* type, const
 }  // namespace
 
 bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
-                     std::vector<uint8_t>& out, int pixel_type) {
-    const uint32_t row_bytes = (pixel_type == 2 ? 16u : 8u) * (uint32_t)W;  // four planes of FLOAT or HALF
+                     std::vector<uint8_t>& out, int pixel_type, int channels) {
+    if (channels != 1 && channels != 3 && channels != 4) return false;
+    const uint32_t row_bytes = (pixel_type == 2 ? 4u : 2u) * (uint32_t)channels * (uint32_t)W;  // planes of FLOAT or HALF
     out.clear();
     out.reserve(n + 512 + (size_t)nchunks * 22);
     const uint8_t start[8] = {0x76, 0x2F, 0x31, 0x01, 2, 0, 0, 0};
     out.insert(out.end(), start, start + 8);
     std::vector<uint8_t> v;
-    for (const char* ch : {"A", "B", "G", "R"}) {
-        put_str(v, ch);
+    const char* const names[4] = {"A", "B", "G", "R"};
+    for (int k = 4 - channels; k < 4; ++k) {
+        put_str(v, channels == 1 ? "Y" : names[k]);
         put_le(v, (uint32_t)pixel_type, 4);  // 1 HALF, 2 FLOAT
         put_le(v, 0, 4);                     // pLinear, 3 reserved bytes
         put_le(v, 1, 4);  // xSampling

@@ -19,33 +19,42 @@ struct JpegTables {
 void jpeg_tables(int quality, JpegTables& t);
 // Quantised coefficients of a whole image: [mcuy][mcux][6 blocks][64], natural
 // order, blocks Y00 Y01 Y10 Y11 Cb Cr (4:2:0, edge-replicated padding).
-size_t jpeg_coeff_count(int W, int H);
+// grey: a one-component file, [mcuy][mcux][64] with MCUs of 8x8 pixels.
+size_t jpeg_coeff_count(int W, int H, bool grey = false);
 bool encode_jpeg_coeffs(const int16_t* coeffs, int W, int H, int quality, std::vector<uint8_t>& out,
                         int threads = 0);
 // The file bytes in front of the entropy-coded segment (SOI ... SOS), and the
 // Huffman tables as 4 x 256 packed code | len << 16 (DC luma, AC luma, DC
 // chroma, AC chroma) for the device coder (jpeg.hip).
-void jpeg_header_bytes(int W, int H, int quality, std::vector<uint8_t>& out);
+void jpeg_header_bytes(int W, int H, int quality, std::vector<uint8_t>& out, bool grey = false);
 void jpeg_huff_tables(uint32_t out[4 * 256]);
-bool encode_jpeg(const uint8_t* rgba, int W, int H, int quality, std::vector<uint8_t>& out, int threads = 0);
-bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, int level = 1, int threads = 0);
+// grey: single-component baseline (SOF0 with one component 1x1, the luma DQT
+// and DHT pair), Y the pixel's grey code (grey.h), restart interval one row of
+// 8x8 MCUs; jpeg.hip writes the same bytes.
+bool encode_jpeg(const uint8_t* rgba, int W, int H, int quality, std::vector<uint8_t>& out, int threads = 0,
+                 bool grey = false);
+// channels: what the file holds of the RGBA8 image: 4 RGBA (colour type 6), 3
+// RGB (2), 1 the grey code of grey.h (0).
+bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, int level = 1, int threads = 0,
+                int channels = 4);
 // The PNG file around a zlib stream coded on the device (png.hip): z = 78 01 +
 // the bands' deflate pieces; band_tab = {Adler-32, filtered bytes} per band,
 // combined here into the stream's Adler-32. Signature, IHDR, one IDAT, IEND.
 // depth: bits per sample of the RGBA image the stream holds, 8 (png.hip) or 16
-// (png16.hip: big-endian samples, rows of 8W + 1 filtered bytes).
+// (png16.hip: big-endian samples, rows of 8W + 1 filtered bytes). color_type:
+// 6 RGBA, 2 RGB, 0 grey, as the stream's rows were formed.
 void png_wrap_stream(int W, int H, const uint8_t* z, size_t n, const uint32_t* band_tab, int nbands,
-                     std::vector<uint8_t>& out, int depth = 8);
+                     std::vector<uint8_t>& out, int depth = 8, int color_type = 6);
 // The OpenEXR file (single-part scanline, version 2; half A, B, G, R; ZIP,
 // chunks of 16 scanlines) around chunks coded on the device (exr.hip): data =
 // the chunks' pieces back to back, chunk_tab = {mode, bytes, Adler-32, chunk
 // bytes} per chunk. Mode 0: deflate data, wrapped here in 78 01 ... Adler-32;
 // mode 1: the raw chunk. pixel_type: 1 HALF (8W bytes a scanline) or 2 FLOAT
 // (16W), the type of all four channels; nothing else in the header depends on
-// it. false: the pieces do not add up to n, or a chunk's size is not what its
-// scanlines allow.
+// it. channels: 4 the list A, B, G, R; 3: B, G, R; 1: Y. false: the pieces do
+// not add up to n, or a chunk's size is not what its scanlines allow.
 bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
-                     std::vector<uint8_t>& out, int pixel_type = 1);
+                     std::vector<uint8_t>& out, int pixel_type = 1, int channels = 4);
 bool write_file(const std::string& path, const std::vector<uint8_t>& data);
 
 }  // namespace rr

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device.hpp"
+#include "grey.h"
 
 namespace rr {
 
@@ -23,15 +24,23 @@ __constant__ uint8_t c_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32,
 // One 64-thread workgroup per 8x8 block; blocks 0..3 = Y (2x2), 4 = Cb, 5 = Cr.
 // tab: dct[64] | qinv_luma[64] | qinv_chroma[64].
 // Returns this lane's quantised coefficient (natural position threadIdx.x).
+// B: blocks of an MCU. 6: the 16x16 MCU above; 1: a grey file's 8x8 MCU, its
+// one block the grey codes (grey.h) as Y.
+template <int B>
 __device__ __forceinline__ int fdct_block(const uchar4* __restrict__ rgba, int W, int H, int mcux,
                                           const float* __restrict__ tab, int16_t* __restrict__ out, int blk) {
     __shared__ float in[64];
     __shared__ float tmp[64];
-    const int mcu = blockIdx.x / 6;
+    const int mcu = blockIdx.x / B;
     const int mx = mcu % mcux, my = mcu / mcux;
     const int t = threadIdx.x;
     const int ty = t >> 3, tx = t & 7;
-    if (blk < 4) {
+    if constexpr (B == 1) {
+        const int sy = min(my * 8 + ty, H - 1);
+        const int sx = min(mx * 8 + tx, W - 1);
+        const uchar4 p = rgba[(size_t)sy * W + sx];
+        in[t] = (float)grey8(p.x, p.y, p.z) - 128.0f;
+    } else if (blk < 4) {
         const int sy = min(my * 16 + (blk >> 1) * 8 + ty, H - 1);
         const int sx = min(mx * 16 + (blk & 1) * 8 + tx, W - 1);
         const uchar4 p = rgba[(size_t)sy * W + sx];
@@ -64,7 +73,7 @@ __device__ __forceinline__ int fdct_block(const uchar4* __restrict__ rgba, int W
         for (int y = 0; y < 8; ++y) s += tab[8 * v + y] * tmp[8 * y + u];
         const float* qinv = tab + (blk < 4 ? 64 : 128);
         const int16_t q = (int16_t)rintf(s * qinv[8 * v + u]);
-        out[((size_t)mcu * 6 + blk) * 64 + 8 * v + u] = q;
+        out[((size_t)mcu * B + blk) * 64 + 8 * v + u] = q;
         return q;
     }
 }
@@ -155,14 +164,15 @@ __device__ uint32_t wg_scan(uint32_t& v, uint32_t* lds_waves) {
 }
 
 // The forward transform of one block (fdct_block) + its AC bit count (acbits[block]).
+template <int B>
 __global__ __launch_bounds__(64) void k_jpeg_fdct_bits(const uchar4* __restrict__ rgba, int W, int H, int mcux,
                                                        const float* __restrict__ tab,
                                                        const uint32_t* __restrict__ huff,
                                                        int16_t* __restrict__ out, uint32_t* __restrict__ acbits) {
     __shared__ int q[64];
-    const int blk = blockIdx.x % 6;
+    const int blk = blockIdx.x % B;
     const int t = threadIdx.x;
-    const int v = fdct_block(rgba, W, H, mcux, tab, out, blk);
+    const int v = fdct_block<B>(rgba, W, H, mcux, tab, out, blk);
     q[t] = v;
     __syncthreads();
     const int z = q[c_zigzag[t]];
@@ -173,7 +183,9 @@ __global__ __launch_bounds__(64) void k_jpeg_fdct_bits(const uchar4* __restrict_
     if (t == 0) acbits[blockIdx.x] = tot;
 }
 
+template <int B>
 __device__ __forceinline__ int dc_pred_block(int b) {  // previous block of b's component in its row, or -1
+    if constexpr (B == 1) return b - 1;
     const int k = b % 6;
     if (k >= 1 && k <= 3) return b - 1;
     if (b < 6) return -1;
@@ -181,6 +193,7 @@ __device__ __forceinline__ int dc_pred_block(int b) {  // previous block of b's 
 }
 
 // Block bit offsets within each row (DC bits added here), row totals, zeroed words.
+template <int B>
 __global__ __launch_bounds__(kJpegThreads) void k_jpeg_scan(const int16_t* __restrict__ coeffs, int mcux,
                                                             const uint32_t* __restrict__ huff,
                                                             const uint32_t* __restrict__ acbits,
@@ -190,26 +203,26 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg_scan(const int16_t* __res
                                                             uint32_t* __restrict__ scratch, size_t scratch_words) {
     __shared__ uint32_t ws[kJpegThreads / 64];
     const int my = blockIdx.x;
-    const int nblk = mcux * 6;
+    const int nblk = mcux * B;
     const int chunk = (nblk + kJpegThreads - 1) / kJpegThreads;
     const int b0 = min(nblk, (int)threadIdx.x * chunk), b1 = min(nblk, b0 + chunk);
     const size_t rb = (size_t)my * nblk;
     uint32_t sum = 0;
     for (int b = b0; b < b1; ++b) {
-        const int p = dc_pred_block(b);
+        const int p = dc_pred_block<B>(b);
         const int diff = coeffs[(rb + b) * 64] - (p >= 0 ? coeffs[(rb + p) * 64] : 0);
         const int n = cat_bits(diff);
-        const uint32_t e = huff[((b % 6) < 4 ? 0 : 512) + n];
+        const uint32_t e = huff[((b % B) < 4 ? 0 : 512) + n];
         sum += (e >> 16) + n + acbits[rb + b];
     }
     uint32_t off = sum;
     const uint32_t total = wg_scan(off, ws);
     for (int b = b0; b < b1; ++b) {
         blk_off[rb + b] = off;
-        const int p = dc_pred_block(b);
+        const int p = dc_pred_block<B>(b);
         const int diff = coeffs[(rb + b) * 64] - (p >= 0 ? coeffs[(rb + p) * 64] : 0);
         const int n = cat_bits(diff);
-        const uint32_t e = huff[((b % 6) < 4 ? 0 : 512) + n];
+        const uint32_t e = huff[((b % B) < 4 ? 0 : 512) + n];
         off += (e >> 16) + n + acbits[rb + b];
     }
     uint32_t* row = scratch + (size_t)my * scratch_words;
@@ -241,6 +254,7 @@ constexpr int kBlockWords = kJpegBlockMaxBytes / 4 + 2;  // a block's bits + ali
 // LDS (aligned like the row: local bit = global bit - 32 * first word), then
 // the wave writes them out: inner words stored, the first and last (shared
 // with the neighbouring blocks) OR-ed atomically.
+template <int B>
 __global__ __launch_bounds__(kJpegThreads) void k_jpeg_emit(const int16_t* __restrict__ coeffs, int mcux, int nblocks,
                                                             const uint32_t* __restrict__ huff,
                                                             const uint32_t* __restrict__ blk_off,
@@ -251,18 +265,18 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg_emit(const int16_t* __res
     const int gb = blockIdx.x * (kJpegThreads / 64) + wv;
     if (gb >= nblocks) return;
     const int t = threadIdx.x & 63;
-    const int nblk = mcux * 6;
+    const int nblk = mcux * B;
     const int my = gb / nblk, b = gb % nblk;
     uint32_t* lw = words[wv];
     for (int i = t; i < kBlockWords; i += 64) lw[i] = 0u;
     const int16_t* blk = coeffs + (size_t)gb * 64;
     const int z = blk[c_zigzag[t]];
     const uint64_t nz = __ballot(z != 0 && t > 0);
-    const bool luma = (b % 6) < 4;
+    const bool luma = (b % B) < 4;
     uint64_t str = 0ull;
     int len;
     if (t == 0) {  // DC difference
-        const int p = dc_pred_block(b);
+        const int p = dc_pred_block<B>(b);
         const int diff = z - (p >= 0 ? coeffs[(size_t)(gb - b + p) * 64] : 0);
         const int n = cat_bits(diff);
         const uint32_t e = huff[(luma ? 0 : 512) + n];
@@ -355,25 +369,41 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg_finish(const uint32_t* __
 
 }  // namespace
 
-size_t jpeg_row_scratch_words(int W) { return (size_t)((W + 15) / 16) * 6 * kJpegBlockMaxBytes / 4 + 2; }
-static size_t jpeg_row_stuffed_bytes(int W) { return (size_t)((W + 15) / 16) * 6 * kJpegBlockMaxBytes * 2 + 16; }
-size_t jpeg_stream_max_bytes(int W, int H) {
-    return (size_t)((H + 15) / 16) * (jpeg_row_stuffed_bytes(W) + 2) + 16;
+// grey: a one-component file, MCUs of one 8x8 block; else six blocks of a 16x16 MCU.
+static size_t row_blocks(int W, bool grey) { return grey ? (size_t)((W + 7) / 8) : (size_t)((W + 15) / 16) * 6; }
+size_t jpeg_mcu_rows(int H, bool grey) { return grey ? (size_t)(H + 7) / 8 : (size_t)(H + 15) / 16; }
+size_t jpeg_block_count(int W, int H, bool grey) { return row_blocks(W, grey) * jpeg_mcu_rows(H, grey); }
+size_t jpeg_row_scratch_words(int W, bool grey) { return row_blocks(W, grey) * kJpegBlockMaxBytes / 4 + 2; }
+static size_t jpeg_row_stuffed_bytes(int W, bool grey) { return row_blocks(W, grey) * kJpegBlockMaxBytes * 2 + 16; }
+size_t jpeg_stream_max_bytes(int W, int H, bool grey) {
+    return jpeg_mcu_rows(H, grey) * (jpeg_row_stuffed_bytes(W, grey) + 2) + 16;
 }
 
-void jpeg_encode_device(const uint8_t* d_rgba, int W, int H, const float* d_tab, const uint32_t* d_huff,
-                        int16_t* d_coeffs, JpegDevBufs& b, uint8_t* host_out, hipStream_t st) {
-    const int mcux = (W + 15) / 16, mcuy = (H + 15) / 16;
-    const int nblocks = mcux * mcuy * 6;
-    const size_t sw = jpeg_row_scratch_words(W);
-    k_jpeg_fdct_bits<<<nblocks, 64, 0, st>>>(reinterpret_cast<const uchar4*>(d_rgba), W, H, mcux, d_tab, d_huff,
-                                             d_coeffs, b.acbits);
-    k_jpeg_scan<<<mcuy, kJpegThreads, 0, st>>>(d_coeffs, mcux, d_huff, b.acbits, b.blk_off, b.row_bits, b.ready,
-                                               b.scratch, sw);
-    k_jpeg_emit<<<(nblocks + 3) / 4, kJpegThreads, 0, st>>>(d_coeffs, mcux, nblocks, d_huff, b.blk_off, b.row_bits,
-                                                             b.scratch, sw);
+namespace {
+
+template <int B>
+void jpeg_launch(const uint8_t* d_rgba, int W, int H, const float* d_tab, const uint32_t* d_huff, int16_t* d_coeffs,
+                 JpegDevBufs& b, uint8_t* host_out, hipStream_t st) {
+    constexpr bool grey = B == 1;
+    const int mcux = grey ? (W + 7) / 8 : (W + 15) / 16, mcuy = (int)jpeg_mcu_rows(H, grey);
+    const int nblocks = mcux * mcuy * B;
+    const size_t sw = jpeg_row_scratch_words(W, grey);
+    k_jpeg_fdct_bits<B><<<nblocks, 64, 0, st>>>(reinterpret_cast<const uchar4*>(d_rgba), W, H, mcux, d_tab, d_huff,
+                                                d_coeffs, b.acbits);
+    k_jpeg_scan<B><<<mcuy, kJpegThreads, 0, st>>>(d_coeffs, mcux, d_huff, b.acbits, b.blk_off, b.row_bits, b.ready,
+                                                  b.scratch, sw);
+    k_jpeg_emit<B><<<(nblocks + 3) / 4, kJpegThreads, 0, st>>>(d_coeffs, mcux, nblocks, d_huff, b.blk_off, b.row_bits,
+                                                                b.scratch, sw);
     k_jpeg_finish<<<mcuy, kJpegThreads, 0, st>>>(b.row_bits, b.scratch, sw, b.ready, mcuy, host_out);
     RR_HIP(hipGetLastError());
+}
+
+}  // namespace
+
+void jpeg_encode_device(const uint8_t* d_rgba, int W, int H, bool grey, const float* d_tab, const uint32_t* d_huff,
+                        int16_t* d_coeffs, JpegDevBufs& b, uint8_t* host_out, hipStream_t st) {
+    if (grey) jpeg_launch<1>(d_rgba, W, H, d_tab, d_huff, d_coeffs, b, host_out, st);
+    else jpeg_launch<6>(d_rgba, W, H, d_tab, d_huff, d_coeffs, b, host_out, st);
 }
 
 }  // namespace rr

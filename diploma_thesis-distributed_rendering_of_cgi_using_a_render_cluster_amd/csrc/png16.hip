@@ -8,7 +8,9 @@
 //
 // A row is 8W + 1 filtered bytes: filter type 1 (Sub), then per pixel R, G, B,
 // A as big-endian 16-bit samples, each byte less the byte 8 positions (one
-// pixel) before it. A = 65535.
+// pixel) before it. A = 65535. With rr_set_color_mode the pixel is R, G, B
+// (rows of 6W + 1 bytes) or one grey sample (2W + 1), the filter distance the
+// pixel's size.
 //
 //  - Png16Sub: the filtered byte at a position, the front end of the deflate
 //    coder (deflate.hpp k_deflate_front). A position computes its own sample
@@ -33,6 +35,7 @@
 
 #include "deflate.hpp"
 #include "device.hpp"
+#include "grey.h"
 #include "view_filmic.h"
 
 namespace rr {
@@ -44,60 +47,105 @@ namespace {
 #define RR_PNG16_DIST3 2
 #endif
 
-// The 16-bit sample of channel ch (0 R, 1 G, 2 B) of a film sum.
-__device__ __forceinline__ uint32_t sample16(const Png16Front& f, float4 acc, uint32_t ch) {
-    if (f.view_transform == 2) {  // Filmic
-        const float c[3] = {acc.x * f.inv_spp * f.exposure_scale, acc.y * f.inv_spp * f.exposure_scale,
-                            acc.z * f.inv_spp * f.exposure_scale};
-        float d[3];
-        filmic_display(f.filmic, c, d);
-        return quantize16(ch == 0 ? d[0] : ch == 1 ? d[1] : d[2]);
-    }
-    const float a = ch == 0 ? acc.x : ch == 1 ? acc.y : acc.z;
+// The display-referred value of one channel's film sum (Standard and Raw):
+// mean, exposure, clamp, view transform.
+__device__ __forceinline__ float display1(const Png16Front& f, float a) {
     const float c = a * f.inv_spp * f.exposure_scale;
     float v = fminf(fmaxf(c, 0.0f), 1.0f);
     if (f.view_transform == 0) v = srgb_oetf16(v, f.srgb16);
-    return quantize16(v);
+    return v;
 }
 
-// Byte q < 8W of an image row before the filter.
+// The three display-referred values of a film sum through the Filmic chain.
+__device__ __forceinline__ void display_filmic(const Png16Front& f, float4 acc, float d[3]) {
+    const float c[3] = {acc.x * f.inv_spp * f.exposure_scale, acc.y * f.inv_spp * f.exposure_scale,
+                        acc.z * f.inv_spp * f.exposure_scale};
+    filmic_display(f.filmic, c, d);
+}
+
+// The 16-bit sample of channel ch (0 R, 1 G, 2 B) of a film sum.
+__device__ __forceinline__ uint32_t sample16(const Png16Front& f, float4 acc, uint32_t ch) {
+    if (f.view_transform == 2) {  // Filmic
+        float d[3];
+        display_filmic(f, acc, d);
+        return quantize16(ch == 0 ? d[0] : ch == 1 ? d[1] : d[2]);
+    }
+    return quantize16(display1(f, ch == 0 ? acc.x : ch == 1 ? acc.y : acc.z));
+}
+
+// The 16-bit grey sample of a film sum (Blender's BW colour mode): Rec.709 luma
+// of the three display-referred values, products and sums rounded one by one.
+__device__ __forceinline__ uint32_t grey16(const Png16Front& f, float4 acc) {
+    float d[3];
+    if (f.view_transform == 2) {  // Filmic
+        display_filmic(f, acc, d);
+    } else {
+        d[0] = display1(f, acc.x);
+        d[1] = display1(f, acc.y);
+        d[2] = display1(f, acc.z);
+    }
+    return quantize16(luma709(d[0], d[1], d[2]));
+}
+
+// Byte q < 2C W of an image row before the filter. C = 4: R, G, B, A = 65535;
+// 3: R, G, B; 1: grey.
+template <int C>
 __device__ __forceinline__ uint32_t row_byte(const Png16Front& f, const float4* __restrict__ row, uint32_t q) {
-    const uint32_t ch = (q >> 1) & 3u;
-    if (ch == 3u) return 0xFFu;  // A = 65535
-    const uint32_t s = sample16(f, row[q >> 3], ch);
+    uint32_t s;
+    if constexpr (C == 4) {
+        const uint32_t ch = (q >> 1) & 3u;
+        if (ch == 3u) return 0xFFu;  // A = 65535
+        s = sample16(f, row[q >> 3], ch);
+    } else if constexpr (C == 3) {
+        const uint32_t k = q >> 1, px = k / 3u;
+        s = sample16(f, row[px], k - 3u * px);
+    } else {
+        s = grey16(f, row[q >> 1]);
+    }
     return (q & 1u) ? s & 0xFFu : s >> 8;
 }
 
 // Byte j of a band: filter type 1 (Sub) in front of every row of differences.
+template <int C>
 struct Png16Sub {
     Png16Front f;
     __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t, uint32_t j) const {
         const uint32_t row = j / p.stride, x = j - row * p.stride;
         if (x == 0) return 1u;
         const float4* src = f.film + (size_t)(row0 + (int)row) * (size_t)p.W;
-        uint32_t v = row_byte(f, src, x - 1u);
-        if (x > 8u) v = (v - row_byte(f, src, x - 9u)) & 0xFFu;
+        uint32_t v = row_byte<C>(f, src, x - 1u);
+        if (x > 2u * C) v = (v - row_byte<C>(f, src, x - 1u - 2u * C)) & 0xFFu;
         return v;
     }
 };
 
 }  // namespace
 
-bool png16_plan(int W, int H, DeflatePlan& p) {
+// The free distance of a grey image, where the sample and the pixel period are
+// one (profiles/color_modes.md).
+#ifndef RR_PNG16_Y_DIST
+#define RR_PNG16_Y_DIST 0
+#endif
+
+bool png16_plan(int W, int H, int C, DeflatePlan& p) {
     // a band's bit offsets (at most 16 bits a byte, 128 W + 16 bytes) stay below 2^32
-    if (W <= 0 || H <= 0 || W > (1 << 19)) return false;
-    const bool ok = deflate_plan(W, H, 8u * (uint32_t)W + 1u, p);
+    if (W <= 0 || H <= 0 || W > (1 << 19) || (C != 1 && C != 3 && C != 4)) return false;
+    const bool ok = deflate_plan(W, H, 2u * (uint32_t)C * (uint32_t)W + 1u, p);
     p.dist[0] = RR_PNG16_DIST3;
-    p.dist[1] = 8u;
+    p.dist[1] = C == 1 ? (uint32_t)RR_PNG16_Y_DIST : 2u * (uint32_t)C;
     p.dist[2] = p.stride <= 32768u ? p.stride : 0u;
+    if (C != 4) deflate_distinct(p);  // narrow images: a row of 3 bytes
     p.own_stream = 0;
     return ok;
 }
 
-void png16_encode_device(const Png16Front& f, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
+void png16_encode_device(const Png16Front& f, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                          uint32_t* host_tab, hipStream_t st) {
     const DeflateBufs c = deflate_carve(p, scratch);
-    k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(Png16Sub{f}, p, c.filt, c.adler_part);
+    const dim3 grid(p.nsub, p.nbands);
+    if (C == 1) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<1>{f}, p, c.filt, c.adler_part);
+    else if (C == 3) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<3>{f}, p, c.filt, c.adler_part);
+    else k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<4>{f}, p, c.filt, c.adler_part);
     deflate_bands_device(p, c, st);
     deflate_gather_device(p, c, host_out, host_tab, st);
 }

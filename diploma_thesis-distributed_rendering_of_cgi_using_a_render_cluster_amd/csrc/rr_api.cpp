@@ -85,6 +85,20 @@ bool device_deflate(Coder k) {
     return k == Coder::Png8 || k == Coder::Png16 || k == Coder::Exr || k == Coder::Exr32;
 }
 
+// The channels a frame's file holds (rr_set_color_mode), which is also the
+// resolved mode's value: RR_COLOR_BW 1, RR_COLOR_RGB 3, RR_COLOR_RGBA 4. mode 0:
+// the format's layout before there was a setting (JPEG three components, PNG
+// and OPEN_EXR four channels). JPEG has no alpha: RGBA resolves to RGB, as in
+// Blender.
+int resolve_color_mode(int mode, bool jpeg) {
+    if (mode == 0) return jpeg ? RR_COLOR_RGB : RR_COLOR_RGBA;
+    return (jpeg && mode == RR_COLOR_RGBA) ? RR_COLOR_RGB : mode;
+}
+
+bool valid_color_mode(int mode) {
+    return mode == RR_COLOR_SCENE || mode == RR_COLOR_BW || mode == RR_COLOR_RGB || mode == RR_COLOR_RGBA;
+}
+
 const char* coder_ext(Coder k) {
     return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : ".png";
 }
@@ -141,6 +155,7 @@ struct FrameSlot {
     std::string out_path;
     int quality = 0;
     Coder coder = Coder::None;
+    int color_mode = RR_COLOR_RGBA;  // resolved when the frame is submitted (resolve_color_mode): the file's channels
     bool count = false;
     bool unit_logged = false;  // its k_tiles launch wrote the unit log into trav_counts (rr_debug_tile_costs)
     float* film_out = nullptr;
@@ -210,6 +225,8 @@ struct rr_ctx {
     int png_depth = 0;
     // channel type of "OPEN_EXR" frames (rr_set_exr_depth / RR_EXR_DEPTH): 0 the scene's, 16 HALF, 32 FLOAT
     int exr_depth = 0;
+    // colour mode of the files (rr_set_color_mode / RR_COLOR_MODE): 0 the scene's, else RR_COLOR_BW / RGB / RGBA
+    int color_mode = 0;
     DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
     std::vector<float> filter_cache;
     float filter_width_cached = -1.f;
@@ -503,7 +520,9 @@ void jpeg_device_table(int quality, float out[192]) {
 
 // Device JPEG encode of an RGBA8 frame (transform into c->jpeg_coeffs +
 // Huffman coding) into the slot's pinned stream buffer, on the context stream.
+// The slot's colour mode decides the file: RR_COLOR_BW a one-component one.
 void enqueue_jpeg_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W, int H, const float* d_tab) {
+    const bool grey = sl.color_mode == RR_COLOR_BW;
     if (!c->jpeg_huff.ptr) {
         quiesce(c);
         uint32_t h[4 * 256];
@@ -511,17 +530,17 @@ void enqueue_jpeg_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W,
         c->jpeg_huff.ensure(4 * 256);
         RR_HIP(hipMemcpy(c->jpeg_huff.ptr, h, sizeof h, hipMemcpyHostToDevice));
     }
-    const size_t mcuy = (size_t)(H + 15) / 16;
-    const size_t nblocks = mcuy * (size_t)((W + 15) / 16) * 6;
-    c->jpeg_coeffs.ensure(jpeg_coeff_count(W, H));
+    const size_t mcuy = jpeg_mcu_rows(H, grey);
+    const size_t nblocks = jpeg_block_count(W, H, grey);
+    c->jpeg_coeffs.ensure(jpeg_coeff_count(W, H, grey));
     c->jpeg_blk.ensure(2 * nblocks + 2 * mcuy);
-    c->jpeg_scratch.ensure(mcuy * jpeg_row_scratch_words(W));
-    sl.host_jpeg.ensure(jpeg_stream_max_bytes(W, H) + 16);
+    c->jpeg_scratch.ensure(mcuy * jpeg_row_scratch_words(W, grey));
+    sl.host_jpeg.ensure(jpeg_stream_max_bytes(W, H, grey) + 16);
     void* dev_host = nullptr;
     RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_jpeg.ptr, 0));
     uint32_t* blk = c->jpeg_blk.ptr;
     JpegDevBufs b{blk, blk + nblocks, blk + 2 * nblocks, blk + 2 * nblocks + mcuy, c->jpeg_scratch.ptr};
-    jpeg_encode_device(d_rgba, W, H, d_tab, c->jpeg_huff.ptr, c->jpeg_coeffs.ptr, b, static_cast<uint8_t*>(dev_host),
+    jpeg_encode_device(d_rgba, W, H, grey, d_tab, c->jpeg_huff.ptr, c->jpeg_coeffs.ptr, b, static_cast<uint8_t*>(dev_host),
                        c->stream);
 }
 
@@ -530,7 +549,7 @@ void jpeg_file_bytes(const FrameSlot& sl, std::vector<uint8_t>& data) {
     uint64_t len = 0;
     std::memcpy(&len, sl.host_jpeg.ptr, sizeof len);
     if (len + 16 > sl.host_jpeg.cap) throw std::runtime_error("device JPEG stream overflow");
-    jpeg_header_bytes(sl.fs.W, sl.fs.H, sl.quality, data);
+    jpeg_header_bytes(sl.fs.W, sl.fs.H, sl.quality, data, sl.color_mode == RR_COLOR_BW);
     data.insert(data.end(), sl.host_jpeg.ptr + 16, sl.host_jpeg.ptr + 16 + len);
 }
 
@@ -547,11 +566,11 @@ void ensure_srgb16(rr_ctx* c) {
 
 // The plan of a deflate-coded frame. A size outside the coder's range is
 // refused, never rerouted: there is no other coder that writes the same file.
-int plan_or_refuse(Coder k, int W, int H, DeflatePlan& p) {
-    const bool ok = k == Coder::Png8    ? png_plan(W, H, p)
-                    : k == Coder::Png16 ? png16_plan(W, H, p)
-                    : k == Coder::Exr32 ? exr32_plan(W, H, p)
-                                        : exr_plan(W, H, p);
+int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p) {
+    const bool ok = k == Coder::Png8    ? png_plan(W, H, C, p)
+                    : k == Coder::Png16 ? png16_plan(W, H, C, p)
+                    : k == Coder::Exr32 ? exr32_plan(W, H, C, p)
+                                        : exr_plan(W, H, C, p);
     if (ok) return RR_OK;
     const char* name = k == Coder::Png8    ? "PNG"
                        : k == Coder::Png16 ? "16-bit PNG"
@@ -561,27 +580,27 @@ int plan_or_refuse(Coder k, int W, int H, DeflatePlan& p) {
 }
 
 // The formats' encode calls as enqueue_deflate's `launch`. film: sums, scaled
-// by inv_spp.
-auto launch_png8(const uint8_t* d_rgba) {
+// by inv_spp. C: the file's channels (FrameSlot::color_mode).
+auto launch_png8(const uint8_t* d_rgba, int C) {
     return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        png_encode_device(d_rgba, p, scratch, out, tab, st);
+        png_encode_device(d_rgba, C, p, scratch, out, tab, st);
     };
 }
 // view_transform is the resolved one (Filmic only with the context's LUTs).
-auto launch_png16(rr_ctx* c, const float4* d_film, float inv_spp, float exposure_scale, int view_transform) {
+auto launch_png16(rr_ctx* c, const float4* d_film, float inv_spp, float exposure_scale, int view_transform, int C) {
     if (view_transform == VIEW_FILMIC && !c->filmic.ready) throw std::runtime_error("Filmic view transform without LUTs");
     ensure_srgb16(c);
     const Png16Front f{d_film, inv_spp, exposure_scale, view_transform, c->srgb16_lut.ptr,
                        view_transform == VIEW_FILMIC ? c->filmic.args() : FilmicArgs{}};
     return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        png16_encode_device(f, p, scratch, out, tab, st);
+        png16_encode_device(f, C, p, scratch, out, tab, st);
     };
 }
 // full: FLOAT channels (Coder::Exr32), else HALF
-auto launch_exr(const float4* d_film, float inv_spp, bool alpha_one, bool full) {
+auto launch_exr(const float4* d_film, float inv_spp, bool alpha_one, bool full, int C) {
     return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        if (full) exr32_encode_device(d_film, inv_spp, alpha_one, p, scratch, out, tab, st);
-        else exr_encode_device(d_film, inv_spp, alpha_one, p, scratch, out, tab, st);
+        if (full) exr32_encode_device(d_film, inv_spp, alpha_one, C, p, scratch, out, tab, st);
+        else exr_encode_device(d_film, inv_spp, alpha_one, C, p, scratch, out, tab, st);
     };
 }
 
@@ -603,8 +622,8 @@ void enqueue_deflate(rr_ctx* c, FrameSlot& sl, const DeflatePlan& p, Launch laun
 }
 
 // The file of a deflate-coded frame: the host-built container of format k
-// around the device stream.
-void deflate_file_bytes(const DeflateOut& o, Coder k, std::vector<uint8_t>& data) {
+// around the device stream. C: the channels the stream was coded with.
+void deflate_file_bytes(const DeflateOut& o, Coder k, int C, std::vector<uint8_t>& data) {
     const DeflatePlan& p = o.plan;
     const uint32_t* tab = reinterpret_cast<const uint32_t*>(o.tab.ptr);
     uint64_t len = 0;
@@ -615,11 +634,13 @@ void deflate_file_bytes(const DeflateOut& o, Coder k, std::vector<uint8_t>& data
     switch (k) {
     case Coder::Png8:
     case Coder::Png16:
-        png_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Png16 ? 16 : 8);
+        png_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Png16 ? 16 : 8,
+                        C == 4 ? 6 : C == 3 ? 2 : 0);
         break;
     case Coder::Exr:
     case Coder::Exr32:
-        if (!exr_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Exr32 ? 2 : 1))
+        if (!exr_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Exr32 ? 2 : 1,
+                             C))
             throw std::runtime_error("device EXR chunk table does not match its stream");
         break;
     default:
@@ -758,11 +779,13 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
         const DeflatePlan& plan = sl.deflate.plan;  // rr_frame_submit's
         const float4* film = c->paths.film.ptr;
         if (sl.coder == Coder::Png8)
-            enqueue_deflate(c, sl, plan, launch_png8(c->paths.rgba8.ptr));
+            enqueue_deflate(c, sl, plan, launch_png8(c->paths.rgba8.ptr, sl.color_mode));
         else if (sl.coder == Coder::Png16)  // the film again, through exposure and view transform, at 16 bits
-            enqueue_deflate(c, sl, plan, launch_png16(c, film, k.inv_spp, k.exposure_scale, fs.view_transform));
+            enqueue_deflate(c, sl, plan,
+                            launch_png16(c, film, k.inv_spp, k.exposure_scale, fs.view_transform, sl.color_mode));
         else  // the film's means: the product finish_frame forms, no view transform
-            enqueue_deflate(c, sl, plan, launch_exr(film, 1.0f / (float)fs.spp, true, sl.coder == Coder::Exr32));
+            enqueue_deflate(c, sl, plan,
+                            launch_exr(film, 1.0f / (float)fs.spp, true, sl.coder == Coder::Exr32, sl.color_mode));
     }
     RR_HIP(hipEventRecord(sl.ev[2], st));
     // the outputs' device-to-host copies follow on the slot's own stream: the
@@ -872,18 +895,20 @@ void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int
     st->n_triangles = n_tris;
 }
 
+// mode: a colour mode as rr_set_color_mode takes it, 0 the format's own layout.
 int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,
-              uint64_t* bytes) {
+              uint64_t* bytes, int mode = 0) {
     if (!out_path || !format) return fail(RR_EINVAL, "out_path and format are required");
     const std::string fmt(format);
     std::vector<uint8_t> data;
     std::string ext;
     if (fmt == "JPEG") {
         if (quality < 1 || quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
-        if (!encode_jpeg(rgba, W, H, quality, data)) return fail(RR_EINVAL, "JPEG encode failed");
+        if (!encode_jpeg(rgba, W, H, quality, data, 0, resolve_color_mode(mode, true) == RR_COLOR_BW))
+            return fail(RR_EINVAL, "JPEG encode failed");
         ext = ".jpg";
     } else if (fmt == "PNG") {
-        if (!encode_png(rgba, W, H, data, 1)) return fail(RR_EIO, "PNG encode failed");
+        if (!encode_png(rgba, W, H, data, 1, 0, resolve_color_mode(mode, false))) return fail(RR_EIO, "PNG encode failed");
         ext = ".png";
     } else {
         return fail(RR_ENOTSUP, "unsupported output format '" + fmt + "' (JPEG and PNG are supported)");
@@ -906,10 +931,10 @@ bool idle(rr_ctx* c) { return c->next_complete == c->next_ticket; }
 // caller's through format k's coder on slot 0, the file's bytes to `out` if
 // `cap` suffices. make(device image) gives enqueue_deflate's launch.
 template <class Make>
-int debug_deflate_device(rr_ctx* c, Coder k, int w, int h, const void* pixels, size_t bytes, uint8_t* out, uint64_t cap,
-                         uint64_t* len, Make make) {
+int debug_deflate_device(rr_ctx* c, Coder k, int C, int w, int h, const void* pixels, size_t bytes, uint8_t* out,
+                         uint64_t cap, uint64_t* len, Make make) {
     DeflatePlan plan;
-    const int rc = plan_or_refuse(k, w, h, plan);
+    const int rc = plan_or_refuse(k, C, w, h, plan);
     if (rc != RR_OK) return rc;
     return guarded([&] {
         if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
@@ -922,9 +947,43 @@ int debug_deflate_device(rr_ctx* c, Coder k, int w, int h, const void* pixels, s
         RR_HIP(hipStreamSynchronize(c->stream));
         img.release();
         std::vector<uint8_t> data;
-        deflate_file_bytes(sl.deflate, k, data);
+        deflate_file_bytes(sl.deflate, k, C, data);
         *len = data.size();
         if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
+        return RR_OK;
+    });
+}
+
+// The body of the JPEG inspection entry points: an RGBA8 image of the caller's
+// through the device JPEG coder on slot 0 in colour mode `mode` (resolved).
+int debug_jpeg_device(rr_ctx* c, int mode, const uint8_t* rgba8, int32_t w, int32_t h, int32_t quality, uint8_t* out,
+                      uint64_t cap, uint64_t* len) {
+    return guarded([&] {
+        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
+        set_device(c);
+        hipStream_t st = c->stream;
+        DevBuf<uint8_t> img;
+        img.ensure((size_t)w * h * 4);
+        RR_HIP(hipMemcpy(img.ptr, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice));
+        float tab[192];
+        jpeg_device_table(quality, tab);
+        DevBuf<float> dtab;
+        dtab.ensure(192);
+        RR_HIP(hipMemcpy(dtab.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
+        c->jpeg_tab_quality = -1;  // the context's cached table is not this one's
+        FrameSlot& sl = c->slots[0];
+        sl.fs.W = w;
+        sl.fs.H = h;
+        sl.quality = quality;
+        sl.color_mode = mode;
+        enqueue_jpeg_device(c, sl, img.ptr, w, h, dtab.ptr);
+        RR_HIP(hipStreamSynchronize(st));
+        std::vector<uint8_t> data;
+        jpeg_file_bytes(sl, data);
+        *len = data.size();
+        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
+        img.release();
+        dtab.release();
         return RR_OK;
     });
 }
@@ -999,6 +1058,14 @@ int rr_create(int device_ordinal, rr_ctx** out) {
             else if (v == "32") exr_depth = 32;
             else if (!v.empty() && v != "0") return fail(RR_EINVAL, "RR_EXR_DEPTH must be 0, 16 or 32, got '" + v + "'");
         }
+        int color_mode = 0;
+        if (const char* d = getenv("RR_COLOR_MODE")) {  // as rr_set_color_mode
+            const std::string v(d);
+            if (v == "BW") color_mode = RR_COLOR_BW;
+            else if (v == "RGB") color_mode = RR_COLOR_RGB;
+            else if (v == "RGBA") color_mode = RR_COLOR_RGBA;
+            else if (!v.empty()) return fail(RR_EINVAL, "RR_COLOR_MODE must be BW, RGB or RGBA, got '" + v + "'");
+        }
         std::unique_ptr<rr_ctx> c(new rr_ctx());
         c->device = device_ordinal;
         set_device(c.get());
@@ -1022,6 +1089,7 @@ int rr_create(int device_ordinal, rr_ctx** out) {
         if (const char* d = getenv("RR_DEVICE_PNG")) c->device_png = std::string(d) == "1";
         c->png_depth = png_depth;
         c->exr_depth = exr_depth;
+        c->color_mode = color_mode;
         *out = c.release();
         return RR_OK;
     });
@@ -1149,8 +1217,10 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         // "PNG". 16 bits per sample: always the device coder (there is no host one)
         else if ((c->png_depth ? c->png_depth : s->desc.render.color_depth) == 16) sl->coder = Coder::Png16;
         else sl->coder = c->device_png ? Coder::Png8 : Coder::HostRgba;
+        // the context's mode, at 0 the scene's, at 0 again the format's own layout
+        sl->color_mode = resolve_color_mode(c->color_mode ? c->color_mode : s->desc.render.color_mode, jpeg);
         if (device_deflate(sl->coder)) {
-            const int rc = plan_or_refuse(sl->coder, sl->fs.W, sl->fs.H, sl->deflate.plan);
+            const int rc = plan_or_refuse(sl->coder, sl->color_mode, sl->fs.W, sl->fs.H, sl->deflate.plan);
             if (rc != RR_OK) return rc;
         }
         if (sl->coder == Coder::Png16) {
@@ -1216,12 +1286,13 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
         if (sl->coder == Coder::Jpeg || device_deflate(sl->coder)) {  // the host's container + the device-coded stream
             std::vector<uint8_t> data;
             if (sl->coder == Coder::Jpeg) jpeg_file_bytes(*sl, data);
-            else deflate_file_bytes(sl->deflate, sl->coder, data);
+            else deflate_file_bytes(sl->deflate, sl->coder, sl->color_mode, data);
             const std::string path = sl->out_path + coder_ext(sl->coder);
             bytes = data.size();
             if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
         } else if (sl->coder == Coder::HostRgba) {  // a submitted frame's: "PNG" by the host coder
-            const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), "PNG", sl->quality, &bytes);
+            const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), "PNG", sl->quality, &bytes,
+                                    sl->color_mode);
             if (e != RR_OK) return e;
         }
         const double enc_ms = ms_since(t_enc);
@@ -1302,33 +1373,7 @@ int rr_debug_jpeg_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, 
                          uint64_t cap, uint64_t* len) {
     if (!c || !rgba8 || !len || w <= 0 || h <= 0 || w > 65535 || h > 65535) return fail(RR_EINVAL, "bad arguments");
     if (quality < 1 || quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        hipStream_t st = c->stream;
-        DevBuf<uint8_t> img;
-        img.ensure((size_t)w * h * 4);
-        RR_HIP(hipMemcpy(img.ptr, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice));
-        float tab[192];
-        jpeg_device_table(quality, tab);
-        DevBuf<float> dtab;
-        dtab.ensure(192);
-        RR_HIP(hipMemcpy(dtab.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
-        c->jpeg_tab_quality = -1;  // the context's cached table is not this one's
-        FrameSlot& sl = c->slots[0];
-        sl.fs.W = w;
-        sl.fs.H = h;
-        sl.quality = quality;
-        enqueue_jpeg_device(c, sl, img.ptr, w, h, dtab.ptr);
-        RR_HIP(hipStreamSynchronize(st));
-        std::vector<uint8_t> data;
-        jpeg_file_bytes(sl, data);
-        *len = data.size();
-        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
-        img.release();
-        dtab.release();
-        return RR_OK;
-    });
+    return debug_jpeg_device(c, RR_COLOR_RGB, rgba8, w, h, quality, out, cap, len);
 }
 
 int rr_set_device_png(rr_ctx* c, int32_t on) {
@@ -1340,16 +1385,16 @@ int rr_set_device_png(rr_ctx* c, int32_t on) {
 int rr_debug_png_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
                         uint64_t* len) {
     if (!c || !rgba8 || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    return debug_deflate_device(c, Coder::Png8, w, h, rgba8, (size_t)w * h * 4, out, cap, len, [](const void* img) {
-        return launch_png8(static_cast<const uint8_t*>(img));
+    return debug_deflate_device(c, Coder::Png8, 4, w, h, rgba8, (size_t)w * h * 4, out, cap, len, [](const void* img) {
+        return launch_png8(static_cast<const uint8_t*>(img), 4);
     });
 }
 
 int rr_debug_exr_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
                         uint64_t* len) {
     if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    return debug_deflate_device(c, Coder::Exr, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
-                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false, false); });
+    return debug_deflate_device(c, Coder::Exr, 4, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
+                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false, false, 4); });
 }
 
 int rr_set_exr_depth(rr_ctx* c, int32_t depth) {
@@ -1363,8 +1408,8 @@ int rr_set_exr_depth(rr_ctx* c, int32_t depth) {
 int rr_debug_exr32_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
                           uint64_t* len) {
     if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    return debug_deflate_device(c, Coder::Exr32, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
-                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false, true); });
+    return debug_deflate_device(c, Coder::Exr32, 4, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
+                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false, true, 4); });
 }
 
 int rr_set_png_depth(rr_ctx* c, int32_t depth) {
@@ -1381,11 +1426,67 @@ int rr_debug_png16_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, in
         return fail(RR_EINVAL, "unsupported view transform");
     if (view_transform == VIEW_FILMIC && !c->filmic.ready)
         return fail(RR_EINVAL, "Filmic view transform without LUTs (rr_set_ocio_config / RR_OCIO_DIR)");
-    return debug_deflate_device(c, Coder::Png16, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
+    return debug_deflate_device(c, Coder::Png16, 4, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
                                 [&](const void* img) {
                                     return launch_png16(c, static_cast<const float4*>(img), 1.0f, exposure_scale,
-                                                        view_transform);
+                                                        view_transform, 4);
                                 });
+}
+
+int rr_set_color_mode(rr_ctx* c, int32_t mode) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    if (!valid_color_mode(mode))
+        return fail(RR_EINVAL, "colour mode must be RR_COLOR_SCENE (0), RR_COLOR_BW (1), RR_COLOR_RGB (3) or RR_COLOR_RGBA (4)");
+    c->color_mode = mode;  // read when a frame is submitted; frames in flight keep their choice
+    return RR_OK;
+}
+
+int rr_encode_image_mode(const uint8_t* rgba8, int32_t w, int32_t h, const char* out_path, const char* format,
+                         int32_t quality, int32_t color_mode, uint64_t* bytes) {
+    if (!rgba8 || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad image");
+    if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
+    return guarded([&] { return do_encode(rgba8, w, h, out_path, format, quality, bytes, color_mode); });
+}
+
+int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t color_mode, const void* image,
+                           int32_t image_is_float, int32_t w, int32_t h, int32_t view_transform, float exposure_scale,
+                           int32_t jpeg_quality, uint8_t* out, uint64_t cap, uint64_t* len) {
+    if (!c || !format || !image || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
+    const std::string fmt(format);
+    const bool jpeg = fmt == "JPEG";
+    const int C = resolve_color_mode(color_mode, jpeg);
+    if (jpeg) {
+        if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "JPEG takes an RGBA8 image at depth 8");
+        if (w > 65535 || h > 65535) return fail(RR_EINVAL, "image size outside the JPEG format's range");
+        if (jpeg_quality < 1 || jpeg_quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
+        return debug_jpeg_device(c, C, static_cast<const uint8_t*>(image), w, h, jpeg_quality, out, cap, len);
+    }
+    if (fmt == "PNG" && (depth == 0 || depth == 8)) {
+        if (image_is_float) return fail(RR_EINVAL, "8-bit PNG takes an RGBA8 image");
+        return debug_deflate_device(c, Coder::Png8, C, w, h, image, (size_t)w * h * 4, out, cap, len,
+                                    [&](const void* img) { return launch_png8(static_cast<const uint8_t*>(img), C); });
+    }
+    if (!image_is_float) return fail(RR_EINVAL, "16-bit PNG and OPEN_EXR take a float RGBA image");
+    const size_t bytes = (size_t)w * h * sizeof(float4);
+    if (fmt == "PNG" && depth == 16) {
+        if (view_transform != VIEW_STANDARD && view_transform != VIEW_RAW && view_transform != VIEW_FILMIC)
+            return fail(RR_EINVAL, "unsupported view transform");
+        if (view_transform == VIEW_FILMIC && !c->filmic.ready)
+            return fail(RR_EINVAL, "Filmic view transform without LUTs (rr_set_ocio_config / RR_OCIO_DIR)");
+        return debug_deflate_device(c, Coder::Png16, C, w, h, image, bytes, out, cap, len, [&](const void* img) {
+            return launch_png16(c, static_cast<const float4*>(img), 1.0f, exposure_scale, view_transform, C);
+        });
+    }
+    if (fmt == "OPEN_EXR" && (depth == 0 || depth == 16 || depth == 32)) {
+        const bool full = depth == 32;
+        // A = 1, as in a rendered frame's file
+        return debug_deflate_device(c, full ? Coder::Exr32 : Coder::Exr, C, w, h, image, bytes, out, cap, len,
+                                    [&](const void* img) {
+                                        return launch_exr(static_cast<const float4*>(img), 1.0f, true, full, C);
+                                    });
+    }
+    return fail(RR_EINVAL, "no such format and depth: '" + fmt + "' at " + std::to_string(depth));
 }
 
 int rr_debug_srgb16_table(float* table, int32_t cap, int32_t* n) {

@@ -659,6 +659,13 @@ SceneDesc load_scene(const std::string& path) {
         if (exr_depth != 16.0 && exr_depth != 32.0)
             throw std::runtime_error("render.exr_depth must be 16 or 32, got " + std::to_string(exr_depth));
         d.exr_depth = (int)exr_depth;
+        // Blender's image_settings.color_mode; no field: each format's own layout (rr_set_color_mode)
+        const std::string color_mode = r.get_str("color_mode", "");
+        if (color_mode == "BW") d.color_mode = RR_COLOR_BW;
+        else if (color_mode == "RGB") d.color_mode = RR_COLOR_RGB;
+        else if (color_mode == "RGBA") d.color_mode = RR_COLOR_RGBA;
+        else if (r.has("color_mode"))
+            throw std::runtime_error("render.color_mode must be \"BW\", \"RGB\" or \"RGBA\", got '" + color_mode + "'");
         d.view_transform_name = r.get_str("view_transform", "Standard");
         // "Filmic" is applied through Blender's OCIO LUTs when the context has
         // them (rr_set_ocio_config); otherwise the frame falls back to Standard

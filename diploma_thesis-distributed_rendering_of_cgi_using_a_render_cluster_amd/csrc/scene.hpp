@@ -112,6 +112,7 @@ struct RenderDesc {
     double clamp_indirect = 10.0, filter_width = 1.5, exposure = 0.0;
     int color_depth = 8;  // PNG output: 8 or 16 bits per sample (rr_set_png_depth 0 takes it)
     int exr_depth = 16;   // OPEN_EXR output: HALF (16) or FLOAT (32) channels (rr_set_exr_depth 0 takes it)
+    int color_mode = 0;   // RR_COLOR_BW / RGB / RGBA, 0: no field (rr_set_color_mode 0 takes it)
     int view_transform = VIEW_STANDARD;
     std::string view_transform_name = "Standard";
     // What of the scene's colour management a frame does not apply, for the

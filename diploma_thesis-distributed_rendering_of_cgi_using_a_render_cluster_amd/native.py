@@ -90,7 +90,23 @@ EXPORTS = [
     "rr_set_device_png", "rr_debug_png_device", "rr_debug_exr_device",
     "rr_set_png_depth", "rr_debug_png16_device", "rr_debug_srgb16_table",
     "rr_set_exr_depth", "rr_debug_exr32_device",
+    "rr_set_color_mode", "rr_encode_image_mode", "rr_debug_encode_device",
 ]
+
+# rr_set_color_mode's values (include/rr.h): the channels the file holds.
+RR_COLOR_SCENE, RR_COLOR_BW, RR_COLOR_RGB, RR_COLOR_RGBA = 0, 1, 3, 4
+COLOR_MODES = {"": RR_COLOR_SCENE, "BW": RR_COLOR_BW, "RGB": RR_COLOR_RGB, "RGBA": RR_COLOR_RGBA}
+
+
+def color_mode_value(mode) -> int:
+    """"BW" / "RGB" / "RGBA" / "" / None, or one of the RR_COLOR_* values, as an int."""
+    if mode is None:
+        return RR_COLOR_SCENE
+    if isinstance(mode, str):
+        if mode not in COLOR_MODES:
+            raise ValueError(f"colour mode must be BW, RGB or RGBA, got {mode!r}")
+        return COLOR_MODES[mode]
+    return int(mode)
 
 _lib = None
 
@@ -152,6 +168,12 @@ def lib() -> ctypes.CDLL:
         "rr_debug_srgb16_table": (c_int, [f32p, i32, i32p]),
         "rr_set_exr_depth": (c_int, [P, i32]),
         "rr_debug_exr32_device": (c_int, [P, f32p, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_set_color_mode": (c_int, [P, i32]),
+        "rr_encode_image_mode": (c_int, [u8p, i32, i32, ctypes.c_char_p, ctypes.c_char_p, i32, i32,
+                                         ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_debug_encode_device": (c_int, [P, ctypes.c_char_p, i32, i32, ctypes.c_void_p, i32, i32, i32, i32,
+                                           ctypes.c_float, i32, u8p, ctypes.c_uint64,
+                                           ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -273,9 +295,10 @@ class Scene:
 class RenderContext:
     """One HIP device (rr_ctx). Not thread-safe; one frame in flight at a time."""
 
-    def __init__(self, device: int = 0, png_depth: int = 0, exr_depth: int = 0):
+    def __init__(self, device: int = 0, png_depth: int = 0, exr_depth: int = 0, color_mode=0):
         """png_depth: bits per sample of "PNG" frames (set_png_depth; 0: the scene's).
-        exr_depth: channel type of "OPEN_EXR" frames (set_exr_depth; 0: the scene's)."""
+        exr_depth: channel type of "OPEN_EXR" frames (set_exr_depth; 0: the scene's).
+        color_mode: "BW" / "RGB" / "RGBA" of every file (set_color_mode; 0: the scene's)."""
         h = ctypes.c_void_p()
         _check(lib().rr_create(int(device), ctypes.byref(h)))
         self.handle = h
@@ -283,6 +306,8 @@ class RenderContext:
             self.set_png_depth(png_depth)
         if exr_depth:
             self.set_exr_depth(exr_depth)
+        if color_mode_value(color_mode):
+            self.set_color_mode(color_mode)
         self.device = device
 
     def close(self):
@@ -475,6 +500,31 @@ class RenderContext:
         bit for bit)."""
         _check(lib().rr_set_exr_depth(self.handle, int(depth)), self.handle)
 
+    def set_color_mode(self, mode=0):
+        """rr_set_color_mode: Blender's image_settings.color_mode for the files of
+        this context: "BW" (grey, Rec.709 luma), "RGB", "RGBA" or the RR_COLOR_*
+        values; 0 / "": the scene's render.color_mode, else each format's own layout."""
+        _check(lib().rr_set_color_mode(self.handle, color_mode_value(mode)), self.handle)
+
+    def encode_device(self, fmt: str, image: np.ndarray, depth: int = 0, color_mode=0, view_transform: int = 0,
+                      exposure_scale: float = 1.0, quality: int = 90) -> bytes:
+        """rr_debug_encode_device: the file bytes of an (H, W, 4) image coded on the
+        device as `fmt` ("JPEG", "PNG", "OPEN_EXR") at `depth` in `color_mode`.
+        uint8 images for JPEG and 8-bit PNG, float32 means for the others."""
+        is_float = image.dtype != np.uint8
+        image = np.ascontiguousarray(image, dtype=np.float32 if is_float else np.uint8)
+        h, w = image.shape[:2]
+        args = (self.handle, fmt.encode(), int(depth), color_mode_value(color_mode),
+                image.ctypes.data_as(ctypes.c_void_p), 1 if is_float else 0, w, h, int(view_transform),
+                ctypes.c_float(exposure_scale), int(quality))
+        n = ctypes.c_uint64()
+        _check(lib().rr_debug_encode_device(*args, None, 0, ctypes.byref(n)), self.handle)
+        out = np.zeros(n.value, np.uint8)
+        _check(lib().rr_debug_encode_device(*args, _ptr(out, ctypes.c_uint8), out.size, ctypes.byref(n)), self.handle)
+        if n.value > out.size:
+            raise RRError(RR_EINVAL, f"device file of {n.value} bytes exceeds the {out.size}-byte buffer")
+        return out[:n.value].tobytes()
+
     def exr32_device(self, rgba: np.ndarray) -> bytes:
         """rr_debug_exr32_device: the OpenEXR file bytes (FLOAT A, B, G, R; ZIP) of
         an (H, W, 4) float32 image of means, encoded on the device (exr.hip)."""
@@ -552,4 +602,14 @@ def encode_image(rgba: np.ndarray, out_path_no_ext: str, fmt: str, quality: int 
     nbytes = ctypes.c_uint64()
     _check(lib().rr_encode_image(_ptr(rgba, ctypes.c_uint8), w, h, out_path_no_ext.encode(), fmt.encode(),
                                  int(quality), ctypes.byref(nbytes)))
+    return nbytes.value
+
+
+def encode_image_mode(rgba: np.ndarray, out_path_no_ext: str, fmt: str, quality: int = 90, color_mode=0) -> int:
+    """rr_encode_image_mode: the host encoders in a colour mode ("BW", "RGB", "RGBA", 0)."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+    h, w = rgba.shape[:2]
+    nbytes = ctypes.c_uint64()
+    _check(lib().rr_encode_image_mode(_ptr(rgba, ctypes.c_uint8), w, h, out_path_no_ext.encode(), fmt.encode(),
+                                      int(quality), color_mode_value(color_mode), ctypes.byref(nbytes)))
     return nbytes.value

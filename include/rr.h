@@ -341,6 +341,55 @@ int rr_set_exr_depth(rr_ctx* ctx, int32_t depth);
 int rr_debug_exr32_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
                           uint8_t* out, uint64_t cap, uint64_t* len);
 
+/* Colour mode of the files of ctx: Blender's image_settings.color_mode behind
+ * write_still (render-timing-script.py:83-92). RR_COLOR_SCENE: the scene's
+ * render.color_mode ("BW", "RGB" or "RGBA"), and where the scene has none the
+ * layout each format had before there was a setting: JPEG three components,
+ * PNG RGBA, OPEN_EXR A, B, G, R. The values of the others are the channels the
+ * file holds.
+ *  - RR_COLOR_RGBA: alpha is 1 (255 / 65535 / 1.0). JPEG has no alpha and
+ *    writes RGB, as Blender does.
+ *  - RR_COLOR_RGB: PNG colour type 2; OPEN_EXR channels B, G, R.
+ *  - RR_COLOR_BW: Rec.709 luma, l = 0.2126 r + 0.7152 g + 0.0722 b, each
+ *    product and sum a float32 operation of its own, left to right. 8-bit
+ *    files (JPEG, 8-bit PNG) take it of the RGBA8 image after the view
+ *    transform, c / 255 a channel: code 0 for l <= 0, 255 for l > 1 - 0.5/255,
+ *    else (uint8)(255 l + 0.5). 16-bit PNG takes it of the display-referred
+ *    floats before quantisation; OPEN_EXR of the film's linear means, into one
+ *    channel "Y". PNG colour type 0; JPEG a single-component baseline file
+ *    with 8x8 MCUs whose Y is the grey code (not the JFIF 0.299/0.587/0.114
+ *    mix).
+ * rr_create reads RR_COLOR_MODE ("BW", "RGB", "RGBA" or empty) from the
+ * environment the same way. Applies to frames submitted after the call; frames
+ * in flight keep the mode of their submit. RR_EINVAL for a NULL ctx or another
+ * value. */
+#define RR_COLOR_SCENE 0
+#define RR_COLOR_BW 1
+#define RR_COLOR_RGB 3
+#define RR_COLOR_RGBA 4
+int rr_set_color_mode(rr_ctx* ctx, int32_t mode);
+
+/* rr_encode_image in a colour mode (RR_COLOR_SCENE: rr_encode_image's own
+ * files). "JPEG": BW or RGB (RGBA writes RGB); "PNG": colour types 0 / 2 / 6. */
+int rr_encode_image_mode(const uint8_t* rgba8, int32_t width, int32_t height,
+                         const char* out_path_no_ext, const char* format,
+                         int32_t jpeg_quality, int32_t color_mode, uint64_t* bytes_written);
+
+/* Encode an image of the caller's with the device coder of a format, depth and
+ * colour mode, through the enqueue, wrap and file code rendered frames take.
+ * format "JPEG" (depth 8) and "PNG" at depth 8 take an RGBA8 image
+ * (image_is_float 0); "PNG" at depth 16 and "OPEN_EXR" at depth 16 (HALF) or 32
+ * (FLOAT) take width * height * 4 floats (image_is_float 1) as means, spp = 1,
+ * alpha 1. depth 0: 8 for PNG, 16 for OPEN_EXR. view_transform and
+ * exposure_scale: 16-bit PNG only, as for rr_debug_png16_device; jpeg_quality:
+ * JPEG only. A size outside the coder's range is RR_EINVAL before anything is
+ * launched. *len receives the file size; the bytes are copied to out if
+ * cap >= *len. Exported for round-trip tests. */
+int rr_debug_encode_device(rr_ctx* ctx, const char* format, int32_t depth, int32_t color_mode,
+                           const void* image, int32_t image_is_float, int32_t width, int32_t height,
+                           int32_t view_transform, float exposure_scale, int32_t jpeg_quality,
+                           uint8_t* out, uint64_t cap, uint64_t* len);
+
 /* The sRGB table of the 16-bit PNG path (host only, no device needed): *n
  * receives the number of floats (intervals + 1), which are copied to table if
  * cap >= *n. Entry i = 1.055 (i / (n - 1))^(1 / 2.4) - 0.055, computed in

@@ -172,6 +172,9 @@ def export_action(bf, act_blk):
     return {"action": idname(bf, act_blk), "fcurves": fcurves}
 
 
+COLOR_MODE_OF_PLANES = {8: "BW", 24: "RGB", 32: "RGBA"}
+
+
 def export(path: str, args) -> dict:
     bf = BlendFile(path)
     sc = bf.blocks_with_code(b"SC")[0]
@@ -212,6 +215,15 @@ def export(path: str, args) -> dict:
         out["render"]["color_depth"] = color_depth
     if exr_depth != 16:  # likewise: 16 is what a scene without the field means
         out["render"]["exr_depth"] = exr_depth
+    # image_settings.color_mode: ImageFormatData.planes holds the bits of a pixel
+    # (R_IMF_PLANES_BW 8, _RGB 24, _RGBA 32). Written only with --color-mode
+    # project: a scene without the field keeps each format's own layout, and
+    # the committed scenes were exported without it.
+    if getattr(args, "color_mode", "keep") == "project":
+        planes = bf.read_struct_at(rd("im_format"), "ImageFormatData", "planes")
+        if planes not in COLOR_MODE_OF_PLANES:
+            raise ValueError(f"{path}: ImageFormatData.planes = {planes}, expected 8, 24 or 32")
+        out["render"]["color_mode"] = COLOR_MODE_OF_PLANES[planes]
     # ID blocks, indexed by old pointer
     mats = bf.blocks_with_code(b"MA")
     mat_index = {b.old_ptr: i for i, b in enumerate(mats)}
@@ -281,6 +293,9 @@ def main(argv=None):
     ap.add_argument("--max-bounces", type=int, default=12)
     ap.add_argument("--clamp-indirect", type=float, default=10.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--color-mode", choices=["keep", "project"], default="keep",
+                    help="keep: write no render.color_mode (the formats' own layouts); "
+                         "project: the project's image_settings.color_mode")
     args = ap.parse_args(argv)
     scene = export(args.blend, args)
     with open(args.out, "w") as f:
