@@ -366,7 +366,7 @@ __global__ __launch_bounds__(kBlock) void k_refit(int n, const uint32_t* __restr
 //    children's first index hi + prefix), so siblings share 128 B lines and a
 //    node stores only the first index;
 //  - the triangles of a node's leaf entries take consecutive positions of the
-//    hierarchy's own triangle array (qtris, swapped into DevScene::tris after
+//    hierarchy's own triangle array (qtris, swapped into DevBuild::tris after
 //    the collapse) in slot order, after the triangles of the levels before and
 //    of the nodes before it in its level (a second count and scan), so a node
 //    stores only the first position and the mask of its internal slots;
@@ -828,7 +828,7 @@ __global__ __launch_bounds__(kBlock) void k_upload(UploadArgs a) {
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-void exclusive_scan(DevScene& s, uint32_t* data, int m, hipStream_t st) {
+void exclusive_scan(DevBuild& s, uint32_t* data, int m, hipStream_t st) {
     const int tiles = cdiv(m, kScanTile);
     s.scan_part.ensure((size_t)tiles);
     k_scan_tiles<<<tiles, kBlock, 0, st>>>(m, data, s.scan_part.ptr);
@@ -854,8 +854,13 @@ bool upload_by_kernarg(const float* src, const UploadSeg* segs, int nseg, hipStr
     return true;
 }
 
-void DevScene::release() {
-    tri_local.release(); tri_obj.release(); tri_mat.release(); obj_xform.release();
+void DevMesh::release() {
+    tri_local.release(); tri_obj.release(); tri_mat.release();
+    uploaded = false;
+}
+
+void DevBuild::release() {
+    obj_xform.release();
     tri_world.release(); bounds.release();
     for (int k = 0; k < 2; ++k) { keys[k].release(); vals[k].release(); }
     hist.release(); scan_part.release(); children.release(); node_parent.release();
@@ -864,22 +869,23 @@ void DevScene::release() {
     tnrm.release();
     for (int k = 0; k < 2; ++k) ploc_cl[k].release();
     ploc_nn.release(); ploc_keep.release(); ploc_mrg.release(); ploc_ctl.release();
+    cached_xform.clear();
+    nq = 0;
     has4 = false;
     ploc = false;
     built = false;
-    uploaded = false;
 }
 
 // PLOC rounds after the Morton sort (sorted order in vals[0]).
-void build_ploc(DevScene& s, hipStream_t st) {
-    const int n = s.n_tris;
+void build_ploc(const DevMesh& mesh, DevBuild& s, hipStream_t st) {
+    const int n = mesh.n_tris;
     s.ploc_cl[0].ensure((size_t)2 * n);
     s.ploc_cl[1].ensure((size_t)2 * n);
     s.ploc_nn.ensure((size_t)n);
     s.ploc_keep.ensure((size_t)n + 1);
     s.ploc_mrg.ensure((size_t)n + 1);
     s.ploc_ctl.ensure(4);
-    k_ploc_init<<<cdiv(n, kBlock), kBlock, 0, st>>>(n, s.vals[0].ptr, s.tri_world.ptr, s.tri_mat.ptr,
+    k_ploc_init<<<cdiv(n, kBlock), kBlock, 0, st>>>(n, s.vals[0].ptr, s.tri_world.ptr, mesh.tri_mat.ptr,
                                                      s.ploc_cl[0].ptr, s.tris.ptr);
     const int init[4] = {n, n - 2, 0, 0};  // ctl[0/1]: count ping-pong, ctl[2/3]: next-index ping-pong
     const int ctl_host[4] = {init[0], 0, init[1], 0};
@@ -929,8 +935,8 @@ __global__ __launch_bounds__(kBlock) void k_tri_nrm(const TriPack* __restrict__ 
 // advance round per level; the host learns the frontier size every 4 levels
 // (one synchronisation) and sizes the next launches by it (a level has at
 // most kQWidth x the nodes of the one before).
-void build_qbvh(DevScene& s, hipStream_t st) {
-    const int n = s.n_tris;
+void build_qbvh(const DevMesh& mesh, DevBuild& s, hipStream_t st) {
+    const int n = mesh.n_tris;
     const int ni = n > 1 ? n - 1 : 1;
     // the walks' grouped stack entries hold a node index in 26 bits (rr_device.h pop_group)
     if (ni >= (1 << 26)) throw std::runtime_error("scene too large for the 6-wide hierarchy (2^26 nodes)");
@@ -971,8 +977,8 @@ void build_qbvh(DevScene& s, hipStream_t st) {
     s.has4 = true;
 }
 
-void build_lbvh(DevScene& s, hipStream_t st, KernelProfiler* prof, bool want4, bool want_ploc) {
-    const int n = s.n_tris;
+void build_lbvh(const DevMesh& mesh, DevBuild& s, hipStream_t st, KernelProfiler* prof, bool want4, bool want_ploc) {
+    const int n = mesh.n_tris;
     s.has4 = false;
     if (n <= 0) {
         s.built = true;
@@ -995,7 +1001,7 @@ void build_lbvh(DevScene& s, hipStream_t st, KernelProfiler* prof, bool want4, b
     s.range.ensure((size_t)(n > 1 ? n - 1 : 1));
 
     if (n <= kSmallBuild && !want4 && !(want_ploc && n > 2)) {
-        k_build_small<<<1, kSmallBuild, 0, st>>>(n, s.tri_local.ptr, s.tri_obj.ptr, s.obj_xform.ptr, s.tri_mat.ptr,
+        k_build_small<<<1, kSmallBuild, 0, st>>>(n, mesh.tri_local.ptr, mesh.tri_obj.ptr, s.obj_xform.ptr, mesh.tri_mat.ptr,
                                                  s.tri_world.ptr, s.bounds.ptr, s.keys[0].ptr, s.vals[0].ptr,
                                                  s.children.ptr, s.node_parent.ptr, s.leaf_parent.ptr, s.range.ptr,
                                                  s.nodes.ptr, s.tris.ptr);
@@ -1008,7 +1014,7 @@ void build_lbvh(DevScene& s, hipStream_t st, KernelProfiler* prof, bool want4, b
 
     RR_HIP(hipMemsetAsync(s.bounds.ptr, 0xFF, 3 * sizeof(uint32_t), st));
     RR_HIP(hipMemsetAsync(s.bounds.ptr + 3, 0x00, 3 * sizeof(uint32_t), st));
-    k_transform<<<nb, kBlock, 0, st>>>(n, s.tri_local.ptr, s.tri_obj.ptr, s.obj_xform.ptr,
+    k_transform<<<nb, kBlock, 0, st>>>(n, mesh.tri_local.ptr, mesh.tri_obj.ptr, s.obj_xform.ptr,
                                         s.tri_world.ptr, s.bounds.ptr);
     k_morton<<<nb, kBlock, 0, st>>>(n, s.tri_world.ptr, s.bounds.ptr, s.keys[0].ptr, s.vals[0].ptr);
     // K3: four stable 8-bit passes over the 30-bit keys
@@ -1030,17 +1036,17 @@ void build_lbvh(DevScene& s, hipStream_t st, KernelProfiler* prof, bool want4, b
     }
     s.ploc = want_ploc && n > 2;
     if (s.ploc) {
-        build_ploc(s, st);
+        build_ploc(mesh, s, st);
     } else if (n > 1) {
         k_karras<<<cdiv(n - 1, kBlock), kBlock, 0, st>>>(n, s.keys[0].ptr, s.children.ptr,
                                                           s.node_parent.ptr, s.leaf_parent.ptr, s.range.ptr);
         RR_HIP(hipMemsetAsync(s.flags.ptr, 0, (size_t)(n - 1) * sizeof(uint32_t), st));
     }
     if (!s.ploc)
-        k_refit<<<nb, kBlock, 0, st>>>(n, s.vals[0].ptr, s.tri_world.ptr, s.tri_mat.ptr, s.leaf_parent.ptr,
+        k_refit<<<nb, kBlock, 0, st>>>(n, s.vals[0].ptr, s.tri_world.ptr, mesh.tri_mat.ptr, s.leaf_parent.ptr,
                                        s.node_parent.ptr, s.children.ptr, s.flags.ptr, s.nodes.ptr,
                                        s.tris.ptr);
-    if (want4) build_qbvh(s, st);
+    if (want4) build_qbvh(mesh, s, st);
     if (prof) prof->end(st);
     RR_HIP(hipGetLastError());
     s.built = true;

@@ -1,7 +1,11 @@
 // Host-side interface of the device module: buffers in HBM and the launch
 // sequences of the LBVH build (bvh.hip) and the path integrator (wavefront.hip:
 // the split path and the frame dispatcher; tiles.hip: the tile path).
-// DESIGN.md §4 describes the layout.
+// Every piece of device state has one owner, and the functions below take the
+// state they work on as parameters: the context owns DevPaths (shared queues
+// and tables) and one DevFrame for the inspection entry points, a frame slot
+// owns a DevFrame and a DevBuild, a scene owns its DevMesh and a DevBuild.
+// DESIGN.md §3 has the table, §4 the layout.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,13 +53,22 @@ struct DevBuf {
     }
 };
 
-// Per-scene geometry + acceleration structure.
-struct DevScene {
+// A scene's uploaded triangles, object space: written once (upload_scene),
+// read by every hierarchy build of the scene.
+struct DevMesh {
     int n_tris = 0;
     int n_objs = 0;
     DevBuf<float4> tri_local;  // 3 per triangle, object space
     DevBuf<int32_t> tri_obj;
     DevBuf<int32_t> tri_mat;
+    bool uploaded = false;
+    void release();
+};
+
+// The products of one hierarchy build of a mesh: transforms, world triangles,
+// build scratch, the acceleration structure and what it was built for. A
+// scene owns one set; every frame slot owns one more for its k_tiles frames.
+struct DevBuild {
     DevBuf<float> obj_xform;   // 12 per object
     DevBuf<float4> tri_world;  // 3 per triangle, world space (this frame)
     // LBVH build scratch
@@ -88,8 +101,7 @@ struct DevScene {
     bool ploc = false;  // the current nodes come from PLOC (else the Karras LBVH)
     std::vector<float> cached_xform;  // obj_xform of the current build
     bool built = false;
-    bool uploaded = false;
-    void release();
+    void release();  // back to the unbuilt state
 };
 
 // Optional per-launch HIP-event timing (RR_FLAG_PROFILE_KERNELS), on the
@@ -134,7 +146,9 @@ struct KernelProfiler {
     }
 };
 
-// Per-context wavefront state (sized for the largest chunk seen).
+// Shared by all frames of a context: the split path's queues (sized for the
+// largest chunk seen) and the read-only tables. Only split-path frames use the
+// queues, and such a frame always waits for its predecessor.
 struct DevPaths {
     size_t cap = 0;
     DevBuf<float4> rad;                        // per path (p-indexed) radiance record
@@ -143,31 +157,49 @@ struct DevPaths {
     DevBuf<float2> hits;                       // split path: (t, leaf index) per queue entry
     DevBuf<uint32_t> qctr;                     // split path: grouped queue append counters
     DevBuf<uint32_t> perm;                     // split path, RR_RAY_SORT: queue position -> slot (k_sort_queue)
+    DevBuf<float4> film_part;  // open sample group's partial sum between chunks (k_accumulate)
+    DevBuf<float> filter_table;
+    DevBuf<float> srgb_lut;
+    int grid_blocks = 0;  // persistent grid for path kernels
+    void ensure_paths(size_t n);  // wavefront.hip
+    void release();
+};
+
+// The device state of one frame. Every frame slot owns one, so frames in
+// flight together share no buffer they write; the context owns one more (the
+// home set) for the inspection entry points. The device code takes the one to
+// work on as a parameter.
+struct DevFrame {
     DevBuf<int32_t> counters;  // per chunk, per bounce b: {paths entering b+1, shadow rays of b}
     DevBuf<int32_t> spill;     // traversal stack spill
     DevBuf<float4> film;
-    DevBuf<float4> film_part;  // open sample group's partial sum between chunks (k_accumulate)
+    DevBuf<uint8_t> rgba8;
     DevBuf<float> tile_slab;   // k_tiles: per sliced tile, one group sum plane per sample group
     DevBuf<uint32_t> tile_ctrs;  // k_tiles: work-unit counters, one 128-B line per shard
+    // kept from frame to frame: the next order is built from the owner's last costs
     DevBuf<uint32_t> tile_cost;  // k_tiles: per screen tile, the real-time ticks its units took (last launch)
     DevBuf<int32_t> tile_order;  // k_tiles: box tiles by descending tile_cost (k_tile_order)
-    DevBuf<uint8_t> rgba8;
-    DevBuf<float> filter_table;
-    DevBuf<float> srgb_lut;
     DevBuf<float> lights, materials;
     DevBuf<float> mat_lut;             // material tables (build_material_lut), uploaded when they change
     std::vector<float> mat_lut_cached;
     DevBuf<unsigned long long> trav_counts;  // RR_FLAG_COUNT_TRAVERSAL: kTravWords
     KernelProfiler prof;
-    bool count_traversal = false;
+    // scratch of the device coders: JPEG coefficients and entropy coder (jpeg.hip), deflate (a frame has one format)
+    DevBuf<int16_t> jpeg_coeffs;
+    DevBuf<uint32_t> jpeg_blk, jpeg_scratch;
+    DevBuf<uint32_t> deflate_scratch;
+    // written by render_frame_device, about the frame it enqueued
+    int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
+    bool unit_logged = false;  // its k_tiles launch wrote the unit log (trav_counts)
+    void ensure_spill(int grid_blocks);  // the traversal stack spill area of a persistent grid
+    void release();
+};
+
+// How render_frame_device renders a frame.
+struct FrameOpts {
+    bool count_traversal = false;  // RR_FLAG_COUNT_TRAVERSAL
     bool force_wavefront = false;  // RR_FLAG_WAVEFRONT: LDS-resident scenes take the split path, not k_tiles
     bool tile_whole = false;       // k_tiles: one work unit per tile (the frame overlaps a pending one)
-    int last_tile_slices = 0;      // render_frame_device: k_tiles units per box tile of the last frame (0: not k_tiles)
-    bool last_unit_logged = false; // render_frame_device: the last k_tiles launch wrote its unit log (trav_counts)
-    int grid_blocks = 0;  // persistent grid for path kernels
-    void ensure_paths(size_t n);  // wavefront.hip
-    void ensure_tiles();  // tiles.hip; k_tiles: only the traversal stack spill area
-    void release();
 };
 
 // Frame constants passed by value to the path kernels.
@@ -196,7 +228,7 @@ struct FrameConsts {
 // Stream-ordered; no host synchronisation inside.
 // want4: also collapse it into the BVH4 the split path traverses.
 // want_ploc: build the PLOC hierarchy instead (large scenes; not with want4).
-void build_lbvh(DevScene& s, hipStream_t st, KernelProfiler* prof = nullptr, bool want4 = false,
+void build_lbvh(const DevMesh& m, DevBuild& s, hipStream_t st, KernelProfiler* prof = nullptr, bool want4 = false,
                 bool want_ploc = false);
 
 // Per-frame constants (lights, materials, object transforms; up to
@@ -234,16 +266,16 @@ bool frame_uses_tiles(const FrameConsts& base, bool force_wavefront);
 
 // Render all chunks of one frame: film accumulate + tonemap to rgba8.
 // counters_per_chunk receives the device counter layout for stats.
-void render_frame_device(DevScene& s, DevPaths& p, const FrameConsts& base, int n_chunks,
-                         hipStream_t st);
+void render_frame_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f, const FrameConsts& base,
+                         int n_chunks, FrameOpts o, hipStream_t st);
 // The k_tiles frame of render_frame_device (frame_uses_tiles holds; tiles.hip):
 // k_tile_order, k_tiles over all samples, k_tiles_fold when tiles are sliced.
-void render_tiles_device(DevScene& s, DevPaths& p, const FrameConsts& base, int n_chunks,
-                         hipStream_t st);
+void render_tiles_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f, const FrameConsts& base,
+                         int n_chunks, FrameOpts o, hipStream_t st);
 
 // Trace a batch of rays (debug / parity entry point).
-void trace_batch_device(DevScene& s, DevPaths& p, int n, const float4* d_rays, float4* d_hits,
-                        int32_t* d_prims, uint8_t* d_occ, hipStream_t st, int width);
+void trace_batch_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f, int n, const float4* d_rays,
+                        float4* d_hits, int32_t* d_prims, uint8_t* d_occ, hipStream_t st, int width);
 
 // BSDF sampling batch at one shading point (debug / parity entry point).
 void bsdf_batch_device(const float* d_mat12, const float* d_lut, const float n3[3], const float wo3[3], int n,

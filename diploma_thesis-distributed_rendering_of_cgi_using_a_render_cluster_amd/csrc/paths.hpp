@@ -59,7 +59,7 @@ struct SceneView {
     FloatP lut;  // material tables (kMatLutStride floats per material, build_material_lut)
     lds_f4w* cam = nullptr;  // LDS scenes, camera kernels: 3 float4 per triangle (stage_camera)
     // unit geometric normal + material per triangle: LDS scenes' staged copy
-    // (shading kernels), HBM scenes' DevScene::tnrm (RR_SHADE_NRM) — one
+    // (shading kernels), HBM scenes' DevBuild::tnrm (RR_SHADE_NRM) — one
     // member for both, so the LDS view passed to k_tiles' out-of-line calls
     // stays the size it was
     typename std::conditional<std::is_same<FloatP, lds_float*>::value, lds_f4w*, const float4*>::type nrm = nullptr;
@@ -67,7 +67,7 @@ struct SceneView {
     lds_f4w* onb = nullptr;   // LDS scenes, shading kernels: make_onb of both sides' normals (kOnbF4 per triangle)
 };
 // RR_SHADE_NRM (default): the split path's shading reads each hit triangle's
-// normal and material from DevScene::tnrm (16 B) instead of its 48 B record
+// normal and material from DevBuild::tnrm (16 B) instead of its 48 B record
 // and a cross product: shading per 02 / 03 / C5 frame slice 11.34 / 11.49 /
 // 9.18 -> 10.77 / 10.85 / 8.61 ms (profiles/r5_ab_spec.txt).
 #ifndef RR_SHADE_NRM

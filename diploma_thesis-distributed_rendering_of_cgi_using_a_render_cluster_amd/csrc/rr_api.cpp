@@ -124,10 +124,10 @@ struct FrameRun {
     unsigned long long trav[kTravWords];
 };
 
-// One frame between rr_frame_submit and rr_frame_complete: its host-side
-// outputs (pinned, so the device-to-host copies stay asynchronous), events,
-// kernel profiler and the request. Several slots = the next queued frames render
-// while the host encodes and writes the previous one.
+// One frame between rr_frame_submit and rr_frame_complete: its stream, its
+// device state, its host-side outputs (pinned, so the device-to-host copies
+// stay asynchronous), events and the request. Several slots = the next queued
+// frames render while the host encodes and writes the previous one.
 struct FrameSlot {
     bool busy = false;
     uint64_t ticket = 0;
@@ -135,14 +135,19 @@ struct FrameSlot {
     // work done, 3 outputs on the host (after their copies), 5 (device PNG
     // and EXR frames) before the deflate coder: the state shared between frames is free
     hipEvent_t ev[6] = {};
-    DevBuf<int32_t> counters;  // this frame's ray counters (swapped into DevPaths while enqueuing)
-    // this frame's device outputs (swapped into DevPaths / rr_ctx while enqueuing):
-    // their copies to the host run while the next frames' kernels write the other
-    // slot's, so no frame waits for its predecessor's device-to-host copies
-    DevBuf<float4> film;
-    DevBuf<uint8_t> rgba8;
-    DevBuf<int16_t> coeffs;
-    KernelProfiler prof;
+    // The slot's frames run on its own stream and write only its own device
+    // state, so a k_tiles frame runs on the GPU beside the other slots'
+    // frames, and the copies of a frame's outputs to the host run while the
+    // next frames' kernels write the other slots'.
+    hipStream_t stream = nullptr;
+    DevFrame dev;
+    // The products of the hierarchy builds of this slot's k_tiles frames, for
+    // the scene `build_scene`. Frames of the split path never overlap their
+    // predecessor, so they use the scene's own set: a large scene is held
+    // once, not once per slot.
+    DevBuild build;
+    const rr_scene* build_scene = nullptr;
+    bool tiles = false;  // this frame renders with k_tiles (may overlap its neighbours)
     PinnedBuf host_rgba, host_counters, host_upload;
     PinnedBuf host_jpeg;   // device-coded JPEG stream: [uint64 length][pad][bytes]
     DeflateOut deflate;    // device-coded PNG / OPEN_EXR frame; the plan is made when the frame is submitted
@@ -156,71 +161,27 @@ struct FrameSlot {
     int quality = 0;
     Coder coder = Coder::None;
     int color_mode = RR_COLOR_RGBA;  // resolved when the frame is submitted (resolve_color_mode): the file's channels
-    bool count = false;
-    bool unit_logged = false;  // its k_tiles launch wrote the unit log into trav_counts (rr_debug_tile_costs)
     float* film_out = nullptr;
     FrameRun r{};
     rr_frame_timing tm{};
     double anim_ms = 0.0;
     std::chrono::steady_clock::time_point t_call;
-    // Device state private to this slot, swapped in while its frame is enqueued
-    // (SlotSwap), so that a k_tiles frame can run on the GPU beside the other
-    // slot's frame: the slot's own stream, the small per-frame buffers of
-    // DevPaths (lights, materials, material tables) and of the JPEG coder, and
-    // — for k_tiles frames only — the per-frame products of its scene's
-    // hierarchy build (`alt`: everything in DevScene but the uploaded
-    // triangles, for the scene `alt_scene`). Frames of the split path never
-    // overlap their predecessor, so they use the scene's own copy: a large
-    // scene is held once, not once per slot.
-    hipStream_t stream = nullptr;
-    bool tiles = false;  // this frame renders with k_tiles (may overlap its neighbours)
-    DevBuf<float> lights, materials, tile_slab;
-    DevBuf<float> mat_lut;  // material tables of this slot's frames (uploaded when they change)
-    std::vector<float> mat_lut_cached;
-    DevBuf<uint32_t> tile_ctrs, tile_cost;
-    DevBuf<int32_t> tile_order, spill;
-    DevBuf<unsigned long long> trav_counts;
-    DevBuf<uint32_t> jpeg_blk, jpeg_scratch;
-    DevBuf<uint32_t> deflate_scratch;
-    DevScene alt;
-    const rr_scene* alt_scene = nullptr;
-    void release_private() {
-        lights.release();
-        materials.release();
-        mat_lut.release();
-        mat_lut_cached.clear();
-        tile_slab.release();
-        tile_ctrs.release();
-        tile_cost.release();
-        tile_order.release();
-        spill.release();
-        trav_counts.release();
-        jpeg_blk.release();
-        jpeg_scratch.release();
-        deflate_scratch.release();
-        alt.release();
-        alt = DevScene{};
-        alt_scene = nullptr;
-    }
 };
 
 struct rr_ctx {
     int device = 0;
-    // the compute stream the device code enqueues on: slot 0's stream outside
-    // frames (inspection entry points), the frame slot's stream while a frame is
-    // enqueued (enqueue_frame SlotSwap)
+    // the home stream, which the inspection entry points enqueue on: slot 0's
+    // (rr_create says why there is no further stream)
     hipStream_t stream = nullptr;
-    DevPaths paths;
-    // device JPEG transform (jpeg.hip): tables for the last quality, coefficients
+    DevPaths paths;  // shared by all frames: the split path's queues, read-only tables
+    DevFrame home;   // the inspection entry points' frame state (a frame uses its slot's)
+    // tables of the device JPEG coder (jpeg.hip), read by every slot's frames:
+    // the transform's for the last quality, the entropy coder's Huffman codes
     DevBuf<float> jpeg_tab;
     int jpeg_tab_quality = -1;
-    DevBuf<int16_t> jpeg_coeffs;
-    // device entropy coder (jpeg.hip): Huffman tables, per-row scratch, stream
     DevBuf<uint32_t> jpeg_huff;
-    DevBuf<uint32_t> jpeg_scratch, jpeg_blk;
     // 8-bit "PNG" frames are coded on the device (rr_set_device_png / RR_DEVICE_PNG)
     bool device_png = false;
-    DevBuf<uint32_t> deflate_scratch;  // the deflate coder's (a frame has one format)
     // bit depth of "PNG" frames (rr_set_png_depth / RR_PNG_DEPTH): 0 the scene's, 8, 16
     int png_depth = 0;
     // channel type of "OPEN_EXR" frames (rr_set_exr_depth / RR_EXR_DEPTH): 0 the scene's, 16 HALF, 32 FLOAT
@@ -235,7 +196,6 @@ struct rr_ctx {
     uint64_t next_ticket = 1;     // tickets are issued in submission order
     uint64_t next_complete = 1;   // the ticket rr_frame_complete expects next
     FrameSlot* last_enqueued = nullptr;  // the slot of the frame enqueued last (its ev[2]: device work done)
-    bool in_slot = false;  // a frame is being enqueued: the slot's private buffers are swapped in
     // UNIX-time estimate of when the compute stream finished the last completed
     // frame (rr_frame_complete): the next frame's device work cannot start before
     double gpu_free_at = 0.0;
@@ -260,7 +220,8 @@ struct rr_ctx {
 struct rr_scene {
     rr_ctx* ctx = nullptr;
     SceneDesc desc;
-    DevScene dev;
+    DevMesh mesh;    // uploaded once
+    DevBuild build;  // split-path frames and the inspection calls build here; k_tiles frames in their slot's set
 };
 
 namespace {
@@ -281,33 +242,18 @@ int guarded(F&& f) {
 
 void set_device(rr_ctx* c) { RR_HIP(hipSetDevice(c->device)); }
 
-// Waits for every compute stream of the context (the home stream and both
-// slots'; while a frame is enqueued its slot stream sits in c->stream). Called
-// before a table that all frames read (filter, sRGB, material, JPEG, Filmic)
-// is rewritten, since a frame of the other slot may still be reading it.
+// Waits for every stream of the context. Called before a table that all
+// frames read (filter, sRGB, JPEG, Filmic) is rewritten, since a frame of
+// another slot may still be reading it.
 void quiesce(rr_ctx* c) {
-    RR_HIP(hipStreamSynchronize(c->stream));
     for (auto& sl : c->slots)
         if (sl.stream) RR_HIP(hipStreamSynchronize(sl.stream));
-}
-
-// Exchanges the per-frame products of a scene's hierarchy build (transforms,
-// world triangles, build scratch, nodes, packed triangles, cache state) between
-// the scene and a slot's private set; the uploaded object-space triangles stay.
-void swap_products(DevScene& home, DevScene& alt) {
-    std::swap(home, alt);
-    std::swap(home.tri_local, alt.tri_local);
-    std::swap(home.tri_obj, alt.tri_obj);
-    std::swap(home.tri_mat, alt.tri_mat);
-    std::swap(home.n_tris, alt.n_tris);
-    std::swap(home.n_objs, alt.n_objs);
-    std::swap(home.uploaded, alt.uploaded);
 }
 
 // One-time upload of the scene's object-space triangles.
 void upload_scene(rr_ctx* c, rr_scene* s) {
     set_device(c);
-    DevScene& d = s->dev;
+    DevMesh& d = s->mesh;
     if (d.uploaded) return;
     if (d.n_tris > 0) {
         d.tri_local.ensure((size_t)3 * d.n_tris);
@@ -361,10 +307,12 @@ std::string resolve_view(const rr_ctx* c, FrameSetup& fs) {
     return w;
 }
 
+// Works on stream st with frame state f and builds into d, a set of products
+// of s's mesh. Returns whether it rebuilt.
 // hier: 0 = the frame's hierarchy, else a kHier* id (inspection entry points).
-bool prepare_frame(rr_ctx* c, rr_scene* s, const FrameSetup& fs, PinnedBuf& staging, int hier = 0) {
+bool prepare_frame(rr_ctx* c, rr_scene* s, DevBuild& d, DevFrame& f, hipStream_t st, const FrameSetup& fs,
+                   PinnedBuf& staging, int hier = 0) {
     bind_scene(c, s);
-    hipStream_t st = c->stream;
     DevPaths& p = c->paths;
     // tables (built on the host once; identical construction in the oracle)
     if (c->filter_width_cached != fs.filter_width) {
@@ -384,44 +332,44 @@ bool prepare_frame(rr_ctx* c, rr_scene* s, const FrameSetup& fs, PinnedBuf& stag
         RR_HIP(hipMemcpy(p.srgb_lut.ptr, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
         c->srgb_uploaded = true;
     }
-    if (p.mat_lut_cached != fs.mat_lut) {  // material tables: static per scene, uploaded when they change
+    if (f.mat_lut_cached != fs.mat_lut) {  // material tables: static per scene, uploaded when they change
         // a frame slot's own table is read only by that slot's frames (the
-        // slot's previous frame has completed); the context's table, used by
-        // the inspection calls, may be read by any stream
-        if (!c->in_slot) quiesce(c);
-        p.mat_lut.ensure(fs.mat_lut.size());
-        RR_HIP(hipMemcpyAsync(p.mat_lut.ptr, fs.mat_lut.data(), fs.mat_lut.size() * sizeof(float),
+        // slot's previous frame has completed); the home set's is rewritten
+        // with every stream idle
+        if (&f == &c->home) quiesce(c);
+        f.mat_lut.ensure(fs.mat_lut.size());
+        RR_HIP(hipMemcpyAsync(f.mat_lut.ptr, fs.mat_lut.data(), fs.mat_lut.size() * sizeof(float),
                               hipMemcpyHostToDevice, st));
         RR_HIP(hipStreamSynchronize(st));  // pageable source: the copy must be done before fs goes away
-        p.mat_lut_cached = fs.mat_lut;
+        f.mat_lut_cached = fs.mat_lut;
     }
     const size_t nl = fs.lights.size(), nm = fs.materials.size(), nx = fs.obj_xform.size();
-    p.lights.ensure(nl ? nl : 1);
-    p.materials.ensure(nm ? nm : 1);
+    f.lights.ensure(nl ? nl : 1);
+    f.materials.ensure(nm ? nm : 1);
     staging.ensure((nl + nm + nx) * sizeof(float));
     float* up = reinterpret_cast<float*>(staging.ptr);
     std::memcpy(up, fs.lights.data(), nl * sizeof(float));
     std::memcpy(up + nl, fs.materials.data(), nm * sizeof(float));
     std::memcpy(up + nl + nm, fs.obj_xform.data(), nx * sizeof(float));
-    DevScene& d = s->dev;
-    if (hier == 0) hier = frame_hier(fs, d.n_tris);
+    const DevMesh& m = s->mesh;
+    if (hier == 0) hier = frame_hier(fs, m.n_tris);
     const bool want4 = hier == kHierQWide;
-    const bool want_ploc = (hier == kHierPloc || hier == kHierQWide) && d.n_tris > 2;
+    const bool want_ploc = (hier == kHierPloc || hier == kHierQWide) && m.n_tris > 2;
     // (a BVH4 collapse reorders the triangles into its leaf order, so a BVH2
     // walk of the same PLOC tree needs a build without it)
     const bool rebuild = !d.built || d.cached_xform != fs.obj_xform || (want4 != d.has4) || (want_ploc != d.ploc);
-    const bool upload_x = rebuild && d.n_tris > 0;
+    const bool upload_x = rebuild && m.n_tris > 0;
     if (upload_x) d.obj_xform.ensure(nx);
-    const UploadSeg segs[3] = {{p.lights.ptr, (int)nl}, {p.materials.ptr, (int)nm},
+    const UploadSeg segs[3] = {{f.lights.ptr, (int)nl}, {f.materials.ptr, (int)nm},
                                {upload_x ? d.obj_xform.ptr : nullptr, upload_x ? (int)nx : 0}};
     if (!upload_by_kernarg(up, segs, 3, st)) {
-        if (nl) RR_HIP(hipMemcpyAsync(p.lights.ptr, up, nl * sizeof(float), hipMemcpyHostToDevice, st));
-        RR_HIP(hipMemcpyAsync(p.materials.ptr, up + nl, nm * sizeof(float), hipMemcpyHostToDevice, st));
+        if (nl) RR_HIP(hipMemcpyAsync(f.lights.ptr, up, nl * sizeof(float), hipMemcpyHostToDevice, st));
+        RR_HIP(hipMemcpyAsync(f.materials.ptr, up + nl, nm * sizeof(float), hipMemcpyHostToDevice, st));
         if (upload_x)
             RR_HIP(hipMemcpyAsync(d.obj_xform.ptr, up + nl + nm, nx * sizeof(float), hipMemcpyHostToDevice, st));
     }
     if (upload_x) {
-        build_lbvh(d, st, &p.prof, want4, want_ploc);
+        build_lbvh(m, d, st, &f.prof, want4, want_ploc);
         d.cached_xform = fs.obj_xform;
     } else if (rebuild) {
         d.built = true;
@@ -518,10 +466,11 @@ void jpeg_device_table(int quality, float out[192]) {
     std::memcpy(out + 128, t.qinv_c, sizeof t.qinv_c);
 }
 
-// Device JPEG encode of an RGBA8 frame (transform into c->jpeg_coeffs +
-// Huffman coding) into the slot's pinned stream buffer, on the context stream.
-// The slot's colour mode decides the file: RR_COLOR_BW a one-component one.
-void enqueue_jpeg_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W, int H, const float* d_tab) {
+// Device JPEG encode of an RGBA8 frame (transform into f.jpeg_coeffs +
+// Huffman coding) into the slot's pinned stream buffer, on stream st with f's
+// scratch. The slot's colour mode decides the file: RR_COLOR_BW a one-component one.
+void enqueue_jpeg_device(rr_ctx* c, FrameSlot& sl, DevFrame& f, hipStream_t st, const uint8_t* d_rgba, int W, int H,
+                         const float* d_tab) {
     const bool grey = sl.color_mode == RR_COLOR_BW;
     if (!c->jpeg_huff.ptr) {
         quiesce(c);
@@ -532,16 +481,16 @@ void enqueue_jpeg_device(rr_ctx* c, FrameSlot& sl, const uint8_t* d_rgba, int W,
     }
     const size_t mcuy = jpeg_mcu_rows(H, grey);
     const size_t nblocks = jpeg_block_count(W, H, grey);
-    c->jpeg_coeffs.ensure(jpeg_coeff_count(W, H, grey));
-    c->jpeg_blk.ensure(2 * nblocks + 2 * mcuy);
-    c->jpeg_scratch.ensure(mcuy * jpeg_row_scratch_words(W, grey));
+    f.jpeg_coeffs.ensure(jpeg_coeff_count(W, H, grey));
+    f.jpeg_blk.ensure(2 * nblocks + 2 * mcuy);
+    f.jpeg_scratch.ensure(mcuy * jpeg_row_scratch_words(W, grey));
     sl.host_jpeg.ensure(jpeg_stream_max_bytes(W, H, grey) + 16);
     void* dev_host = nullptr;
     RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_jpeg.ptr, 0));
-    uint32_t* blk = c->jpeg_blk.ptr;
-    JpegDevBufs b{blk, blk + nblocks, blk + 2 * nblocks, blk + 2 * nblocks + mcuy, c->jpeg_scratch.ptr};
-    jpeg_encode_device(d_rgba, W, H, grey, d_tab, c->jpeg_huff.ptr, c->jpeg_coeffs.ptr, b, static_cast<uint8_t*>(dev_host),
-                       c->stream);
+    uint32_t* blk = f.jpeg_blk.ptr;
+    JpegDevBufs b{blk, blk + nblocks, blk + 2 * nblocks, blk + 2 * nblocks + mcuy, f.jpeg_scratch.ptr};
+    jpeg_encode_device(d_rgba, W, H, grey, d_tab, c->jpeg_huff.ptr, f.jpeg_coeffs.ptr, b, static_cast<uint8_t*>(dev_host),
+                       st);
 }
 
 // The file of a device-coded JPEG frame: host-built header + the device stream.
@@ -605,20 +554,20 @@ auto launch_exr(const float4* d_film, float inv_spp, bool alpha_one, bool full, 
 }
 
 // Device deflate of one frame into the slot's pinned stream buffer and band
-// table, on the context stream.
+// table, on stream st with f's scratch and profiler.
 template <class Launch>
-void enqueue_deflate(rr_ctx* c, FrameSlot& sl, const DeflatePlan& p, Launch launch) {
+void enqueue_deflate(FrameSlot& sl, DevFrame& f, hipStream_t st, const DeflatePlan& p, Launch launch) {
     DeflateOut& o = sl.deflate;
     o.plan = p;
-    c->deflate_scratch.ensure(deflate_scratch_words(p));
+    f.deflate_scratch.ensure(deflate_scratch_words(p));
     o.stream.ensure((p.own_stream ? exr_stream_max_bytes(p) : deflate_stream_max_bytes(p)) + 32);
     o.tab.ensure((size_t)p.nbands * (p.own_stream ? 4 : 2) * sizeof(uint32_t));
     void *dev_host = nullptr, *dev_tab = nullptr;
     RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
     RR_HIP(hipHostGetDevicePointer(&dev_tab, o.tab.ptr, 0));
-    c->paths.prof.begin(c->stream, RR_K_PNG);
-    launch(p, c->deflate_scratch.ptr, static_cast<uint8_t*>(dev_host), static_cast<uint32_t*>(dev_tab), c->stream);
-    c->paths.prof.end(c->stream);
+    f.prof.begin(st, RR_K_PNG);
+    launch(p, f.deflate_scratch.ptr, static_cast<uint8_t*>(dev_host), static_cast<uint32_t*>(dev_tab), st);
+    f.prof.end(st);
 }
 
 // The file of a deflate-coded frame: the host-built container of format k
@@ -648,9 +597,9 @@ void deflate_file_bytes(const DeflateOut& o, Coder k, int C, std::vector<uint8_t
     }
 }
 
-// Enqueue the device part of one frame on the context stream (no host
-// synchronisation): LBVH (if needed), wavefront, tonemap, optionally the JPEG
-// transform, and the asynchronous copies of the slot's outputs.
+// Enqueue the device part of one frame on its slot's stream, with the slot's
+// device state (no host synchronisation): LBVH (if needed), wavefront, tonemap,
+// optionally the JPEG transform, and the asynchronous copies of the slot's outputs.
 void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     set_device(c);
     rr_scene* s = sl.scene;
@@ -661,46 +610,23 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     r.H = fs.H;
     for (auto& e : sl.ev)
         if (!e) RR_HIP(hipEventCreate(&e));
-    if (sl.alt_scene != s) {  // products of another scene (or none): start this scene's set afresh
-        sl.alt.release();
-        sl.alt = DevScene{};
-        sl.alt_scene = s;
+    if (sl.build_scene != s) {  // products of another scene (or none): start this scene's set afresh
+        sl.build.release();
+        sl.build_scene = s;
     }
-    // This frame runs on its slot's stream with the slot's private buffers
-    // swapped in (the other slot's frame may still be running). A k_tiles frame
-    // following a k_tiles frame does not wait for it: k_tiles and its helper
-    // kernels touch only slot buffers and read-only tables, so frame N+1's
-    // build and launch fill the CUs that frame N's tail and its JPEG kernels
-    // leave idle. Any other frame shares the wavefront queues of DevPaths and
-    // waits for the previous frame's device work.
-    struct SlotSwap {
-        rr_ctx* c;
-        FrameSlot& sl;
-        void swap() {
-            DevPaths& p = c->paths;
-            std::swap(c->stream, sl.stream);
-            std::swap(p.lights, sl.lights);
-            std::swap(p.materials, sl.materials);
-            std::swap(p.mat_lut, sl.mat_lut);
-            std::swap(p.mat_lut_cached, sl.mat_lut_cached);
-            std::swap(p.tile_slab, sl.tile_slab);
-            std::swap(p.tile_ctrs, sl.tile_ctrs);
-            std::swap(p.tile_cost, sl.tile_cost);
-            std::swap(p.tile_order, sl.tile_order);
-            std::swap(p.spill, sl.spill);
-            std::swap(p.trav_counts, sl.trav_counts);
-            std::swap(c->jpeg_blk, sl.jpeg_blk);
-            std::swap(c->jpeg_scratch, sl.jpeg_scratch);
-            std::swap(c->deflate_scratch, sl.deflate_scratch);
-            if (sl.tiles) swap_products(sl.scene->dev, sl.alt);
-            c->in_slot = !c->in_slot;
-        }
-        SlotSwap(rr_ctx* c_, FrameSlot& s_) : c(c_), sl(s_) { swap(); }
-        ~SlotSwap() { swap(); }
-    };
-    sl.tiles = frame_uses_tiles(make_consts(fs, s->dev.n_tris), (fs.flags & RR_FLAG_WAVEFRONT) != 0);
-    SlotSwap slot_swap(c, sl);
-    hipStream_t st = c->stream;
+    FrameOpts opts;
+    opts.count_traversal = (fs.flags & RR_FLAG_COUNT_TRAVERSAL) != 0;
+    opts.force_wavefront = (fs.flags & RR_FLAG_WAVEFRONT) != 0;
+    sl.tiles = frame_uses_tiles(make_consts(fs, s->mesh.n_tris), opts.force_wavefront);
+    // A k_tiles frame following a k_tiles frame does not wait for it: k_tiles
+    // and its helper kernels touch only the slot's state and read-only tables,
+    // and the frame builds into the slot's own products, so frame N+1's build
+    // and launch fill the CUs that frame N's tail and its JPEG kernels leave
+    // idle. Any other frame shares the wavefront queues of DevPaths and the
+    // scene's products, and waits for the previous frame's device work.
+    hipStream_t st = sl.stream;
+    DevFrame& f = sl.dev;
+    DevBuild& build = sl.tiles ? sl.build : s->build;
     FrameSlot* prev = c->last_enqueued;
     // (the deflate coder reads its slot's rgba8 / film and writes slot buffers
     // only, so the next frame waits for the image, ev[5], not for the coder)
@@ -714,52 +640,27 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     bool pending_tiles = false;
     for (auto& o : c->slots)
         if (&o != &sl && o.busy && o.tiles) pending_tiles = true;
-    c->paths.tile_whole = sl.tiles && pending_tiles;
-    sl.prof.reset((fs.flags & RR_FLAG_PROFILE_KERNELS) != 0);
-    struct ProfSwap {  // the device code records into paths.prof; swapped back on every exit
-        KernelProfiler &a, &b;
-        ProfSwap(KernelProfiler& x, KernelProfiler& y) : a(x), b(y) { std::swap(a, b); }
-        ~ProfSwap() { std::swap(a, b); }
-    } prof_swap(c->paths.prof, sl.prof);
-    struct CtrSwap {  // per-slot counters: the previous frame's may still be on their way to the host
-        DevBuf<int32_t>&a, &b;
-        CtrSwap(DevBuf<int32_t>& x, DevBuf<int32_t>& y) : a(x), b(y) { std::swap(a, b); }
-        ~CtrSwap() { std::swap(a, b); }
-    } ctr_swap(c->paths.counters, sl.counters);
-    struct OutSwap {  // per-slot output buffers (film, rgba8, JPEG coefficients)
-        rr_ctx* c;
-        FrameSlot& sl;
-        void swap() {
-            std::swap(c->paths.film, sl.film);
-            std::swap(c->paths.rgba8, sl.rgba8);
-            std::swap(c->jpeg_coeffs, sl.coeffs);
-        }
-        OutSwap(rr_ctx* c_, FrameSlot& s_) : c(c_), sl(s_) { swap(); }
-        ~OutSwap() { swap(); }
-    } out_swap(c, sl);
-    sl.count = (fs.flags & RR_FLAG_COUNT_TRAVERSAL) != 0;
-    c->paths.count_traversal = sl.count;
-    c->paths.force_wavefront = (fs.flags & RR_FLAG_WAVEFRONT) != 0;
+    opts.tile_whole = sl.tiles && pending_tiles;
+    f.prof.reset((fs.flags & RR_FLAG_PROFILE_KERNELS) != 0);
     RR_HIP(hipEventRecord(sl.ev[0], st));
     {
         hipEvent_t& se = c->start_ring[sl.ticket % rr_ctx::kStartRing];
         if (!se) RR_HIP(hipEventCreate(&se));
         RR_HIP(hipEventRecord(se, st));
     }
-    r.rebuilt = prepare_frame(c, s, fs, sl.host_upload);
+    r.rebuilt = prepare_frame(c, s, build, f, st, fs, sl.host_upload);
     RR_HIP(hipEventRecord(sl.ev[1], st));
-    FrameConsts k = make_consts(fs, s->dev.n_tris);
+    FrameConsts k = make_consts(fs, s->mesh.n_tris);
     r.spp_chunk = fit_spp_chunk(fs, c->paths);
     r.chunks = (fs.spp + r.spp_chunk - 1) / r.spp_chunk;
     k.spp_chunk = r.spp_chunk;
     k.div_spp = FastDiv::make((uint32_t)k.spp_chunk);
-    render_frame_device(s->dev, c->paths, k, r.chunks, st);
-    r.tile_slices = c->paths.last_tile_slices;
-    sl.unit_logged = c->paths.last_unit_logged;
+    render_frame_device(s->mesh, build, c->paths, f, k, r.chunks, opts, st);
+    r.tile_slices = f.tile_slices;
     if (fs.view_transform == VIEW_FILMIC) {  // film -> Filmic -> rgba8 (overwrites the kernels' tonemap)
-        c->paths.prof.begin(st, RR_K_ACCUM);
-        view_filmic_device(c->filmic, k, c->paths.film.ptr, reinterpret_cast<uchar4*>(c->paths.rgba8.ptr), st);
-        c->paths.prof.end(st);
+        f.prof.begin(st, RR_K_ACCUM);
+        view_filmic_device(c->filmic, k, f.film.ptr, reinterpret_cast<uchar4*>(f.rgba8.ptr), st);
+        f.prof.end(st);
     }
     RR_HIP(hipEventRecord(sl.ev[4], st));
     const size_t npix = (size_t)fs.W * fs.H;
@@ -772,41 +673,38 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
             RR_HIP(hipMemcpy(c->jpeg_tab.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
             c->jpeg_tab_quality = sl.quality;
         }
-        enqueue_jpeg_device(c, sl, c->paths.rgba8.ptr, fs.W, fs.H, c->jpeg_tab.ptr);
+        enqueue_jpeg_device(c, sl, f, st, f.rgba8.ptr, fs.W, fs.H, c->jpeg_tab.ptr);
     }
     if (device_deflate(sl.coder)) {
         RR_HIP(hipEventRecord(sl.ev[5], st));
         const DeflatePlan& plan = sl.deflate.plan;  // rr_frame_submit's
-        const float4* film = c->paths.film.ptr;
+        const float4* film = f.film.ptr;
         if (sl.coder == Coder::Png8)
-            enqueue_deflate(c, sl, plan, launch_png8(c->paths.rgba8.ptr, sl.color_mode));
+            enqueue_deflate(sl, f, st, plan, launch_png8(f.rgba8.ptr, sl.color_mode));
         else if (sl.coder == Coder::Png16)  // the film again, through exposure and view transform, at 16 bits
-            enqueue_deflate(c, sl, plan,
+            enqueue_deflate(sl, f, st, plan,
                             launch_png16(c, film, k.inv_spp, k.exposure_scale, fs.view_transform, sl.color_mode));
         else  // the film's means: the product finish_frame forms, no view transform
-            enqueue_deflate(c, sl, plan,
+            enqueue_deflate(sl, f, st, plan,
                             launch_exr(film, 1.0f / (float)fs.spp, true, sl.coder == Coder::Exr32, sl.color_mode));
     }
     RR_HIP(hipEventRecord(sl.ev[2], st));
     // the outputs' device-to-host copies follow on the slot's own stream: the
     // next frames run on the other slots' streams, so nothing waits for them
-    hipStream_t cs = st;
     if (sl.coder == Coder::HostRgba) {
         sl.host_rgba.ensure(npix * 4);
-        RR_HIP(hipMemcpyAsync(sl.host_rgba.ptr, c->paths.rgba8.ptr, npix * 4, hipMemcpyDeviceToHost, cs));
+        RR_HIP(hipMemcpyAsync(sl.host_rgba.ptr, f.rgba8.ptr, npix * 4, hipMemcpyDeviceToHost, st));
     }
     const int cpc = counters_per_chunk(fs.max_bounces);
     const size_t nctr = (size_t)cpc * r.chunks;
     sl.host_counters.ensure(nctr * sizeof(int32_t));
-    RR_HIP(hipMemcpyAsync(sl.host_counters.ptr, c->paths.counters.ptr, nctr * sizeof(int32_t), hipMemcpyDeviceToHost,
-                          cs));
+    RR_HIP(hipMemcpyAsync(sl.host_counters.ptr, f.counters.ptr, nctr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (sl.film_out)
-        RR_HIP(hipMemcpyAsync(sl.film_out, c->paths.film.ptr, npix * sizeof(float4), hipMemcpyDeviceToHost, cs));
-    RR_HIP(hipEventRecord(sl.ev[3], cs));
-    if (sl.count) {  // measurement mode: read the traversal counters now
+        RR_HIP(hipMemcpyAsync(sl.film_out, f.film.ptr, npix * sizeof(float4), hipMemcpyDeviceToHost, st));
+    RR_HIP(hipEventRecord(sl.ev[3], st));
+    if (opts.count_traversal) {  // measurement mode: read the traversal counters now
         RR_HIP(hipStreamSynchronize(st));
-        RR_HIP(hipMemcpy(r.trav, c->paths.trav_counts.ptr, sizeof r.trav, hipMemcpyDeviceToHost));
-        c->paths.count_traversal = false;
+        RR_HIP(hipMemcpy(r.trav, f.trav_counts.ptr, sizeof r.trav, hipMemcpyDeviceToHost));
     }
 }
 
@@ -824,8 +722,8 @@ void finish_frame(rr_ctx* c, FrameSlot& sl) {
     const int cpc = counters_per_chunk(fs.max_bounces);
     r.counters.assign(reinterpret_cast<const int32_t*>(sl.host_counters.ptr),
                       reinterpret_cast<const int32_t*>(sl.host_counters.ptr) + (size_t)cpc * r.chunks);
-    sl.prof.collect(r.kernel_ms, r.kernel_launches);
-    sl.prof.reset(false);
+    sl.dev.prof.collect(r.kernel_ms, r.kernel_launches);
+    sl.dev.prof.reset(false);
     if (sl.film_out) {  // film holds sums; report the mean
         const size_t npix = (size_t)fs.W * fs.H;
         const float inv = 1.0f / (float)fs.spp;
@@ -921,14 +819,14 @@ int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const cha
 
 // BVH width the frame kernels traverse for this scene (2: LDS-resident fused
 // path, 4: split path from HBM).
-int frame_hier_of(rr_scene* s, const FrameSetup& fs) { return frame_hier(fs, s->dev.n_tris); }
+int frame_hier_of(rr_scene* s, const FrameSetup& fs) { return frame_hier(fs, s->mesh.n_tris); }
 
 FrameSlot* slot_for(rr_ctx* c, uint64_t ticket) { return &c->slots[ticket % RR_MAX_FRAMES_IN_FLIGHT]; }
 
 bool idle(rr_ctx* c) { return c->next_complete == c->next_ticket; }
 
 // The body of the deflate formats' inspection entry points: an image of the
-// caller's through format k's coder on slot 0, the file's bytes to `out` if
+// caller's through format k's coder (the home set's scratch, slot 0's pinned outputs), the file's bytes to `out` if
 // `cap` suffices. make(device image) gives enqueue_deflate's launch.
 template <class Make>
 int debug_deflate_device(rr_ctx* c, Coder k, int C, int w, int h, const void* pixels, size_t bytes, uint8_t* out,
@@ -943,7 +841,7 @@ int debug_deflate_device(rr_ctx* c, Coder k, int C, int w, int h, const void* pi
         img.ensure(bytes);
         RR_HIP(hipMemcpy(img.ptr, pixels, bytes, hipMemcpyHostToDevice));
         FrameSlot& sl = c->slots[0];
-        enqueue_deflate(c, sl, plan, make(img.ptr));
+        enqueue_deflate(sl, c->home, c->stream, plan, make(img.ptr));
         RR_HIP(hipStreamSynchronize(c->stream));
         img.release();
         std::vector<uint8_t> data;
@@ -955,7 +853,8 @@ int debug_deflate_device(rr_ctx* c, Coder k, int C, int w, int h, const void* pi
 }
 
 // The body of the JPEG inspection entry points: an RGBA8 image of the caller's
-// through the device JPEG coder on slot 0 in colour mode `mode` (resolved).
+// through the device JPEG coder (the home set's scratch, slot 0's pinned
+// output) in colour mode `mode` (resolved).
 int debug_jpeg_device(rr_ctx* c, int mode, const uint8_t* rgba8, int32_t w, int32_t h, int32_t quality, uint8_t* out,
                       uint64_t cap, uint64_t* len) {
     return guarded([&] {
@@ -976,7 +875,7 @@ int debug_jpeg_device(rr_ctx* c, int mode, const uint8_t* rgba8, int32_t w, int3
         sl.fs.H = h;
         sl.quality = quality;
         sl.color_mode = mode;
-        enqueue_jpeg_device(c, sl, img.ptr, w, h, dtab.ptr);
+        enqueue_jpeg_device(c, sl, c->home, st, img.ptr, w, h, dtab.ptr);
         RR_HIP(hipStreamSynchronize(st));
         std::vector<uint8_t> data;
         jpeg_file_bytes(sl, data);
@@ -1098,36 +997,28 @@ int rr_create(int device_ordinal, rr_ctx** out) {
 void rr_destroy(rr_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& sl : c->slots)
         if (sl.stream) (void)hipStreamSynchronize(sl.stream);
     c->paths.release();
+    c->home.release();
     c->filmic.release();
     c->jpeg_tab.release();
-    c->jpeg_coeffs.release();
     c->jpeg_huff.release();
-    c->jpeg_scratch.release();
-    c->jpeg_blk.release();
-    c->deflate_scratch.release();
     c->srgb16_lut.release();
-    for (auto& sl : c->slots) {
+    for (auto& sl : c->slots)
         for (auto& e : sl.ev)
             if (e) (void)hipEventDestroy(e);
-        sl.prof.release();
-    }
     for (auto& e : c->start_ring)
         if (e) (void)hipEventDestroy(e);
     for (rr_scene* s : c->scenes) {  // still-open scenes: back to host-only handles
-        s->dev.release();
+        s->mesh.release();
+        s->build.release();
         s->ctx = nullptr;
     }
     for (auto& sl : c->slots) {
         if (sl.stream) (void)hipStreamDestroy(sl.stream);  // c->stream is slot 0's
-        sl.release_private();
-        sl.counters.release();
-        sl.film.release();
-        sl.rgba8.release();
-        sl.coeffs.release();
+        sl.dev.release();
+        sl.build.release();
     }
     delete c;
 }
@@ -1143,8 +1034,8 @@ int rr_scene_load(rr_ctx* c, const char* path, rr_scene** out) {
     return guarded([&] {
         std::unique_ptr<rr_scene> s(new rr_scene());
         s->desc = load_scene(path);
-        s->dev.n_tris = (int)s->desc.tri_obj.size();
-        s->dev.n_objs = (int)s->desc.objects.size();
+        s->mesh.n_tris = (int)s->desc.tri_obj.size();
+        s->mesh.n_objs = (int)s->desc.objects.size();
         if (c) bind_scene(c, s.get());  // NULL: host-only handle, bound to a context at its first render
         *out = s.release();
         return RR_OK;
@@ -1155,18 +1046,17 @@ void rr_scene_free(rr_scene* s) {
     if (!s) return;
     if (rr_ctx* c = s->ctx) {
         (void)hipSetDevice(c->device);
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
         for (auto& sl : c->slots) {
             if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-            if (sl.alt_scene == s) {  // the slot's build products of this scene
-                sl.alt.release();
-                sl.alt = DevScene{};
-                sl.alt_scene = nullptr;
+            if (sl.build_scene == s) {  // the slot's build products of this scene
+                sl.build.release();
+                sl.build_scene = nullptr;
             }
         }
         c->scenes.erase(s);
     }
-    s->dev.release();
+    s->mesh.release();
+    s->build.release();
     delete s;
 }
 
@@ -1300,7 +1190,7 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
         if (timing) *timing = sl->tm;
         c->frame_warning = sl->view_warning;
         if (stats) {
-            fill_stats(stats, fs, r, sl->scene->dev.n_tris);
+            fill_stats(stats, fs, r, sl->scene->mesh.n_tris);
             stats->view_transform_substituted = sl->view_substituted ? 1 : 0;
             stats->anim_ms = sl->anim_ms;
             stats->encode_ms = enc_ms;
@@ -1355,7 +1245,7 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         if (rgba8) std::memcpy(rgba8, sl->host_rgba.ptr, (size_t)fs.W * fs.H * 4);
         c->frame_warning = sl->view_warning;
         if (stats) {
-            fill_stats(stats, fs, sl->r, s->dev.n_tris);
+            fill_stats(stats, fs, sl->r, s->mesh.n_tris);
             stats->view_transform_substituted = sl->view_substituted ? 1 : 0;
             stats->total_ms = ms_since(sl->t_call);
         }
@@ -1530,17 +1420,17 @@ int rr_debug_frame_state(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_
     return guarded([&] {
         FrameSetup fs = setup_frame(s->desc, frame, params);
         if (c) resolve_view(c, fs);  // render_ints[5]: the transform a frame on c is rendered with
-        const int n = s->dev.n_tris;
+        const int n = s->mesh.n_tris;
         if (c) {  // host-only queries (c == NULL) skip the device part
             if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
             set_device(c);
             PinnedBuf staging;
-            prepare_frame(c, s, fs, staging);
+            prepare_frame(c, s, s->build, c->home, c->stream, fs, staging);
             RR_HIP(hipStreamSynchronize(c->stream));
         }
         if (tris_world && n > 0) {
             std::vector<float4> w((size_t)3 * n);
-            RR_HIP(hipMemcpyAsync(w.data(), s->dev.tri_world.ptr, w.size() * sizeof(float4), hipMemcpyDeviceToHost,
+            RR_HIP(hipMemcpyAsync(w.data(), s->build.tri_world.ptr, w.size() * sizeof(float4), hipMemcpyDeviceToHost,
                                   c->stream));
             RR_HIP(hipStreamSynchronize(c->stream));
             for (size_t i = 0; i < w.size(); ++i) {
@@ -1583,9 +1473,9 @@ int rr_debug_bvh_hier(rr_ctx* c, rr_scene* s, int32_t frame, int32_t hier, uint3
         FrameSetup fs = setup_frame(s->desc, frame, nullptr);
         set_device(c);
         PinnedBuf staging;
-        prepare_frame(c, s, fs, staging, hier);
-        DevScene& d = s->dev;
-        const int n = d.n_tris;
+        prepare_frame(c, s, s->build, c->home, c->stream, fs, staging, hier);
+        const DevBuild& d = s->build;
+        const int n = s->mesh.n_tris;
         hipStream_t st = c->stream;
         if (n > 0) {
             if (keys) RR_HIP(hipMemcpyAsync(keys, d.keys[0].ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -1616,10 +1506,10 @@ int rr_debug_qbvh(rr_ctx* c, rr_scene* s, int32_t frame, int32_t* nq, int32_t* c
         FrameSetup fs = setup_frame(s->desc, frame, nullptr);
         set_device(c);
         PinnedBuf staging;
-        prepare_frame(c, s, fs, staging, kHierQWide);
-        DevScene& d = s->dev;
+        prepare_frame(c, s, s->build, c->home, c->stream, fs, staging, kHierQWide);
+        const DevBuild& d = s->build;
         hipStream_t st = c->stream;
-        const int n = d.n_tris;
+        const int n = s->mesh.n_tris;
         *nq = 0;
         if (n > 0) {
             const uint32_t cnt = (uint32_t)d.nq;
@@ -1665,7 +1555,7 @@ int rr_debug_trace(rr_ctx* c, rr_scene* s, int32_t frame, int32_t bvh_width, int
         set_device(c);
         PinnedBuf staging;
         const int hier = bvh_width >= 5 ? kHierQWide : (bvh_width ? bvh_width : frame_hier_of(s, fs));
-        prepare_frame(c, s, fs, staging, hier);
+        prepare_frame(c, s, s->build, c->home, c->stream, fs, staging, hier);
         const int width = bvh_width >= 5 ? bvh_width : (hier == kHierQWide ? 4 : 2);
         hipStream_t st = c->stream;
         DevBuf<float4> dr, dh;
@@ -1677,7 +1567,7 @@ int rr_debug_trace(rr_ctx* c, rr_scene* s, int32_t frame, int32_t bvh_width, int
         dp.ensure(m);
         dq.ensure(m);
         if (n > 0) RR_HIP(hipMemcpyAsync(dr.ptr, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice, st));
-        trace_batch_device(s->dev, c->paths, n, dr.ptr, dh.ptr, dp.ptr, dq.ptr, st, width);
+        trace_batch_device(s->mesh, s->build, c->paths, c->home, n, dr.ptr, dh.ptr, dp.ptr, dq.ptr, st, width);
         std::vector<float4> h(m);
         if (n > 0) {
             RR_HIP(hipMemcpyAsync(h.data(), dh.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, st));
@@ -1708,19 +1598,20 @@ int rr_debug_tile_costs(rr_ctx* c, int32_t capacity, uint32_t* costs, int32_t* o
         const FrameSlot* sl = c->last_enqueued;
         if (!sl || !sl->tiles) return RR_OK;  // no tile frame yet
         set_device(c);
-        const size_t n = std::min(sl->tile_cost.cap, sl->tile_order.cap);
+        const DevFrame& f = sl->dev;
+        const size_t n = std::min(f.tile_cost.cap, f.tile_order.cap);
         *n_tiles = (int32_t)n;
         const size_t m = std::min<size_t>(n, (size_t)capacity);
         if (m > 0) {
-            RR_HIP(hipMemcpy(costs, sl->tile_cost.ptr, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            RR_HIP(hipMemcpy(order, sl->tile_order.ptr, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+            RR_HIP(hipMemcpy(costs, f.tile_cost.ptr, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            RR_HIP(hipMemcpy(order, f.tile_order.ptr, m * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
         const size_t nu = std::min<size_t>((size_t)unit_capacity, kUnitLog);
         if (nu > 0) {
             std::memset(unit_log, 0, 2 * nu * sizeof(uint64_t));
             // only the launch that wrote it (a counting frame): an older frame's log stays unreported
-            if (sl->unit_logged && sl->trav_counts.cap >= (size_t)(kTravWords + 2 * kUnitLog))
-                RR_HIP(hipMemcpy(unit_log, sl->trav_counts.ptr + kTravWords, 2 * nu * sizeof(uint64_t),
+            if (f.unit_logged && f.trav_counts.cap >= (size_t)(kTravWords + 2 * kUnitLog))
+                RR_HIP(hipMemcpy(unit_log, f.trav_counts.ptr + kTravWords, 2 * nu * sizeof(uint64_t),
                                  hipMemcpyDeviceToHost));
         }
         return RR_OK;

@@ -1009,62 +1009,59 @@ struct TileGrid {
 };
 }  // namespace
 
-void DevPaths::ensure_tiles() {
-    if (grid_blocks == 0) grid_blocks = device_cu_count() * kMaxBlocksPerCu;
-    spill.ensure((size_t)kSpillLane * grid_blocks * kBlock);
-}
-
-void render_tiles_device(DevScene& s, DevPaths& p, const FrameConsts& base, int n_chunks, hipStream_t st) {
+void render_tiles_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f, const FrameConsts& base, int n_chunks,
+                         FrameOpts o, hipStream_t st) {
     const int npix = base.npix;
-    const TileGrid G(base, p.count_traversal, p.tile_whole);
-    p.ensure_tiles();
-    p.film.ensure((size_t)npix);
-    p.rgba8.ensure((size_t)npix * 4);
+    const TileGrid G(base, o.count_traversal, o.tile_whole);
+    if (p.grid_blocks == 0) p.grid_blocks = device_cu_count() * kMaxBlocksPerCu;
+    f.ensure_spill(p.grid_blocks);  // k_tiles: only the traversal stack spill area
+    f.film.ensure((size_t)npix);
+    f.rgba8.ensure((size_t)npix * 4);
     const int cpc = counters_per_chunk(base.max_bounces);
     const long tiles = (long)((base.W + 7) / 8) * ((base.H + 7) / 8);
     const size_t n_ctr = (size_t)cpc * n_chunks;
-    p.counters.ensure(n_ctr);  // zeroed by k_tile_order
+    f.counters.ensure(n_ctr);  // zeroed by k_tile_order
     unsigned long long* tc = nullptr;
-    if (p.count_traversal || RR_TILES_LOG_ALWAYS) {  // (RR_TILES_LOG_ALWAYS: diagnostic builds log every launch's units)
-        p.trav_counts.ensure(kTravWords + 2 * kUnitLog);
-        RR_HIP(hipMemsetAsync(p.trav_counts.ptr, 0, (kTravWords + 2 * kUnitLog) * sizeof(unsigned long long), st));
-        tc = p.trav_counts.ptr;
-        p.last_unit_logged = true;
+    if (o.count_traversal || RR_TILES_LOG_ALWAYS) {  // (RR_TILES_LOG_ALWAYS: diagnostic builds log every launch's units)
+        f.trav_counts.ensure(kTravWords + 2 * kUnitLog);
+        RR_HIP(hipMemsetAsync(f.trav_counts.ptr, 0, (kTravWords + 2 * kUnitLog) * sizeof(unsigned long long), st));
+        tc = f.trav_counts.ptr;
+        f.unit_logged = true;
     }
-    const SceneArgs sa{s.nodes.ptr, s.qnodes.ptr, s.tris.ptr, p.materials.ptr, p.lights.ptr, p.filter_table.ptr,
-                       p.mat_lut.ptr, std::max(s.n_tris - 1, 1), s.n_tris, base.n_mats, base.n_lights, s.nq};
+    const SceneArgs sa{s.nodes.ptr, s.qnodes.ptr, s.tris.ptr, f.materials.ptr, f.lights.ptr, p.filter_table.ptr,
+                       f.mat_lut.ptr, std::max(m.n_tris - 1, 1), m.n_tris, base.n_mats, base.n_lights, s.nq};
     FrameConsts fc = base;
     fc.first_sample = 0;
     fc.spp_chunk = base.spp_total;
-    uint32_t* tot = reinterpret_cast<uint32_t*>(p.counters.ptr);
-    if (p.tile_cost.cap < (size_t)tiles) {  // costs of a new size start at 0 (the first order is the box's)
-        p.tile_cost.ensure((size_t)tiles);
-        RR_HIP(hipMemsetAsync(p.tile_cost.ptr, 0, sizeof(uint32_t) * tiles, st));
+    uint32_t* tot = reinterpret_cast<uint32_t*>(f.counters.ptr);
+    if (f.tile_cost.cap < (size_t)tiles) {  // costs of a new size start at 0 (the first order is the box's)
+        f.tile_cost.ensure((size_t)tiles);
+        RR_HIP(hipMemsetAsync(f.tile_cost.ptr, 0, sizeof(uint32_t) * tiles, st));
     }
-    p.tile_order.ensure((size_t)tiles);
+    f.tile_order.ensure((size_t)tiles);
     // units: one per (box tile, sample group) when the frame runs alone, so
     // the heaviest tiles do not finish the launch on a nearly empty chip;
     // one per tile (every group of it, summed in order in the unit) when
-    // the frame overlaps a pending one (p.tile_whole): the other frame's
+    // the frame overlaps a pending one (o.tile_whole): the other frame's
     // waves fill the tail, and the slab writes and the fold launch go
-    TileSlices sl{p.tile_whole ? 1 : film_groups(base.spp_total), (size_t)192 * film_groups(base.spp_total), nullptr,
-                  p.tile_order.ptr, p.tile_cost.ptr};
-    p.last_tile_slices = sl.n;
+    TileSlices sl{o.tile_whole ? 1 : film_groups(base.spp_total), (size_t)192 * film_groups(base.spp_total), nullptr,
+                  f.tile_order.ptr, f.tile_cost.ptr};
+    f.tile_slices = sl.n;
     if (sl.n > 1) {
-        p.tile_slab.ensure(sl.floats * (size_t)tiles);
-        sl.slab = p.tile_slab.ptr;
+        f.tile_slab.ensure(sl.floats * (size_t)tiles);
+        sl.slab = f.tile_slab.ptr;
     }
     const int g = clamp_grid(tiles * 64, G.grid);
-    p.prof.begin(st, RR_K_TILES);
-    p.tile_ctrs.ensure((size_t)kTileShards * kTileCtrStride);
-    k_tile_order<<<1, kOrderThreads, 0, st>>>(fc, s.nodes.ptr, p.tile_cost.ptr, p.tile_order.ptr, p.tile_ctrs.ptr,
-                                              reinterpret_cast<uint32_t*>(p.counters.ptr), (int)n_ctr);
-    G.kx<<<g, kBlock, G.dyn, st>>>(fc, sa, p.tile_ctrs.ptr, p.film.ptr, p.srgb_lut.ptr,
-                                           reinterpret_cast<uchar4*>(p.rgba8.ptr), tot, p.spill.ptr, tc, sl);
+    f.prof.begin(st, RR_K_TILES);
+    f.tile_ctrs.ensure((size_t)kTileShards * kTileCtrStride);
+    k_tile_order<<<1, kOrderThreads, 0, st>>>(fc, s.nodes.ptr, f.tile_cost.ptr, f.tile_order.ptr, f.tile_ctrs.ptr,
+                                              reinterpret_cast<uint32_t*>(f.counters.ptr), (int)n_ctr);
+    G.kx<<<g, kBlock, G.dyn, st>>>(fc, sa, f.tile_ctrs.ptr, f.film.ptr, p.srgb_lut.ptr,
+                                           reinterpret_cast<uchar4*>(f.rgba8.ptr), tot, f.spill.ptr, tc, sl);
     if (sl.n > 1)
         k_tiles_fold<<<(int)std::min<long>((tiles + kWavesPerBlock - 1) / kWavesPerBlock, 2048), kBlock, 0, st>>>(
-            fc, s.nodes.ptr, sl, p.film.ptr, p.srgb_lut.ptr, reinterpret_cast<uchar4*>(p.rgba8.ptr));
-    p.prof.end(st);
+            fc, s.nodes.ptr, sl, f.film.ptr, p.srgb_lut.ptr, reinterpret_cast<uchar4*>(f.rgba8.ptr));
+    f.prof.end(st);
     RR_HIP(hipGetLastError());
 }
 

@@ -619,7 +619,7 @@ constexpr int kPacketStack = 128;             // a node pushes <= 5: about 25 le
 #ifndef RR_CAM_BEAM
 #define RR_CAM_BEAM 1  // packet_trace_beam for camera packets (0: packet_trace, per-lane box tests)
 #endif
-constexpr int kPacketSpill = kSpillStack * 64;  // per wave in HBM (DevPaths::spill holds kSpillStack per lane)
+constexpr int kPacketSpill = kSpillStack * 64;  // per wave in HBM (DevFrame::spill holds kSpillStack per lane)
 template <bool kCount, int kStack = kPacketStack>
 RR_D void packet_trace(const QNode6* __restrict__ nodes, const TriPack* __restrict__ tris, lds_int* stk,
                        int* __restrict__ gstk, uint32_t* __restrict__ drops, bool act, float3 o, float3 d, float tmin,
@@ -1282,30 +1282,37 @@ void DevPaths::ensure_paths(size_t n) {
         hits.ensure(n);
         cap = n;
     }
-    spill.ensure((size_t)kSpillLane * grid_blocks * kBlock);
 }
 
 void DevPaths::release() {
     for (DevBuf<float4>* b : {&rad, &ps_o[0], &ps_d[0], &ps_t[0], &ps_o[1], &ps_d[1], &ps_t[1], &sh_o, &sh_d,
-                              &sh_c, &film})
+                              &sh_c, &film_part})
         b->release();
-    perm.release();
-    counters.release(); tile_ctrs.release(); tile_cost.release(); tile_order.release(); spill.release(); tile_slab.release(); film_part.release(); hits.release(); qctr.release();
-    rgba8.release(); filter_table.release(); srgb_lut.release(); lights.release(); materials.release();
+    perm.release(); hits.release(); qctr.release();
+    filter_table.release(); srgb_lut.release();
+    cap = 0;
+}
+
+void DevFrame::ensure_spill(int grid_blocks) { spill.ensure((size_t)kSpillLane * grid_blocks * kBlock); }
+
+void DevFrame::release() {
+    counters.release(); spill.release(); film.release(); rgba8.release();
+    tile_slab.release(); tile_ctrs.release(); tile_cost.release(); tile_order.release();
+    lights.release(); materials.release();
     mat_lut.release();
     mat_lut_cached.clear();
     trav_counts.release();
     prof.release();
-    cap = 0;
+    jpeg_coeffs.release(); jpeg_blk.release(); jpeg_scratch.release(); deflate_scratch.release();
 }
 
 namespace {
 // Large scenes: per chunk trace_primary -> shade_primary -> for each bounce b:
 // shadow(b), trace_extend(b+1), shade_extend(b+1) -> accumulate. Radiance
 // additions per path happen in the same order as the fused kernels'.
-void render_split(DevPaths& p, const FrameConsts& base, int n_chunks, hipStream_t st, const SceneArgs& sa,
+void render_split(DevPaths& p, DevFrame& f, const FrameConsts& base, int n_chunks, hipStream_t st, const SceneArgs& sa,
                   unsigned long long* tc, PathQueue pq[2], const ShadowQueue& sq, const float4* tnrm) {
-    KernelProfiler& pr = p.prof;
+    KernelProfiler& pr = f.prof;
     const SplitGrids G(tc != nullptr);
     const int npix = base.npix;
     const int cpc = counters_per_chunk(base.max_bounces);
@@ -1333,7 +1340,7 @@ void render_split(DevPaths& p, const FrameConsts& base, int n_chunks, hipStream_
         if (fc.first_sample + fc.spp_chunk > base.spp_total) fc.spp_chunk = base.spp_total - fc.first_sample;
         fc.div_spp = FastDiv::make((uint32_t)fc.spp_chunk);
         const int np = npix * fc.spp_chunk;
-        uint32_t* tot = reinterpret_cast<uint32_t*>(p.counters.ptr + (size_t)cpc * c);
+        uint32_t* tot = reinterpret_cast<uint32_t*>(f.counters.ptr + (size_t)cpc * c);
         uint32_t* tail = tot + camera_traced_slot(base.max_bounces);  // traced, drops (device.hpp)
         uint32_t* qc = p.qctr.ptr + per_chunk * c;
         auto qpath = [&](int b) { return qc + ((size_t)b * 2 + 0) * per_q; };    // paths entering b+1
@@ -1346,9 +1353,9 @@ void render_split(DevPaths& p, const FrameConsts& base, int n_chunks, hipStream_
         pr.begin(st, RR_K_PRIMARY);
         if (packets)
             G.ktpk<<<clamp_grid(np, G.packet), kBlock, 0, st>>>(fc, sa, np, p.hits.ptr, deal_host(qpath(0), 2),
-                                                               p.spill.ptr, tc, tail);
+                                                               f.spill.ptr, tc, tail);
         else
-            G.ktp<<<clamp_grid(np, G.trace_p, kTraceBlock), kTraceBlock, 0, st>>>(fc, sa, np, p.hits.ptr, p.spill.ptr,
+            G.ktp<<<clamp_grid(np, G.trace_p, kTraceBlock), kTraceBlock, 0, st>>>(fc, sa, np, p.hits.ptr, f.spill.ptr,
                                                                                    tc, tail);
         pr.end(st);
         pr.begin(st, RR_K_SHADE);
@@ -1372,7 +1379,7 @@ void render_split(DevPaths& p, const FrameConsts& base, int n_chunks, hipStream_
             }
             G.kts<<<clamp_grid(np, G.shadow, kTraceBlock), kTraceBlock, 0, st>>>(
                 sa, sq, QueueIn{qshadow(b), cap_prev, tot + 2 * b + 1}, perm_s, Rad{reinterpret_cast<float*>(p.rad.ptr)},
-                p.spill.ptr, tc, tail);
+                f.spill.ptr, tc, tail);
             pr.end(st);
             if (b == base.max_bounces) break;
             const int nb = b + 1;  // bounce being traced and shaded
@@ -1384,7 +1391,7 @@ void render_split(DevPaths& p, const FrameConsts& base, int n_chunks, hipStream_
                 perm_e = p.perm.ptr;
             }
             G.kte<<<clamp_grid(np, G.trace_e, kTraceBlock), kTraceBlock, 0, st>>>(sa, pq[nb & 1], qin, perm_e,
-                                                                                p.hits.ptr, p.spill.ptr, tc, tail);
+                                                                                p.hits.ptr, f.spill.ptr, tc, tail);
             pr.end(st);
             pr.begin(st, RR_K_SHADE);
             k_shade_extend<<<gse, kBlock, 0, st>>>(fc, nb, sa, pq[nb & 1], QueueIn{qpath(b), cap_prev, nullptr},
@@ -1395,48 +1402,50 @@ void render_split(DevPaths& p, const FrameConsts& base, int n_chunks, hipStream_
         }
         const int ga = clamp_grid(npix, accum_grid());
         pr.begin(st, RR_K_ACCUM);
-        k_accumulate<<<ga, kBlock, 0, st>>>(fc, Rad{reinterpret_cast<float*>(p.rad.ptr)}, p.film.ptr, p.film_part.ptr, c == 0 ? 1 : 0, c == n_chunks - 1 ? 1 : 0,
-                                            p.srgb_lut.ptr, reinterpret_cast<uchar4*>(p.rgba8.ptr));
+        k_accumulate<<<ga, kBlock, 0, st>>>(fc, Rad{reinterpret_cast<float*>(p.rad.ptr)}, f.film.ptr, p.film_part.ptr, c == 0 ? 1 : 0, c == n_chunks - 1 ? 1 : 0,
+                                            p.srgb_lut.ptr, reinterpret_cast<uchar4*>(f.rgba8.ptr));
         pr.end(st);
     }
 }
 }  // namespace
 
-void render_frame_device(DevScene& s, DevPaths& p, const FrameConsts& base, int n_chunks, hipStream_t st) {
+void render_frame_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f, const FrameConsts& base, int n_chunks,
+                         FrameOpts o, hipStream_t st) {
     const int npix = base.npix;
     const size_t npaths = (size_t)npix * base.spp_chunk;
-    p.last_tile_slices = 0;
-    p.last_unit_logged = false;
-    if (frame_uses_tiles(base, p.force_wavefront)) {  // one launch: all samples of every tile
-        render_tiles_device(s, p, base, n_chunks, st);
+    f.tile_slices = 0;
+    f.unit_logged = false;
+    if (frame_uses_tiles(base, o.force_wavefront)) {  // one launch: all samples of every tile
+        render_tiles_device(m, s, p, f, base, n_chunks, o, st);
         return;
     }
-    p.film.ensure((size_t)npix);
-    p.rgba8.ensure((size_t)npix * 4);
+    f.film.ensure((size_t)npix);
+    f.rgba8.ensure((size_t)npix * 4);
     const int cpc = counters_per_chunk(base.max_bounces);
-    p.counters.ensure((size_t)cpc * n_chunks);
-    RR_HIP(hipMemsetAsync(p.counters.ptr, 0, sizeof(int32_t) * cpc * n_chunks, st));
+    f.counters.ensure((size_t)cpc * n_chunks);
+    RR_HIP(hipMemsetAsync(f.counters.ptr, 0, sizeof(int32_t) * cpc * n_chunks, st));
     if (base.n_tris <= 0) {  // nothing to hit: every sample is the world term
-        p.prof.begin(st, RR_K_ACCUM);
-        k_world<<<clamp_grid(npix, accum_grid()), kBlock, 0, st>>>(base, p.film.ptr, p.srgb_lut.ptr,
-                                                                   reinterpret_cast<uchar4*>(p.rgba8.ptr));
-        p.prof.end(st);
+        f.prof.begin(st, RR_K_ACCUM);
+        k_world<<<clamp_grid(npix, accum_grid()), kBlock, 0, st>>>(base, f.film.ptr, p.srgb_lut.ptr,
+                                                                   reinterpret_cast<uchar4*>(f.rgba8.ptr));
+        f.prof.end(st);
         RR_HIP(hipGetLastError());
         return;
     }
     p.ensure_paths(npaths);
+    f.ensure_spill(p.grid_blocks);
     if (n_chunks > 1) p.film_part.ensure((size_t)npix);
     unsigned long long* tc = nullptr;
-    if (p.count_traversal) {
-        p.trav_counts.ensure(kTravWords);
-        RR_HIP(hipMemsetAsync(p.trav_counts.ptr, 0, kTravWords * sizeof(unsigned long long), st));
-        tc = p.trav_counts.ptr;
+    if (o.count_traversal) {
+        f.trav_counts.ensure(kTravWords);
+        RR_HIP(hipMemsetAsync(f.trav_counts.ptr, 0, kTravWords * sizeof(unsigned long long), st));
+        tc = f.trav_counts.ptr;
     }
     PathQueue pq[2] = {{p.ps_o[0].ptr, p.ps_d[0].ptr, p.ps_t[0].ptr}, {p.ps_o[1].ptr, p.ps_d[1].ptr, p.ps_t[1].ptr}};
     ShadowQueue sq{p.sh_o.ptr, p.sh_d.ptr, p.sh_c.ptr};
-    const SceneArgs sa{s.nodes.ptr, s.qnodes.ptr, s.tris.ptr, p.materials.ptr, p.lights.ptr, p.filter_table.ptr,
-                       p.mat_lut.ptr, std::max(s.n_tris - 1, 1), s.n_tris, base.n_mats, base.n_lights, s.nq};
-    render_split(p, base, n_chunks, st, sa, tc, pq, sq, s.has4 ? s.tnrm.ptr : nullptr);
+    const SceneArgs sa{s.nodes.ptr, s.qnodes.ptr, s.tris.ptr, f.materials.ptr, f.lights.ptr, p.filter_table.ptr,
+                       f.mat_lut.ptr, std::max(m.n_tris - 1, 1), m.n_tris, base.n_mats, base.n_lights, s.nq};
+    render_split(p, f, base, n_chunks, st, sa, tc, pq, sq, s.has4 ? s.tnrm.ptr : nullptr);
     RR_HIP(hipGetLastError());
 }
 
@@ -1485,33 +1494,34 @@ void bsdf_batch_device(const float* d_mat12, const float* d_lut, const float n3[
     RR_HIP(hipGetLastError());
 }
 
-void trace_batch_device(DevScene& s, DevPaths& p, int n, const float4* d_rays, float4* d_hits, int32_t* d_prims,
-                        uint8_t* d_occ, hipStream_t st, int width) {
+void trace_batch_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f, int n, const float4* d_rays,
+                        float4* d_hits, int32_t* d_prims, uint8_t* d_occ, hipStream_t st, int width) {
     p.ensure_paths(1);
+    f.ensure_spill(p.grid_blocks);
     const int g = (int)std::min<long>((n + kBlock - 1) / kBlock, p.grid_blocks);
     if (width == 5 || width == 7) {  // packet walk (7: beam) with a 4-entry stack: the HBM part runs
         if (!s.has4) throw std::runtime_error("BVH4 not built");
         if (n > 0) {
             if (width == 7)
-                k_debug_packet<4, true><<<g, kBlock, 0, st>>>(s.qnodes.ptr, s.tris.ptr, s.n_tris, n, d_rays, d_hits,
-                                                              d_prims, d_occ, p.spill.ptr);
+                k_debug_packet<4, true><<<g, kBlock, 0, st>>>(s.qnodes.ptr, s.tris.ptr, m.n_tris, n, d_rays, d_hits,
+                                                              d_prims, d_occ, f.spill.ptr);
             else
-                k_debug_packet<4><<<g, kBlock, 0, st>>>(s.qnodes.ptr, s.tris.ptr, s.n_tris, n, d_rays, d_hits,
-                                                        d_prims, d_occ, p.spill.ptr);
+                k_debug_packet<4><<<g, kBlock, 0, st>>>(s.qnodes.ptr, s.tris.ptr, m.n_tris, n, d_rays, d_hits,
+                                                        d_prims, d_occ, f.spill.ptr);
         }
     } else if (width == 4 || width == 6) {  // 6: the same walk with one LDS stack entry per lane
         if (!s.has4) throw std::runtime_error("BVH4 not built");
         if (n > 0) {
             if (width == 6)
-                k_debug_trace4<1><<<g, kBlock, 0, st>>>(s.qnodes.ptr, s.tris.ptr, s.n_tris, n, d_rays, d_hits, d_prims,
-                                                        d_occ, p.spill.ptr);
+                k_debug_trace4<1><<<g, kBlock, 0, st>>>(s.qnodes.ptr, s.tris.ptr, m.n_tris, n, d_rays, d_hits, d_prims,
+                                                        d_occ, f.spill.ptr);
             else
-                k_debug_trace4<kLdsStack><<<g, kBlock, 0, st>>>(s.qnodes.ptr, s.tris.ptr, s.n_tris, n, d_rays, d_hits,
-                                                                d_prims, d_occ, p.spill.ptr);
+                k_debug_trace4<kLdsStack><<<g, kBlock, 0, st>>>(s.qnodes.ptr, s.tris.ptr, m.n_tris, n, d_rays, d_hits,
+                                                                d_prims, d_occ, f.spill.ptr);
         }
     } else if (n > 0)
-        k_debug_trace<<<g, kBlock, 0, st>>>(s.nodes.ptr, s.tris.ptr, s.n_tris, n, d_rays, d_hits, d_prims, d_occ,
-                                            p.spill.ptr);
+        k_debug_trace<<<g, kBlock, 0, st>>>(s.nodes.ptr, s.tris.ptr, m.n_tris, n, d_rays, d_hits, d_prims, d_occ,
+                                            f.spill.ptr);
     RR_HIP(hipGetLastError());
 }
 #endif  // !RR_TILES_TU

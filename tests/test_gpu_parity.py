@@ -691,3 +691,109 @@ def test_tile_schedule_record(ctx, rr, s04):
     logged = np.nonzero(log[:, 1])[0]
     assert logged.size >= 4 * busy.size
     assert (log[logged, 0] <= log[logged, 1]).all() and (log[logged, 0] > 0).all()
+
+
+def _overlapped(c, rr, plan, stem):
+    """Submits plan's (scene, frame, params) with RR_MAX_FRAMES_IN_FLIGHT in
+    flight, as JPEG files stem0, stem1, ...; returns (files' bytes, stats)."""
+    pending, stats = [], []
+    for i, (s, f, p) in enumerate(plan):
+        if len(pending) == rr.native.RR_MAX_FRAMES_IN_FLIGHT:
+            stats.append(c.complete_frame(pending.pop(0))[1])
+        pending.append(c.submit_frame(s, f, p, f"{stem}{i}", "JPEG", 90))
+    stats += [c.complete_frame(t)[1] for t in pending]
+    data = []
+    for i in range(len(plan)):
+        with open(f"{stem}{i}.jpg", "rb") as fh:
+            data.append(fh.read())
+    return data, stats
+
+
+def test_scene_lifetime_across_slots(rr, tmp_path):
+    """Every slot holds build products of soup A when A is closed; soup B,
+    loaded next (possibly at A's address), finds none of them: each
+    overlapped frame of A and of B equals the file rr_render_frame writes for
+    it in a fresh context."""
+    import soups
+    p = rr.default_params(width=96, height=54, spp=4)
+    frames = (2, 11, 23)
+    paths, sizes = {}, {}
+    for name, seed in (("A", 3), ("B", 6)):
+        paths[name] = str(tmp_path / f"soup{name}.rrscene")
+        sizes[name] = len(soups.soup_scene(S04, seed, paths[name]))
+    assert sizes["A"] != sizes["B"] and max(sizes.values()) <= 60, sizes
+    with rr.RenderContext(0) as c:
+        for name in ("A", "B"):
+            s = c.load_scene(paths[name])
+            try:
+                got, _ = _overlapped(c, rr, [(s, f, p) for f in frames], str(tmp_path / f"o{name}"))
+            finally:
+                s.close()
+            for i, f in enumerate(frames):
+                with rr.RenderContext(0) as fresh:
+                    sf = fresh.load_scene(paths[name])
+                    fresh.render_frame(sf, f, p, str(tmp_path / f"f{name}{i}"), "JPEG", 90)
+                    sf.close()
+                assert got[i] == (tmp_path / f"f{name}{i}.jpg").read_bytes(), f"soup {name}, frame {f} differs"
+
+
+def test_inspection_calls_between_batches_use_the_home_set(ctx, rr, tmp_path, s04):
+    """frame_state and rr_debug_trace between two batches of overlapped tile
+    frames work on the context's own frame state and the scenes' own build
+    products: the slots' (material tables, tile costs, build products) are as
+    the first batch left them, and the second batch writes the same files,
+    the serial render's."""
+    p = rr.default_params(width=96, height=54, spp=4)
+    frames = (4, 5, 31)
+    serial = []
+    for i, f in enumerate(frames):
+        ctx.render_frame(s04, f, p, str(tmp_path / f"s{i}"), "JPEG", 90)
+        serial.append((tmp_path / f"s{i}.jpg").read_bytes())
+    first, _ = _overlapped(ctx, rr, [(s04, f, p) for f in frames], str(tmp_path / "a"))
+    s02 = ctx.load_scene(scene_path("02_physics-standin.rrscene"))
+    try:
+        st = ctx.frame_state(s02, 60)
+        rays = _rays_random(np.random.default_rng(7), 256, st.tris.reshape(-1, 3).mean(axis=0), 6.0)
+        _, prims, _ = ctx.trace(s02, 60, rays, width=4)
+        assert (prims >= 0).any()
+    finally:
+        s02.close()
+    ctx.frame_state(s04, frames[1], p)
+    second, _ = _overlapped(ctx, rr, [(s04, f, p) for f in frames], str(tmp_path / "b"))
+    assert first == serial and second == serial
+
+
+def test_rebuild_flags_follow_the_slot(rr, tmp_path):
+    """stats.bvh_rebuilt of a fixed plan with three frames in flight, in a
+    fresh context (tickets from 1, slot = ticket % 3, so the frames take slots
+    1, 2, 0, 1, 2, 0, ...). A k_tiles frame uses and updates its slot's build
+    products of its scene, which start afresh when the slot last held a frame
+    of another scene; a split-path frame and every inspection call use the
+    scene's own. A build is kept while the object transforms (the same frame
+    number here) and the hierarchy kind stay."""
+    import soups
+    path_b = str(tmp_path / "soupB.rrscene")
+    soups.soup_scene(S04, 3, path_b)
+    pt = rr.default_params(width=96, height=54, spp=4)
+    pc = rr.default_params(width=160, height=90, spp=4)
+    with rr.RenderContext(0) as c:
+        a, b, s02 = c.load_scene(S04), c.load_scene(path_b), c.load_scene(scene_path("02_physics-standin.rrscene"))
+        try:
+            plan = [(a, 5, pt),     # slot 1, nothing built there: 1
+                    (a, 5, pt),     # slot 2, nothing built there: 1
+                    (b, 5, pt),     # slot 0, nothing built there: 1
+                    (a, 5, pt),     # slot 1 holds a's build at these transforms: 0
+                    (s02, 60, pc),  # slot 2, split path: the scene's own products, nothing built: 1
+                    (b, 5, pt),     # slot 0 holds b's build: 0
+                    (a, 5, pt),     # slot 1 holds a's build: 0
+                    (a, 5, pt),     # slot 2 last held a frame of s02: afresh, 1
+                    (s02, 60, pc),  # slot 0, split path: the scene's own products, built by the fifth frame: 0
+                    (b, 5, pt)]     # slot 1 last held a frame of a: afresh, 1
+            _, stats = _overlapped(c, rr, plan, str(tmp_path / "r"))
+            rebuilt = [int(st.bvh_rebuilt) for st in stats]
+            print("bvh_rebuilt:", rebuilt)
+            # recorded from the parent of the change that gave the slots their own state
+            assert rebuilt == [1, 1, 1, 0, 1, 0, 0, 1, 0, 1]
+        finally:
+            for s in (a, b, s02):
+                s.close()
