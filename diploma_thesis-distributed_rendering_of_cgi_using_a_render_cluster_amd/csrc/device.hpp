@@ -342,12 +342,19 @@ bool exr32_plan(int W, int H, int C, DeflatePlan& p);
 void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
                          uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
-// The Filmic LUTs of one device as kernel arguments (view.hpp FilmicDev::args).
+// The view settings of a frame as kernel arguments (view.hpp FilmicDev::args):
+// the Filmic LUTs of one device and the display gamma. lut1 is the curve the
+// frame's look selects (the base curve for None and Medium Contrast); fcube
+// the false-colour cube (RR_VIEW_FALSE_COLOR only). Views outside the Filmic
+// family leave the LUT fields zero.
 struct FilmicArgs {
     const float4* cube;
     const float* lut1;
     int n3, n1, comps;
     float lo1, hi1;
+    const float4* fcube;
+    int nf;
+    float inv_gamma;  // 1 / display gamma; 0: gamma 1, no gamma step
 };
 
 // Device 16-bit PNG encode (png16.hip): the film's display-referred image as
@@ -361,9 +368,9 @@ bool png16_plan(int W, int H, int C, DeflatePlan& p);
 struct Png16Front {
     const float4* film;  // W x H sums
     float inv_spp, exposure_scale;
-    int view_transform;  // RR_VIEW_STANDARD / RAW / FILMIC (FILMIC: `filmic` holds the LUTs)
+    int view_transform;  // RR_VIEW_STANDARD / RAW, or one of the Filmic family (`filmic` holds the LUTs)
     const float* srgb16;  // kSrgb16LutSize + 2 floats (scene.hpp build_srgb16_lut)
-    FilmicArgs filmic;
+    FilmicArgs filmic;    // the LUTs, and for every view the display gamma
 };
 void png16_encode_device(const Png16Front& f, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                          uint32_t* host_tab, hipStream_t st);

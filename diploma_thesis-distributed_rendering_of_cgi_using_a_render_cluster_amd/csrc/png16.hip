@@ -15,14 +15,16 @@
 //  - Png16Sub: the filtered byte at a position, the front end of the deflate
 //    coder (deflate.hpp k_deflate_front). A position computes its own sample
 //    and its left neighbour's. Per sample, in the
-//    operation order of paths.hpp tonemap / view.hip k_view_filmic:
+//    operation order of paths.hpp tonemap / view.hip k_view:
 //    c = sum * inv_spp * exposure_scale, then
 //      Standard: quantize16(srgb_oetf16(clamp(c, 0, 1)))
 //      Raw:      quantize16(clamp(c, 0, 1))
-//      Filmic:   quantize16(filmic_display(c)) (the chain clamps by itself, as
-//                at 8 bits)
+//      Filmic, Filmic Log, False Color: quantize16(filmic_display(c)) (the
+//                quantiser clamps, as at 8 bits)
+//    and with a display gamma other than 1, display_gamma of the value before
+//    quantize16 (and before the BW luma), for every view;
 //    with contraction off, so a host restatement gives the same bits
-//    (tests/png16_reader.py).
+//    (tests/png16_reader.py, tests/view_settings.py).
 //  - deflate.hip's stages over the bands of one zlib stream with the stored
 //    fallback, with the distances
 //    2 (equal neighbouring samples: grey pixels, and every zero run), 8 (the
@@ -56,68 +58,91 @@ __device__ __forceinline__ float display1(const Png16Front& f, float a) {
     return v;
 }
 
-// The three display-referred values of a film sum through the Filmic chain.
+// X, below: the front end of a frame whose settings go beyond Standard, Raw
+// and Filmic at display gamma 1 (png16_extended): the other views of the
+// Filmic family and the display gamma are compiled into it alone, so the
+// plain one keeps the instructions and registers it had before them.
+
+// The three display-referred values of a film sum through the Filmic family's chain.
+template <bool X>
 __device__ __forceinline__ void display_filmic(const Png16Front& f, float4 acc, float d[3]) {
     const float c[3] = {acc.x * f.inv_spp * f.exposure_scale, acc.y * f.inv_spp * f.exposure_scale,
                         acc.z * f.inv_spp * f.exposure_scale};
-    filmic_display(f.filmic, c, d);
+    filmic_display(f.filmic, X ? f.view_transform : RR_VIEW_FILMIC, c, d);
+    if (X && f.filmic.inv_gamma != 0.0f)
+        for (int k = 0; k < 3; ++k) d[k] = display_gamma(d[k], f.filmic.inv_gamma);
+}
+
+// display1 and the display gamma.
+template <bool X>
+__device__ __forceinline__ float display1g(const Png16Front& f, float a) {
+    const float v = display1(f, a);
+    if (X && f.filmic.inv_gamma != 0.0f) return display_gamma(v, f.filmic.inv_gamma);
+    return v;
 }
 
 // The 16-bit sample of channel ch (0 R, 1 G, 2 B) of a film sum.
+template <bool X>
 __device__ __forceinline__ uint32_t sample16(const Png16Front& f, float4 acc, uint32_t ch) {
-    if (f.view_transform == 2) {  // Filmic
+    if (f.view_transform >= RR_VIEW_FILMIC) {  // the Filmic family
         float d[3];
-        display_filmic(f, acc, d);
+        display_filmic<X>(f, acc, d);
         return quantize16(ch == 0 ? d[0] : ch == 1 ? d[1] : d[2]);
     }
-    return quantize16(display1(f, ch == 0 ? acc.x : ch == 1 ? acc.y : acc.z));
+    return quantize16(display1g<X>(f, ch == 0 ? acc.x : ch == 1 ? acc.y : acc.z));
 }
 
 // The 16-bit grey sample of a film sum (Blender's BW colour mode): Rec.709 luma
 // of the three display-referred values, products and sums rounded one by one.
+template <bool X>
 __device__ __forceinline__ uint32_t grey16(const Png16Front& f, float4 acc) {
     float d[3];
-    if (f.view_transform == 2) {  // Filmic
-        display_filmic(f, acc, d);
+    if (f.view_transform >= RR_VIEW_FILMIC) {  // the Filmic family
+        display_filmic<X>(f, acc, d);
     } else {
-        d[0] = display1(f, acc.x);
-        d[1] = display1(f, acc.y);
-        d[2] = display1(f, acc.z);
+        d[0] = display1g<X>(f, acc.x);
+        d[1] = display1g<X>(f, acc.y);
+        d[2] = display1g<X>(f, acc.z);
     }
     return quantize16(luma709(d[0], d[1], d[2]));
 }
 
 // Byte q < 2C W of an image row before the filter. C = 4: R, G, B, A = 65535;
 // 3: R, G, B; 1: grey.
-template <int C>
+template <int C, bool X>
 __device__ __forceinline__ uint32_t row_byte(const Png16Front& f, const float4* __restrict__ row, uint32_t q) {
     uint32_t s;
     if constexpr (C == 4) {
         const uint32_t ch = (q >> 1) & 3u;
         if (ch == 3u) return 0xFFu;  // A = 65535
-        s = sample16(f, row[q >> 3], ch);
+        s = sample16<X>(f, row[q >> 3], ch);
     } else if constexpr (C == 3) {
         const uint32_t k = q >> 1, px = k / 3u;
-        s = sample16(f, row[px], k - 3u * px);
+        s = sample16<X>(f, row[px], k - 3u * px);
     } else {
-        s = grey16(f, row[q >> 1]);
+        s = grey16<X>(f, row[q >> 1]);
     }
     return (q & 1u) ? s & 0xFFu : s >> 8;
 }
 
 // Byte j of a band: filter type 1 (Sub) in front of every row of differences.
-template <int C>
+template <int C, bool X = false>
 struct Png16Sub {
     Png16Front f;
     __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t, uint32_t j) const {
         const uint32_t row = j / p.stride, x = j - row * p.stride;
         if (x == 0) return 1u;
         const float4* src = f.film + (size_t)(row0 + (int)row) * (size_t)p.W;
-        uint32_t v = row_byte<C>(f, src, x - 1u);
-        if (x > 2u * C) v = (v - row_byte<C>(f, src, x - 1u - 2u * C)) & 0xFFu;
+        uint32_t v = row_byte<C, X>(f, src, x - 1u);
+        if (x > 2u * C) v = (v - row_byte<C, X>(f, src, x - 1u - 2u * C)) & 0xFFu;
         return v;
     }
 };
+
+// Whether a frame's settings need the extended front end.
+bool png16_extended(const Png16Front& f) {
+    return f.view_transform > RR_VIEW_FILMIC || f.filmic.inv_gamma != 0.0f;
+}
 
 }  // namespace
 
@@ -143,7 +168,11 @@ void png16_encode_device(const Png16Front& f, int C, const DeflatePlan& p, uint3
                          uint32_t* host_tab, hipStream_t st) {
     const DeflateBufs c = deflate_carve(p, scratch);
     const dim3 grid(p.nsub, p.nbands);
-    if (C == 1) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<1>{f}, p, c.filt, c.adler_part);
+    if (png16_extended(f)) {
+        if (C == 1) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<1, true>{f}, p, c.filt, c.adler_part);
+        else if (C == 3) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<3, true>{f}, p, c.filt, c.adler_part);
+        else k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<4, true>{f}, p, c.filt, c.adler_part);
+    } else if (C == 1) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<1>{f}, p, c.filt, c.adler_part);
     else if (C == 3) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<3>{f}, p, c.filt, c.adler_part);
     else k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<4>{f}, p, c.filt, c.adler_part);
     deflate_bands_device(p, c, st);

@@ -188,6 +188,10 @@ struct rr_ctx {
     int exr_depth = 0;
     // colour mode of the files (rr_set_color_mode / RR_COLOR_MODE): 0 the scene's, else RR_COLOR_BW / RGB / RGBA
     int color_mode = 0;
+    // look of Filmic frames (rr_set_look / RR_LOOK): a view.hpp kLooks id, -1 the scene's
+    int look = -1;
+    // display gamma (rr_set_display_gamma / RR_DISPLAY_GAMMA): 0 the scene's
+    float gamma = 0.f;
     DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
     std::vector<float> filter_cache;
     float filter_width_cached = -1.f;
@@ -199,7 +203,7 @@ struct rr_ctx {
     // UNIX-time estimate of when the compute stream finished the last completed
     // frame (rr_frame_complete): the next frame's device work cannot start before
     double gpu_free_at = 0.0;
-    FilmicDev filmic;             // RR_VIEW_FILMIC LUTs (rr_set_ocio_config / RR_OCIO_DIR)
+    FilmicDev filmic;             // the Filmic family's LUTs (rr_set_ocio_config / RR_OCIO_DIR)
     // rr_last_warning = the context's warning (a broken RR_OCIO_DIR, kept for
     // the context's lifetime) + the last completed frame's
     std::string ctx_warning, frame_warning, warning;
@@ -292,19 +296,67 @@ int frame_hier(const FrameSetup& fs, int n_tris) {
     return frame_uses_tiles(make_consts(fs, n_tris), (fs.flags & RR_FLAG_WAVEFRONT) != 0) ? kHierLbvh : kHierQWide;
 }
 
-// The view transform a frame on ctx is rendered with: Filmic needs the
-// context's LUTs, without them Standard. Returns what of the scene's view
-// settings the frame does not apply ("" if nothing): that fallback, and the
-// scene's own notes (FrameSetup::view_note: an unsupported view transform,
-// look or display gamma).
+// The view transform, look and display gamma a frame on ctx is rendered with
+// (fs.view_transform, fs.look, fs.gamma). The context's look and gamma come
+// before the scene's. The Filmic family needs the context's LUTs, without them
+// Standard; False Color its cube, without it Standard; a look the Filmic view
+// and its curve, without either no look. Returns what of the view settings
+// the frame does not apply ("" if nothing): those fallbacks, and the scene's
+// own notes (FrameSetup::view_note: a view transform or look nobody knows).
 std::string resolve_view(const rr_ctx* c, FrameSetup& fs) {
     std::string w = fs.view_note;
-    if (fs.view_transform == VIEW_FILMIC && !(c && c->filmic.ready)) {
+    auto note = [&](const std::string& m) { w += (w.empty() ? "" : "; ") + m; };
+    if (c && c->look >= 0) fs.look = c->look;
+    if (c && c->gamma != 0.f) fs.gamma = c->gamma;
+    const int asked = fs.view_transform;
+    if (asked >= VIEW_FILMIC && !(c && c->filmic.ready)) {
         fs.view_transform = VIEW_STANDARD;
-        w = "scene view transform Filmic rendered as Standard: no OCIO LUTs configured "
+        w = std::string("scene view transform ") + view_name(asked) +
+            " rendered as Standard: no OCIO LUTs configured "
             "(rr_set_ocio_config / RR_OCIO_DIR)" + (w.empty() ? "" : "; " + w);
+    } else if (asked == VIEW_FALSE_COLOR && !c->filmic.has_false_color()) {
+        fs.view_transform = VIEW_STANDARD;
+        note(std::string("view transform False Color rendered as Standard: no ") + kFalseColorFile + " under " +
+             c->filmic.dir + " (or its luts/)");
+    }
+    if (fs.look != 0) {
+        const LookDef& l = kLooks[fs.look];
+        if (fs.view_transform != VIEW_FILMIC) {
+            note(std::string("look '") + l.name + "' ignored: the frame's view is " + view_name(fs.view_transform) +
+                 ", looks belong to Filmic");
+            fs.look = 0;
+        } else if (!c->filmic.has_look(fs.look)) {
+            note(std::string("look '") + l.name + "' ignored: no " + l.file + " under " + c->filmic.dir +
+                 " (or its luts/)");
+            fs.look = 0;
+        }
     }
     return w;
+}
+
+// The view settings as kernel arguments, for a view, look and gamma that
+// resolve_view (or an inspection call's own check) has passed.
+FilmicArgs view_args(const rr_ctx* c, int view, int look, float gamma) {
+    FilmicArgs a = view >= VIEW_FILMIC ? c->filmic.args(view == VIEW_FILMIC ? look : 0) : FilmicArgs{};
+    a.inv_gamma = inv_gamma_of(gamma);
+    return a;
+}
+
+// The view settings of an inspection call on c with a view of the caller's:
+// the context's look (with the Filmic view) and display gamma, None and 1
+// where the context leaves them to a scene. Nothing is substituted here: a
+// view or look whose LUT is not loaded is RR_EINVAL.
+int debug_view_settings(const rr_ctx* c, int view, int& look, float& gamma) {
+    if (view < VIEW_STANDARD || view > VIEW_FALSE_COLOR) return fail(RR_EINVAL, "unsupported view transform");
+    if (view >= VIEW_FILMIC && !c->filmic.ready)
+        return fail(RR_EINVAL, "Filmic view transform without LUTs (rr_set_ocio_config / RR_OCIO_DIR)");
+    if (view == VIEW_FALSE_COLOR && !c->filmic.has_false_color())
+        return fail(RR_EINVAL, std::string("False Color view transform without ") + kFalseColorFile);
+    look = (view == VIEW_FILMIC && c->look > 0) ? c->look : 0;
+    if (look && !c->filmic.has_look(look))
+        return fail(RR_EINVAL, std::string("look '") + kLooks[look].name + "' without " + kLooks[look].file);
+    gamma = c->gamma != 0.f ? c->gamma : 1.f;
+    return RR_OK;
 }
 
 // Works on stream st with frame state f and builds into d, a set of products
@@ -535,12 +587,14 @@ auto launch_png8(const uint8_t* d_rgba, int C) {
         png_encode_device(d_rgba, C, p, scratch, out, tab, st);
     };
 }
-// view_transform is the resolved one (Filmic only with the context's LUTs).
-auto launch_png16(rr_ctx* c, const float4* d_film, float inv_spp, float exposure_scale, int view_transform, int C) {
-    if (view_transform == VIEW_FILMIC && !c->filmic.ready) throw std::runtime_error("Filmic view transform without LUTs");
+// view_transform, look and gamma are the resolved ones (the Filmic family and
+// a look only with the context's LUTs for them).
+auto launch_png16(rr_ctx* c, const float4* d_film, float inv_spp, float exposure_scale, int view_transform, int look,
+                  float gamma, int C) {
+    if (view_transform >= VIEW_FILMIC && !c->filmic.ready) throw std::runtime_error("Filmic view transform without LUTs");
     ensure_srgb16(c);
     const Png16Front f{d_film, inv_spp, exposure_scale, view_transform, c->srgb16_lut.ptr,
-                       view_transform == VIEW_FILMIC ? c->filmic.args() : FilmicArgs{}};
+                       view_args(c, view_transform, look, gamma)};
     return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
         png16_encode_device(f, C, p, scratch, out, tab, st);
     };
@@ -657,9 +711,11 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     k.div_spp = FastDiv::make((uint32_t)k.spp_chunk);
     render_frame_device(s->mesh, build, c->paths, f, k, r.chunks, opts, st);
     r.tile_slices = f.tile_slices;
-    if (fs.view_transform == VIEW_FILMIC) {  // film -> Filmic -> rgba8 (overwrites the kernels' tonemap)
+    // the Filmic family, or a display gamma: film -> view settings -> rgba8 (overwrites the kernels' tonemap)
+    if (view_needs_pass(fs.view_transform, fs.gamma)) {
         f.prof.begin(st, RR_K_ACCUM);
-        view_filmic_device(c->filmic, k, f.film.ptr, reinterpret_cast<uchar4*>(f.rgba8.ptr), st);
+        view_device(view_args(c, fs.view_transform, fs.look, fs.gamma), k, c->paths.srgb_lut.ptr, f.film.ptr,
+                    reinterpret_cast<uchar4*>(f.rgba8.ptr), st);
         f.prof.end(st);
     }
     RR_HIP(hipEventRecord(sl.ev[4], st));
@@ -683,7 +739,8 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
             enqueue_deflate(sl, f, st, plan, launch_png8(f.rgba8.ptr, sl.color_mode));
         else if (sl.coder == Coder::Png16)  // the film again, through exposure and view transform, at 16 bits
             enqueue_deflate(sl, f, st, plan,
-                            launch_png16(c, film, k.inv_spp, k.exposure_scale, fs.view_transform, sl.color_mode));
+                            launch_png16(c, film, k.inv_spp, k.exposure_scale, fs.view_transform, fs.look, fs.gamma,
+                                         sl.color_mode));
         else  // the film's means: the product finish_frame forms, no view transform
             enqueue_deflate(sl, f, st, plan,
                             launch_exr(film, 1.0f / (float)fs.spp, true, sl.coder == Coder::Exr32, sl.color_mode));
@@ -965,6 +1022,19 @@ int rr_create(int device_ordinal, rr_ctx** out) {
             else if (v == "RGBA") color_mode = RR_COLOR_RGBA;
             else if (!v.empty()) return fail(RR_EINVAL, "RR_COLOR_MODE must be BW, RGB or RGBA, got '" + v + "'");
         }
+        int look = -1;
+        if (const char* d = getenv("RR_LOOK")) {  // as rr_set_look
+            look = *d ? look_id(d) : -1;
+            if (*d && look < 0) return fail(RR_EINVAL, std::string("RR_LOOK: unknown look '") + d + "'");
+        }
+        float gamma = 0.f;
+        if (const char* d = getenv("RR_DISPLAY_GAMMA")) {  // as rr_set_display_gamma
+            char* end = nullptr;
+            const double v = *d ? std::strtod(d, &end) : 0.0;
+            if (*d && (end == d || *end || !(v >= 0.0) || v > (double)kGammaMax))
+                return fail(RR_EINVAL, std::string("RR_DISPLAY_GAMMA must be 0 or in (0, 5], got '") + d + "'");
+            gamma = (float)v;
+        }
         std::unique_ptr<rr_ctx> c(new rr_ctx());
         c->device = device_ordinal;
         set_device(c.get());
@@ -989,6 +1059,8 @@ int rr_create(int device_ordinal, rr_ctx** out) {
         c->png_depth = png_depth;
         c->exr_depth = exr_depth;
         c->color_mode = color_mode;
+        c->look = look;
+        c->gamma = gamma;
         *out = c.release();
         return RR_OK;
     });
@@ -1312,15 +1384,87 @@ int rr_set_png_depth(rr_ctx* c, int32_t depth) {
 int rr_debug_png16_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int32_t view_transform,
                           float exposure_scale, uint8_t* out, uint64_t cap, uint64_t* len) {
     if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    if (view_transform != VIEW_STANDARD && view_transform != VIEW_RAW && view_transform != VIEW_FILMIC)
-        return fail(RR_EINVAL, "unsupported view transform");
-    if (view_transform == VIEW_FILMIC && !c->filmic.ready)
-        return fail(RR_EINVAL, "Filmic view transform without LUTs (rr_set_ocio_config / RR_OCIO_DIR)");
+    int look = 0;
+    float gamma = 1.f;
+    if (const int rc = debug_view_settings(c, view_transform, look, gamma)) return rc;
     return debug_deflate_device(c, Coder::Png16, 4, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
                                 [&](const void* img) {
                                     return launch_png16(c, static_cast<const float4*>(img), 1.0f, exposure_scale,
-                                                        view_transform, 4);
+                                                        view_transform, look, gamma, 4);
                                 });
+}
+
+int rr_set_look(rr_ctx* c, const char* name) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    const int id = (name && *name) ? look_id(name) : -1;
+    if (name && *name && id < 0) return fail(RR_EINVAL, std::string("unknown look '") + name + "'");
+    c->look = id;  // read when a frame is submitted; frames in flight keep theirs
+    return RR_OK;
+}
+
+int rr_set_display_gamma(rr_ctx* c, float gamma) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    if (!(gamma >= 0.f) || gamma > kGammaMax)
+        return fail(RR_EINVAL, "display gamma must be 0 (the scene's) or above 0 and at most 5");
+    c->gamma = gamma;  // read when a frame is submitted; frames in flight keep theirs
+    return RR_OK;
+}
+
+int rr_debug_view_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int32_t view_transform,
+                         float exposure_scale, uint8_t* rgba8_out) {
+    if (!c || !rgba || !rgba8_out || w <= 0 || h <= 0 || (int64_t)w * h > (int64_t)1 << 28)
+        return fail(RR_EINVAL, "bad arguments");
+    int look = 0;
+    float gamma = 1.f;
+    if (const int rc = debug_view_settings(c, view_transform, look, gamma)) return rc;
+    return guarded([&] {
+        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
+        set_device(c);
+        const size_t npix = (size_t)w * h;
+        if (!c->srgb_uploaded) {  // the 8-bit path's table (prepare_frame uploads it with a frame)
+            quiesce(c);
+            std::vector<float> lut(kSrgbLutSize + 1);
+            build_srgb_lut(lut.data());
+            c->paths.srgb_lut.ensure(lut.size());
+            RR_HIP(hipMemcpy(c->paths.srgb_lut.ptr, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
+            c->srgb_uploaded = true;
+        }
+        DevBuf<float4> img;
+        DevBuf<uchar4> q;
+        img.ensure(npix);
+        q.ensure(npix);
+        RR_HIP(hipMemcpy(img.ptr, rgba, npix * sizeof(float4), hipMemcpyHostToDevice));
+        FrameConsts k{};
+        k.W = w;
+        k.H = h;
+        k.npix = (int)npix;
+        k.inv_spp = 1.0f;
+        k.exposure_scale = exposure_scale;
+        k.view_transform = view_transform;
+        view_device(view_args(c, view_transform, look, gamma), k, c->paths.srgb_lut.ptr, img.ptr, q.ptr, c->stream);
+        RR_HIP(hipStreamSynchronize(c->stream));
+        RR_HIP(hipMemcpy(rgba8_out, q.ptr, npix * 4, hipMemcpyDeviceToHost));
+        img.release();
+        q.release();
+        return RR_OK;
+    });
+}
+
+int rr_debug_display_gamma(const float* in, uint64_t n, float gamma, float* out) {
+    if ((!in || !out) && n) return fail(RR_EINVAL, "NULL array");
+    if (!(gamma > 0.f) || gamma > kGammaMax) return fail(RR_EINVAL, "display gamma must be above 0 and at most 5");
+    display_gamma_host(in, (size_t)n, gamma, out);
+    return RR_OK;
+}
+
+int rr_debug_scene_view(rr_scene* s, int32_t* view_transform, char* look, int32_t cap, float* gamma) {
+    if (!s) return fail(RR_EINVAL, "scene is NULL");
+    const RenderDesc& r = s->desc.render;
+    if (view_transform) *view_transform = r.view_transform;
+    const char* name = kLooks[r.look].name;
+    if (look && cap > (int32_t)std::strlen(name)) std::strcpy(look, name);
+    if (gamma) *gamma = (float)r.gamma;
+    return RR_OK;
 }
 
 int rr_set_color_mode(rr_ctx* c, int32_t mode) {
@@ -1360,12 +1504,12 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
     if (!image_is_float) return fail(RR_EINVAL, "16-bit PNG and OPEN_EXR take a float RGBA image");
     const size_t bytes = (size_t)w * h * sizeof(float4);
     if (fmt == "PNG" && depth == 16) {
-        if (view_transform != VIEW_STANDARD && view_transform != VIEW_RAW && view_transform != VIEW_FILMIC)
-            return fail(RR_EINVAL, "unsupported view transform");
-        if (view_transform == VIEW_FILMIC && !c->filmic.ready)
-            return fail(RR_EINVAL, "Filmic view transform without LUTs (rr_set_ocio_config / RR_OCIO_DIR)");
+        int look = 0;
+        float gamma = 1.f;
+        if (const int rc = debug_view_settings(c, view_transform, look, gamma)) return rc;
         return debug_deflate_device(c, Coder::Png16, C, w, h, image, bytes, out, cap, len, [&](const void* img) {
-            return launch_png16(c, static_cast<const float4*>(img), 1.0f, exposure_scale, view_transform, C);
+            return launch_png16(c, static_cast<const float4*>(img), 1.0f, exposure_scale, view_transform, look, gamma,
+                                C);
         });
     }
     if (fmt == "OPEN_EXR" && (depth == 0 || depth == 16 || depth == 32)) {

@@ -11,6 +11,7 @@
 #include <stdexcept>
 
 #include "json.hpp"
+#include "view.hpp"
 
 namespace rr {
 
@@ -667,25 +668,33 @@ SceneDesc load_scene(const std::string& path) {
         else if (r.has("color_mode"))
             throw std::runtime_error("render.color_mode must be \"BW\", \"RGB\" or \"RGBA\", got '" + color_mode + "'");
         d.view_transform_name = r.get_str("view_transform", "Standard");
-        // "Filmic" is applied through Blender's OCIO LUTs when the context has
-        // them (rr_set_ocio_config); otherwise the frame falls back to Standard
-        // and says so (rr_frame_stats.view_transform_substituted). Any other
-        // Blender 3.6 view ("Filmic Log", "False Color", "Standard" looks, ...)
-        // renders as Standard with the same flag and a warning naming it, as
-        // does a look or a display gamma the renderer does not apply: the job
-        // still renders, and the substitution is never silent.
+        // The Filmic family ("Filmic" with its looks, "Filmic Log", "False
+        // Color") is applied through Blender's OCIO LUTs when the context has
+        // them (rr_set_ocio_config); otherwise the frame falls back and says
+        // so (rr_frame_stats.view_transform_substituted; rr_api.cpp
+        // resolve_view). Any other view renders as Standard with the same flag
+        // and a warning naming it, and a look this renderer does not know is
+        // ignored the same way: the job still renders, and the substitution is
+        // never silent. The display gamma is applied to every view.
         if (d.view_transform_name == "Standard") d.view_transform = VIEW_STANDARD;
         else if (d.view_transform_name == "Raw") d.view_transform = VIEW_RAW;
         else if (d.view_transform_name == "Filmic") d.view_transform = VIEW_FILMIC;
+        else if (d.view_transform_name == "Filmic Log") d.view_transform = VIEW_FILMIC_LOG;
+        else if (d.view_transform_name == "False Color") d.view_transform = VIEW_FALSE_COLOR;
         else {
             d.view_transform = VIEW_STANDARD;
             d.view_note = "view transform '" + d.view_transform_name + "' is not supported, rendered as Standard";
         }
         const std::string look = r.get_str("look", "None");
         auto note = [&](const std::string& m) { d.view_note += (d.view_note.empty() ? "" : "; ") + m; };
-        if (look != "None" && !look.empty()) note("look '" + look + "' ignored");
-        const double gamma = r.get_num("gamma", 1.0);
-        if (gamma != 1.0) note("display gamma " + std::to_string(gamma) + " ignored");
+        d.look = look.empty() ? 0 : look_id(look);
+        if (d.look < 0) {
+            d.look = 0;
+            note("look '" + look + "' is not supported, ignored");
+        }
+        d.gamma = r.get_num("gamma", 1.0);
+        if (!(d.gamma > 0.0) || d.gamma > (double)kGammaMax)
+            throw std::runtime_error("render.gamma must be above 0 and at most 5, got " + std::to_string(d.gamma));
     }
     if (s.render.resx <= 0 || s.render.resy <= 0 || s.render.percent <= 0)
         throw std::runtime_error("invalid resolution");
@@ -914,8 +923,12 @@ FrameSetup setup_frame(const SceneDesc& s, int frame, const rr_render_params* p)
     f.clamp_indirect = (float)(p->clamp_indirect >= 0.f ? p->clamp_indirect : r.clamp_indirect);
     f.seed = p->use_scene_seed ? r.seed : p->seed;
     f.view_transform = p->view_transform >= 0 ? p->view_transform : r.view_transform;
-    if (p->view_transform < 0) f.view_note = r.view_note;
-    if (f.view_transform != VIEW_STANDARD && f.view_transform != VIEW_RAW && f.view_transform != VIEW_FILMIC)
+    if (p->view_transform < 0) {
+        f.view_note = r.view_note;
+        f.look = r.look;
+        f.gamma = (float)r.gamma;
+    }
+    if (f.view_transform < VIEW_STANDARD || f.view_transform > VIEW_FALSE_COLOR)
         throw std::runtime_error("unsupported view transform");
     f.spp_per_chunk = p->spp_per_chunk > 0 ? p->spp_per_chunk : r.spp_per_chunk;
     f.flags = p->flags;

@@ -21,7 +21,7 @@ enum ObjType { OBJ_EMPTY = 0, OBJ_MESH = 1, OBJ_CAMERA = 2, OBJ_LIGHT = 3 };
 enum LightType { LIGHT_POINT = 0, LIGHT_SUN = 1 };
 enum Ipo { IPO_CONSTANT = 0, IPO_LINEAR = 1, IPO_BEZIER = 2 };
 enum SensorFit { FIT_AUTO = 0, FIT_HORIZONTAL = 1, FIT_VERTICAL = 2 };
-enum ViewTransform { VIEW_STANDARD = 0, VIEW_RAW = 1, VIEW_FILMIC = 2 };
+enum ViewTransform { VIEW_STANDARD = 0, VIEW_RAW = 1, VIEW_FILMIC = 2, VIEW_FILMIC_LOG = 3, VIEW_FALSE_COLOR = 4 };
 
 // Blender stores BezTriple coordinates as float; evaluation happens in float
 // (with double inside the cubic solver), see eval_fcurve().
@@ -115,10 +115,13 @@ struct RenderDesc {
     int color_mode = 0;   // RR_COLOR_BW / RGB / RGBA, 0: no field (rr_set_color_mode 0 takes it)
     int view_transform = VIEW_STANDARD;
     std::string view_transform_name = "Standard";
-    // What of the scene's colour management a frame does not apply, for the
-    // frame's warning ("" when all of it is applied): a view transform other
-    // than Standard / Raw / Filmic (rendered as Standard), a look other than
-    // None, a display gamma other than 1 (both ignored).
+    int look = 0;        // view.hpp kLooks id of render.look (0 None; rr_set_look NULL takes it)
+    double gamma = 1.0;  // render.gamma, in (0, 5] (rr_set_display_gamma 0 takes it)
+    // What of the scene's colour management no frame can apply, for the
+    // frame's warning ("" when there is nothing): a view transform this
+    // renderer does not know (rendered as Standard), a look it does not know
+    // (ignored). What a context cannot apply for want of a LUT is noted when
+    // the frame is submitted (rr_api.cpp resolve_view).
     std::string view_note;
     uint32_t seed = 0;
     int spp_per_chunk = 0;
@@ -145,6 +148,10 @@ struct FrameSetup {
     int32_t W = 0, H = 0, spp = 0, max_bounces = 0, view_transform = 0, spp_per_chunk = 0, flags = 0;
     int32_t max_diffuse = 4, max_glossy = 4;
     std::string view_note;  // RenderDesc::view_note when the view comes from the scene
+    // the scene's look and display gamma when the view comes from the scene, else
+    // None and 1; resolved against the context's settings and LUTs by resolve_view
+    int32_t look = 0;
+    float gamma = 1.f;
     uint32_t seed = 0;
     float clamp_indirect = 0.f, filter_width = 1.5f, exposure_scale = 1.f;
     float cam[RR_CAM_FLOATS] = {};

@@ -1,12 +1,14 @@
-// Filmic view transform: OCIO LUT parsing (host) and the per-pixel chain
-// (device). See view.hpp for the chain and where it comes from. The float
-// operations are written in the order oracle/rr_oracle.c orc_filmic uses, so
-// the 8-bit output is bit-identical to the oracle's (tests/test_gpu_view.py).
+// View settings: OCIO LUT parsing (host) and the per-pixel second pass over
+// the film (device). See view.hpp for the chain and where it comes from. The
+// float operations of the base chain are written in the order
+// oracle/rr_oracle.c orc_filmic uses, so its 8-bit output is bit-identical to
+// the oracle's (tests/test_gpu_view.py).
 #pragma clang fp contract(off)
 
 #include "view.hpp"
 #include "view_filmic.h"
 
+#include <cstring>
 #include <fstream>
 #include <sstream>
 
@@ -14,18 +16,42 @@ namespace rr {
 
 namespace {
 
-__global__ __launch_bounds__(256) void k_view_filmic(FrameConsts fc, FilmicArgs f, const float4* __restrict__ film,
-                                                     uchar4* __restrict__ out) {
+// 8-bit sRGB table intervals of the render kernels' tonemap (paths.hpp kSrgbN)
+constexpr int kViewSrgbN = 4096;
+
+// The view pass: VIEW and GAMMA are compile-time, so Filmic at gamma 1 keeps
+// the instructions it had before there were other settings. Standard and Raw
+// (here for their display gamma) repeat paths.hpp tonemap up to the quantiser.
+template <int VIEW, bool GAMMA>
+__global__ __launch_bounds__(256) void k_view(FrameConsts fc, FilmicArgs f, const float* __restrict__ srgb,
+                                              const float4* __restrict__ film, uchar4* __restrict__ out) {
     for (int pix = blockIdx.x * 256 + threadIdx.x; pix < fc.npix; pix += gridDim.x * 256) {
         const float4 acc = film[pix];
         const float c[3] = {acc.x * fc.inv_spp * fc.exposure_scale, acc.y * fc.inv_spp * fc.exposure_scale,
                             acc.z * fc.inv_spp * fc.exposure_scale};
         float d[3];
-        filmic_display(f, c, d);
+        if constexpr (VIEW >= RR_VIEW_FILMIC) {
+            filmic_display(f, VIEW, c, d);
+        } else {
+            for (int k = 0; k < 3; ++k) {
+                float v = fminf(fmaxf(c[k], 0.0f), 1.0f);
+                if (VIEW == RR_VIEW_STANDARD) v = srgb_oetf(v, srgb, kViewSrgbN);
+                d[k] = v;
+            }
+        }
+        if constexpr (GAMMA)
+            for (int k = 0; k < 3; ++k) d[k] = display_gamma(d[k], f.inv_gamma);
         uint8_t q[3];
         for (int k = 0; k < 3; ++k) q[k] = quantize8(d[k]);
         out[pix] = make_uchar4(q[0], q[1], q[2], 255);
     }
+}
+
+template <int VIEW>
+void launch_view(bool gamma, int grid, hipStream_t st, const FrameConsts& fc, const FilmicArgs& a, const float* srgb,
+                 const float4* film, uchar4* out) {
+    if (gamma) k_view<VIEW, true><<<grid, 256, 0, st>>>(fc, a, srgb, film, out);
+    else k_view<VIEW, false><<<grid, 256, 0, st>>>(fc, a, srgb, film, out);
 }
 
 bool read_lines(const std::string& path, std::vector<std::string>& lines, std::string& err) {
@@ -46,7 +72,7 @@ bool read_lines(const std::string& path, std::vector<std::string>& lines, std::s
 
 // OCIO's .spi3d (Sony Pictures Imageworks): "SPILUT 1.0", "3 3", "N N N",
 // then one line "i j k r g b" per cube entry (i indexes red).
-bool parse_spi3d(const std::string& path, FilmicLuts& out, std::string& err) {
+bool parse_spi3d(const std::string& path, int& n3, std::vector<float>& cube, std::string& err) {
     std::vector<std::string> L;
     if (!read_lines(path, L, err)) return false;
     if (L.size() < 3 || L[0].rfind("SPILUT", 0) != 0) {
@@ -62,8 +88,8 @@ bool parse_spi3d(const std::string& path, FilmicLuts& out, std::string& err) {
         }
     }
     const int n = na;
-    out.n3 = n;
-    out.cube.assign((size_t)n * n * n * 3, 0.f);
+    n3 = n;
+    cube.assign((size_t)n * n * n * 3, 0.f);
     std::vector<char> seen((size_t)n * n * n, 0);
     size_t count = 0;
     for (size_t li = 3; li < L.size(); ++li) {
@@ -78,9 +104,9 @@ bool parse_spi3d(const std::string& path, FilmicLuts& out, std::string& err) {
         const size_t e = ((size_t)i * n + j) * n + k;
         if (!seen[e]) ++count;
         seen[e] = 1;
-        out.cube[3 * e] = (float)r;
-        out.cube[3 * e + 1] = (float)g;
-        out.cube[3 * e + 2] = (float)b;
+        cube[3 * e] = (float)r;
+        cube[3 * e + 1] = (float)g;
+        cube[3 * e + 2] = (float)b;
     }
     if (count != (size_t)n * n * n) {
         err = path + ": " + std::to_string(count) + " of " + std::to_string((size_t)n * n * n) + " cube entries";
@@ -91,7 +117,7 @@ bool parse_spi3d(const std::string& path, FilmicLuts& out, std::string& err) {
 
 // OCIO's .spi1d: "Version 1", "From lo hi", "Length N", "Components C",
 // "{", N lines of C values, "}".
-bool parse_spi1d(const std::string& path, FilmicLuts& out, std::string& err) {
+bool parse_spi1d(const std::string& path, Curve1& out, std::string& err) {
     std::vector<std::string> L;
     if (!read_lines(path, L, err)) return false;
     int n = -1, comps = -1;
@@ -123,77 +149,158 @@ bool parse_spi1d(const std::string& path, FilmicLuts& out, std::string& err) {
         err = path + ": bad Length/Components";
         return false;
     }
-    out.n1 = n;
+    out.n = n;
     out.comps = comps;
-    out.lo1 = (float)lo;
-    out.hi1 = (float)hi;
-    out.lut1.clear();
+    out.lo = (float)lo;
+    out.hi = (float)hi;
+    out.v.clear();
     for (; li < L.size(); ++li) {
         std::istringstream s(L[li]);
         std::string tok;
         while (s >> tok) {
             if (tok == "}") goto done;
-            out.lut1.push_back((float)std::stod(tok));
+            out.v.push_back((float)std::stod(tok));
         }
     }
 done:
-    if (out.lut1.size() != (size_t)n * comps) {
-        err = path + ": " + std::to_string(out.lut1.size()) + " values, expected " + std::to_string((size_t)n * comps);
+    if (out.v.size() != (size_t)n * comps) {
+        err = path + ": " + std::to_string(out.v.size()) + " values, expected " + std::to_string((size_t)n * comps);
         return false;
     }
     return true;
 }
 
+namespace {
+
+// dir/luts/name or dir/name, "" if neither is there
+std::string find_lut(const std::string& dir, const char* name) {
+    for (const std::string& sub : {std::string("/luts/"), std::string("/")}) {
+        const std::string p = dir + sub + name;
+        if (std::ifstream(p)) return p;
+    }
+    return "";
+}
+
+}  // namespace
+
 bool load_filmic_luts(const std::string& dir, FilmicLuts& out, std::string& err) {
     const char* names[2] = {"filmic_desat65cube.spi3d", "filmic_to_0-70_1-03.spi1d"};
     std::string paths[2];
     for (int k = 0; k < 2; ++k) {
-        for (const std::string& sub : {std::string("/luts/"), std::string("/")}) {
-            const std::string p = dir + sub + names[k];
-            if (std::ifstream(p)) {
-                paths[k] = p;
-                break;
-            }
-        }
+        paths[k] = find_lut(dir, names[k]);
         if (paths[k].empty()) {
             err = std::string("no ") + names[k] + " under " + dir + " (or its luts/)";
             return false;
         }
     }
-    return parse_spi3d(paths[0], out, err) && parse_spi1d(paths[1], out, err);
+    if (!parse_spi3d(paths[0], out.n3, out.cube, err) || !parse_spi1d(paths[1], out.base, err)) return false;
+    // optional: a look's curve, the false-colour cube
+    for (int id = 0; id < kNumLooks; ++id) {
+        out.look[id] = Curve1{};
+        if (!kLooks[id].file) continue;
+        const std::string p = find_lut(dir, kLooks[id].file);
+        if (!p.empty() && !parse_spi1d(p, out.look[id], err)) return false;
+    }
+    out.nf = 0;
+    out.fcube.clear();
+    const std::string p = find_lut(dir, kFalseColorFile);
+    if (!p.empty() && !parse_spi3d(p, out.nf, out.fcube, err)) return false;
+    return true;
+}
+
+int look_id(const std::string& name) {
+    const std::string prefix = "Filmic - ";
+    const std::string n = name.rfind(prefix, 0) == 0 ? name.substr(prefix.size()) : name;
+    for (int id = 0; id < kNumLooks; ++id)
+        if (n == kLooks[id].name) return id;
+    return -1;
+}
+
+const char* view_name(int view_transform) {
+    switch (view_transform) {
+    case RR_VIEW_STANDARD: return "Standard";
+    case RR_VIEW_RAW: return "Raw";
+    case RR_VIEW_FILMIC: return "Filmic";
+    case RR_VIEW_FILMIC_LOG: return "Filmic Log";
+    case RR_VIEW_FALSE_COLOR: return "False Color";
+    default: return "?";
+    }
+}
+
+namespace {
+
+void upload_cube(const std::vector<float>& src, int n, DevBuf<float4>& dst) {
+    const size_t nc = (size_t)n * n * n;
+    if (nc == 0) return;
+    std::vector<float4> c(nc);
+    for (size_t i = 0; i < nc; ++i) c[i] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], 0.f);
+    dst.ensure(nc);
+    RR_HIP(hipMemcpy(dst.ptr, c.data(), nc * sizeof(float4), hipMemcpyHostToDevice));
+}
+
+}  // namespace
+
+void Curve1Dev::upload(const Curve1& c) {
+    n = 0;  // an absent curve leaves none behind
+    if (c.n == 0) return;
+    v.ensure(c.v.size());
+    RR_HIP(hipMemcpy(v.ptr, c.v.data(), c.v.size() * sizeof(float), hipMemcpyHostToDevice));
+    n = c.n;
+    comps = c.comps;
+    lo = c.lo;
+    hi = c.hi;
 }
 
 void FilmicDev::upload(const FilmicLuts& l, const std::string& from) {
-    const size_t n3c = (size_t)l.n3 * l.n3 * l.n3;
-    std::vector<float4> c(n3c);
-    for (size_t i = 0; i < n3c; ++i) c[i] = make_float4(l.cube[3 * i], l.cube[3 * i + 1], l.cube[3 * i + 2], 0.f);
-    cube.ensure(n3c);
-    lut1.ensure(l.lut1.size());
-    RR_HIP(hipMemcpy(cube.ptr, c.data(), n3c * sizeof(float4), hipMemcpyHostToDevice));
-    RR_HIP(hipMemcpy(lut1.ptr, l.lut1.data(), l.lut1.size() * sizeof(float), hipMemcpyHostToDevice));
+    upload_cube(l.cube, l.n3, cube);
     n3 = l.n3;
-    n1 = l.n1;
-    comps = l.comps;
-    lo1 = l.lo1;
-    hi1 = l.hi1;
+    base.upload(l.base);
+    for (int id = 0; id < kNumLooks; ++id) look[id].upload(l.look[id]);
+    nf = 0;
+    upload_cube(l.fcube, l.nf, fcube);
+    nf = l.nf;
     dir = from;
     ready = true;
 }
 
 void FilmicDev::release() {
     cube.release();
-    lut1.release();
+    base.v.release();
+    base.n = 0;
+    for (auto& c : look) {
+        c.v.release();
+        c.n = 0;
+    }
+    fcube.release();
+    nf = 0;
     ready = false;
     dir.clear();
 }
 
-void view_filmic_device(const FilmicDev& f, const FrameConsts& fc, const float4* film, uchar4* out,
-                        hipStream_t st) {
-    if (!f.ready) throw std::runtime_error("Filmic view transform without LUTs");
-    const FilmicArgs a = f.args();
+void view_device(const FilmicArgs& a, const FrameConsts& fc, const float* srgb, const float4* film, uchar4* out,
+                 hipStream_t st) {
+    const int view = fc.view_transform;
+    if (view >= RR_VIEW_FILMIC && (!a.cube || (view == RR_VIEW_FILMIC && !a.lut1) ||
+                                   (view == RR_VIEW_FALSE_COLOR && !a.fcube)))
+        throw std::runtime_error(std::string(view_name(view)) + " view transform without its LUTs");
+    if (view == RR_VIEW_STANDARD && !srgb) throw std::runtime_error("Standard view transform without its table");
+    const bool gamma = a.inv_gamma != 0.0f;
     const int grid = std::max(1, std::min((fc.npix + 255) / 256, 4096));
-    k_view_filmic<<<grid, 256, 0, st>>>(fc, a, film, out);
+    switch (view) {
+    case RR_VIEW_STANDARD: launch_view<RR_VIEW_STANDARD>(gamma, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_RAW: launch_view<RR_VIEW_RAW>(gamma, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_FILMIC: launch_view<RR_VIEW_FILMIC>(gamma, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_FILMIC_LOG: launch_view<RR_VIEW_FILMIC_LOG>(gamma, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_FALSE_COLOR: launch_view<RR_VIEW_FALSE_COLOR>(gamma, grid, st, fc, a, srgb, film, out); break;
+    default: throw std::runtime_error("unsupported view transform");
+    }
     RR_HIP(hipGetLastError());
 }
 
+void display_gamma_host(const float* in, size_t n, float g, float* out) {
+    const float inv = 1.0f / g;
+    for (size_t i = 0; i < n; ++i) out[i] = display_gamma(in[i], inv);
+}
+
 }  // namespace rr
+

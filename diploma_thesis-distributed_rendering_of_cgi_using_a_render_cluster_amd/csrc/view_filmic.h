@@ -1,9 +1,11 @@
-// The Filmic chain per pixel (device): see view.hpp for the chain and where it
-// comes from. Shared by k_view_filmic (view.hip, 8-bit) and k_png16_front
-// (png16.hip, 16-bit): both quantise the float result of filmic_display. The
-// float operations are written in the order oracle/rr_oracle.c orc_filmic
-// uses, contraction off, so the 8-bit output is bit-identical to the oracle's
-// (tests/test_gpu_view.py).
+// The Filmic family's chain per pixel (device) and the display gamma (host and
+// device): see view.hpp for the chain and where it comes from. Shared by
+// k_view (view.hip, 8-bit) and Png16Sub (png16.hip, 16-bit): both quantise the
+// float result of filmic_display / display_gamma. The float operations of the
+// base chain are written in the order oracle/rr_oracle.c orc_filmic uses,
+// contraction off, so the 8-bit output is bit-identical to the oracle's
+// (tests/test_gpu_view.py); tests/view_settings.py restates every mode in
+// numpy float32 (tests/test_gpu_view_settings.py).
 #pragma once
 #pragma clang fp contract(off)
 
@@ -26,6 +28,30 @@ RR_HD float log2_fixed(float x) {
     const float t2 = t * t;
     const float p = ((((t2 * 0.111111112f + 0.142857149f) * t2 + 0.2f) * t2 + 0.333333343f) * t2 + 1.0f) * t;
     return (float)e + p * 2.88539004f;
+}
+
+// 2^x without libm, written like log2_fixed: x = n + f, n the nearest integer
+// (f in [-1/2, 1/2]), 2^f = e^u with u = f ln 2 by its series to u^7
+// (|u| < 0.347: truncation < 6e-9), 2^n added to the exponent field. 0 below
+// 2^-125, 2^127 from there up.
+RR_HD float exp2_fixed(float x) {
+    if (x < -125.0f) return 0.0f;
+    if (x >= 127.0f) return 1.70141183e38f;
+    const float h = x + 0.5f;
+    int n = (int)h;
+    if ((float)n > h) n = n - 1;
+    const float f = x - (float)n;
+    const float u = f * 0.693147182f;
+    const float p = ((((((u * 1.98412701e-4f + 1.38888892e-3f) * u + 8.33333377e-3f) * u + 4.16666679e-2f) * u +
+                       0.166666672f) * u + 0.5f) * u + 1.0f) * u + 1.0f;
+    return i2f(f2i(p) + n * 8388608);
+}
+
+// Display gamma g on a display-referred value d: d^(1/g), 0 for d <= 0
+// (inv_g = 1.0f / g; callers skip the step for g = 1).
+RR_HD float display_gamma(float d, float inv_g) {
+    if (d <= 0.0f) return 0.0f;
+    return exp2_fixed(log2_fixed(d) * inv_g);
 }
 
 RR_HD float sat(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
@@ -86,14 +112,39 @@ RR_D float3 lut3d_tetra(const float4* __restrict__ cube, int n, float r, float g
                        ((w0 * c000.z + w1 * c1.z) + w2 * c2.z) + w3 * c111.z);
 }
 
-// Scene-linear c (the film's mean times the exposure scale) -> display-referred
-// values, before quantisation.
-RR_D void filmic_display(const FilmicArgs& f, const float c[3], float d[3]) {
+// Scene-linear c (the film's mean times the exposure scale) -> Filmic Log: the
+// cube's output over its allocation [0, 0.66].
+RR_D void filmic_log(const FilmicArgs& f, const float c[3], float L[3]) {
     float a[3];
     for (int k = 0; k < 3; ++k) a[k] = (log2_fixed(fmaxf(c[k], 1.17549435e-38f)) + 12.473931188f) / 25.0f;
     const float3 b = lut3d_tetra(f.cube, f.n3, a[0], a[1], a[2]);
-    const float bb[3] = {b.x, b.y, b.z};
-    for (int k = 0; k < 3; ++k) d[k] = lut1d(f.lut1, f.n1, f.comps, f.comps == 3 ? k : 0, f.lo1, f.hi1, bb[k] / 0.66f);
+    L[0] = b.x / 0.66f;
+    L[1] = b.y / 0.66f;
+    L[2] = b.z / 0.66f;
+}
+
+// Scene-linear c -> display-referred values of a view of the Filmic family,
+// before display gamma and quantisation.
+//   RR_VIEW_FILMIC:      the 1D curve of f (the base curve, or the look's in
+//                        its place) of Filmic Log
+//   RR_VIEW_FILMIC_LOG:  Filmic Log itself
+//   RR_VIEW_FALSE_COLOR: the false-colour cube at Filmic Log's luminance
+RR_D void filmic_display(const FilmicArgs& f, int view, const float c[3], float d[3]) {
+    float L[3];
+    filmic_log(f, c, L);
+    if (view == RR_VIEW_FILMIC_LOG) {
+        for (int k = 0; k < 3; ++k) d[k] = L[k];
+    } else if (view == RR_VIEW_FALSE_COLOR) {
+        const float pr = 0.2126729f * L[0], pg = 0.7151521f * L[1], pb = 0.0721750f * L[2];
+        const float s = pr + pg;
+        const float y = s + pb;
+        const float3 v = lut3d_tetra(f.fcube, f.nf, y, y, y);
+        d[0] = v.x;
+        d[1] = v.y;
+        d[2] = v.z;
+    } else {
+        for (int k = 0; k < 3; ++k) d[k] = lut1d(f.lut1, f.n1, f.comps, f.comps == 3 ? k : 0, f.lo1, f.hi1, L[k]);
+    }
 }
 
 }  // namespace rr

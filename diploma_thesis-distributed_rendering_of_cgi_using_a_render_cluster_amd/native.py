@@ -21,6 +21,10 @@ RR_OK, RR_ENOENT, RR_EIO, RR_ENOMEM, RR_ENODEV, RR_EINVAL, RR_ENOTSUP = 0, -2, -
 RR_EBUSY = -16
 RR_MAX_FRAMES_IN_FLIGHT = 3
 RR_VIEW_SCENE, RR_VIEW_STANDARD, RR_VIEW_RAW, RR_VIEW_FILMIC = -1, 0, 1, 2
+RR_VIEW_FILMIC_LOG, RR_VIEW_FALSE_COLOR = 3, 4
+# rr_set_look's names (include/rr.h), each also with Blender's "Filmic - " prefix
+LOOKS = ["None", "Very High Contrast", "High Contrast", "Medium High Contrast", "Medium Contrast",
+         "Medium Low Contrast", "Low Contrast", "Very Low Contrast"]
 RR_ABI_VERSION = 8
 QWIDTH = 6  # children per quantised node of the split path (rr_device.h kQWidth)
 RR_CAM_FLOATS, RR_LIGHT_FLOATS, RR_MAT_FLOATS, RR_RENDER_INTS, RR_RENDER_FLOATS = 16, 12, 12, 10, 4
@@ -91,6 +95,7 @@ EXPORTS = [
     "rr_set_png_depth", "rr_debug_png16_device", "rr_debug_srgb16_table",
     "rr_set_exr_depth", "rr_debug_exr32_device",
     "rr_set_color_mode", "rr_encode_image_mode", "rr_debug_encode_device",
+    "rr_set_look", "rr_set_display_gamma", "rr_debug_view_device", "rr_debug_display_gamma", "rr_debug_scene_view",
 ]
 
 # rr_set_color_mode's values (include/rr.h): the channels the file holds.
@@ -174,6 +179,11 @@ def lib() -> ctypes.CDLL:
         "rr_debug_encode_device": (c_int, [P, ctypes.c_char_p, i32, i32, ctypes.c_void_p, i32, i32, i32, i32,
                                            ctypes.c_float, i32, u8p, ctypes.c_uint64,
                                            ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_set_look": (c_int, [P, ctypes.c_char_p]),
+        "rr_set_display_gamma": (c_int, [P, ctypes.c_float]),
+        "rr_debug_view_device": (c_int, [P, f32p, i32, i32, i32, ctypes.c_float, u8p]),
+        "rr_debug_display_gamma": (c_int, [f32p, ctypes.c_uint64, ctypes.c_float, f32p]),
+        "rr_debug_scene_view": (c_int, [P, i32p, ctypes.c_char_p, i32, f32p]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -286,6 +296,14 @@ class Scene:
         return FrameState(np.zeros((0, 3, 3), np.float32), tm[:c["triangles"]], cam, lights[:nl], mats[:nm],
                           world, ri, rf)
 
+    def view_settings(self) -> tuple[int, str, float]:
+        """rr_debug_scene_view: the view transform (RR_VIEW_*), look name (no
+        prefix) and display gamma the scene file asks for (host only)."""
+        v, g = ctypes.c_int32(), ctypes.c_float()
+        look = ctypes.create_string_buffer(64)
+        _check(lib().rr_debug_scene_view(self.handle, ctypes.byref(v), look, 64, ctypes.byref(g)))
+        return v.value, look.value.decode(), g.value
+
     def object_matrix(self, obj: int, frame: float) -> np.ndarray:
         m = (ctypes.c_double * 16)()
         _check(lib().rr_debug_object_matrix(self.handle, obj, float(frame), m))
@@ -295,10 +313,13 @@ class Scene:
 class RenderContext:
     """One HIP device (rr_ctx). Not thread-safe; one frame in flight at a time."""
 
-    def __init__(self, device: int = 0, png_depth: int = 0, exr_depth: int = 0, color_mode=0):
+    def __init__(self, device: int = 0, png_depth: int = 0, exr_depth: int = 0, color_mode=0,
+                 look: str | None = None, display_gamma: float = 0.0):
         """png_depth: bits per sample of "PNG" frames (set_png_depth; 0: the scene's).
         exr_depth: channel type of "OPEN_EXR" frames (set_exr_depth; 0: the scene's).
-        color_mode: "BW" / "RGB" / "RGBA" of every file (set_color_mode; 0: the scene's)."""
+        color_mode: "BW" / "RGB" / "RGBA" of every file (set_color_mode; 0: the scene's).
+        look: the look of Filmic frames (set_look; None: the scene's).
+        display_gamma: the display gamma of every frame (set_display_gamma; 0: the scene's)."""
         h = ctypes.c_void_p()
         _check(lib().rr_create(int(device), ctypes.byref(h)))
         self.handle = h
@@ -308,6 +329,10 @@ class RenderContext:
             self.set_exr_depth(exr_depth)
         if color_mode_value(color_mode):
             self.set_color_mode(color_mode)
+        if look:
+            self.set_look(look)
+        if display_gamma:
+            self.set_display_gamma(display_gamma)
         self.device = device
 
     def close(self):
@@ -506,6 +531,27 @@ class RenderContext:
         values; 0 / "": the scene's render.color_mode, else each format's own layout."""
         _check(lib().rr_set_color_mode(self.handle, color_mode_value(mode)), self.handle)
 
+    def set_look(self, name: str | None = None):
+        """rr_set_look: the look of this context's Filmic frames, one of LOOKS
+        (also with Blender's "Filmic - " prefix); None / "": the scene's render.look."""
+        _check(lib().rr_set_look(self.handle, name.encode() if name else None), self.handle)
+
+    def set_display_gamma(self, gamma: float = 0.0):
+        """rr_set_display_gamma: the display gamma of this context's frames, in
+        (0, 5]; 0: the scene's render.gamma. 1 skips the step."""
+        _check(lib().rr_set_display_gamma(self.handle, ctypes.c_float(gamma)), self.handle)
+
+    def view_device(self, rgba: np.ndarray, view_transform: int = 0, exposure_scale: float = 1.0) -> np.ndarray:
+        """rr_debug_view_device: the (H, W, 4) uint8 image the 8-bit view pass
+        makes of an (H, W, 4) float32 image of means, with this context's look
+        and display gamma."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+        h, w = rgba.shape[:2]
+        out = np.zeros((h, w, 4), np.uint8)
+        _check(lib().rr_debug_view_device(self.handle, _ptr(rgba, ctypes.c_float), w, h, int(view_transform),
+                                          ctypes.c_float(exposure_scale), _ptr(out, ctypes.c_uint8)), self.handle)
+        return out
+
     def encode_device(self, fmt: str, image: np.ndarray, depth: int = 0, color_mode=0, view_transform: int = 0,
                       exposure_scale: float = 1.0, quality: int = 90) -> bytes:
         """rr_debug_encode_device: the file bytes of an (H, W, 4) image coded on the
@@ -594,6 +640,16 @@ def srgb16_table() -> np.ndarray:
     t = np.zeros(n.value, np.float32)
     _check(lib().rr_debug_srgb16_table(_ptr(t, ctypes.c_float), t.size, ctypes.byref(n)))
     return t
+
+
+def display_gamma(values: np.ndarray, gamma: float) -> np.ndarray:
+    """rr_debug_display_gamma: values ** (1 / gamma) by the renderer's fixed
+    log2 / exp2 polynomials, evaluated on the host (no device needed)."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.zeros_like(v)
+    _check(lib().rr_debug_display_gamma(_ptr(v.reshape(-1), ctypes.c_float), v.size, ctypes.c_float(gamma),
+                                        _ptr(out.reshape(-1), ctypes.c_float)))
+    return out
 
 
 def encode_image(rgba: np.ndarray, out_path_no_ext: str, fmt: str, quality: int = 90) -> int:

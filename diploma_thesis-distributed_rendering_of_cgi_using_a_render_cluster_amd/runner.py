@@ -41,7 +41,8 @@ class RenderError(RuntimeError):
 class BackendRunner:
     def __init__(self, base_directory_path: str | os.PathLike, tracer: WorkerTraceBuilder | None = None,
                  device: int = 0, params: RenderParams | None = None, ctx=None, device_png: bool = False,
-                 png_depth: int = 0, exr_depth: int = 0, color_mode=0):
+                 png_depth: int = 0, exr_depth: int = 0, color_mode=0, look: str | None = None,
+                 display_gamma: float = 0.0):
         """ctx: a RenderContext on `device` is created here; tests of the host
         logic alone pass a stand-in with the same methods (no rendering).
         device_png: "PNG" jobs are coded on the device (rr_set_device_png).
@@ -52,7 +53,11 @@ class BackendRunner:
         exr_depth: channel type of "OPEN_EXR" jobs (rr_set_exr_depth): 16 (HALF),
         32 (FLOAT), or 0 for each scene's own render.exr_depth (HALF without one).
         color_mode: Blender's colour mode of every job's files (rr_set_color_mode):
-        "BW", "RGB", "RGBA", or 0 for each scene's own render.color_mode."""
+        "BW", "RGB", "RGBA", or 0 for each scene's own render.color_mode.
+        look: the look of every job's Filmic frames (rr_set_look), or None for
+        each scene's own render.look.
+        display_gamma: the display gamma of every job's frames
+        (rr_set_display_gamma), or 0 for each scene's own render.gamma."""
         base = Path(base_directory_path)
         if not base.is_dir():
             raise RenderError("Provided base directory path is not a directory.")
@@ -68,6 +73,10 @@ class BackendRunner:
             self.ctx.set_exr_depth(exr_depth)
         if color_mode:
             self.ctx.set_color_mode(color_mode)
+        if look:
+            self.ctx.set_look(look)
+        if display_gamma:
+            self.ctx.set_display_gamma(display_gamma)
         self._scenes: dict[str, Scene] = {}
         self._lock = threading.Lock()  # one caller at a time per context (queue.rs:79-118)
         self.last_stats = None

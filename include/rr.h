@@ -52,10 +52,14 @@ typedef struct rr_scene rr_scene;
 #define RR_VIEW_SCENE (-1)  /* use the scene file's setting */
 #define RR_VIEW_STANDARD 0  /* sRGB OETF, Blender "Standard" */
 #define RR_VIEW_RAW 1       /* linear values, clamped, no OETF */
-#define RR_VIEW_FILMIC 2    /* Blender "Filmic" (display sRGB, look None) through the OCIO LUTs of a
-                             * Blender colour-management directory (rr_set_ocio_config); without
-                             * them the frame is rendered with Standard and flagged
+#define RR_VIEW_FILMIC 2    /* Blender "Filmic" (display sRGB) through the OCIO LUTs of a
+                             * Blender colour-management directory (rr_set_ocio_config), with
+                             * the frame's look (rr_set_look); without the LUTs the frame is
+                             * rendered with Standard and flagged
                              * (rr_frame_stats.view_transform_substituted, rr_last_warning) */
+#define RR_VIEW_FILMIC_LOG 3   /* Blender "Filmic Log": the Filmic chain without its 1D curve */
+#define RR_VIEW_FALSE_COLOR 4  /* Blender "False Color": Filmic Log's luminance through
+                                * filmic_false_color.spi3d; without that file Standard, flagged */
 
 /* Render parameters. Any field left at its "use scene" value takes the value
  * exported from the project (scene file "render" block). Zero-initialising the
@@ -136,7 +140,8 @@ typedef struct rr_frame_stats {
      * their tile) are resolved as background without a traversal */
     uint64_t camera_rays_traced;
     int32_t view_transform;            /* RR_VIEW_* the frame was rendered with */
-    int32_t view_transform_substituted;/* 1: the scene asked for Filmic, no LUTs were configured, Standard used */
+    int32_t view_transform_substituted;/* 1: a view setting was not applied (a view or look without its LUT,
+                                        * a look with a view that takes none, an unknown name); rr_last_warning */
     /* RR_FLAG_COUNT_TRAVERSAL, LDS-resident scenes: the shader clock the tile
      * kernel ran at, in GHz, measured inside it (shader-clock ticks over the
      * 100 MHz real-time counter across each wave's lifetime, summed over waves);
@@ -311,8 +316,9 @@ int rr_set_png_depth(rr_ctx* ctx, int32_t depth);
  * taken as means: spp = 1; alpha is forced to 1) with the device 16-bit PNG
  * path (the one 16-bit "PNG" frames take; write_still,
  * render-timing-script.py:83-92): value * exposure_scale, clamp to [0, 1],
- * view_transform (RR_VIEW_STANDARD, RR_VIEW_RAW, or RR_VIEW_FILMIC with the
- * context's LUTs; Filmic without LUTs is RR_EINVAL here), 16-bit quantisation,
+ * view_transform (RR_VIEW_STANDARD, RR_VIEW_RAW, or one of the Filmic family
+ * with the context's LUTs and look; a view or look without its LUT is
+ * RR_EINVAL here), the context's display gamma, 16-bit quantisation,
  * Sub filter, deflate. *len receives the file size; the bytes are copied to out
  * if cap >= *len. Exported for round-trip tests. */
 int rr_debug_png16_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
@@ -406,11 +412,62 @@ const char* rr_last_warning(rr_ctx* ctx);
 
 /* Blender colour-management directory (datafiles/colormanagement: config.ocio
  * and luts/) whose Filmic LUTs (filmic_desat65cube.spi3d,
- * filmic_to_0-70_1-03.spi1d) implement RR_VIEW_FILMIC on ctx. NULL or "":
- * no LUTs (Filmic frames fall back to Standard, flagged). rr_create reads
- * the RR_OCIO_DIR environment variable the same way. RR_ENOENT / RR_EINVAL
- * if the LUT files are missing or malformed (ctx keeps no LUTs then). */
+ * filmic_to_0-70_1-03.spi1d) implement RR_VIEW_FILMIC and RR_VIEW_FILMIC_LOG
+ * on ctx. NULL or "": no LUTs (frames of the Filmic family fall back to
+ * Standard, flagged). The looks' curves (filmic_to_1.20_1-00.spi1d,
+ * filmic_to_0.99_1-0075.spi1d, filmic_to_0-85_1-011.spi1d,
+ * filmic_to_0-60_1-04.spi1d, filmic_to_0-48_1-09.spi1d,
+ * filmic_to_0-35_1-30.spi1d) and filmic_false_color.spi3d are loaded from the
+ * same place when present; an absent one only makes its look or view
+ * unavailable. rr_create reads the RR_OCIO_DIR environment variable the same
+ * way. RR_ENOENT / RR_EINVAL if the two base files are missing or any file
+ * found is malformed (ctx keeps no LUTs then). */
 int rr_set_ocio_config(rr_ctx* ctx, const char* dir);
+
+/* The look of ctx's Filmic frames (Blender's view_settings.look): "None",
+ * "Very High Contrast", "High Contrast", "Medium High Contrast", "Medium
+ * Contrast", "Medium Low Contrast", "Low Contrast", "Very Low Contrast", each
+ * also with Blender's "Filmic - " prefix. NULL or "": the scene's render.look.
+ * A look puts its 1D curve in the place of Filmic's base curve ("Medium
+ * Contrast" is the base curve: the bits of "None"). With a view other than
+ * RR_VIEW_FILMIC the look is ignored, and with its curve's file not loaded the
+ * frame renders without the look; both are flagged
+ * (view_transform_substituted, rr_last_warning). rr_create reads RR_LOOK from
+ * the environment the same way. Applies to frames submitted after the call
+ * and to rr_debug_view_device / rr_debug_png16_device /
+ * rr_debug_encode_device; frames in flight keep theirs. RR_EINVAL for a NULL
+ * ctx or an unknown name. */
+int rr_set_look(rr_ctx* ctx, const char* name);
+
+/* Display gamma of ctx's frames (Blender's view_settings.gamma), for every
+ * view transform: after the view transform d' = d^(1 / gamma), 0 for d <= 0,
+ * by fixed polynomials of log2 and exp2 (the same bits on host and device),
+ * before BW luma and quantisation. 0: the scene's render.gamma. 1 skips the
+ * step. OPEN_EXR files are linear and unaffected. rr_create reads
+ * RR_DISPLAY_GAMMA from the environment the same way. Applies as rr_set_look
+ * does. RR_EINVAL for a NULL ctx, gamma < 0 or gamma > 5 (Blender's range). */
+int rr_set_display_gamma(rr_ctx* ctx, float gamma);
+
+/* Run the 8-bit view pass (the one frames of the Filmic family and frames
+ * with a display gamma take after rendering) on a float RGBA image of the
+ * caller's (width * height * 4 floats, taken as means: spp = 1): value *
+ * exposure_scale, view_transform (RR_VIEW_STANDARD .. RR_VIEW_FALSE_COLOR)
+ * with ctx's look and display gamma, 8-bit quantisation, alpha 255, into
+ * rgba8_out (width * height * 4 bytes). A view or look whose LUT is not loaded
+ * is RR_EINVAL here. Exported for tests. */
+int rr_debug_view_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
+                         int32_t view_transform, float exposure_scale, uint8_t* rgba8_out);
+
+/* out[i] = in[i]^(1 / gamma) as rr_set_display_gamma defines it, evaluated on
+ * the host (no device needed), gamma 1 included (which frames skip). RR_EINVAL
+ * for gamma <= 0 or gamma > 5. Exported for tests. */
+int rr_debug_display_gamma(const float* in, uint64_t n, float gamma, float* out);
+
+/* The view settings a scene file asks for (host only): its view transform
+ * (RR_VIEW_*; Standard for a view this renderer does not know), its look's
+ * name without prefix (copied to look if cap exceeds its length; "None" for
+ * an unknown look) and its display gamma. Any pointer may be NULL. */
+int rr_debug_scene_view(rr_scene* scene, int32_t* view_transform, char* look, int32_t cap, float* gamma);
 
 void rr_scene_free(rr_scene* scene);
 void rr_destroy(rr_ctx* ctx);
