@@ -81,8 +81,10 @@ RR_D uint32_t hull_flags(lds_tri* tris, int n_tris, int i) {
 // edge lines e[k] = (nx, ny, c): nx*x + ny*y + c >= 0 inside, |n| = 1, so the
 // value is a signed distance in pixels. A triangle at or behind the camera
 // plane, or degenerate on screen, keeps the unbounded rectangle / edges that
-// every point satisfies.
-RR_D void tri_screen_rect(const FrameConsts& fc, const float3 p[3], float r[4], float e[3][3]) {
+// every point satisfies. Returns whether the edge lines are the triangle's own
+// and good to a small fraction of a pixel (every projected vertex within 2^16
+// pixels of the origin: fp32 rounding of the line's offset stays below 2^-5 px).
+RR_D bool tri_screen_rect(const FrameConsts& fc, const float3 p[3], float r[4], float e[3][3]) {
     float x0 = kFltMax, x1 = -kFltMax, y0 = kFltMax, y1 = -kFltMax;
     float fx[3], fy[3];
     for (int k = 0; k < 3; ++k) e[k][0] = e[k][1] = 0.0f, e[k][2] = 1.0f;
@@ -92,7 +94,7 @@ RR_D void tri_screen_rect(const FrameConsts& fc, const float3 p[3], float r[4], 
         if (!(depth > 1.0e-4f)) {  // at or behind the camera plane: no bound, every tile keeps it
             r[0] = r[2] = -kFltMax;
             r[1] = r[3] = kFltMax;
-            return;
+            return false;
         }
         const float sx = dot3(v, fc.cam_right) / depth;
         const float sy = dot3(v, fc.cam_up) / depth;
@@ -108,7 +110,7 @@ RR_D void tri_screen_rect(const FrameConsts& fc, const float3 p[3], float r[4], 
     r[2] = y0 - 1.0f;
     r[3] = y1 + 1.0f;
     const float area = (fx[1] - fx[0]) * (fy[2] - fy[0]) - (fy[1] - fy[0]) * (fx[2] - fx[0]);
-    if (!(fabsf(area) > 1.0e-3f)) return;  // (near-)degenerate on screen: edges stay open
+    if (!(fabsf(area) > 1.0e-3f)) return false;  // (near-)degenerate on screen: edges stay open
     const float sgn = area > 0.0f ? 1.0f : -1.0f;
     for (int k = 0; k < 3; ++k) {
         const int a = k, b = (k + 1) % 3;
@@ -120,6 +122,48 @@ RR_D void tri_screen_rect(const FrameConsts& fc, const float3 p[3], float r[4], 
         e[k][1] = ny;
         e[k][2] = -(nx * fx[a] + ny * fy[a]);
     }
+    return fmaxf(fmaxf(fabsf(x0), fabsf(x1)), fmaxf(fabsf(y0), fabsf(y1))) <= 0x1p16f;
+}
+
+RR_D float l1norm(float3 a) { return fabsf(a.x) + fabsf(a.y) + fabsf(a.z); }
+
+// Inverse-depth plane of a triangle: along the camera ray through the sample
+// position (fx, fy) (pixels, camera_ray_xy's), the triangle's plane lies at
+// depth z along the camera axis with 1 / z = w(fx, fy) = pl[0] fx + pl[1] fy +
+// pl[2], affine because the ray is cam_pos + z (sx right + sy up - back) with
+// sx, sy affine in fx, fy: n . (z s) = n . (p0 - cam_pos) = d0, so
+// w = n . s / d0. w <= 0: the ray does not meet the plane in front of the
+// camera. tile_mask compares these planes with an error allowance of
+// 2^-10 M, M = |pl[0]| W + |pl[1]| H + |pl[2]| >= (|n.right| half_w +
+// |n.up| half_h + |n.back|) / |d0|, which bounds |w| on the screen. The plane
+// stays (0, 0, 0) — tile_mask then neither lets the triangle hide another nor
+// drops it — unless the fp32 error of the coefficients is far below that
+// allowance:
+//   * the edges meet at a fair angle, |n|_1 >= 2^-4 |e1|_1 |e2|_1: the cross
+//     product's rounding (four roundings per product pair, the pairs sum to
+//     at most |e1|_1 |e2|_1: <= 2^-22 |e1|_1 |e2|_1; e1, e2 are single
+//     subtractions of the staged vertices) is below 2^-18 |n|_1;
+//   * the plane passes the camera at a fair distance, |d0| >= 2^-4 |n|_2
+//     |p0 - cam_pos|_2 (p0 is seen more than 3.5 degrees off the plane): d0
+//     is good to 2^-13 relative;
+//   * the sensor's half extents lie in [2^-4, 1.5]: M >= 2^-4 |n|_2 / |d0|
+//     and |s| <= 2.4, so the 2^-18 |n|_1 |s| / |d0| that n's rounding moves w
+//     by is below 2^-12 M.
+RR_D void tri_inv_depth_plane(const FrameConsts& fc, const float3 p[3], float pl[3]) {
+    pl[0] = pl[1] = pl[2] = 0.0f;
+    const float3 e1 = sub3(p[1], p[0]), e2 = sub3(p[2], p[0]);
+    const float3 n = cross3(e1, e2), a = sub3(p[0], fc.cam_pos);
+    const float an = l1norm(n), d0 = dot3(n, a);
+    if (!(an >= 0x1p-4f * (l1norm(e1) * l1norm(e2)))) return;
+    if (!(fabsf(d0) >= 0x1p-4f * (sqrtf(dot3(n, n)) * sqrtf(dot3(a, a)))) || !(fabsf(d0) > 0.0f)) return;
+    if (!(fminf(fc.half_w, fc.half_h) >= 0x1p-4f) || !(fmaxf(fc.half_w, fc.half_h) <= 1.5f)) return;
+    const float gx = dot3(n, fc.cam_right) * fc.half_w, gy = dot3(n, fc.cam_up) * fc.half_h;
+    const float gz = -dot3(n, fc.cam_back);
+    const float q0 = gx * fc.inv_w2 / d0, q1 = -(gy * fc.inv_h2) / d0, q2 = ((gz - gx) + gy) / d0;
+    if (!(fabsf(q0) < 0x1p100f && fabsf(q1) < 0x1p100f && fabsf(q2) < 0x1p100f)) return;  // (also NaN)
+    pl[0] = q0;
+    pl[1] = q1;
+    pl[2] = q2;
 }
 
 // Camera-ray data of one triangle (sorted index i), staged next to the scene
@@ -133,17 +177,19 @@ RR_D void tri_screen_rect(const FrameConsts& fc, const float3 p[3], float r[4], 
 // 8x8 tiles whose samples can hit it.
 //   [13i + 3kz + k] = (rot3(v_k - o, kz), orig id for k = 0, else 0), kz, k = 0..2
 //   [13i + 9] = (x0, x1, y0, y1), [13i + 10..12] = the screen edge lines
+//   (nx, ny, c, pl[k]): their fourth words hold the inverse-depth plane
+//   (tri_inv_depth_plane; zeros when the edge lines are open)
 // Camera-ray data per triangle in LDS: the vertices relative to the camera in
 // the three permutations (9 float4), the screen rectangle, the three screen
-// edge lines.
+// edge lines with the inverse-depth plane in their spare words.
 constexpr int kCamF4 = 13;
 constexpr int kCamRect = 9;  // float4 offset of the screen rectangle, the edge lines follow
 RR_D void stage_camera(lds_f4w* q, lds_tri* tris, int n_tris, const FrameConsts& fc) {
     for (int i = threadIdx.x; i < n_tris; i += kBlock) {
         const TriPack tp = load_tri(tris, i);
         const float3 pts[3] = {xyz(tp.p0), xyz(tp.p1), xyz(tp.p2)};
-        float r[4], e[3][3];
-        tri_screen_rect(fc, pts, r, e);
+        float r[4], e[3][3], pl[3] = {0.0f, 0.0f, 0.0f};
+        if (tri_screen_rect(fc, pts, r, e)) tri_inv_depth_plane(fc, pts, pl);
         for (int k = 0; k < 3; ++k) {
             const float3 a = sub3(pts[k], fc.cam_pos);
             for (int kz = 0; kz < 3; ++kz) {
@@ -158,7 +204,7 @@ RR_D void stage_camera(lds_f4w* q, lds_tri* tris, int n_tris, const FrameConsts&
         q[kCamF4 * i + kCamRect] = c;
         for (int k = 0; k < 3; ++k) {
             rr_f4v l;
-            l.x = e[k][0]; l.y = e[k][1]; l.z = e[k][2]; l.w = 0.0f;
+            l.x = e[k][0]; l.y = e[k][1]; l.z = e[k][2]; l.w = pl[k];
             q[kCamF4 * i + kCamRect + 1 + k] = l;
         }
     }
@@ -303,22 +349,71 @@ RR_D void camera_hit(const LdsView& v, uint64_t m0, uint64_t m1, float3 d, float
 // Triangles whose screen rectangle meets the sample positions of pixels
 // [x0, x1] x [y0, y1] (centres + filter offsets below fc.filter_reach), as a
 // wave-uniform 128-bit mask; n_tris <= 128 (every LDS-resident scene).
+//
+// Occlusion: a triangle that another one hides from every
+// sample position of the expanded tile X0..X1 x Y0..Y1 is dropped from the
+// mask. Triangle A covers the tile when the tile's worst corner lies inside
+// each of A's edge lines by a pixel or more (the slack of the inclusion test,
+// on the other side), A's inverse depth w_A (tri_inv_depth_plane) is positive
+// over the tile and its depth there lies inside (clip_start, clip_end) — the
+// ray parameters are those depths times the ray's length factor, which
+// camera_ray_xy puts on tmin / tmax alike. Then every traced ray of the tile
+// hits A at a t that `closer` accepts. Of the covering triangles the one with
+// the largest lower bound lo_A of w over the tile (the nearest) is taken, and
+// every triangle B with 0 < w_B over the tile and upper bound hi_B < lo_A
+// goes: wherever a ray meets B, it meets A at a smaller t, so B is never the
+// closest hit, and `closer` is order-independent. An affine function takes
+// its extrema over a rectangle at the corners; lo / hi are those minus / plus
+// 2^-10 (|a| W + |b| H + |c|), which is at least 2^-10 |w| (the relative
+// margin that keeps ties, coplanar and interpenetrating triangles in the
+// mask) and 2^2 times and more the fp32 error that tri_inv_depth_plane admits
+// in the staged coefficients plus that of evaluating them here. A triangle
+// without a plane (zeros) has lo = hi = 0: it neither covers nor goes, and A
+// itself stays since hi_A >= lo_A.
 RR_D void tile_mask(const FrameConsts& fc, const LdsView& v, int n_tris, float x0, float x1, float y0, float y1,
                     uint64_t& m0, uint64_t& m1) {
     const float r = fc.filter_reach;
     const float X0 = x0 + 0.5f - r, X1 = x1 + 0.5f + r, Y0 = y0 + 0.5f - r, Y1 = y1 + 0.5f + r;
+    const float Wf = (float)fc.W, Hf = (float)fc.H;
+    constexpr float kEps = 0x1p-10f;
     uint64_t a = 0, b = 0;
+    float best = 0.0f;  // the largest lo_A of a covering triangle (0: none covers)
     for (int i = 0; i < n_tris; ++i) {
         const float4 q = lds_ld4(v.cam + kCamF4 * i + kCamRect);
         bool in = !(q.y < X0 || q.x > X1 || q.w < Y0 || q.z > Y1);
+        bool cov = true;
+        float pl[3] = {0.0f, 0.0f, 0.0f};
         for (int k = 0; k < 3 && in; ++k) {  // the expanded tile wholly outside an edge (+1 px of slack)
             const float4 l = lds_ld4(v.cam + kCamF4 * i + kCamRect + 1 + k);
             const float m = l.x * (l.x > 0.0f ? X1 : X0) + l.y * (l.y > 0.0f ? Y1 : Y0) + l.z;
             in = m >= -1.0f;
+            // ... and wholly inside it by a pixel
+            cov = cov && l.x * (l.x > 0.0f ? X0 : X1) + l.y * (l.y > 0.0f ? Y0 : Y1) + l.z >= 1.0f;
+            pl[k] = l.w;
         }
         if (in) {
             if (i < 64) a |= 1ull << i;
             else b |= 1ull << (i - 64);
+            if (cov) {
+                const float e = kEps * (fabsf(pl[0]) * Wf + fabsf(pl[1]) * Hf + fabsf(pl[2]));
+                const float lo = pl[0] * (pl[0] > 0.0f ? X0 : X1) + pl[1] * (pl[1] > 0.0f ? Y0 : Y1) + pl[2] - e;
+                const float hi = pl[0] * (pl[0] > 0.0f ? X1 : X0) + pl[1] * (pl[1] > 0.0f ? Y1 : Y0) + pl[2] + e;
+                if (lo > 0.0f && hi * fc.clip_start * (1.0f + kEps) < 1.0f && lo * fc.clip_end > 1.0f + kEps)
+                    best = fmaxf(best, lo);
+            }
+        }
+    }
+    if (best > 0.0f) {
+        for (int i = 0; i < n_tris; ++i) {
+            const lds_f4w* l = v.cam + kCamF4 * i + kCamRect + 1;
+            const float pa = lds_ld4(l).w, pb = lds_ld4(l + 1).w, pc = lds_ld4(l + 2).w;
+            const float e = kEps * (fabsf(pa) * Wf + fabsf(pb) * Hf + fabsf(pc));
+            const float lo = pa * (pa > 0.0f ? X0 : X1) + pb * (pb > 0.0f ? Y0 : Y1) + pc - e;
+            const float hi = pa * (pa > 0.0f ? X1 : X0) + pb * (pb > 0.0f ? Y1 : Y0) + pc + e;
+            if (lo > 0.0f && hi < best) {
+                if (i < 64) a &= ~(1ull << i);
+                else b &= ~(1ull << (i - 64));
+            }
         }
     }
     m0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32) |
