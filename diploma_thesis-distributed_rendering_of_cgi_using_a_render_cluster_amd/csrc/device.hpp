@@ -346,12 +346,16 @@ void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, in
 // the Filmic LUTs of one device and the display gamma. lut1 is the curve the
 // frame's look selects (the base curve for None and Medium Contrast); fcube
 // the false-colour cube (RR_VIEW_FALSE_COLOR only). Views outside the Filmic
-// family leave the LUT fields zero.
+// family leave the LUT fields zero. dither: the intensity of the 8-bit image's
+// dither (rr_set_dither; view_device only, the 16-bit front end does not read
+// it). It stands where the struct had four bytes of padding, so the other
+// fields, and the kernel arguments behind the struct, keep their offsets.
 struct FilmicArgs {
     const float4* cube;
     const float* lut1;
     int n3, n1, comps;
     float lo1, hi1;
+    float dither;  // 0: none
     const float4* fcube;
     int nf;
     float inv_gamma;  // 1 / display gamma; 0: gamma 1, no gamma step

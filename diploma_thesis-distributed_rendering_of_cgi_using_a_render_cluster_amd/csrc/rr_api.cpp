@@ -192,6 +192,8 @@ struct rr_ctx {
     int look = -1;
     // display gamma (rr_set_display_gamma / RR_DISPLAY_GAMMA): 0 the scene's
     float gamma = 0.f;
+    // dither of the 8-bit image (rr_set_dither / RR_DITHER): an intensity in [0, 2], RR_DITHER_SCENE the scene's
+    float dither = 0.f;
     DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
     std::vector<float> filter_cache;
     float filter_width_cached = -1.f;
@@ -308,6 +310,8 @@ std::string resolve_view(const rr_ctx* c, FrameSetup& fs) {
     auto note = [&](const std::string& m) { w += (w.empty() ? "" : "; ") + m; };
     if (c && c->look >= 0) fs.look = c->look;
     if (c && c->gamma != 0.f) fs.gamma = c->gamma;
+    // the context's intensity (0 on a new one); only RR_DITHER_SCENE keeps the scene's
+    if (!c || c->dither != RR_DITHER_SCENE) fs.dither = c ? c->dither : 0.f;
     const int asked = fs.view_transform;
     if (asked >= VIEW_FILMIC && !(c && c->filmic.ready)) {
         fs.view_transform = VIEW_STANDARD;
@@ -335,10 +339,12 @@ std::string resolve_view(const rr_ctx* c, FrameSetup& fs) {
 }
 
 // The view settings as kernel arguments, for a view, look and gamma that
-// resolve_view (or an inspection call's own check) has passed.
-FilmicArgs view_args(const rr_ctx* c, int view, int look, float gamma) {
+// resolve_view (or an inspection call's own check) has passed. dither: the
+// 8-bit pass's intensity (the 16-bit front end takes none).
+FilmicArgs view_args(const rr_ctx* c, int view, int look, float gamma, float dither = 0.f) {
     FilmicArgs a = view >= VIEW_FILMIC ? c->filmic.args(view == VIEW_FILMIC ? look : 0) : FilmicArgs{};
     a.inv_gamma = inv_gamma_of(gamma);
+    a.dither = dither;
     return a;
 }
 
@@ -711,11 +717,11 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     k.div_spp = FastDiv::make((uint32_t)k.spp_chunk);
     render_frame_device(s->mesh, build, c->paths, f, k, r.chunks, opts, st);
     r.tile_slices = f.tile_slices;
-    // the Filmic family, or a display gamma: film -> view settings -> rgba8 (overwrites the kernels' tonemap)
-    if (view_needs_pass(fs.view_transform, fs.gamma)) {
+    // the Filmic family, a display gamma or a dither: film -> view settings -> rgba8 (overwrites the kernels' tonemap)
+    if (view_needs_pass(fs.view_transform, fs.gamma, fs.dither)) {
         f.prof.begin(st, RR_K_ACCUM);
-        view_device(view_args(c, fs.view_transform, fs.look, fs.gamma), k, c->paths.srgb_lut.ptr, f.film.ptr,
-                    reinterpret_cast<uchar4*>(f.rgba8.ptr), st);
+        view_device(view_args(c, fs.view_transform, fs.look, fs.gamma, fs.dither), k, c->paths.srgb_lut.ptr,
+                    f.film.ptr, reinterpret_cast<uchar4*>(f.rgba8.ptr), st);
         f.prof.end(st);
     }
     RR_HIP(hipEventRecord(sl.ev[4], st));
@@ -1035,6 +1041,15 @@ int rr_create(int device_ordinal, rr_ctx** out) {
                 return fail(RR_EINVAL, std::string("RR_DISPLAY_GAMMA must be 0 or in (0, 5], got '") + d + "'");
             gamma = (float)v;
         }
+        float dither = 0.f;
+        if (const char* d = getenv("RR_DITHER")) {  // as rr_set_dither: a number, or "scene"
+            char* end = nullptr;
+            const double v = *d ? std::strtod(d, &end) : 0.0;
+            if (std::string(d) == "scene") dither = RR_DITHER_SCENE;
+            else if (*d && (end == d || *end || !(v >= 0.0) || v > (double)kDitherMax))
+                return fail(RR_EINVAL, std::string("RR_DITHER must be in [0, 2] or 'scene', got '") + d + "'");
+            else dither = (float)v;
+        }
         std::unique_ptr<rr_ctx> c(new rr_ctx());
         c->device = device_ordinal;
         set_device(c.get());
@@ -1061,6 +1076,7 @@ int rr_create(int device_ordinal, rr_ctx** out) {
         c->color_mode = color_mode;
         c->look = look;
         c->gamma = gamma;
+        c->dither = dither;
         *out = c.release();
         return RR_OK;
     });
@@ -1410,6 +1426,26 @@ int rr_set_display_gamma(rr_ctx* c, float gamma) {
     return RR_OK;
 }
 
+int rr_set_dither(rr_ctx* c, float intensity) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    if (intensity != RR_DITHER_SCENE && (!(intensity >= 0.f) || intensity > kDitherMax))
+        return fail(RR_EINVAL, "dither intensity must be in [0, 2], or RR_DITHER_SCENE (the scene's)");
+    c->dither = intensity;  // read when a frame is submitted; frames in flight keep theirs
+    return RR_OK;
+}
+
+int rr_debug_sin_fixed(const float* in, uint64_t n, float* out) {
+    if ((!in || !out) && n) return fail(RR_EINVAL, "NULL array");
+    sin_fixed_host(in, (size_t)n, out);
+    return RR_OK;
+}
+
+int rr_debug_dither_noise(int32_t w, int32_t h, float* out) {
+    if (!out || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    dither_noise_host(w, h, out);
+    return RR_OK;
+}
+
 int rr_debug_view_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int32_t view_transform,
                          float exposure_scale, uint8_t* rgba8_out) {
     if (!c || !rgba || !rgba8_out || w <= 0 || h <= 0 || (int64_t)w * h > (int64_t)1 << 28)
@@ -1441,7 +1477,11 @@ int rr_debug_view_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int
         k.inv_spp = 1.0f;
         k.exposure_scale = exposure_scale;
         k.view_transform = view_transform;
-        view_device(view_args(c, view_transform, look, gamma), k, c->paths.srgb_lut.ptr, img.ptr, q.ptr, c->stream);
+        k.div_w = FastDiv::make((uint32_t)w);
+        // the context's dither; none where it leaves the intensity to a scene
+        const float dither = c->dither > 0.f ? c->dither : 0.f;
+        view_device(view_args(c, view_transform, look, gamma, dither), k, c->paths.srgb_lut.ptr, img.ptr, q.ptr,
+                    c->stream);
         RR_HIP(hipStreamSynchronize(c->stream));
         RR_HIP(hipMemcpy(rgba8_out, q.ptr, npix * 4, hipMemcpyDeviceToHost));
         img.release();

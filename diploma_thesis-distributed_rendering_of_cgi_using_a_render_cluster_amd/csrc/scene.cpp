@@ -695,6 +695,16 @@ SceneDesc load_scene(const std::string& path) {
         d.gamma = r.get_num("gamma", 1.0);
         if (!(d.gamma > 0.0) || d.gamma > (double)kGammaMax)
             throw std::runtime_error("render.gamma must be above 0 and at most 5, got " + std::to_string(d.gamma));
+        // Blender's image_settings.dither_intensity; applied where the context
+        // asks for the scene's (rr_set_dither RR_DITHER_SCENE)
+        if (r.has("dither_intensity")) {
+            const Json& v = r["dither_intensity"];
+            if (v.type != Json::Number)
+                throw std::runtime_error("render.dither_intensity must be a number in [0, 2]");
+            if (!(v.num >= 0.0) || v.num > (double)kDitherMax)
+                throw std::runtime_error("render.dither_intensity must be in [0, 2], got " + std::to_string(v.num));
+            d.dither_intensity = v.num;
+        }
     }
     if (s.render.resx <= 0 || s.render.resy <= 0 || s.render.percent <= 0)
         throw std::runtime_error("invalid resolution");
@@ -928,6 +938,7 @@ FrameSetup setup_frame(const SceneDesc& s, int frame, const rr_render_params* p)
         f.look = r.look;
         f.gamma = (float)r.gamma;
     }
+    f.dither = (float)r.dither_intensity;
     if (f.view_transform < VIEW_STANDARD || f.view_transform > VIEW_FALSE_COLOR)
         throw std::runtime_error("unsupported view transform");
     f.spp_per_chunk = p->spp_per_chunk > 0 ? p->spp_per_chunk : r.spp_per_chunk;

@@ -117,6 +117,7 @@ struct RenderDesc {
     std::string view_transform_name = "Standard";
     int look = 0;        // view.hpp kLooks id of render.look (0 None; rr_set_look NULL takes it)
     double gamma = 1.0;  // render.gamma, in (0, 5] (rr_set_display_gamma 0 takes it)
+    double dither_intensity = 0.0;  // render.dither_intensity, in [0, 2] (rr_set_dither RR_DITHER_SCENE takes it)
     // What of the scene's colour management no frame can apply, for the
     // frame's warning ("" when there is nothing): a view transform this
     // renderer does not know (rendered as Standard), a look it does not know
@@ -152,6 +153,9 @@ struct FrameSetup {
     // None and 1; resolved against the context's settings and LUTs by resolve_view
     int32_t look = 0;
     float gamma = 1.f;
+    // the scene's render.dither_intensity; resolve_view puts the frame's own in
+    // its place (the context's, 0 on a new one; RR_DITHER_SCENE keeps this)
+    float dither = 0.f;
     uint32_t seed = 0;
     float clamp_indirect = 0.f, filter_width = 1.5f, exposure_scale = 1.f;
     float cam[RR_CAM_FLOATS] = {};

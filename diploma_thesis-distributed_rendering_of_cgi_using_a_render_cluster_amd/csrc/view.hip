@@ -6,6 +6,7 @@
 #pragma clang fp contract(off)
 
 #include "view.hpp"
+#include "dither.h"
 #include "view_filmic.h"
 
 #include <cstring>
@@ -19,12 +20,19 @@ namespace {
 // 8-bit sRGB table intervals of the render kernels' tonemap (paths.hpp kSrgbN)
 constexpr int kViewSrgbN = 4096;
 
-// The view pass: VIEW and GAMMA are compile-time, so Filmic at gamma 1 keeps
-// the instructions it had before there were other settings. Standard and Raw
-// (here for their display gamma) repeat paths.hpp tonemap up to the quantiser.
-template <int VIEW, bool GAMMA>
+// The view pass: VIEW, GAMMA and DITHER are compile-time, so Filmic at gamma 1
+// keeps the instructions it had before there were other settings. Standard and
+// Raw (here for their display gamma or the dither) repeat paths.hpp tonemap up
+// to the quantiser. DITHER adds dither.h's noise of the pixel, scaled by
+// f.dither, to the three display-referred values before they are quantised.
+template <int VIEW, bool GAMMA, bool DITHER>
 __global__ __launch_bounds__(256) void k_view(FrameConsts fc, FilmicArgs f, const float* __restrict__ srgb,
                                               const float4* __restrict__ film, uchar4* __restrict__ out) {
+    float inv_w = 0.0f, inv_h = 0.0f;
+    if constexpr (DITHER) {
+        inv_w = 1.0f / (float)fc.W;
+        inv_h = 1.0f / (float)fc.H;
+    }
     for (int pix = blockIdx.x * 256 + threadIdx.x; pix < fc.npix; pix += gridDim.x * 256) {
         const float4 acc = film[pix];
         const float c[3] = {acc.x * fc.inv_spp * fc.exposure_scale, acc.y * fc.inv_spp * fc.exposure_scale,
@@ -41,6 +49,12 @@ __global__ __launch_bounds__(256) void k_view(FrameConsts fc, FilmicArgs f, cons
         }
         if constexpr (GAMMA)
             for (int k = 0; k < 3; ++k) d[k] = display_gamma(d[k], f.inv_gamma);
+        if constexpr (DITHER) {
+            // rows run top to bottom here, Blender's bottom-up
+            const int row = (int)fc.div_w.div((uint32_t)pix), x = pix - row * fc.W;
+            const float dv = dither_noise(x, fc.H - 1 - row, inv_w, inv_h) * kDitherScale * f.dither;
+            for (int k = 0; k < 3; ++k) d[k] = d[k] + dv;
+        }
         uint8_t q[3];
         for (int k = 0; k < 3; ++k) q[k] = quantize8(d[k]);
         out[pix] = make_uchar4(q[0], q[1], q[2], 255);
@@ -48,10 +62,15 @@ __global__ __launch_bounds__(256) void k_view(FrameConsts fc, FilmicArgs f, cons
 }
 
 template <int VIEW>
-void launch_view(bool gamma, int grid, hipStream_t st, const FrameConsts& fc, const FilmicArgs& a, const float* srgb,
-                 const float4* film, uchar4* out) {
-    if (gamma) k_view<VIEW, true><<<grid, 256, 0, st>>>(fc, a, srgb, film, out);
-    else k_view<VIEW, false><<<grid, 256, 0, st>>>(fc, a, srgb, film, out);
+void launch_view(bool gamma, bool dither, int grid, hipStream_t st, const FrameConsts& fc, const FilmicArgs& a,
+                 const float* srgb, const float4* film, uchar4* out) {
+    if (dither) {
+        if (gamma) k_view<VIEW, true, true><<<grid, 256, 0, st>>>(fc, a, srgb, film, out);
+        else k_view<VIEW, false, true><<<grid, 256, 0, st>>>(fc, a, srgb, film, out);
+    } else {
+        if (gamma) k_view<VIEW, true, false><<<grid, 256, 0, st>>>(fc, a, srgb, film, out);
+        else k_view<VIEW, false, false><<<grid, 256, 0, st>>>(fc, a, srgb, film, out);
+    }
 }
 
 bool read_lines(const std::string& path, std::vector<std::string>& lines, std::string& err) {
@@ -284,14 +303,16 @@ void view_device(const FilmicArgs& a, const FrameConsts& fc, const float* srgb, 
                                    (view == RR_VIEW_FALSE_COLOR && !a.fcube)))
         throw std::runtime_error(std::string(view_name(view)) + " view transform without its LUTs");
     if (view == RR_VIEW_STANDARD && !srgb) throw std::runtime_error("Standard view transform without its table");
-    const bool gamma = a.inv_gamma != 0.0f;
+    const bool gamma = a.inv_gamma != 0.0f, dither = a.dither > 0.0f;
+    if (dither && (fc.W <= 0 || fc.H <= 0 || (long long)fc.W * fc.H != fc.npix))
+        throw std::runtime_error("dither needs the frame's width and height");
     const int grid = std::max(1, std::min((fc.npix + 255) / 256, 4096));
     switch (view) {
-    case RR_VIEW_STANDARD: launch_view<RR_VIEW_STANDARD>(gamma, grid, st, fc, a, srgb, film, out); break;
-    case RR_VIEW_RAW: launch_view<RR_VIEW_RAW>(gamma, grid, st, fc, a, srgb, film, out); break;
-    case RR_VIEW_FILMIC: launch_view<RR_VIEW_FILMIC>(gamma, grid, st, fc, a, srgb, film, out); break;
-    case RR_VIEW_FILMIC_LOG: launch_view<RR_VIEW_FILMIC_LOG>(gamma, grid, st, fc, a, srgb, film, out); break;
-    case RR_VIEW_FALSE_COLOR: launch_view<RR_VIEW_FALSE_COLOR>(gamma, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_STANDARD: launch_view<RR_VIEW_STANDARD>(gamma, dither, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_RAW: launch_view<RR_VIEW_RAW>(gamma, dither, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_FILMIC: launch_view<RR_VIEW_FILMIC>(gamma, dither, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_FILMIC_LOG: launch_view<RR_VIEW_FILMIC_LOG>(gamma, dither, grid, st, fc, a, srgb, film, out); break;
+    case RR_VIEW_FALSE_COLOR: launch_view<RR_VIEW_FALSE_COLOR>(gamma, dither, grid, st, fc, a, srgb, film, out); break;
     default: throw std::runtime_error("unsupported view transform");
     }
     RR_HIP(hipGetLastError());
@@ -300,6 +321,16 @@ void view_device(const FilmicArgs& a, const FrameConsts& fc, const float* srgb, 
 void display_gamma_host(const float* in, size_t n, float g, float* out) {
     const float inv = 1.0f / g;
     for (size_t i = 0; i < n; ++i) out[i] = display_gamma(in[i], inv);
+}
+
+void sin_fixed_host(const float* in, size_t n, float* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = sin_fixed(in[i]);
+}
+
+void dither_noise_host(int w, int h, float* out) {
+    const float inv_w = 1.0f / (float)w, inv_h = 1.0f / (float)h;
+    for (int r = 0; r < h; ++r)
+        for (int x = 0; x < w; ++x) out[(size_t)r * w + x] = dither_noise(x, h - 1 - r, inv_w, inv_h);
 }
 
 }  // namespace rr

@@ -62,6 +62,8 @@ constexpr LookDef kLooks[kNumLooks] = {
 constexpr const char* kFalseColorFile = "filmic_false_color.spi3d";
 // Blender's range of view_settings.gamma
 constexpr float kGammaMax = 5.0f;
+// Blender's range of image_settings.dither_intensity: [0, kDitherMax]
+constexpr float kDitherMax = 2.0f;
 
 // The id of a look by its name, with or without Blender's "Filmic - " prefix;
 // -1 for a name that is not in kLooks.
@@ -119,7 +121,7 @@ struct FilmicDev {
     // the arguments of a Filmic-family frame with look `id` (has_look holds)
     FilmicArgs args(int id = 0) const {
         const Curve1Dev& c = kLooks[id].file ? look[id] : base;
-        return FilmicArgs{cube.ptr, c.v.ptr, n3, c.n, c.comps, c.lo, c.hi, fcube.ptr, nf, 0.0f};
+        return FilmicArgs{cube.ptr, c.v.ptr, n3, c.n, c.comps, c.lo, c.hi, 0.0f, fcube.ptr, nf, 0.0f};
     }
 };
 
@@ -128,18 +130,26 @@ inline float inv_gamma_of(float g) { return g == 1.0f ? 0.0f : 1.0f / g; }
 
 // Whether a frame's rgba8 comes from view_device (the second pass over the
 // film) and not from the render kernels' own tonemap (paths.hpp: Standard and
-// Raw at gamma 1).
-inline bool view_needs_pass(int view_transform, float gamma) {
-    return view_transform >= RR_VIEW_FILMIC || gamma != 1.0f;
+// Raw at gamma 1 without dither).
+inline bool view_needs_pass(int view_transform, float gamma, float dither) {
+    return view_transform >= RR_VIEW_FILMIC || gamma != 1.0f || dither > 0.0f;
 }
 
 // rgba8 = quantize8(view(film sums * inv_spp * exposure_scale)) for every
 // pixel: fc.view_transform with a's LUTs and display gamma. srgb: the 8-bit
-// path's sRGB table (DevPaths::srgb_lut; Standard only).
+// path's sRGB table (DevPaths::srgb_lut; Standard only). a.dither > 0: the
+// dither of dither.h before the quantiser, which needs fc.W, fc.H (W H = npix)
+// and fc.div_w.
 void view_device(const FilmicArgs& a, const FrameConsts& fc, const float* srgb, const float4* film, uchar4* out,
                  hipStream_t st);
 
 // out[i] = display_gamma(in[i], 1 / g) on the host, g != 1 (rr_debug_display_gamma).
 void display_gamma_host(const float* in, size_t n, float g, float* out);
+
+// dither.h on the host: out[i] = sin_fixed(in[i]) (rr_debug_sin_fixed), and the
+// noise n of every pixel of a w x h image, rows top to bottom
+// (rr_debug_dither_noise).
+void sin_fixed_host(const float* in, size_t n, float* out);
+void dither_noise_host(int w, int h, float* out);
 
 }  // namespace rr

@@ -96,7 +96,11 @@ EXPORTS = [
     "rr_set_exr_depth", "rr_debug_exr32_device",
     "rr_set_color_mode", "rr_encode_image_mode", "rr_debug_encode_device",
     "rr_set_look", "rr_set_display_gamma", "rr_debug_view_device", "rr_debug_display_gamma", "rr_debug_scene_view",
+    "rr_set_dither", "rr_debug_dither_noise", "rr_debug_sin_fixed",
 ]
+
+# rr_set_dither's value for "the scene's render.dither_intensity" (include/rr.h)
+RR_DITHER_SCENE = -1.0
 
 # rr_set_color_mode's values (include/rr.h): the channels the file holds.
 RR_COLOR_SCENE, RR_COLOR_BW, RR_COLOR_RGB, RR_COLOR_RGBA = 0, 1, 3, 4
@@ -184,6 +188,9 @@ def lib() -> ctypes.CDLL:
         "rr_debug_view_device": (c_int, [P, f32p, i32, i32, i32, ctypes.c_float, u8p]),
         "rr_debug_display_gamma": (c_int, [f32p, ctypes.c_uint64, ctypes.c_float, f32p]),
         "rr_debug_scene_view": (c_int, [P, i32p, ctypes.c_char_p, i32, f32p]),
+        "rr_set_dither": (c_int, [P, ctypes.c_float]),
+        "rr_debug_dither_noise": (c_int, [i32, i32, f32p]),
+        "rr_debug_sin_fixed": (c_int, [f32p, ctypes.c_uint64, f32p]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -314,8 +321,10 @@ class RenderContext:
     """One HIP device (rr_ctx). Not thread-safe; one frame in flight at a time."""
 
     def __init__(self, device: int = 0, png_depth: int = 0, exr_depth: int = 0, color_mode=0,
-                 look: str | None = None, display_gamma: float = 0.0):
-        """png_depth: bits per sample of "PNG" frames (set_png_depth; 0: the scene's).
+                 look: str | None = None, display_gamma: float = 0.0, dither=None):
+        """dither: the dither of the 8-bit images (set_dither): an intensity in [0, 2] or
+        "scene"; None: the context's own (0, or what RR_DITHER says).
+        png_depth: bits per sample of "PNG" frames (set_png_depth; 0: the scene's).
         exr_depth: channel type of "OPEN_EXR" frames (set_exr_depth; 0: the scene's).
         color_mode: "BW" / "RGB" / "RGBA" of every file (set_color_mode; 0: the scene's).
         look: the look of Filmic frames (set_look; None: the scene's).
@@ -333,6 +342,8 @@ class RenderContext:
             self.set_look(look)
         if display_gamma:
             self.set_display_gamma(display_gamma)
+        if dither is not None:
+            self.set_dither(dither)
         self.device = device
 
     def close(self):
@@ -541,6 +552,13 @@ class RenderContext:
         (0, 5]; 0: the scene's render.gamma. 1 skips the step."""
         _check(lib().rr_set_display_gamma(self.handle, ctypes.c_float(gamma)), self.handle)
 
+    def set_dither(self, intensity=0.0):
+        """rr_set_dither: the dither of this context's 8-bit images, an intensity
+        in [0, 2] (0: none), or "scene" (RR_DITHER_SCENE) for each scene's
+        render.dither_intensity."""
+        v = RR_DITHER_SCENE if intensity == "scene" else float(intensity)
+        _check(lib().rr_set_dither(self.handle, ctypes.c_float(v)), self.handle)
+
     def view_device(self, rgba: np.ndarray, view_transform: int = 0, exposure_scale: float = 1.0) -> np.ndarray:
         """rr_debug_view_device: the (H, W, 4) uint8 image the 8-bit view pass
         makes of an (H, W, 4) float32 image of means, with this context's look
@@ -649,6 +667,23 @@ def display_gamma(values: np.ndarray, gamma: float) -> np.ndarray:
     out = np.zeros_like(v)
     _check(lib().rr_debug_display_gamma(_ptr(v.reshape(-1), ctypes.c_float), v.size, ctypes.c_float(gamma),
                                         _ptr(out.reshape(-1), ctypes.c_float)))
+    return out
+
+
+def sin_fixed(values: np.ndarray) -> np.ndarray:
+    """rr_debug_sin_fixed: the dither's fixed sine of float32 values, evaluated
+    on the host (no device needed)."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.zeros_like(v)
+    _check(lib().rr_debug_sin_fixed(_ptr(v.reshape(-1), ctypes.c_float), v.size, _ptr(out.reshape(-1), ctypes.c_float)))
+    return out
+
+
+def dither_noise(width: int, height: int) -> np.ndarray:
+    """rr_debug_dither_noise: the dither's noise n of every pixel, (height,
+    width) float32, rows top to bottom, evaluated on the host."""
+    out = np.zeros((int(height), int(width)), np.float32)
+    _check(lib().rr_debug_dither_noise(int(width), int(height), _ptr(out.reshape(-1), ctypes.c_float)))
     return out
 
 

@@ -448,11 +448,55 @@ int rr_set_look(rr_ctx* ctx, const char* name);
  * does. RR_EINVAL for a NULL ctx, gamma < 0 or gamma > 5 (Blender's range). */
 int rr_set_display_gamma(rr_ctx* ctx, float gamma);
 
+/* Dither of ctx's 8-bit images (Blender's image_settings.dither_intensity
+ * behind write_still, render-timing-script.py:83-92): noise added to the
+ * display-referred values, after the view transform and the display gamma,
+ * before they are quantised to bytes. For the pixel in column x (0 = left) and
+ * row r (0 = top) of a W x H frame, with intensity g:
+ *   yb = H - 1 - r                      (Blender's rows run bottom-up)
+ *   s = (float)x * (1.0f / (float)W),  t = (float)yb * (1.0f / (float)H)
+ *   h0 = fract(sin_fixed(s * 12.9898f + t * 78.233f) * 43758.5453f)
+ *   h1 = fract(sin_fixed(s * 19.9898f + t * 119.233f) * 798.5453f)
+ *   n = h0 + h1 - 0.5f                  (triangle-shaped, in [-0.5, 1.5))
+ *   code_k = quantize8(d_k + n * 0.0033f * g)   the same n for R, G, B; alpha 255
+ * each product and sum a float32 operation of its own, left to right, and
+ * sin_fixed a sine of fixed float32 operations (rr_debug_sin_fixed), so host
+ * and device give the same bits. The rule is restated from Blender 3.6's
+ * imbuf and not pinned against Blender's own files.
+ * intensity: a value in [0, 2] (Blender's range; 0: none), or RR_DITHER_SCENE
+ * for the scene's render.dither_intensity (0 where the scene has none). A new
+ * context's value is 0 whatever the scene says. It applies to whatever the
+ * 8-bit image feeds: JPEG files, 8-bit PNG files (host and device coder,
+ * BW luma included, which is taken of the dithered image), the rgba8 of
+ * rr_render_frame_to_memory and rr_debug_view_device (where RR_DITHER_SCENE
+ * means none). 16-bit PNG and OPEN_EXR files are not dithered. A frame with an
+ * intensity above 0 takes the view pass whatever its view; at 0 a frame's
+ * device work is what it was before there was a setting. rr_create reads
+ * RR_DITHER (a number, or "scene") from the environment the same way. Applies
+ * to frames submitted after the call; frames in flight keep theirs. RR_EINVAL
+ * for a NULL ctx, NaN or any other value. */
+#define RR_DITHER_SCENE (-1.0f)
+int rr_set_dither(rr_ctx* ctx, float intensity);
+
+/* The n of rr_set_dither for every pixel of a w x h image, evaluated on the
+ * host (no device needed; write_still's dither, render-timing-script.py:83-92):
+ * out receives w * h floats, rows top to bottom. RR_EINVAL for a NULL out or a
+ * size below 1. Exported for tests. */
+int rr_debug_dither_noise(int32_t w, int32_t h, float* out /* w*h, rows top to bottom */);
+
+/* out[i] = sin_fixed(in[i]), the sine of rr_set_dither (write_still's dither,
+ * render-timing-script.py:83-92), evaluated on the host: the argument less the
+ * nearest multiple of pi/2 (pi/2 in three parts), then a polynomial of sin or
+ * cos on [-pi/4, pi/4]. Within 2^-18 of sin for |in[i]| <= 256 (the dither's
+ * arguments stay below 139.3); 0 for |in[i]| > 8192 and NaN. Exported for
+ * tests. */
+int rr_debug_sin_fixed(const float* in, uint64_t n, float* out);
+
 /* Run the 8-bit view pass (the one frames of the Filmic family and frames
- * with a display gamma take after rendering) on a float RGBA image of the
- * caller's (width * height * 4 floats, taken as means: spp = 1): value *
+ * with a display gamma or a dither take after rendering) on a float RGBA image
+ * of the caller's (width * height * 4 floats, taken as means: spp = 1): value *
  * exposure_scale, view_transform (RR_VIEW_STANDARD .. RR_VIEW_FALSE_COLOR)
- * with ctx's look and display gamma, 8-bit quantisation, alpha 255, into
+ * with ctx's look, display gamma and dither, 8-bit quantisation, alpha 255, into
  * rgba8_out (width * height * 4 bytes). A view or look whose LUT is not loaded
  * is RR_EINVAL here. Exported for tests. */
 int rr_debug_view_device(rr_ctx* ctx, const float* rgba, int32_t width, int32_t height,
