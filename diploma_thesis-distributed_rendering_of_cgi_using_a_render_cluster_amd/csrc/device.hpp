@@ -177,7 +177,8 @@ struct DevFrame {
     DevBuf<float> tile_slab;   // k_tiles: per sliced tile, one group sum plane per sample group
     DevBuf<uint32_t> tile_ctrs;  // k_tiles: work-unit counters, one 128-B line per shard
     // kept from frame to frame: the next order is built from the owner's last costs
-    DevBuf<uint32_t> tile_cost;  // k_tiles: per screen tile, the real-time ticks its units took (last launch)
+    DevBuf<uint32_t> tile_cost;  // k_tiles: per screen tile, the real-time ticks its units took (last launch); then,
+                                 // per screen tile, the samples its covered body ran (counting launches, tiles.hip)
     DevBuf<int32_t> tile_order;  // k_tiles: box tiles by descending tile_cost (k_tile_order)
     DevBuf<float> lights, materials;
     DevBuf<float> mat_lut;             // material tables (build_material_lut), uploaded when they change

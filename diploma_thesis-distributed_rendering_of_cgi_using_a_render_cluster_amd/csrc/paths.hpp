@@ -397,6 +397,184 @@ __device__ __forceinline__ void shade(const FC& fc, int bounce, const View& v, f
     out.lob = lob + (glossy ? kGlossyOne : 1u);
 }
 
+// shade() for k_tiles' tiles that one triangle covers (tiles.hip tile_mask,
+// DESIGN.md §4): every lane of the wave shades the same triangle `tri` of an
+// LDS-resident scene, seen from the same side (`flip`: from behind, what
+// shade() takes from the sign of dot(N, d)), and the scene has at most one
+// light (the caller checks fc.n_lights <= 1). What shade() fetches by the
+// lane's own h.idx and light pick — the staged normal and material word, the
+// derived material, the table base, the shading frame, the light's record —
+// is read here at wave-uniform addresses, the side, the emission test and the
+// light's kind become wave-uniform branches, and the pick, the flip's selects
+// and the per-lane hull bit are gone. `hit`: this lane's ray met the triangle
+// inside its clip range; else the miss term, as shade() for h.idx < 0. Of h
+// only h.t is read. Every float operation on what varies per lane is
+// shade()'s, in shade()'s order, so the radiance has the same bits; shade()
+// itself is left as it is so that the kernels that call it compile to the
+// same instructions. A change of shade() is to be made here as well
+// (tests/test_gpu_tile_covered.py compares the two bit for bit).
+//
+// Held: where the unit's values live. CoveredInLoop: read from LDS at the
+// uniform addresses in every sample (kept, RR_TILES_COVERED=1). CoveredHeld:
+// read once per work unit by the caller into wave-uniform registers
+// (RR_TILES_COVERED=2; measured, not kept: profiles/tile_covered.md).
+struct CoveredInLoop {
+    static constexpr bool kHeld = false;
+};
+struct CoveredHeld {
+    static constexpr bool kHeld = true;
+    float3 N;        // the side seen (flipped already)
+    int mid;
+    bool esc;        // that side is a hull side
+    Mat m;
+    float3 tb, bb;   // the staged frame of that side
+    float lt[11];    // the light's record (n_lights == 1)
+};
+template <typename Shadow, typename FC, typename Cont, typename Held = CoveredInLoop>
+__device__ __forceinline__ void shade_covered(const FC& fc, int bounce, const LdsView& v, int tri, bool flip, bool hit,
+                                              float3 o, float3 d, float3 T, uint32_t lob, const Hit& h, uint32_t key,
+                                              float3& L, ShadeOut& out, const Shadow& trace_shadow,
+                                              const Cont& on_cont, const Held& held = Held{}) {
+    static_assert(Shadow::kInline, "the shadow ray is traced in place");
+    out.cont = false;
+    out.shadow = false;
+    out.esc = false;
+    if (!hit) {
+        float3 c = mul3(T, fc.world);
+        if (bounce > 0) c = clamp_contrib(c, fc.clamp_indirect);
+        add_to(L, c);
+        return;
+    }
+    float3 N;
+    int mid;
+    bool esc;
+    Mat m;
+    if constexpr (Held::kHeld) {
+        N = held.N;
+        mid = held.mid;
+        esc = held.esc;
+        m = held.m;
+    } else {
+        const float4 nm = lds_ld4(v.nrm + tri);  // staged: norm3(cross3(e1, e2)), material id | hull flags
+        N = xyz(nm);
+        mid = f2i(nm.w) & ((1 << kHullShift) - 1);
+        const uint32_t hull = (uint32_t)f2i(nm.w) >> kHullShift;
+        m = view_mat(v, mid);
+        if (flip) N = mk3(-N.x, -N.y, -N.z);
+        esc = ((hull >> (flip ? 1 : 0)) & 1u) != 0u;
+    }
+    __builtin_assume(mid >= 0 && mid < 4096);
+    const auto lut = v.lut + kMatLutStride * mid;
+    const float t = h.t;
+    const float3 P = madd3(o, d, t);
+    out.esc = esc;
+    const float3 wo = mk3(-d.x, -d.y, -d.z);
+    if (m.emission.x != 0.0f || m.emission.y != 0.0f || m.emission.z != 0.0f) {
+        float3 c = mul3(T, m.emission);
+        if (bounce > 0) c = clamp_contrib(c, fc.clamp_indirect);
+        add_to(L, c);
+    }
+    if (path_capped(fc, bounce, lob)) return;
+    const BsdfView vw = bsdf_view(m, lut, N, wo);
+    const uint32_t dim0 = 2u + (uint32_t)(kDimsPerBounce * bounce);
+    float u_light, u_lobe;
+    rng2(key, dim0, u_light, u_lobe);
+    const float3 Po = offset_ray(P, N);
+    if (fc.n_lights > 0) {  // the one light: every u_light picks it
+        const auto lt = [&](int k) {
+            if constexpr (Held::kHeld) return held.lt[k];
+            else return v.lights[k];
+        };
+        float3 wi, Li;
+        float dist;
+        if (lt(0) == 0.0f) {  // point / disk light
+            const float3 lp = mk3(lt(1), lt(2), lt(3));
+            const float radius = lt(7);
+            const float3 I = mk3(lt(8), lt(9), lt(10));
+            const float3 tl = sub3(lp, P);
+            const float dl2 = dot3(tl, tl);
+            if (radius > 0.0f) {
+                float sl, rl;
+                sqrt_rcp_any(dl2, sl, rl);
+                const float3 wl = scl3(tl, rl);
+                float3 b1, b2;
+                make_onb(wl, b1, b2);
+                float dx, dy;
+                float u1, u2;
+                rng2(key, dim0 + 1u, u1, u2);
+                concentric_disk(u1, u2, dx, dy);
+                dx = dx * radius;
+                dy = dy * radius;
+                const float3 sp = madd3(madd3(lp, b1, dx), b2, dy);
+                const float3 ts = sub3(sp, P);
+                const float ds2 = dot3(ts, ts);
+                float id;
+                sqrt_rcp_any(ds2, dist, id);
+                wi = scl3(ts, id);
+                const float cl = fabsf(dot3(wl, wi));
+                Li = scl3(I, cl * id * id);
+            } else {
+                float id;
+                sqrt_rcp_any(dl2, dist, id);
+                wi = scl3(tl, id);
+                Li = scl3(I, 1.0f / dl2);
+            }
+        } else {  // sun: delta direction, irradiance
+            wi = mk3(-lt(4), -lt(5), -lt(6));
+            dist = kFltMax;
+            Li = mk3(lt(8), lt(9), lt(10));
+        }
+        const float cosN = dot3(N, wi);
+        if (cosN > 0.0f) {
+            float pdf;
+            const float3 f = bsdf_eval_v(m, lut, vw, N, wo, wi, pdf);  // f * cosN
+            const float k = (float)fc.n_lights;
+            float3 c = mk3(T.x * f.x * k * Li.x, T.y * f.y * k * Li.y, T.z * f.z * k * Li.z);
+            if (bounce > 0) c = clamp_contrib(c, fc.clamp_indirect);
+            if (max3f(c) > 0.0f) {
+                out.shadow = true;
+                if (esc || !trace_shadow(Po, wi, dist)) add_to(L, c);
+            }
+        }
+    }
+    // continue the path
+    float3 wi, f;
+    float pdf;
+    bool glossy;
+    float u_b1, u_b2;
+    rng2(key, dim0 + 4u, u_b1, u_b2);
+    float3 ft, fb;  // the staged frame of the side seen
+    if constexpr (Held::kHeld) {
+        ft = held.tb;
+        fb = held.bb;
+    } else {
+        const lds_f4w* fr = v.onb + kOnbF4 * tri + (flip ? 2 : 0);
+        const float4 tb = lds_ld4(fr), bb = lds_ld4(fr + 1);
+        ft = xyz(tb);
+        fb = mk3(tb.w, bb.x, bb.y);
+    }
+    if (!bsdf_sample_onb(m, lut, vw, N, ft, fb, wo, u_lobe, u_b1, u_b2, wi, f, pdf, glossy))
+        return;
+    const float k = 1.0f / pdf;  // f = f * cosL already
+    T = mk3(T.x * f.x * k, T.y * f.y * k, T.z * f.z * k);
+    if (!(max3f(T) > 0.0f)) return;
+    if (bounce >= kRrStartBounce) {
+        const float q = fminf(max3f(T), 1.0f);
+        if (rng(key, dim0 + 6u) >= q) return;
+        const float iq = 1.0f / q;
+        T = mk3(T.x * iq, T.y * iq, T.z * iq);
+    }
+    out.cont = true;
+    if constexpr (Cont::kInline) {
+        on_cont(Po, wi, T, lob + (glossy ? kGlossyOne : 1u), esc, L);
+        return;
+    }
+    out.o = Po;
+    out.d = wi;
+    out.T = T;
+    out.lob = lob + (glossy ? kGlossyOne : 1u);
+}
+
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kMaxBlocksPerCu = 8;  // grid cap per CU
 

@@ -1787,7 +1787,10 @@ int rr_debug_tile_costs(rr_ctx* c, int32_t capacity, uint32_t* costs, int32_t* o
         *n_tiles = (int32_t)n;
         const size_t m = std::min<size_t>(n, (size_t)capacity);
         if (m > 0) {
-            RR_HIP(hipMemcpy(costs, f.tile_cost.ptr, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            // the cost buffer is longer than the order's: behind the frame's tile costs it holds, per tile, the
+            // samples a counting launch's covered body ran (tiles.hip); a caller with room gets those words too
+            const size_t mc = std::min<size_t>(f.tile_cost.cap, (size_t)capacity);
+            RR_HIP(hipMemcpy(costs, f.tile_cost.ptr, mc * sizeof(uint32_t), hipMemcpyDeviceToHost));
             RR_HIP(hipMemcpy(order, f.tile_order.ptr, m * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
         const size_t nu = std::min<size_t>((size_t)unit_capacity, kUnitLog);

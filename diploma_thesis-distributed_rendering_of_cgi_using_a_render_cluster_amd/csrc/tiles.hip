@@ -370,14 +370,26 @@ RR_D void camera_hit(const LdsView& v, uint64_t m0, uint64_t m1, float3 d, float
 // in the staged coefficients plus that of evaluating them here. A triangle
 // without a plane (zeros) has lo = hi = 0: it neither covers nor goes, and A
 // itself stays since hi_A >= lo_A.
+//
+// Covered by one: `covered` receives the covering triangle A
+// when the final mask holds A alone, else -1 (wave-uniform). Then every sample
+// position of the tile lies a pixel and more inside A's edges, in front of the
+// camera and inside the clip range, and nothing else can be hit: the sample
+// loop of tiles_body takes its single-triangle body. No arithmetic of its own:
+// the index that set `best`, and a popcount.
+#ifndef RR_TILES_COVERED
+#define RR_TILES_COVERED 1  // 0: the single-triangle body compiled out (the reference of tests and A/B runs);
+                            // 2: its per-unit values held in registers (step (b), measured and not kept)
+#endif
 RR_D void tile_mask(const FrameConsts& fc, const LdsView& v, int n_tris, float x0, float x1, float y0, float y1,
-                    uint64_t& m0, uint64_t& m1) {
+                    uint64_t& m0, uint64_t& m1, int& covered) {
     const float r = fc.filter_reach;
     const float X0 = x0 + 0.5f - r, X1 = x1 + 0.5f + r, Y0 = y0 + 0.5f - r, Y1 = y1 + 0.5f + r;
     const float Wf = (float)fc.W, Hf = (float)fc.H;
     constexpr float kEps = 0x1p-10f;
     uint64_t a = 0, b = 0;
     float best = 0.0f;  // the largest lo_A of a covering triangle (0: none covers)
+    int best_i = -1;    // ... and that triangle
     for (int i = 0; i < n_tris; ++i) {
         const float4 q = lds_ld4(v.cam + kCamF4 * i + kCamRect);
         bool in = !(q.y < X0 || q.x > X1 || q.w < Y0 || q.z > Y1);
@@ -398,8 +410,10 @@ RR_D void tile_mask(const FrameConsts& fc, const LdsView& v, int n_tris, float x
                 const float e = kEps * (fabsf(pl[0]) * Wf + fabsf(pl[1]) * Hf + fabsf(pl[2]));
                 const float lo = pl[0] * (pl[0] > 0.0f ? X0 : X1) + pl[1] * (pl[1] > 0.0f ? Y0 : Y1) + pl[2] - e;
                 const float hi = pl[0] * (pl[0] > 0.0f ? X1 : X0) + pl[1] * (pl[1] > 0.0f ? Y1 : Y0) + pl[2] + e;
-                if (lo > 0.0f && hi * fc.clip_start * (1.0f + kEps) < 1.0f && lo * fc.clip_end > 1.0f + kEps)
+                if (lo > 0.0f && hi * fc.clip_start * (1.0f + kEps) < 1.0f && lo * fc.clip_end > 1.0f + kEps) {
+                    if (lo > best) best_i = i;
                     best = fmaxf(best, lo);
+                }
             }
         }
     }
@@ -420,6 +434,11 @@ RR_D void tile_mask(const FrameConsts& fc, const LdsView& v, int n_tris, float x
          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
     m1 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+    covered = -1;
+    if (RR_TILES_COVERED && best_i >= 0 && __popcll(m0) + __popcll(m1) == 1) {
+        const int only = m0 ? (int)__builtin_ctzll(m0) : 64 + (int)__builtin_ctzll(m1);
+        covered = only == __builtin_amdgcn_readfirstlane(best_i) ? only : -1;
+    }
 }
 
 // K-tiles (LDS-resident scenes): one wave per 8x8 pixel tile
@@ -713,7 +732,8 @@ struct TileSlices {
     size_t floats;     // slab floats per tile: 192 * groups
     float* slab;
     const int32_t* order;  // box tiles in hand-out order (k_tile_order)
-    uint32_t* cost;        // per screen tile: real-time ticks of its units, for the next launch's order
+    uint32_t* cost;        // per screen tile: real-time ticks of its units, for the next launch's order; after
+                           // them, per screen tile: samples run by the covered body (counting launches only)
 };
 namespace {
 
@@ -805,8 +825,9 @@ RR_D void tiles_body(const FrameConsts& fc, const LdsView& v, uint32_t* __restri
         const int s_lo = nk > 1 ? k * kFilmGroup : 0;
         const int s_hi = nk > 1 ? min(fc.spp_total, s_lo + kFilmGroup) : fc.spp_total;
         uint64_t cm0, cm1;
+        int cov;
         tile_mask(fc, v, fc.n_tris, (float)(tx * kTile), (float)(tx * kTile + kTile - 1), (float)(ty * kTile),
-                  (float)(ty * kTile + kTile - 1), cm0, cm1);
+                  (float)(ty * kTile + kTile - 1), cm0, cm1, cov);
         const uint32_t pk = pixel_key(fc.seed, (uint32_t)pix);
         // no triangle can be hit from this tile (wave-uniform): every sample is
         // the world term, summed as the sample loop would (0 + world + ...)
@@ -826,7 +847,95 @@ RR_D void tiles_body(const FrameConsts& fc, const LdsView& v, uint32_t* __restri
             add_to(P, fc.world);
             group_end(s);
         }
-        for (int s = s_lo; s < s_run; ++s) {
+        // Covered tiles: triangle `cov` alone is in the mask and
+        // covers every sample position of the tile, all 64 pixels lie inside
+        // the image, no sample position lies outside the screen rectangle
+        // (the expanded tile is inside it) and the scene has at most one
+        // light. Then every lane is valid, no ray is culled and every ray
+        // meets `cov`: the body below is the general one further down without
+        // the predicates, the mask loop and the per-lane triangle index — the
+        // same float operations per sample in the same order. A ray that
+        // fails the test or the clip range all the same is a miss, as there.
+        bool covered = cov >= 0 && tx * kTile + kTile <= fc.W && ty * kTile + kTile <= fc.H && fc.n_lights <= 1;
+        if (covered && cull.on) {
+            const float r = fc.filter_reach, cx = (float)(tx * kTile) + 0.5f, cy = (float)(ty * kTile) + 0.5f;
+            covered = cx - r >= cull.r[0] && cx + (float)(kTile - 1) + r <= cull.r[1] && cy - r >= cull.r[2] &&
+                      cy + (float)(kTile - 1) + r <= cull.r[3];
+        }
+        int s_gen = s_run;  // the samples left to the general body: none of a covered tile
+        if (RR_TILES_COVERED && covered) {
+            // the side every ray sees: dot(N, d) has the sign of dot(N, v0 - cam_pos) wherever the ray meets
+            // the plane in front of the camera (w > 0 over the tile), and tri_inv_depth_plane admitted the
+            // triangle only with |dot(N, v0 - cam_pos)| >= 2^-4 |v0 - cam_pos|
+            const float4 nm = lds_ld4(v.nrm + cov), a0 = lds_ld4(v.cam + kCamF4 * cov);  // a0 = rot3(v0 - cam_pos, 0)
+            const bool flip = uniform_i(dot3(xyz(nm), mk3(a0.z, a0.x, a0.y)) > 0.0f ? 1 : 0) != 0;
+#if RR_TILES_COVERED == 2
+            // step (b), measured and not kept: the unit's values read once, held wave-uniform across the loop
+            CoveredHeld held;
+            {
+                const auto uf3 = [](float3 a) { return mk3(uniform_f(a.x), uniform_f(a.y), uniform_f(a.z)); };
+                const int word = uniform_i(f2i(nm.w));
+                held.mid = word & ((1 << kHullShift) - 1);
+                held.esc = ((((uint32_t)word >> kHullShift) >> (flip ? 1 : 0)) & 1u) != 0u;
+                held.N = uf3(flip ? mk3(-nm.x, -nm.y, -nm.z) : xyz(nm));
+                const Mat m = view_mat(v, held.mid);
+                held.m.base = uf3(m.base);
+                held.m.roughness = uniform_f(m.roughness);
+                held.m.emission = uf3(m.emission);
+                held.m.model = uniform_i(m.model);
+                held.m.alpha = uniform_f(m.alpha);
+                held.m.a2 = uniform_f(m.a2);
+                held.m.kd0 = uniform_f(m.kd0);
+                held.m.spec_on = uniform_i(m.spec_on);
+                held.m.cspec0 = uf3(m.cspec0);
+                held.m.metallic = held.m.specular = held.m.ior = 0.0f;
+                const lds_f4w* fr = v.onb + kOnbF4 * cov + (flip ? 2 : 0);
+                const float4 tb = lds_ld4(fr), bb = lds_ld4(fr + 1);
+                held.tb = uf3(xyz(tb));
+                held.bb = uf3(mk3(tb.w, bb.x, bb.y));
+                for (int k = 0; k < 11; ++k) held.lt[k] = fc.n_lights > 0 ? uniform_f(v.lights[k]) : 0.0f;
+            }
+#else
+            const CoveredInLoop held;
+#endif
+            for (int s = s_lo; s < s_hi; ++s) {
+                const uint32_t key = sample_key(pk, (uint32_t)s);
+                float3 o, d, L = mk3(0.0f, 0.0f, 0.0f);
+                float tmin, tmax;
+                camera_ray_xy(fc, v.filter, px, py, key, o, d, tmin, tmax);
+                n_t0 += 64u;
+                const Shear sh = make_shear_unit(d);
+                if (kCount) ++cp.tris;
+                const lds_f4w* q = v.cam + kCamF4 * cov + 3 * sh.kz;  // this ray's permutation
+                const float4 ca = lds_ld4(q), cb = lds_ld4(q + 1), cc = lds_ld4(q + 2);
+                Hit h;
+                set_miss(h, tmax);
+                float t = tmax, u, vv;
+                bool hit = woop_core(sh, xyz(ca), xyz(cb), xyz(cc), t, u, vv);
+                hit = hit && closer(t, f2i(ca.w), tmin, h);
+                h.t = hit ? t : tmax;
+                ShadeOut so;
+                const ShadeConsts sc{fc.world, fc.clamp_indirect, fc.max_bounces, fc.max_diffuse, fc.max_glossy,
+                                     fc.n_lights, fc.n_tris};
+                if constexpr ((RR_TILES_CONT_INPLACE & (kWhole ? 1 : 2)) != 0) {
+                    shade_covered(fc, 0, v, cov, flip, hit, o, d, mk3(1.0f, 1.0f, 1.0f), 0u, h, key, L, so,
+                                  InlineShadow<kCount>{v, fc.n_tris, tt}, TileCont<kCount>{sc, v, tt, key}, held);
+                } else {
+                    shade_covered(fc, 0, v, cov, flip, hit, o, d, mk3(1.0f, 1.0f, 1.0f), 0u, h, key, L, so,
+                                  InlineShadow<kCount>{v, fc.n_tris, tt}, EmitCont{}, held);
+                    if (so.cont) TileCont<kCount>{sc, v, tt, key}(so.o, so.d, so.T, so.lob, so.esc, L);
+                }
+                n_c0 += wave_count(so.cont);
+                n_s0 += wave_count(so.shadow);
+                add_to(P, L);
+                group_end(s);
+            }
+            s_gen = s_lo;
+            // counting launches: the samples this body ran, per tile, in the second half of the cost buffer
+            // (rr_debug_tile_costs hands out the whole buffer; tests/test_gpu_tile_covered.py reads it)
+            if (kCount && lane == 0) atomicAdd(&sl.cost[to.n + ty * to.tx + tx], (uint32_t)(s_hi - s_lo));
+        }
+        for (int s = s_lo; s < s_gen; ++s) {
             const uint32_t key = sample_key(pk, (uint32_t)s);
             float3 o = mk3(0.0f, 0.0f, 0.0f), d = o, L = o;
             float tmin = 0.0f, tmax = -1.0f;
@@ -1129,10 +1238,12 @@ void render_tiles_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f
     fc.first_sample = 0;
     fc.spp_chunk = base.spp_total;
     uint32_t* tot = reinterpret_cast<uint32_t*>(f.counters.ptr);
-    if (f.tile_cost.cap < (size_t)tiles) {  // costs of a new size start at 0 (the first order is the box's)
-        f.tile_cost.ensure((size_t)tiles);
+    if (f.tile_cost.cap < 2 * (size_t)tiles) {  // costs of a new size start at 0 (the first order is the box's)
+        f.tile_cost.ensure(2 * (size_t)tiles);
         RR_HIP(hipMemsetAsync(f.tile_cost.ptr, 0, sizeof(uint32_t) * tiles, st));
     }
+    if (o.count_traversal)  // the covered body's sample counts of this launch (tiles_body)
+        RR_HIP(hipMemsetAsync(f.tile_cost.ptr + tiles, 0, sizeof(uint32_t) * tiles, st));
     f.tile_order.ensure((size_t)tiles);
     // units: one per (box tile, sample group) when the frame runs alone, so
     // the heaviest tiles do not finish the launch on a nearly empty chip;

@@ -622,11 +622,13 @@ class RenderContext:
         _check(lib().rr_debug_fastmath_check(self.handle, int(lo), int(n), out), self.handle)
         return tuple(int(v) for v in out)
 
-    def tile_costs(self, capacity: int = 1 << 20, units: int = 1 << 16):
+    def tile_costs(self, capacity: int = 1 << 20, units: int = 1 << 16, raw: bool = False):
         """rr_debug_tile_costs: (per-tile real-time ticks of the last tile frame's
         units, the box tiles' hand-out order it used, each of the slot buffers'
         length; per box unit u its (start, end) ticks when that frame was a
-        counting frame, shape (units, 2))."""
+        counting frame, shape (units, 2)). raw: the cost array untrimmed (all
+        `capacity` words): behind the frame's own tile count T it holds, at
+        [T, 2T), the samples a counting launch's covered body ran per tile."""
         costs = np.zeros(capacity, np.uint32)
         order = np.zeros(capacity, np.int32)
         log = np.zeros((max(units, 1), 2), np.uint64)
@@ -635,7 +637,7 @@ class RenderContext:
                                          _ptr(order, ctypes.c_int32), ctypes.byref(n),
                                          _ptr(log, ctypes.c_uint64), units), self.handle)
         m = min(int(n.value), capacity)
-        return costs[:m], order[:m], log[:units]
+        return (costs if raw else costs[:m]), order[:m], log[:units]
 
     def trace(self, scene: Scene, frame: int, rays: np.ndarray, width: int = 0):
         """rr_debug_trace; width 0 = the hierarchy the frame kernels use."""
