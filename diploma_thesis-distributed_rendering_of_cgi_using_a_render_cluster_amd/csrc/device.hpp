@@ -189,6 +189,9 @@ struct DevFrame {
     DevBuf<int16_t> jpeg_coeffs;
     DevBuf<uint32_t> jpeg_blk, jpeg_scratch;
     DevBuf<uint32_t> deflate_scratch;
+    // PNG frames with the adaptive filter (rr_set_png_compression): a filter type per image row, and at 16 bits
+    // the raw big-endian scanlines (png16.hip k_png16_raw); grow-only, untouched by legacy frames
+    DevBuf<uint8_t> png_ftype, png_raw;
     // written by render_frame_device, about the frame it enqueued
     int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log (trav_counts)
@@ -324,6 +327,10 @@ struct DeflatePlan;
 bool png_plan(int W, int H, int C, DeflatePlan& p);
 void png_encode_device(const uint8_t* d_rgba, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                        uint32_t* host_tab, hipStream_t st);
+// The same file with libpng's adaptive filter on every row (rr_set_png_compression
+// 0 .. 100; png_filter.h): same plan. ftype: p.H bytes, the rows' filter types.
+void png_encode_device_adaptive(const uint8_t* d_rgba, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* ftype,
+                                uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 // OpenEXR (exr.hip): the film's means as half-float A, B, G, R planes in ZIP
 // chunks of kDeflateBandRows scanlines (half conversion, plane split, byte
@@ -379,6 +386,11 @@ struct Png16Front {
 };
 void png16_encode_device(const Png16Front& f, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                          uint32_t* host_tab, hipStream_t st);
+// The same file with the adaptive filter (as png_encode_device_adaptive). raw:
+// 2C W H bytes, the raw scanlines (below 2 GB, as the plan's stream is);
+// ftype: p.H bytes.
+void png16_encode_device_adaptive(const Png16Front& f, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* raw,
+                                  uint8_t* ftype, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 // Per chunk: one pair per bounce b = 0..max_bounces {paths entering b+1,
 // shadow rays of b}, one pair of slack, then the words below.

@@ -9,6 +9,7 @@
 #include "image_io.hpp"
 
 #include "grey.h"
+#include "png_filter.h"
 
 #include <zlib.h>
 
@@ -473,6 +474,11 @@ bool encode_jpeg_coeffs(const int16_t* coeffs, int W, int H, int quality, std::v
     return true;
 }
 
+int png_zlib_level(int compression) {
+    const int level = (int)((float)compression / 11.1111f);
+    return std::min(std::max(level, 0), 9);
+}
+
 // PNG (8-bit RGBA, filter Sub on every row). The zlib stream is deflated in
 // bands of rows on host threads, pigz-style: each band is a raw deflate stream
 // ended with a sync flush (an empty stored block, byte-aligned), the last one
@@ -482,8 +488,13 @@ bool encode_jpeg_coeffs(const int16_t* coeffs, int W, int H, int quality, std::v
 // and no correctness. A 1080p 02 frame: one thread took most of the frame's
 // time on the host, more than the GPU's.
 // channels: 4 RGBA (colour type 6), 3 RGB (2), 1 grey (0, the grey code of grey.h).
-bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, int level, int threads, int channels) {
+// adaptive (rr_set_png_compression 0 .. 100): libpng's adaptive filter on every
+// row (png_filter.h) and the zlib header's level hint as zlib writes it; a row
+// is filtered against the image's row above, also across the thread bands.
+bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, int level, int threads, int channels,
+                bool adaptive) {
     if (W <= 0 || H <= 0 || (channels != 1 && channels != 3 && channels != 4)) return false;
+    if (level < 0 || level > 9) return false;
     std::vector<uint8_t> packed;  // the image with the file's channels
     if (channels != 4) {
         packed.resize((size_t)W * H * channels);
@@ -507,6 +518,13 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
         for (int y = y0; y < y1; ++y) {
             uint8_t* dst = &raw[(stride + 1) * y];
             const uint8_t* src = rgba + stride * y;
+            if (adaptive) {
+                const uint8_t* up = y > 0 ? src - stride : nullptr;
+                const uint32_t type = png_pick_row(src, up, stride, C, (size_t)H);
+                dst[0] = (uint8_t)type;
+                png_filter_row(type, src, up, stride, C, dst + 1);
+                continue;
+            }
             dst[0] = 1;
             for (size_t x = 0; x < stride; ++x) dst[1 + x] = (uint8_t)(src[x] - (x >= C ? src[x - C] : 0));
         }
@@ -534,7 +552,9 @@ bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, in
         for (int b = 0; b < bands; ++b) pool.emplace_back(band, b);
         for (auto& t : pool) t.join();
     }
-    std::vector<uint8_t> z = {0x78, 0x01};  // zlib header: deflate, 32 KB window, no dictionary
+    // zlib header: deflate, 32 KB window, no dictionary; FLEVEL says 0 ("fastest") unless the setting chose the level
+    const uint8_t flg = !adaptive || level < 2 ? 0x01 : level < 6 ? 0x5E : level == 6 ? 0x9C : 0xDA;
+    std::vector<uint8_t> z = {0x78, flg};
     uLong a = adler32(0L, Z_NULL, 0);
     for (int b = 0; b < bands; ++b) {
         if (!ok[b]) return false;

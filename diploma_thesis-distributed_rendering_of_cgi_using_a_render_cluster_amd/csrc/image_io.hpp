@@ -34,9 +34,14 @@ void jpeg_huff_tables(uint32_t out[4 * 256]);
 bool encode_jpeg(const uint8_t* rgba, int W, int H, int quality, std::vector<uint8_t>& out, int threads = 0,
                  bool grey = false);
 // channels: what the file holds of the RGBA8 image: 4 RGBA (colour type 6), 3
-// RGB (2), 1 the grey code of grey.h (0).
+// RGB (2), 1 the grey code of grey.h (0). level: zlib's, 0 (stored blocks) to
+// 9. adaptive: every row takes libpng's adaptive filter (png_filter.h), against
+// the image's row above whatever the thread bands; false: Sub on every row.
 bool encode_png(const uint8_t* rgba, int W, int H, std::vector<uint8_t>& out, int level = 1, int threads = 0,
-                int channels = 4);
+                int channels = 4, bool adaptive = false);
+// zlib's level of Blender's image_settings.compression (0 .. 100):
+// (int)(compression / 11.1111f), clamped to 0 .. 9.
+int png_zlib_level(int compression);
 // The PNG file around a zlib stream coded on the device (png.hip): z = 78 01 +
 // the bands' deflate pieces; band_tab = {Adler-32, filtered bytes} per band,
 // combined here into the stream's Adler-32. Signature, IHDR, one IDAT, IEND.

@@ -8,12 +8,16 @@
 // pixel) before it. The bands are the pieces of one zlib stream with the stored
 // fallback; the match distances are 1 (zero runs), C (the pixel period) and
 // C W + 1 (the filtered row above).
+// With rr_set_png_compression 0 .. 100 a row takes libpng's adaptive filter
+// instead (png_filter.h): k_png_pick chooses every row's type, and
+// PngAdaptiveFront forms the rows (png_adaptive.hpp); same plan, same coder.
 // Same image -> same bytes.
 #include <hip/hip_runtime.h>
 
 #include "deflate.hpp"
 #include "device.hpp"
 #include "grey.h"
+#include "png_adaptive.hpp"
 
 namespace rr {
 
@@ -39,6 +43,16 @@ struct Png8Front {
             v = (png8_byte<C>(src, x - 1) - (x > (uint32_t)C ? png8_byte<C>(src, x - 1 - C) : 0u)) & 0xFFu;
         }
         return v;
+    }
+};
+
+// The raw scanlines of the adaptive filter, read in place from the RGBA8 frame.
+template <int C>
+struct Png8Rows {
+    const uint8_t* __restrict__ rgba;
+    uint32_t W;
+    __device__ __forceinline__ uint32_t operator()(uint32_t row, uint32_t q) const {
+        return png8_byte<C>(rgba + (size_t)row * ((size_t)W * 4), q);
     }
 };
 
@@ -68,6 +82,17 @@ void png_encode_device(const uint8_t* d_rgba, int C, const DeflatePlan& p, uint3
     if (C == 1) k_deflate_front<<<grid, 256, 0, st>>>(Png8Front<1>{d_rgba}, p, c.filt, c.adler_part);
     else if (C == 3) k_deflate_front<<<grid, 256, 0, st>>>(Png8Front<3>{d_rgba}, p, c.filt, c.adler_part);
     else k_deflate_front<<<grid, 256, 0, st>>>(Png8Front<4>{d_rgba}, p, c.filt, c.adler_part);
+    deflate_bands_device(p, c, st);
+    deflate_gather_device(p, c, host_out, host_tab, st);
+}
+
+void png_encode_device_adaptive(const uint8_t* d_rgba, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* ftype,
+                                uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
+    const DeflateBufs c = deflate_carve(p, scratch);
+    const uint32_t W = (uint32_t)p.W;
+    if (C == 1) png_adaptive_front_device<1>(Png8Rows<1>{d_rgba, W}, p, c, ftype, st);
+    else if (C == 3) png_adaptive_front_device<3>(Png8Rows<3>{d_rgba, W}, p, c, ftype, st);
+    else png_adaptive_front_device<4>(Png8Rows<4>{d_rgba, W}, p, c, ftype, st);
     deflate_bands_device(p, c, st);
     deflate_gather_device(p, c, host_out, host_tab, st);
 }

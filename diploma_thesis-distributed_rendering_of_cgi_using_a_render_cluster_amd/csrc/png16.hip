@@ -30,6 +30,12 @@
 //    2 (equal neighbouring samples: grey pixels, and every zero run), 8 (the
 //    pixel period) and 8W + 1 (the filtered row above).
 //  - deflate.hip's scan + gather into pinned host memory.
+// With rr_set_png_compression 0 .. 100 a row takes libpng's adaptive filter
+// instead (png_filter.h). A raw byte costs a view-transform evaluation and an
+// adaptive row needs each under five filters with three neighbours, so
+// k_png16_raw writes the raw big-endian scanlines once (every sample evaluated
+// once, by sample16 / grey16 as above); k_png_pick and PngAdaptiveFront
+// (png_adaptive.hpp) read those bytes. Same plan, same coder.
 // Same film -> same bytes.
 #include <hip/hip_runtime.h>
 
@@ -38,6 +44,7 @@
 #include "deflate.hpp"
 #include "device.hpp"
 #include "grey.h"
+#include "png_adaptive.hpp"
 #include "view_filmic.h"
 
 namespace rr {
@@ -139,6 +146,29 @@ struct Png16Sub {
     }
 };
 
+// The raw scanlines of a frame, 2C W bytes a row, one pixel a lane: the
+// samples row_byte gives, each evaluated once.
+template <int C, bool X>
+__global__ __launch_bounds__(256) void k_png16_raw(Png16Front f, size_t npix, uint8_t* __restrict__ raw) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix) return;
+    const float4 acc = f.film[i];
+    auto be = [](uint32_t s) { return (s >> 8) | ((s & 0xFFu) << 8); };  // the sample's two bytes, high first
+    if constexpr (C == 1) {
+        reinterpret_cast<uint16_t*>(raw)[i] = (uint16_t)be(grey16<X>(f, acc));
+    } else {
+        const uint32_t r = be(sample16<X>(f, acc, 0u)), g = be(sample16<X>(f, acc, 1u)), b = be(sample16<X>(f, acc, 2u));
+        if constexpr (C == 3) {
+            uint16_t* o = reinterpret_cast<uint16_t*>(raw) + 3 * i;
+            o[0] = (uint16_t)r;
+            o[1] = (uint16_t)g;
+            o[2] = (uint16_t)b;
+        } else {
+            reinterpret_cast<uint2*>(raw)[i] = make_uint2(r | (g << 16), b | 0xFFFF0000u);  // A = 65535
+        }
+    }
+}
+
 // Whether a frame's settings need the extended front end.
 bool png16_extended(const Png16Front& f) {
     return f.view_transform > RR_VIEW_FILMIC || f.filmic.inv_gamma != 0.0f;
@@ -175,6 +205,26 @@ void png16_encode_device(const Png16Front& f, int C, const DeflatePlan& p, uint3
     } else if (C == 1) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<1>{f}, p, c.filt, c.adler_part);
     else if (C == 3) k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<3>{f}, p, c.filt, c.adler_part);
     else k_deflate_front<<<grid, 256, 0, st>>>(Png16Sub<4>{f}, p, c.filt, c.adler_part);
+    deflate_bands_device(p, c, st);
+    deflate_gather_device(p, c, host_out, host_tab, st);
+}
+
+void png16_encode_device_adaptive(const Png16Front& f, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* raw,
+                                  uint8_t* ftype, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
+    const DeflateBufs c = deflate_carve(p, scratch);
+    const size_t npix = (size_t)p.W * (size_t)p.H;  // < 2^30: the plan's stream is below 2 GB
+    const dim3 grid((unsigned)((npix + 255) / 256));
+    if (png16_extended(f)) {
+        if (C == 1) k_png16_raw<1, true><<<grid, 256, 0, st>>>(f, npix, raw);
+        else if (C == 3) k_png16_raw<3, true><<<grid, 256, 0, st>>>(f, npix, raw);
+        else k_png16_raw<4, true><<<grid, 256, 0, st>>>(f, npix, raw);
+    } else if (C == 1) k_png16_raw<1, false><<<grid, 256, 0, st>>>(f, npix, raw);
+    else if (C == 3) k_png16_raw<3, false><<<grid, 256, 0, st>>>(f, npix, raw);
+    else k_png16_raw<4, false><<<grid, 256, 0, st>>>(f, npix, raw);
+    const PngRawRows rows{raw, p.stride - 1u};
+    if (C == 1) png_adaptive_front_device<2>(rows, p, c, ftype, st);
+    else if (C == 3) png_adaptive_front_device<6>(rows, p, c, ftype, st);
+    else png_adaptive_front_device<8>(rows, p, c, ftype, st);
     deflate_bands_device(p, c, st);
     deflate_gather_device(p, c, host_out, host_tab, st);
 }

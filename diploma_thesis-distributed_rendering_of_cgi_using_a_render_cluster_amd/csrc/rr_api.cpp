@@ -28,6 +28,7 @@
 #include "deflate.hpp"
 #include "device.hpp"
 #include "image_io.hpp"
+#include "png_filter.h"
 #include "rr.h"
 #include "scene.hpp"
 #include "view.hpp"
@@ -99,6 +100,9 @@ bool valid_color_mode(int mode) {
     return mode == RR_COLOR_SCENE || mode == RR_COLOR_BW || mode == RR_COLOR_RGB || mode == RR_COLOR_RGBA;
 }
 
+// rr_set_png_compression's values: LEGACY, SCENE or a percentage.
+bool valid_png_compression(int v) { return v >= RR_PNG_COMPRESSION_SCENE && v <= 100; }
+
 const char* coder_ext(Coder k) {
     return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : ".png";
 }
@@ -161,6 +165,8 @@ struct FrameSlot {
     int quality = 0;
     Coder coder = Coder::None;
     int color_mode = RR_COLOR_RGBA;  // resolved when the frame is submitted (resolve_color_mode): the file's channels
+    // resolved when the frame is submitted: RR_PNG_COMPRESSION_LEGACY, or 0 .. 100 (rr_set_png_compression)
+    int png_compression = RR_PNG_COMPRESSION_LEGACY;
     float* film_out = nullptr;
     FrameRun r{};
     rr_frame_timing tm{};
@@ -194,6 +200,8 @@ struct rr_ctx {
     float gamma = 0.f;
     // dither of the 8-bit image (rr_set_dither / RR_DITHER): an intensity in [0, 2], RR_DITHER_SCENE the scene's
     float dither = 0.f;
+    // compression of "PNG" files (rr_set_png_compression / RR_PNG_COMPRESSION): LEGACY, SCENE or 0 .. 100
+    int png_compression = RR_PNG_COMPRESSION_LEGACY;
     DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
     std::vector<float> filter_cache;
     float filter_width_cached = -1.f;
@@ -247,6 +255,12 @@ int guarded(F&& f) {
 }
 
 void set_device(rr_ctx* c) { RR_HIP(hipSetDevice(c->device)); }
+
+// The PNG compression of an image that comes with no scene (the inspection
+// entry points): the context's, SCENE meaning legacy.
+int png_compression_of(const rr_ctx* c) {
+    return c->png_compression >= 0 ? c->png_compression : RR_PNG_COMPRESSION_LEGACY;
+}
 
 // Waits for every stream of the context. Called before a table that all
 // frames read (filter, sRGB, JPEG, Filmic) is rewritten, since a frame of
@@ -588,21 +602,40 @@ int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p) {
 
 // The formats' encode calls as enqueue_deflate's `launch`. film: sums, scaled
 // by inv_spp. C: the file's channels (FrameSlot::color_mode).
-auto launch_png8(const uint8_t* d_rgba, int C) {
+// compression: the frame's resolved setting (rr_set_png_compression): LEGACY the
+// Sub front end, 0 .. 100 the adaptive one with a filter type per row of the
+// H rows in f's png_ftype (the device coders have one effort level).
+auto launch_png8(DevFrame& f, const uint8_t* d_rgba, int C, int compression, int H) {
+    uint8_t* ftype = nullptr;
+    if (compression >= 0) {
+        f.png_ftype.ensure((size_t)H);
+        ftype = f.png_ftype.ptr;
+    }
     return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        png_encode_device(d_rgba, C, p, scratch, out, tab, st);
+        if (ftype) png_encode_device_adaptive(d_rgba, C, p, scratch, ftype, out, tab, st);
+        else png_encode_device(d_rgba, C, p, scratch, out, tab, st);
     };
 }
 // view_transform, look and gamma are the resolved ones (the Filmic family and
 // a look only with the context's LUTs for them).
-auto launch_png16(rr_ctx* c, const float4* d_film, float inv_spp, float exposure_scale, int view_transform, int look,
-                  float gamma, int C) {
+// compression as for launch_png8; the adaptive front end also takes the raw
+// scanlines, 2C W H bytes (less than the plan's stream, which is below 2 GB), in df's png_raw.
+auto launch_png16(rr_ctx* c, DevFrame& df, const float4* d_film, float inv_spp, float exposure_scale, int view_transform,
+                  int look, float gamma, int C, int compression, int W, int H) {
     if (view_transform >= VIEW_FILMIC && !c->filmic.ready) throw std::runtime_error("Filmic view transform without LUTs");
     ensure_srgb16(c);
     const Png16Front f{d_film, inv_spp, exposure_scale, view_transform, c->srgb16_lut.ptr,
                        view_args(c, view_transform, look, gamma)};
+    uint8_t *ftype = nullptr, *raw = nullptr;
+    if (compression >= 0) {
+        df.png_ftype.ensure((size_t)H);
+        df.png_raw.ensure((size_t)2 * (size_t)C * (size_t)W * (size_t)H);
+        ftype = df.png_ftype.ptr;
+        raw = df.png_raw.ptr;
+    }
     return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        png16_encode_device(f, C, p, scratch, out, tab, st);
+        if (ftype) png16_encode_device_adaptive(f, C, p, scratch, raw, ftype, out, tab, st);
+        else png16_encode_device(f, C, p, scratch, out, tab, st);
     };
 }
 // full: FLOAT channels (Coder::Exr32), else HALF
@@ -742,11 +775,11 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
         const DeflatePlan& plan = sl.deflate.plan;  // rr_frame_submit's
         const float4* film = f.film.ptr;
         if (sl.coder == Coder::Png8)
-            enqueue_deflate(sl, f, st, plan, launch_png8(f.rgba8.ptr, sl.color_mode));
+            enqueue_deflate(sl, f, st, plan, launch_png8(f, f.rgba8.ptr, sl.color_mode, sl.png_compression, fs.H));
         else if (sl.coder == Coder::Png16)  // the film again, through exposure and view transform, at 16 bits
             enqueue_deflate(sl, f, st, plan,
-                            launch_png16(c, film, k.inv_spp, k.exposure_scale, fs.view_transform, fs.look, fs.gamma,
-                                         sl.color_mode));
+                            launch_png16(c, f, film, k.inv_spp, k.exposure_scale, fs.view_transform, fs.look, fs.gamma,
+                                         sl.color_mode, sl.png_compression, fs.W, fs.H));
         else  // the film's means: the product finish_frame forms, no view transform
             enqueue_deflate(sl, f, st, plan,
                             launch_exr(film, 1.0f / (float)fs.spp, true, sl.coder == Coder::Exr32, sl.color_mode));
@@ -857,8 +890,9 @@ void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int
 }
 
 // mode: a colour mode as rr_set_color_mode takes it, 0 the format's own layout.
+// compression ("PNG"): LEGACY, or 0 .. 100 (rr_set_png_compression).
 int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,
-              uint64_t* bytes, int mode = 0) {
+              uint64_t* bytes, int mode = 0, int compression = RR_PNG_COMPRESSION_LEGACY) {
     if (!out_path || !format) return fail(RR_EINVAL, "out_path and format are required");
     const std::string fmt(format);
     std::vector<uint8_t> data;
@@ -869,7 +903,10 @@ int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const cha
             return fail(RR_EINVAL, "JPEG encode failed");
         ext = ".jpg";
     } else if (fmt == "PNG") {
-        if (!encode_png(rgba, W, H, data, 1, 0, resolve_color_mode(mode, false))) return fail(RR_EIO, "PNG encode failed");
+        const bool adaptive = compression >= 0;
+        if (!encode_png(rgba, W, H, data, adaptive ? png_zlib_level(compression) : 1, 0, resolve_color_mode(mode, false),
+                        adaptive))
+            return fail(RR_EIO, "PNG encode failed");
         ext = ".png";
     } else {
         return fail(RR_ENOTSUP, "unsupported output format '" + fmt + "' (JPEG and PNG are supported)");
@@ -1041,6 +1078,15 @@ int rr_create(int device_ordinal, rr_ctx** out) {
                 return fail(RR_EINVAL, std::string("RR_DISPLAY_GAMMA must be 0 or in (0, 5], got '") + d + "'");
             gamma = (float)v;
         }
+        int png_compression = RR_PNG_COMPRESSION_LEGACY;
+        if (const char* d = getenv("RR_PNG_COMPRESSION")) {  // as rr_set_png_compression: a number, or "scene"
+            char* end = nullptr;
+            const long v = *d ? std::strtol(d, &end, 10) : 0;
+            if (std::string(d) == "scene") png_compression = RR_PNG_COMPRESSION_SCENE;
+            else if (*d && (end == d || *end || v < 0 || v > 100))
+                return fail(RR_EINVAL, std::string("RR_PNG_COMPRESSION must be 0 .. 100 or 'scene', got '") + d + "'");
+            else if (*d) png_compression = (int)v;
+        }
         float dither = 0.f;
         if (const char* d = getenv("RR_DITHER")) {  // as rr_set_dither: a number, or "scene"
             char* end = nullptr;
@@ -1077,6 +1123,7 @@ int rr_create(int device_ordinal, rr_ctx** out) {
         c->look = look;
         c->gamma = gamma;
         c->dither = dither;
+        c->png_compression = png_compression;
         *out = c.release();
         return RR_OK;
     });
@@ -1197,6 +1244,9 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         else sl->coder = c->device_png ? Coder::Png8 : Coder::HostRgba;
         // the context's mode, at 0 the scene's, at 0 again the format's own layout
         sl->color_mode = resolve_color_mode(c->color_mode ? c->color_mode : s->desc.render.color_mode, jpeg);
+        // the context's setting, at SCENE the scene's (-1, legacy, where it has no field)
+        sl->png_compression =
+            c->png_compression == RR_PNG_COMPRESSION_SCENE ? s->desc.render.png_compression : c->png_compression;
         if (device_deflate(sl->coder)) {
             const int rc = plan_or_refuse(sl->coder, sl->color_mode, sl->fs.W, sl->fs.H, sl->deflate.plan);
             if (rc != RR_OK) return rc;
@@ -1270,7 +1320,7 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
             if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
         } else if (sl->coder == Coder::HostRgba) {  // a submitted frame's: "PNG" by the host coder
             const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), "PNG", sl->quality, &bytes,
-                                    sl->color_mode);
+                                    sl->color_mode, sl->png_compression);
             if (e != RR_OK) return e;
         }
         const double enc_ms = ms_since(t_enc);
@@ -1363,8 +1413,8 @@ int rr_set_device_png(rr_ctx* c, int32_t on) {
 int rr_debug_png_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
                         uint64_t* len) {
     if (!c || !rgba8 || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    return debug_deflate_device(c, Coder::Png8, 4, w, h, rgba8, (size_t)w * h * 4, out, cap, len, [](const void* img) {
-        return launch_png8(static_cast<const uint8_t*>(img), 4);
+    return debug_deflate_device(c, Coder::Png8, 4, w, h, rgba8, (size_t)w * h * 4, out, cap, len, [&](const void* img) {
+        return launch_png8(c->home, static_cast<const uint8_t*>(img), 4, png_compression_of(c), h);
     });
 }
 
@@ -1405,8 +1455,9 @@ int rr_debug_png16_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, in
     if (const int rc = debug_view_settings(c, view_transform, look, gamma)) return rc;
     return debug_deflate_device(c, Coder::Png16, 4, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
                                 [&](const void* img) {
-                                    return launch_png16(c, static_cast<const float4*>(img), 1.0f, exposure_scale,
-                                                        view_transform, look, gamma, 4);
+                                    return launch_png16(c, c->home, static_cast<const float4*>(img), 1.0f,
+                                                        exposure_scale, view_transform, look, gamma, 4,
+                                                        png_compression_of(c), w, h);
                                 });
 }
 
@@ -1431,6 +1482,38 @@ int rr_set_dither(rr_ctx* c, float intensity) {
     if (intensity != RR_DITHER_SCENE && (!(intensity >= 0.f) || intensity > kDitherMax))
         return fail(RR_EINVAL, "dither intensity must be in [0, 2], or RR_DITHER_SCENE (the scene's)");
     c->dither = intensity;  // read when a frame is submitted; frames in flight keep theirs
+    return RR_OK;
+}
+
+int rr_set_png_compression(rr_ctx* c, int32_t percent) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    if (!valid_png_compression(percent))
+        return fail(RR_EINVAL, "PNG compression must be 0 .. 100, RR_PNG_COMPRESSION_LEGACY or RR_PNG_COMPRESSION_SCENE");
+    c->png_compression = percent;  // read when a frame is submitted; frames in flight keep theirs
+    return RR_OK;
+}
+
+int rr_encode_image_png(const uint8_t* rgba8, int32_t w, int32_t h, const char* out_path, int32_t color_mode,
+                        int32_t compression, uint64_t* bytes) {
+    if (!rgba8 || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad image");
+    if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
+    if (!valid_png_compression(compression) || compression == RR_PNG_COMPRESSION_SCENE)
+        return fail(RR_EINVAL, "PNG compression must be 0 .. 100 or RR_PNG_COMPRESSION_LEGACY");
+    return guarded([&] { return do_encode(rgba8, w, h, out_path, "PNG", 90, bytes, color_mode, compression); });
+}
+
+int rr_debug_png_filters(const uint8_t* raw, int32_t row_bytes, int32_t rows, int32_t bpp, uint8_t* types) {
+    if (!raw || !types || row_bytes <= 0 || rows <= 0 || bpp < 1 || bpp > 8) return fail(RR_EINVAL, "bad arguments");
+    for (int32_t y = 0; y < rows; ++y) {
+        const uint8_t* cur = raw + (size_t)y * (size_t)row_bytes;
+        types[y] = (uint8_t)png_pick_row(cur, y ? cur - row_bytes : nullptr, (size_t)row_bytes, (size_t)bpp, (size_t)rows);
+    }
+    return RR_OK;
+}
+
+int rr_debug_scene_png_compression(rr_scene* s, int32_t* compression) {
+    if (!s || !compression) return fail(RR_EINVAL, "NULL argument");
+    *compression = s->desc.render.png_compression;
     return RR_OK;
 }
 
@@ -1539,7 +1622,10 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
     if (fmt == "PNG" && (depth == 0 || depth == 8)) {
         if (image_is_float) return fail(RR_EINVAL, "8-bit PNG takes an RGBA8 image");
         return debug_deflate_device(c, Coder::Png8, C, w, h, image, (size_t)w * h * 4, out, cap, len,
-                                    [&](const void* img) { return launch_png8(static_cast<const uint8_t*>(img), C); });
+                                    [&](const void* img) {
+                                        return launch_png8(c->home, static_cast<const uint8_t*>(img), C,
+                                                           png_compression_of(c), h);
+                                    });
     }
     if (!image_is_float) return fail(RR_EINVAL, "16-bit PNG and OPEN_EXR take a float RGBA image");
     const size_t bytes = (size_t)w * h * sizeof(float4);
@@ -1548,8 +1634,8 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
         float gamma = 1.f;
         if (const int rc = debug_view_settings(c, view_transform, look, gamma)) return rc;
         return debug_deflate_device(c, Coder::Png16, C, w, h, image, bytes, out, cap, len, [&](const void* img) {
-            return launch_png16(c, static_cast<const float4*>(img), 1.0f, exposure_scale, view_transform, look, gamma,
-                                C);
+            return launch_png16(c, c->home, static_cast<const float4*>(img), 1.0f, exposure_scale, view_transform, look,
+                                gamma, C, png_compression_of(c), w, h);
         });
     }
     if (fmt == "OPEN_EXR" && (depth == 0 || depth == 16 || depth == 32)) {

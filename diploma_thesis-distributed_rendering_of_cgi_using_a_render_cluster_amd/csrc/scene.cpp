@@ -705,6 +705,16 @@ SceneDesc load_scene(const std::string& path) {
                 throw std::runtime_error("render.dither_intensity must be in [0, 2], got " + std::to_string(v.num));
             d.dither_intensity = v.num;
         }
+        // Blender's image_settings.compression (PNG); applied where the context
+        // asks for the scene's (rr_set_png_compression RR_PNG_COMPRESSION_SCENE)
+        if (r.has("png_compression")) {
+            const Json& v = r["png_compression"];
+            if (v.type != Json::Number || v.num != std::floor(v.num))
+                throw std::runtime_error("render.png_compression must be an integer in 0 .. 100");
+            if (!(v.num >= 0.0) || v.num > 100.0)
+                throw std::runtime_error("render.png_compression must be in 0 .. 100, got " + std::to_string(v.num));
+            d.png_compression = (int)v.num;
+        }
     }
     if (s.render.resx <= 0 || s.render.resy <= 0 || s.render.percent <= 0)
         throw std::runtime_error("invalid resolution");

@@ -1304,6 +1304,7 @@ void DevFrame::release() {
     trav_counts.release();
     prof.release();
     jpeg_coeffs.release(); jpeg_blk.release(); jpeg_scratch.release(); deflate_scratch.release();
+    png_ftype.release(); png_raw.release();
 }
 
 namespace {

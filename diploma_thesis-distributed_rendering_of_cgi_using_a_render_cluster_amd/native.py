@@ -97,7 +97,23 @@ EXPORTS = [
     "rr_set_color_mode", "rr_encode_image_mode", "rr_debug_encode_device",
     "rr_set_look", "rr_set_display_gamma", "rr_debug_view_device", "rr_debug_display_gamma", "rr_debug_scene_view",
     "rr_set_dither", "rr_debug_dither_noise", "rr_debug_sin_fixed",
+    "rr_set_png_compression", "rr_encode_image_png", "rr_debug_png_filters", "rr_debug_scene_png_compression",
 ]
+
+# rr_set_png_compression's values beside 0 .. 100 (include/rr.h)
+RR_PNG_COMPRESSION_LEGACY, RR_PNG_COMPRESSION_SCENE = -1, -2
+
+
+def png_compression_value(v) -> int:
+    """0 .. 100, "legacy" / None, "scene", or one of the RR_PNG_COMPRESSION_* values, as an int."""
+    if v is None or v == "legacy":
+        return RR_PNG_COMPRESSION_LEGACY
+    if v == "scene":
+        return RR_PNG_COMPRESSION_SCENE
+    if isinstance(v, str):
+        raise ValueError(f"PNG compression must be 0 .. 100, 'legacy' or 'scene', got {v!r}")
+    return int(v)
+
 
 # rr_set_dither's value for "the scene's render.dither_intensity" (include/rr.h)
 RR_DITHER_SCENE = -1.0
@@ -191,6 +207,10 @@ def lib() -> ctypes.CDLL:
         "rr_set_dither": (c_int, [P, ctypes.c_float]),
         "rr_debug_dither_noise": (c_int, [i32, i32, f32p]),
         "rr_debug_sin_fixed": (c_int, [f32p, ctypes.c_uint64, f32p]),
+        "rr_set_png_compression": (c_int, [P, i32]),
+        "rr_encode_image_png": (c_int, [u8p, i32, i32, ctypes.c_char_p, i32, i32, ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_debug_png_filters": (c_int, [u8p, i32, i32, i32, u8p]),
+        "rr_debug_scene_png_compression": (c_int, [P, i32p]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -311,6 +331,13 @@ class Scene:
         _check(lib().rr_debug_scene_view(self.handle, ctypes.byref(v), look, 64, ctypes.byref(g)))
         return v.value, look.value.decode(), g.value
 
+    def png_compression(self) -> int:
+        """rr_debug_scene_png_compression: the scene file's render.png_compression,
+        0 .. 100, or RR_PNG_COMPRESSION_LEGACY where it has none (host only)."""
+        v = ctypes.c_int32()
+        _check(lib().rr_debug_scene_png_compression(self.handle, ctypes.byref(v)))
+        return v.value
+
     def object_matrix(self, obj: int, frame: float) -> np.ndarray:
         m = (ctypes.c_double * 16)()
         _check(lib().rr_debug_object_matrix(self.handle, obj, float(frame), m))
@@ -321,9 +348,11 @@ class RenderContext:
     """One HIP device (rr_ctx). Not thread-safe; one frame in flight at a time."""
 
     def __init__(self, device: int = 0, png_depth: int = 0, exr_depth: int = 0, color_mode=0,
-                 look: str | None = None, display_gamma: float = 0.0, dither=None):
+                 look: str | None = None, display_gamma: float = 0.0, dither=None, png_compression=None):
         """dither: the dither of the 8-bit images (set_dither): an intensity in [0, 2] or
         "scene"; None: the context's own (0, or what RR_DITHER says).
+        png_compression: the compression of "PNG" files (set_png_compression): 0 .. 100,
+        "scene" or "legacy"; None: the context's own (legacy, or what RR_PNG_COMPRESSION says).
         png_depth: bits per sample of "PNG" frames (set_png_depth; 0: the scene's).
         exr_depth: channel type of "OPEN_EXR" frames (set_exr_depth; 0: the scene's).
         color_mode: "BW" / "RGB" / "RGBA" of every file (set_color_mode; 0: the scene's).
@@ -344,6 +373,8 @@ class RenderContext:
             self.set_display_gamma(display_gamma)
         if dither is not None:
             self.set_dither(dither)
+        if png_compression is not None:
+            self.set_png_compression(png_compression)
         self.device = device
 
     def close(self):
@@ -559,6 +590,14 @@ class RenderContext:
         v = RR_DITHER_SCENE if intensity == "scene" else float(intensity)
         _check(lib().rr_set_dither(self.handle, ctypes.c_float(v)), self.handle)
 
+    def set_png_compression(self, percent="legacy"):
+        """rr_set_png_compression: Blender's image_settings.compression for this
+        context's "PNG" files: 0 .. 100 (libpng's adaptive row filters; the host
+        coder at Blender's zlib level), "scene" for each scene's
+        render.png_compression, or "legacy" (the default: Sub on every row, host
+        level 1)."""
+        _check(lib().rr_set_png_compression(self.handle, png_compression_value(percent)), self.handle)
+
     def view_device(self, rgba: np.ndarray, view_transform: int = 0, exposure_scale: float = 1.0) -> np.ndarray:
         """rr_debug_view_device: the (H, W, 4) uint8 image the 8-bit view pass
         makes of an (H, W, 4) float32 image of means, with this context's look
@@ -706,3 +745,27 @@ def encode_image_mode(rgba: np.ndarray, out_path_no_ext: str, fmt: str, quality:
     _check(lib().rr_encode_image_mode(_ptr(rgba, ctypes.c_uint8), w, h, out_path_no_ext.encode(), fmt.encode(),
                                       int(quality), color_mode_value(color_mode), ctypes.byref(nbytes)))
     return nbytes.value
+
+
+def encode_image_png(rgba: np.ndarray, out_path_no_ext: str, color_mode=0, compression="legacy") -> int:
+    """rr_encode_image_png: the host PNG coder in a colour mode with a compression
+    setting (0 .. 100, or "legacy" for encode_image_mode's bytes)."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+    h, w = rgba.shape[:2]
+    nbytes = ctypes.c_uint64()
+    _check(lib().rr_encode_image_png(_ptr(rgba, ctypes.c_uint8), w, h, out_path_no_ext.encode(),
+                                     color_mode_value(color_mode), png_compression_value(compression),
+                                     ctypes.byref(nbytes)))
+    return nbytes.value
+
+
+def png_filters(raw: np.ndarray, bpp: int) -> np.ndarray:
+    """rr_debug_png_filters: the filter type rr_set_png_compression's rule gives
+    every row of (rows, row_bytes) uint8 raw scanlines with `bpp` bytes a pixel,
+    evaluated on the host."""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    rows, row_bytes = raw.shape
+    out = np.zeros(rows, np.uint8)
+    _check(lib().rr_debug_png_filters(_ptr(raw.reshape(-1), ctypes.c_uint8), row_bytes, rows, int(bpp),
+                                      _ptr(out, ctypes.c_uint8)))
+    return out

@@ -42,7 +42,7 @@ class BackendRunner:
     def __init__(self, base_directory_path: str | os.PathLike, tracer: WorkerTraceBuilder | None = None,
                  device: int = 0, params: RenderParams | None = None, ctx=None, device_png: bool = False,
                  png_depth: int = 0, exr_depth: int = 0, color_mode=0, look: str | None = None,
-                 display_gamma: float = 0.0, dither=None):
+                 display_gamma: float = 0.0, dither=None, png_compression=None):
         """ctx: a RenderContext on `device` is created here; tests of the host
         logic alone pass a stand-in with the same methods (no rendering).
         device_png: "PNG" jobs are coded on the device (rr_set_device_png).
@@ -60,7 +60,11 @@ class BackendRunner:
         (rr_set_display_gamma), or 0 for each scene's own render.gamma.
         dither: the dither of every job's 8-bit images (rr_set_dither): an
         intensity in [0, 2], "scene" for each scene's own
-        render.dither_intensity, or None for the context's own (0, or RR_DITHER)."""
+        render.dither_intensity, or None for the context's own (0, or RR_DITHER).
+        png_compression: Blender's compression of every job's "PNG" files
+        (rr_set_png_compression): 0 .. 100, "scene" for each scene's own
+        render.png_compression, "legacy", or None for the context's own (legacy,
+        or RR_PNG_COMPRESSION)."""
         base = Path(base_directory_path)
         if not base.is_dir():
             raise RenderError("Provided base directory path is not a directory.")
@@ -82,6 +86,8 @@ class BackendRunner:
             self.ctx.set_display_gamma(display_gamma)
         if dither is not None:
             self.ctx.set_dither(dither)
+        if png_compression is not None:
+            self.ctx.set_png_compression(png_compression)
         self._scenes: dict[str, Scene] = {}
         self._lock = threading.Lock()  # one caller at a time per context (queue.rs:79-118)
         self.last_stats = None

@@ -492,6 +492,63 @@ int rr_debug_dither_noise(int32_t w, int32_t h, float* out /* w*h, rows top to b
  * tests. */
 int rr_debug_sin_fixed(const float* in, uint64_t n, float* out);
 
+/* Compression of ctx's "PNG" files: Blender's image_settings.compression
+ * behind write_still (render-timing-script.py:83-92), a percentage 0 .. 100
+ * (Blender's default is 15).
+ *  - RR_PNG_COMPRESSION_LEGACY (the default): the files as they were before
+ *    there was a setting: filter type 1 (Sub) on every row, the host coder at
+ *    zlib level 1. Byte for byte.
+ *  - RR_PNG_COMPRESSION_SCENE: the scene's render.png_compression; legacy
+ *    where the scene has none.
+ *  - 0 .. 100: every row takes libpng's adaptive filter, which Blender leaves
+ *    at libpng's default: for byte x of a row with a the byte one pixel before
+ *    it, b the byte above it in the image and c the byte above a (0 where
+ *    absent), the residuals mod 256 of type 0 None x, 1 Sub x - a, 2 Up x - b,
+ *    3 Average x - ((a + b) >> 1), 4 Paeth x - paeth(a, b, c); a type's score is
+ *    the sum over the row of r < 128 ? r : 256 - r; the row takes the smallest,
+ *    types tried in the order 0 .. 4, a later one only when strictly smaller
+ *    (in an image of one row or one pixel's width Average is not tried, as in
+ *    libpng, which leaves out the types whose neighbours such an image lacks).
+ *    In all three PNG coders (host, device 8-bit, device 16-bit), at both
+ *    depths and in every colour mode. The rule is pinned against libpng
+ *    1.6.37's own files; that Blender 3.6 links a libpng with this default is
+ *    not pinned.
+ *    The host coder deflates at Blender's zlib level, (int)(percent /
+ *    11.1111f) clamped to 0 .. 9 (a formula restated from memory): 0 writes
+ *    stored blocks. The device coders have one effort level: 0 .. 100 all give
+ *    the adaptive filters in front of the coder as it is, so a device-coded
+ *    file at 0 is smaller than Blender's and decodes to the same pixels.
+ * JPEG and OPEN_EXR files are unaffected. rr_create reads RR_PNG_COMPRESSION
+ * (a number, or "scene") from the environment the same way; a bad value fails
+ * rr_create with RR_EINVAL. Applies to frames submitted after the call and to
+ * rr_debug_encode_device / rr_debug_png_device / rr_debug_png16_device (where
+ * RR_PNG_COMPRESSION_SCENE means legacy); frames in flight keep theirs.
+ * RR_EINVAL for a NULL ctx or any other value. */
+#define RR_PNG_COMPRESSION_LEGACY (-1)
+#define RR_PNG_COMPRESSION_SCENE (-2)
+int rr_set_png_compression(rr_ctx* ctx, int32_t percent);
+
+/* rr_encode_image_mode's "PNG" with a compression setting (write_still,
+ * render-timing-script.py:83-92): the host coder of rr_set_png_compression.
+ * compression 0 .. 100, or RR_PNG_COMPRESSION_LEGACY for rr_encode_image_mode's
+ * bytes; RR_PNG_COMPRESSION_SCENE is RR_EINVAL here. */
+int rr_encode_image_png(const uint8_t* rgba8, int32_t width, int32_t height,
+                        const char* out_path_no_ext, int32_t color_mode,
+                        int32_t compression, uint64_t* bytes_written);
+
+/* The filter type rr_set_png_compression's rule gives every row of an image
+ * of `rows` raw scanlines of row_bytes bytes, bpp bytes a pixel (1 .. 8),
+ * evaluated on the host (no device needed; write_still's PNG filter,
+ * render-timing-script.py:83-92). Exported so that tests tie the C statement
+ * to numpy and to libpng. RR_EINVAL for a NULL array or a size below 1. */
+int rr_debug_png_filters(const uint8_t* raw, int32_t row_bytes, int32_t rows,
+                         int32_t bpp, uint8_t* types /* rows */);
+
+/* The compression a scene file asks for (host only; write_still's
+ * image_settings.compression, render-timing-script.py:83-92): 0 .. 100, or
+ * RR_PNG_COMPRESSION_LEGACY for a scene without render.png_compression. */
+int rr_debug_scene_png_compression(rr_scene* scene, int32_t* compression);
+
 /* Run the 8-bit view pass (the one frames of the Filmic family and frames
  * with a display gamma or a dither take after rendering) on a float RGBA image
  * of the caller's (width * height * 4 floats, taken as means: spp = 1): value *

@@ -224,6 +224,15 @@ def export(path: str, args) -> dict:
         if planes not in COLOR_MODE_OF_PLANES:
             raise ValueError(f"{path}: ImageFormatData.planes = {planes}, expected 8, 24 or 32")
         out["render"]["color_mode"] = COLOR_MODE_OF_PLANES[planes]
+    # image_settings.compression (PNG): ImageFormatData.compress, 0 .. 100.
+    # Written only with --png-compression project, as color_mode is: a scene
+    # without the field keeps the files of before the setting, and the
+    # committed scenes were exported without it.
+    if getattr(args, "png_compression", "keep") == "project":
+        compress = bf.read_struct_at(rd("im_format"), "ImageFormatData", "compress")
+        if not 0 <= compress <= 100:
+            raise ValueError(f"{path}: ImageFormatData.compress = {compress}, expected 0 .. 100")
+        out["render"]["png_compression"] = int(compress)
     # ID blocks, indexed by old pointer
     mats = bf.blocks_with_code(b"MA")
     mat_index = {b.old_ptr: i for i, b in enumerate(mats)}
@@ -296,6 +305,9 @@ def main(argv=None):
     ap.add_argument("--color-mode", choices=["keep", "project"], default="keep",
                     help="keep: write no render.color_mode (the formats' own layouts); "
                          "project: the project's image_settings.color_mode")
+    ap.add_argument("--png-compression", choices=["keep", "project"], default="keep",
+                    help="keep: write no render.png_compression (PNG files as before the setting); "
+                         "project: the project's image_settings.compression")
     args = ap.parse_args(argv)
     scene = export(args.blend, args)
     with open(args.out, "w") as f:
