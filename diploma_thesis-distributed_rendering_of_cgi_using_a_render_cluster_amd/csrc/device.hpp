@@ -32,11 +32,32 @@ struct HipError : std::runtime_error {
             throw ::rr::HipError(std::string(#call) + ": " + hipGetErrorString(_e), (int)_e);   \
     } while (0)
 
-// Grow-only device allocation.
+// Grow-only device allocation with one owner: freed with it, moved but never
+// copied. The long-lived owners still release() in an order of their own, with
+// their device current (rr_destroy); the destructor is for the locals of the
+// inspection entry points, which an exception would otherwise leak.
 template <typename T>
 struct DevBuf {
     T* ptr = nullptr;
     size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : ptr(o.ptr), cap(o.cap) {
+        o.ptr = nullptr;
+        o.cap = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            ptr = o.ptr;
+            cap = o.cap;
+            o.ptr = nullptr;
+            o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     void ensure(size_t n) {
         if (n <= cap) return;
         if (ptr) (void)hipFree(ptr);
@@ -247,7 +268,7 @@ constexpr int kUploadMax = 720;
 // class); k_tiles' counting launch: [6] shader-clock ticks and [7] real-time
 // ticks after the scene staging, [8] waves, [9] real-time ticks from entry,
 // [10] ~first entry, [11] last end, [12] last entry, [13] ~first end
-// (rr_api.cpp fill_stats). (Traversal-stack drops are counted in every
+// (frame.cpp fill_stats). (Traversal-stack drops are counted in every
 // frame, in the chunk counters: drops_slot.)
 constexpr int kTravWords = 14;
 // k_tiles' counting launch also logs each box unit u < kUnitLog: words

@@ -1,0 +1,291 @@
+// The state behind the C ABI's handles (rr_ctx, rr_scene, a frame slot) and
+// the life of one frame: prepare, enqueue, finish, statistics (frame.cpp), and
+// the device coders that write its file (coders.cpp). rr_api.cpp and
+// rr_debug.cpp hold the extern "C" entry points that call these.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdint>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+#include "deflate.hpp"
+#include "device.hpp"
+#include "rr.h"
+#include "scene.hpp"
+#include "settings.hpp"
+#include "view.hpp"
+
+namespace rr {
+
+// Pinned host memory, grow-only, freed with its owner.
+struct PinnedBuf {
+    uint8_t* ptr = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    void ensure(size_t n) {
+        if (n <= cap) return;
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr;
+        cap = 0;
+        RR_HIP(hipHostMalloc(reinterpret_cast<void**>(&ptr), n, hipHostMallocDefault));
+        cap = n;
+    }
+    ~PinnedBuf() {
+        if (ptr) (void)hipHostFree(ptr);
+    }
+};
+
+// The pinned outputs of a deflate-coded image (deflate.hpp): the stream
+// [uint64 length][pad][bytes] and the bands' table, 2 or 4 words per band by
+// the plan's own_stream. The plan is made before the coder is enqueued
+// (plan_or_refuse).
+struct DeflateOut {
+    PinnedBuf stream, tab;
+    rr::DeflatePlan plan{};
+};
+
+// The pinned output of a device-coded JPEG, [uint64 length][pad][bytes], and
+// what it was coded with: the file's header is built from these.
+struct JpegOut {
+    PinnedBuf stream;
+    int W = 0, H = 0, quality = 0;
+    bool grey = false;
+};
+
+// Where the device coders write: a frame slot has one, and the context one
+// more for the inspection entry points.
+struct CodedOut {
+    JpegOut jpeg;
+    DeflateOut deflate;
+};
+
+struct FrameRun {
+    int W, H, chunks, spp_chunk, tile_slices;
+    bool rebuilt;
+    float build_ms, trace_ms, readback_ms;
+    float render_ms, device_ms;  // ev0 -> ev4 (build + trace + view transform), ev0 -> ev2 (+ device JPEG)
+    std::vector<int32_t> counters;
+    double kernel_ms[RR_K_CLASSES];
+    int32_t kernel_launches[RR_K_CLASSES];
+    unsigned long long trav[rr::kTravWords];
+};
+
+// One frame between rr_frame_submit and rr_frame_complete: its stream, its
+// device state, its host-side outputs (pinned, so the device-to-host copies
+// stay asynchronous), events and the request. Several slots = the next queued
+// frames render while the host encodes and writes the previous one.
+struct FrameSlot {
+    bool busy = false;
+    uint64_t ticket = 0;
+    // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
+    // work done, 3 outputs on the host (after their copies), 5 (device PNG
+    // and EXR frames) before the deflate coder: the state shared between frames is free
+    hipEvent_t ev[6] = {};
+    // The slot's frames run on its own stream and write only its own device
+    // state, so a k_tiles frame runs on the GPU beside the other slots'
+    // frames, and the copies of a frame's outputs to the host run while the
+    // next frames' kernels write the other slots'.
+    hipStream_t stream = nullptr;
+    rr::DevFrame dev;
+    // The products of the hierarchy builds of this slot's k_tiles frames, for
+    // the scene `build_scene`. Frames of the split path never overlap their
+    // predecessor, so they use the scene's own set: a large scene is held
+    // once, not once per slot.
+    rr::DevBuild build;
+    const rr_scene* build_scene = nullptr;
+    bool tiles = false;  // this frame renders with k_tiles (may overlap its neighbours)
+    PinnedBuf host_rgba, host_counters, host_upload;
+    CodedOut coded;  // the device-coded file's stream; a deflate frame's plan is made when the frame is submitted
+    rr::FrameSetup fs;
+    bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
+    std::string view_warning;
+    double submit_at = 0.0;         // UNIX time when the device work was enqueued
+    bool anchor = false;            // submitted to an idle context: its device start is submit_at
+    rr_scene* scene = nullptr;
+    std::string out_path;
+    rr::FrameOutput out;  // the frame's file, resolved when the frame is submitted (resolve_output)
+    float* film_out = nullptr;
+    FrameRun r{};
+    rr_frame_timing tm{};
+    double anim_ms = 0.0;
+    std::chrono::steady_clock::time_point t_call;
+};
+
+}  // namespace rr
+
+struct rr_ctx {
+    int device = 0;
+    // the home stream, which the inspection entry points enqueue on: slot 0's
+    // (rr_create says why there is no further stream)
+    hipStream_t stream = nullptr;
+    rr::DevPaths paths;  // shared by all frames: the split path's queues, read-only tables
+    rr::DevFrame home;   // the inspection entry points' frame state (a frame uses its slot's)
+    rr::CodedOut home_coded;  // and their coders' outputs: an inspection call touches no frame slot
+    // tables of the device JPEG coder (jpeg.hip), read by every slot's frames:
+    // the transform's for the last quality, the entropy coder's Huffman codes
+    rr::DevBuf<float> jpeg_tab;
+    int jpeg_tab_quality = -1;
+    rr::DevBuf<uint32_t> jpeg_huff;
+    rr::OutputSettings settings;  // rr_set_* / RR_* (settings.hpp)
+    rr::DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
+    std::vector<float> filter_cache;
+    float filter_width_cached = -1.f;
+    bool srgb_uploaded = false;
+    rr::FrameSlot slots[RR_MAX_FRAMES_IN_FLIGHT];
+    uint64_t next_ticket = 1;     // tickets are issued in submission order
+    uint64_t next_complete = 1;   // the ticket rr_frame_complete expects next
+    rr::FrameSlot* last_enqueued = nullptr;  // the slot of the frame enqueued last (its ev[2]: device work done)
+    // UNIX-time estimate of when the compute stream finished the last completed
+    // frame (rr_frame_complete): the next frame's device work cannot start before
+    double gpu_free_at = 0.0;
+    rr::FilmicDev filmic;         // the Filmic family's LUTs (rr_set_ocio_config / RR_OCIO_DIR)
+    // rr_last_warning = the context's warning (a broken RR_OCIO_DIR, kept for
+    // the context's lifetime) + the last completed frame's
+    std::string ctx_warning, frame_warning, warning;
+    // Device start times of completed frames (rr_frame_complete): every frame
+    // also records its start on start_ring[ticket % kStartRing], which outlives
+    // the frame slot's own events by a few frames, so the next frame's start is
+    // the previous one's plus the device clock's difference between the two.
+    static constexpr int kStartRing = 8;
+    hipEvent_t start_ring[kStartRing] = {};
+    uint64_t chain_ticket = 0;   // last completed frame whose device start is known (0: none)
+    double chain_unix = 0.0;     // its device start, UNIX seconds
+    double last_render_end = 0.0;  // finished_rendering_at of the last completed frame
+    // scenes bound to this context: rr_destroy releases their device buffers
+    // and unbinds them, so a scene freed after its context touches no freed state
+    std::unordered_set<rr_scene*> scenes;
+};
+
+struct rr_scene {
+    rr_ctx* ctx = nullptr;
+    rr::SceneDesc desc;
+    rr::DevMesh mesh;    // uploaded once
+    rr::DevBuild build;  // split-path frames and the inspection calls build here; k_tiles frames in their slot's set
+};
+
+namespace rr {
+
+inline void set_device(rr_ctx* c) { RR_HIP(hipSetDevice(c->device)); }
+inline FrameSlot* slot_for(rr_ctx* c, uint64_t ticket) { return &c->slots[ticket % RR_MAX_FRAMES_IN_FLIGHT]; }
+inline bool idle(rr_ctx* c) { return c->next_complete == c->next_ticket; }
+
+// Waits for every stream of the context. Called before a table that all
+// frames read (filter, sRGB, JPEG, Filmic) is rewritten, since a frame of
+// another slot may still be reading it.
+void quiesce(rr_ctx* c);
+
+// A scene is used with exactly one context; a host-only handle binds on first
+// use, which uploads its triangles.
+void bind_scene(rr_ctx* c, rr_scene* s);
+
+// Hierarchy ids (render_ints[7] of rr_debug_frame_state, rr_debug_trace):
+// 2 = Karras LBVH (BVH2), 3 = PLOC (BVH2), 4 = PLOC (LBVH below 3 triangles)
+// collapsed to the quantised 6-wide hierarchy (rr_device.h QNode6).
+constexpr int kHierLbvh = 2, kHierPloc = 3, kHierQWide = 4;  // 4: the quantised 6-wide collapse (ABI value kept)
+
+FrameConsts make_consts(const FrameSetup& fs, int n_tris);
+
+// The hierarchy the frame kernels walk: the LBVH for frames k_tiles renders
+// (LDS-resident scenes), the quantised BVH4 for the split path (larger scenes,
+// and LDS-resident ones under RR_FLAG_WAVEFRONT).
+int frame_hier(const FrameSetup& fs, int n_tris);
+
+// The samples a chunk of the split path takes: by the frame's size alone, and
+// lowered to what the device's free memory holds.
+int choose_spp_chunk(const FrameSetup& fs);
+int fit_spp_chunk(const FrameSetup& fs, const DevPaths& p);
+
+// The view transform, look and display gamma a frame on ctx is rendered with
+// (fs.view_transform, fs.look, fs.gamma). The context's look and gamma come
+// before the scene's. The Filmic family needs the context's LUTs, without them
+// Standard; False Color its cube, without it Standard; a look the Filmic view
+// and its curve, without either no look. Returns what of the view settings
+// the frame does not apply ("" if nothing): those fallbacks, and the scene's
+// own notes (FrameSetup::view_note: a view transform or look nobody knows).
+std::string resolve_view(const rr_ctx* c, FrameSetup& fs);
+
+// The view settings as kernel arguments, for a view, look and gamma that
+// resolve_view (or an inspection call's own check) has passed. dither: the
+// 8-bit pass's intensity (the 16-bit front end takes none).
+FilmicArgs view_args(const rr_ctx* c, int view, int look, float gamma, float dither = 0.f);
+
+// The 8-bit path's sRGB table on the device (DevPaths::srgb_lut), uploaded
+// once with every stream idle.
+void ensure_srgb(rr_ctx* c);
+
+// Upload per-frame constants and (re)build the LBVH if object transforms changed.
+// `staging` (pinned, per frame slot) keeps the host-to-device copies
+// asynchronous, so a frame can be enqueued while the previous one still runs.
+// Works on stream st with frame state f and builds into d, a set of products
+// of s's mesh. Returns whether it rebuilt.
+// hier: 0 = the frame's hierarchy, else a kHier* id (inspection entry points).
+bool prepare_frame(rr_ctx* c, rr_scene* s, DevBuild& d, DevFrame& f, hipStream_t st, const FrameSetup& fs,
+                   PinnedBuf& staging, int hier = 0);
+
+// Enqueue the device part of one frame on its slot's stream, with the slot's
+// device state (no host synchronisation): LBVH (if needed), wavefront, tonemap,
+// optionally the file's device coder, and the asynchronous copies of the slot's outputs.
+void enqueue_frame(rr_ctx* c, FrameSlot& sl);
+// Wait for a slot's device work and collect its timings and counters.
+void finish_frame(rr_ctx* c, FrameSlot& sl);
+// The frame's render span in the worker's record (sl.tm), from the device's
+// own clock, once finish_frame has returned. t_sync: the UNIX time then.
+void set_render_span(rr_ctx* c, FrameSlot& sl, double t_sync);
+void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int n_tris);
+
+// ---- the device coders (coders.cpp) ----------------------------------------
+
+// The image a coder reads. rgba8: Jpeg and Png8; film: Png16, Exr and Exr32,
+// W x H float4 sums scaled by inv_spp. exposure_scale, view_transform, look
+// and gamma (resolved: resolve_view, or an inspection call's own check): Png16,
+// which takes the film through exposure and view transform again at 16 bits.
+// alpha_one (Exr, Exr32): A = 1, as in a rendered frame's file; else the
+// image's own alpha. jpeg_tab: the transform's table for the file's quality
+// (ensure_jpeg_table).
+struct CoderInput {
+    const uint8_t* rgba8 = nullptr;
+    const float4* film = nullptr;
+    int W = 0, H = 0;
+    float inv_spp = 1.0f, exposure_scale = 1.0f;
+    int view_transform = VIEW_STANDARD, look = 0;
+    float gamma = 1.0f;
+    bool alpha_one = true;
+    const float* jpeg_tab = nullptr;
+};
+
+// The plan of a deflate-coded image of C channels. A size outside the coder's
+// range is refused (RR_EINVAL), never rerouted: there is no other coder that
+// writes the same file.
+int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p);
+
+// The 16-bit path's sRGB table on the device. Written once, before the first
+// kernel that reads it is enqueued, and never again.
+void ensure_srgb16(rr_ctx* c);
+// The device JPEG transform's table for `quality` in c->jpeg_tab, rewritten
+// with every stream idle when the quality changes.
+void ensure_jpeg_table(rr_ctx* c, int quality);
+
+// Enqueue the device coder that `fo` names (Jpeg ... Exr32) on stream st, with
+// f's scratch and profiler, into o's pinned buffers. fo.color_mode: the file's
+// channels; fo.png_compression ("PNG"): LEGACY the Sub front end, 0 .. 100 the
+// adaptive one (the device coders have one effort level). A deflate format
+// codes by o.deflate.plan (plan_or_refuse).
+void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o);
+
+// The file of a device-coded image, once its stream is on the host: the
+// host-built header or container around it.
+void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data);
+
+// The host coders: an RGBA8 image as a "JPEG" or "PNG" file at out_path + its
+// extension. mode: a colour mode as rr_set_color_mode takes it, 0 the format's
+// own layout. compression ("PNG"): LEGACY, or 0 .. 100 (rr_set_png_compression).
+int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,
+              uint64_t* bytes, int mode = 0, int compression = RR_PNG_COMPRESSION_LEGACY);
+
+}  // namespace rr

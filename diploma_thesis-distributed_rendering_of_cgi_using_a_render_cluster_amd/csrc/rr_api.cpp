@@ -1,991 +1,23 @@
 // C ABI of the renderer (include/rr.h). One rr_ctx per GPU; one rr_scene per
-// exported project, cached for the worker's lifetime.
-//
-// Reference behaviour mirrored here (BlenderJobRunner::render_frame,
-// /root/reference/worker/src/rendering/runner/mod.rs:72-203 and
-// scripts/render-timing-script.py:13-100):
-//  * loaded_at            <- time the frame request starts (scene already loaded;
-//                            the reference pays a Blender start + .blend read here)
-//  * frame_set(N)         -> host animation evaluation (scene.cpp)
-//  * started_rendering_at <- before the device work (script :86)
-//  * render               -> LBVH build (if transforms changed) + wavefront
-//  * finished_rendering_at = file_saving_started_at <- after the 8-bit image is on
-//                            the host (utilities.rs:185-192)
-//  * write_still          -> JPEG/PNG encode + write, "<path>.jpg|.png"
-//  * file_saving_finished_at <- after the write (utilities.rs:195-198)
-#include <hip/hip_runtime.h>
-
+// exported project, cached for the worker's lifetime. Every function here is
+// an argument check and a call: the frame's life is in frame.cpp, the coders
+// in coders.cpp, the settings in settings.cpp; rr_debug.cpp has the
+// inspection entry points.
 #include <cerrno>
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
+#include <cstdio>
 #include <cstring>
 #include <memory>
-#include <string>
-#include <unordered_set>
-#include <vector>
 
-#include "deflate.hpp"
-#include "device.hpp"
+#include "api_util.hpp"
+#include "frame.hpp"
 #include "image_io.hpp"
-#include "png_filter.h"
-#include "rr.h"
-#include "scene.hpp"
-#include "view.hpp"
 
 using namespace rr;
 
-static_assert(kMatLutIntervals == kMatLutN && kMatLutFloatsPerMat == kMatLutStride && kMatLutPsOffset == kMatLutPs,
-              "scene.hpp material-table layout must match rr_device.h");
-
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-double unix_now() {
-    using namespace std::chrono;
-    return duration_cast<duration<double>>(system_clock::now().time_since_epoch()).count();
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-struct PinnedBuf {
-    uint8_t* ptr = nullptr;
-    size_t cap = 0;
-    void ensure(size_t n) {
-        if (n <= cap) return;
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        RR_HIP(hipHostMalloc(reinterpret_cast<void**>(&ptr), n, hipHostMallocDefault));
-        cap = n;
-    }
-    ~PinnedBuf() {
-        if (ptr) (void)hipHostFree(ptr);
-    }
-};
-
-// Who codes a frame's output. HostRgba: the 8-bit image comes back to the host
-// (rr_render_frame_to_memory; a "PNG" file from the host's zlib threads where a
-// path is given). Jpeg ... Exr32: coded on the device, the file written from the
-// slot's pinned stream. Png8: "PNG" with rr_set_device_png; Png16: "PNG" at 16
-// bits per sample, for which there is no host coder. Exr: "OPEN_EXR" with HALF
-// channels; Exr32: with FLOAT channels (rr_set_exr_depth).
-enum class Coder { None, HostRgba, Jpeg, Png8, Png16, Exr, Exr32 };
-
-// The formats behind the deflate coder (deflate.hip): their coder reads only
-// its slot's rgba8 / film and writes slot buffers only.
-bool device_deflate(Coder k) {
-    return k == Coder::Png8 || k == Coder::Png16 || k == Coder::Exr || k == Coder::Exr32;
-}
-
-// The channels a frame's file holds (rr_set_color_mode), which is also the
-// resolved mode's value: RR_COLOR_BW 1, RR_COLOR_RGB 3, RR_COLOR_RGBA 4. mode 0:
-// the format's layout before there was a setting (JPEG three components, PNG
-// and OPEN_EXR four channels). JPEG has no alpha: RGBA resolves to RGB, as in
-// Blender.
-int resolve_color_mode(int mode, bool jpeg) {
-    if (mode == 0) return jpeg ? RR_COLOR_RGB : RR_COLOR_RGBA;
-    return (jpeg && mode == RR_COLOR_RGBA) ? RR_COLOR_RGB : mode;
-}
-
-bool valid_color_mode(int mode) {
-    return mode == RR_COLOR_SCENE || mode == RR_COLOR_BW || mode == RR_COLOR_RGB || mode == RR_COLOR_RGBA;
-}
-
-// rr_set_png_compression's values: LEGACY, SCENE or a percentage.
-bool valid_png_compression(int v) { return v >= RR_PNG_COMPRESSION_SCENE && v <= 100; }
-
-const char* coder_ext(Coder k) {
-    return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : ".png";
-}
-
-// The pinned outputs of a deflate-coded frame (deflate.hpp): the stream
-// [uint64 length][pad][bytes] and the bands' table, 2 or 4 words per band by
-// the plan's own_stream.
-struct DeflateOut {
-    PinnedBuf stream, tab;
-    DeflatePlan plan{};
-};
-
-}  // namespace
-
-struct FrameRun {
-    int W, H, chunks, spp_chunk, tile_slices;
-    bool rebuilt;
-    float build_ms, trace_ms, readback_ms;
-    float render_ms, device_ms;  // ev0 -> ev4 (build + trace + view transform), ev0 -> ev2 (+ device JPEG)
-    std::vector<int32_t> counters;
-    double kernel_ms[RR_K_CLASSES];
-    int32_t kernel_launches[RR_K_CLASSES];
-    unsigned long long trav[kTravWords];
-};
-
-// One frame between rr_frame_submit and rr_frame_complete: its stream, its
-// device state, its host-side outputs (pinned, so the device-to-host copies
-// stay asynchronous), events and the request. Several slots = the next queued
-// frames render while the host encodes and writes the previous one.
-struct FrameSlot {
-    bool busy = false;
-    uint64_t ticket = 0;
-    // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
-    // work done, 3 outputs on the host (after their copies), 5 (device PNG
-    // and EXR frames) before the deflate coder: the state shared between frames is free
-    hipEvent_t ev[6] = {};
-    // The slot's frames run on its own stream and write only its own device
-    // state, so a k_tiles frame runs on the GPU beside the other slots'
-    // frames, and the copies of a frame's outputs to the host run while the
-    // next frames' kernels write the other slots'.
-    hipStream_t stream = nullptr;
-    DevFrame dev;
-    // The products of the hierarchy builds of this slot's k_tiles frames, for
-    // the scene `build_scene`. Frames of the split path never overlap their
-    // predecessor, so they use the scene's own set: a large scene is held
-    // once, not once per slot.
-    DevBuild build;
-    const rr_scene* build_scene = nullptr;
-    bool tiles = false;  // this frame renders with k_tiles (may overlap its neighbours)
-    PinnedBuf host_rgba, host_counters, host_upload;
-    PinnedBuf host_jpeg;   // device-coded JPEG stream: [uint64 length][pad][bytes]
-    DeflateOut deflate;    // device-coded PNG / OPEN_EXR frame; the plan is made when the frame is submitted
-    FrameSetup fs;
-    bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
-    std::string view_warning;
-    double submit_at = 0.0;         // UNIX time when the device work was enqueued
-    bool anchor = false;            // submitted to an idle context: its device start is submit_at
-    rr_scene* scene = nullptr;
-    std::string out_path;
-    int quality = 0;
-    Coder coder = Coder::None;
-    int color_mode = RR_COLOR_RGBA;  // resolved when the frame is submitted (resolve_color_mode): the file's channels
-    // resolved when the frame is submitted: RR_PNG_COMPRESSION_LEGACY, or 0 .. 100 (rr_set_png_compression)
-    int png_compression = RR_PNG_COMPRESSION_LEGACY;
-    float* film_out = nullptr;
-    FrameRun r{};
-    rr_frame_timing tm{};
-    double anim_ms = 0.0;
-    std::chrono::steady_clock::time_point t_call;
-};
-
-struct rr_ctx {
-    int device = 0;
-    // the home stream, which the inspection entry points enqueue on: slot 0's
-    // (rr_create says why there is no further stream)
-    hipStream_t stream = nullptr;
-    DevPaths paths;  // shared by all frames: the split path's queues, read-only tables
-    DevFrame home;   // the inspection entry points' frame state (a frame uses its slot's)
-    // tables of the device JPEG coder (jpeg.hip), read by every slot's frames:
-    // the transform's for the last quality, the entropy coder's Huffman codes
-    DevBuf<float> jpeg_tab;
-    int jpeg_tab_quality = -1;
-    DevBuf<uint32_t> jpeg_huff;
-    // 8-bit "PNG" frames are coded on the device (rr_set_device_png / RR_DEVICE_PNG)
-    bool device_png = false;
-    // bit depth of "PNG" frames (rr_set_png_depth / RR_PNG_DEPTH): 0 the scene's, 8, 16
-    int png_depth = 0;
-    // channel type of "OPEN_EXR" frames (rr_set_exr_depth / RR_EXR_DEPTH): 0 the scene's, 16 HALF, 32 FLOAT
-    int exr_depth = 0;
-    // colour mode of the files (rr_set_color_mode / RR_COLOR_MODE): 0 the scene's, else RR_COLOR_BW / RGB / RGBA
-    int color_mode = 0;
-    // look of Filmic frames (rr_set_look / RR_LOOK): a view.hpp kLooks id, -1 the scene's
-    int look = -1;
-    // display gamma (rr_set_display_gamma / RR_DISPLAY_GAMMA): 0 the scene's
-    float gamma = 0.f;
-    // dither of the 8-bit image (rr_set_dither / RR_DITHER): an intensity in [0, 2], RR_DITHER_SCENE the scene's
-    float dither = 0.f;
-    // compression of "PNG" files (rr_set_png_compression / RR_PNG_COMPRESSION): LEGACY, SCENE or 0 .. 100
-    int png_compression = RR_PNG_COMPRESSION_LEGACY;
-    DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
-    std::vector<float> filter_cache;
-    float filter_width_cached = -1.f;
-    bool srgb_uploaded = false;
-    FrameSlot slots[RR_MAX_FRAMES_IN_FLIGHT];
-    uint64_t next_ticket = 1;     // tickets are issued in submission order
-    uint64_t next_complete = 1;   // the ticket rr_frame_complete expects next
-    FrameSlot* last_enqueued = nullptr;  // the slot of the frame enqueued last (its ev[2]: device work done)
-    // UNIX-time estimate of when the compute stream finished the last completed
-    // frame (rr_frame_complete): the next frame's device work cannot start before
-    double gpu_free_at = 0.0;
-    FilmicDev filmic;             // the Filmic family's LUTs (rr_set_ocio_config / RR_OCIO_DIR)
-    // rr_last_warning = the context's warning (a broken RR_OCIO_DIR, kept for
-    // the context's lifetime) + the last completed frame's
-    std::string ctx_warning, frame_warning, warning;
-    // Device start times of completed frames (rr_frame_complete): every frame
-    // also records its start on start_ring[ticket % kStartRing], which outlives
-    // the frame slot's own events by a few frames, so the next frame's start is
-    // the previous one's plus the device clock's difference between the two.
-    static constexpr int kStartRing = 8;
-    hipEvent_t start_ring[kStartRing] = {};
-    uint64_t chain_ticket = 0;   // last completed frame whose device start is known (0: none)
-    double chain_unix = 0.0;     // its device start, UNIX seconds
-    double last_render_end = 0.0;  // finished_rendering_at of the last completed frame
-    // scenes bound to this context: rr_destroy releases their device buffers
-    // and unbinds them, so a scene freed after its context touches no freed state
-    std::unordered_set<rr_scene*> scenes;
-};
-
-struct rr_scene {
-    rr_ctx* ctx = nullptr;
-    SceneDesc desc;
-    DevMesh mesh;    // uploaded once
-    DevBuild build;  // split-path frames and the inspection calls build here; k_tiles frames in their slot's set
-};
-
-namespace {
-
-// Catch-all wrapper: C++ exceptions never cross the C ABI.
-template <typename F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const HipError& e) {
-        return fail(RR_ENODEV, e.what());
-    } catch (const std::bad_alloc&) {
-        return fail(RR_ENOMEM, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(RR_EINVAL, e.what());
-    }
-}
-
-void set_device(rr_ctx* c) { RR_HIP(hipSetDevice(c->device)); }
-
-// The PNG compression of an image that comes with no scene (the inspection
-// entry points): the context's, SCENE meaning legacy.
-int png_compression_of(const rr_ctx* c) {
-    return c->png_compression >= 0 ? c->png_compression : RR_PNG_COMPRESSION_LEGACY;
-}
-
-// Waits for every stream of the context. Called before a table that all
-// frames read (filter, sRGB, JPEG, Filmic) is rewritten, since a frame of
-// another slot may still be reading it.
-void quiesce(rr_ctx* c) {
-    for (auto& sl : c->slots)
-        if (sl.stream) RR_HIP(hipStreamSynchronize(sl.stream));
-}
-
-// One-time upload of the scene's object-space triangles.
-void upload_scene(rr_ctx* c, rr_scene* s) {
-    set_device(c);
-    DevMesh& d = s->mesh;
-    if (d.uploaded) return;
-    if (d.n_tris > 0) {
-        d.tri_local.ensure((size_t)3 * d.n_tris);
-        d.tri_obj.ensure((size_t)d.n_tris);
-        d.tri_mat.ensure((size_t)d.n_tris);
-        RR_HIP(hipMemcpy(d.tri_local.ptr, s->desc.tri_local.data(), s->desc.tri_local.size() * sizeof(float),
-                         hipMemcpyHostToDevice));
-        RR_HIP(hipMemcpy(d.tri_obj.ptr, s->desc.tri_obj.data(), d.n_tris * sizeof(int32_t), hipMemcpyHostToDevice));
-        RR_HIP(hipMemcpy(d.tri_mat.ptr, s->desc.tri_mat.data(), d.n_tris * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    d.uploaded = true;
-}
-
-// A scene is used with exactly one context; a host-only handle binds on first use.
-void bind_scene(rr_ctx* c, rr_scene* s) {
-    if (s->ctx && s->ctx != c) throw std::runtime_error("scene belongs to another context");
-    s->ctx = c;
-    c->scenes.insert(s);
-    upload_scene(c, s);
-}
-
-// Upload per-frame constants and (re)build the LBVH if object transforms changed.
-// `staging` (pinned, per frame slot) keeps the host-to-device copies
-// asynchronous, so a frame can be enqueued while the previous one still runs.
-// Hierarchy ids (render_ints[7] of rr_debug_frame_state, rr_debug_trace):
-// 2 = Karras LBVH (BVH2), 3 = PLOC (BVH2), 4 = PLOC (LBVH below 3 triangles)
-// collapsed to the quantised 6-wide hierarchy (rr_device.h QNode6).
-constexpr int kHierLbvh = 2, kHierPloc = 3, kHierQWide = 4;  // 4: the quantised 6-wide collapse (ABI value kept)
-
-FrameConsts make_consts(const FrameSetup& fs, int n_tris);
-
-// The hierarchy the frame kernels walk: the LBVH for frames k_tiles renders
-// (LDS-resident scenes), the quantised BVH4 for the split path (larger scenes,
-// and LDS-resident ones under RR_FLAG_WAVEFRONT).
-int frame_hier(const FrameSetup& fs, int n_tris) {
-    return frame_uses_tiles(make_consts(fs, n_tris), (fs.flags & RR_FLAG_WAVEFRONT) != 0) ? kHierLbvh : kHierQWide;
-}
-
-// The view transform, look and display gamma a frame on ctx is rendered with
-// (fs.view_transform, fs.look, fs.gamma). The context's look and gamma come
-// before the scene's. The Filmic family needs the context's LUTs, without them
-// Standard; False Color its cube, without it Standard; a look the Filmic view
-// and its curve, without either no look. Returns what of the view settings
-// the frame does not apply ("" if nothing): those fallbacks, and the scene's
-// own notes (FrameSetup::view_note: a view transform or look nobody knows).
-std::string resolve_view(const rr_ctx* c, FrameSetup& fs) {
-    std::string w = fs.view_note;
-    auto note = [&](const std::string& m) { w += (w.empty() ? "" : "; ") + m; };
-    if (c && c->look >= 0) fs.look = c->look;
-    if (c && c->gamma != 0.f) fs.gamma = c->gamma;
-    // the context's intensity (0 on a new one); only RR_DITHER_SCENE keeps the scene's
-    if (!c || c->dither != RR_DITHER_SCENE) fs.dither = c ? c->dither : 0.f;
-    const int asked = fs.view_transform;
-    if (asked >= VIEW_FILMIC && !(c && c->filmic.ready)) {
-        fs.view_transform = VIEW_STANDARD;
-        w = std::string("scene view transform ") + view_name(asked) +
-            " rendered as Standard: no OCIO LUTs configured "
-            "(rr_set_ocio_config / RR_OCIO_DIR)" + (w.empty() ? "" : "; " + w);
-    } else if (asked == VIEW_FALSE_COLOR && !c->filmic.has_false_color()) {
-        fs.view_transform = VIEW_STANDARD;
-        note(std::string("view transform False Color rendered as Standard: no ") + kFalseColorFile + " under " +
-             c->filmic.dir + " (or its luts/)");
-    }
-    if (fs.look != 0) {
-        const LookDef& l = kLooks[fs.look];
-        if (fs.view_transform != VIEW_FILMIC) {
-            note(std::string("look '") + l.name + "' ignored: the frame's view is " + view_name(fs.view_transform) +
-                 ", looks belong to Filmic");
-            fs.look = 0;
-        } else if (!c->filmic.has_look(fs.look)) {
-            note(std::string("look '") + l.name + "' ignored: no " + l.file + " under " + c->filmic.dir +
-                 " (or its luts/)");
-            fs.look = 0;
-        }
-    }
-    return w;
-}
-
-// The view settings as kernel arguments, for a view, look and gamma that
-// resolve_view (or an inspection call's own check) has passed. dither: the
-// 8-bit pass's intensity (the 16-bit front end takes none).
-FilmicArgs view_args(const rr_ctx* c, int view, int look, float gamma, float dither = 0.f) {
-    FilmicArgs a = view >= VIEW_FILMIC ? c->filmic.args(view == VIEW_FILMIC ? look : 0) : FilmicArgs{};
-    a.inv_gamma = inv_gamma_of(gamma);
-    a.dither = dither;
-    return a;
-}
-
-// The view settings of an inspection call on c with a view of the caller's:
-// the context's look (with the Filmic view) and display gamma, None and 1
-// where the context leaves them to a scene. Nothing is substituted here: a
-// view or look whose LUT is not loaded is RR_EINVAL.
-int debug_view_settings(const rr_ctx* c, int view, int& look, float& gamma) {
-    if (view < VIEW_STANDARD || view > VIEW_FALSE_COLOR) return fail(RR_EINVAL, "unsupported view transform");
-    if (view >= VIEW_FILMIC && !c->filmic.ready)
-        return fail(RR_EINVAL, "Filmic view transform without LUTs (rr_set_ocio_config / RR_OCIO_DIR)");
-    if (view == VIEW_FALSE_COLOR && !c->filmic.has_false_color())
-        return fail(RR_EINVAL, std::string("False Color view transform without ") + kFalseColorFile);
-    look = (view == VIEW_FILMIC && c->look > 0) ? c->look : 0;
-    if (look && !c->filmic.has_look(look))
-        return fail(RR_EINVAL, std::string("look '") + kLooks[look].name + "' without " + kLooks[look].file);
-    gamma = c->gamma != 0.f ? c->gamma : 1.f;
-    return RR_OK;
-}
-
-// Works on stream st with frame state f and builds into d, a set of products
-// of s's mesh. Returns whether it rebuilt.
-// hier: 0 = the frame's hierarchy, else a kHier* id (inspection entry points).
-bool prepare_frame(rr_ctx* c, rr_scene* s, DevBuild& d, DevFrame& f, hipStream_t st, const FrameSetup& fs,
-                   PinnedBuf& staging, int hier = 0) {
-    bind_scene(c, s);
-    DevPaths& p = c->paths;
-    // tables (built on the host once; identical construction in the oracle)
-    if (c->filter_width_cached != fs.filter_width) {
-        quiesce(c);
-        c->filter_cache.assign(kFilterTableSize, 0.f);
-        build_filter_table(fs.filter_width, c->filter_cache.data());
-        p.filter_table.ensure(kFilterTableSize);
-        RR_HIP(hipMemcpy(p.filter_table.ptr, c->filter_cache.data(), kFilterTableSize * sizeof(float),
-                         hipMemcpyHostToDevice));
-        c->filter_width_cached = fs.filter_width;
-    }
-    if (!c->srgb_uploaded) {
-        quiesce(c);
-        std::vector<float> lut(kSrgbLutSize + 1);
-        build_srgb_lut(lut.data());
-        p.srgb_lut.ensure(lut.size());
-        RR_HIP(hipMemcpy(p.srgb_lut.ptr, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
-        c->srgb_uploaded = true;
-    }
-    if (f.mat_lut_cached != fs.mat_lut) {  // material tables: static per scene, uploaded when they change
-        // a frame slot's own table is read only by that slot's frames (the
-        // slot's previous frame has completed); the home set's is rewritten
-        // with every stream idle
-        if (&f == &c->home) quiesce(c);
-        f.mat_lut.ensure(fs.mat_lut.size());
-        RR_HIP(hipMemcpyAsync(f.mat_lut.ptr, fs.mat_lut.data(), fs.mat_lut.size() * sizeof(float),
-                              hipMemcpyHostToDevice, st));
-        RR_HIP(hipStreamSynchronize(st));  // pageable source: the copy must be done before fs goes away
-        f.mat_lut_cached = fs.mat_lut;
-    }
-    const size_t nl = fs.lights.size(), nm = fs.materials.size(), nx = fs.obj_xform.size();
-    f.lights.ensure(nl ? nl : 1);
-    f.materials.ensure(nm ? nm : 1);
-    staging.ensure((nl + nm + nx) * sizeof(float));
-    float* up = reinterpret_cast<float*>(staging.ptr);
-    std::memcpy(up, fs.lights.data(), nl * sizeof(float));
-    std::memcpy(up + nl, fs.materials.data(), nm * sizeof(float));
-    std::memcpy(up + nl + nm, fs.obj_xform.data(), nx * sizeof(float));
-    const DevMesh& m = s->mesh;
-    if (hier == 0) hier = frame_hier(fs, m.n_tris);
-    const bool want4 = hier == kHierQWide;
-    const bool want_ploc = (hier == kHierPloc || hier == kHierQWide) && m.n_tris > 2;
-    // (a BVH4 collapse reorders the triangles into its leaf order, so a BVH2
-    // walk of the same PLOC tree needs a build without it)
-    const bool rebuild = !d.built || d.cached_xform != fs.obj_xform || (want4 != d.has4) || (want_ploc != d.ploc);
-    const bool upload_x = rebuild && m.n_tris > 0;
-    if (upload_x) d.obj_xform.ensure(nx);
-    const UploadSeg segs[3] = {{f.lights.ptr, (int)nl}, {f.materials.ptr, (int)nm},
-                               {upload_x ? d.obj_xform.ptr : nullptr, upload_x ? (int)nx : 0}};
-    if (!upload_by_kernarg(up, segs, 3, st)) {
-        if (nl) RR_HIP(hipMemcpyAsync(f.lights.ptr, up, nl * sizeof(float), hipMemcpyHostToDevice, st));
-        RR_HIP(hipMemcpyAsync(f.materials.ptr, up + nl, nm * sizeof(float), hipMemcpyHostToDevice, st));
-        if (upload_x)
-            RR_HIP(hipMemcpyAsync(d.obj_xform.ptr, up + nl + nm, nx * sizeof(float), hipMemcpyHostToDevice, st));
-    }
-    if (upload_x) {
-        build_lbvh(m, d, st, &f.prof, want4, want_ploc);
-        d.cached_xform = fs.obj_xform;
-    } else if (rebuild) {
-        d.built = true;
-        d.cached_xform = fs.obj_xform;
-    }
-    return rebuild;
-}
-
-FrameConsts make_consts(const FrameSetup& fs, int n_tris) {
-    FrameConsts k{};
-    k.cam_pos = make_float3(fs.cam[0], fs.cam[1], fs.cam[2]);
-    k.cam_right = make_float3(fs.cam[3], fs.cam[4], fs.cam[5]);
-    k.cam_up = make_float3(fs.cam[6], fs.cam[7], fs.cam[8]);
-    k.cam_back = make_float3(fs.cam[9], fs.cam[10], fs.cam[11]);
-    k.half_w = fs.cam[12];
-    k.half_h = fs.cam[13];
-    k.clip_start = fs.cam[14];
-    k.clip_end = fs.cam[15];
-    k.inv_w2 = 2.0f / (float)fs.W;
-    k.inv_h2 = 2.0f / (float)fs.H;
-    k.W = fs.W;
-    k.H = fs.H;
-    k.npix = fs.W * fs.H;
-    k.div_w = FastDiv::make((uint32_t)fs.W);
-    k.div_spp = FastDiv::make(1u);  // per chunk (render_split)
-    k.spp_total = fs.spp;
-    k.max_bounces = fs.max_bounces;
-    k.max_diffuse = fs.max_diffuse;
-    k.max_glossy = fs.max_glossy;
-    k.n_lights = (int)(fs.lights.size() / RR_LIGHT_FLOATS);
-    k.n_mats = (int)(fs.materials.size() / RR_MAT_FLOATS);
-    k.seed = fs.seed;
-    k.clamp_indirect = fs.clamp_indirect;
-    k.exposure_scale = fs.exposure_scale;
-    k.inv_spp = 1.0f / (float)fs.spp;
-    k.view_transform = fs.view_transform;
-    k.world = make_float3(fs.world[0], fs.world[1], fs.world[2]);
-    k.n_tris = n_tris;
-    // build_filter_table: offsets within the support [-width, width]
-    k.filter_reach = std::fabs(fs.filter_width) + 1.0f;
-    return k;
-}
-
-int choose_spp_chunk(const FrameSetup& fs) {
-    if (fs.spp_per_chunk > 0) return std::min(fs.spp_per_chunk, fs.spp);
-    // Paths in flight per chunk: the SoA path state is 168 B/path (radiance
-    // record 16 B, two path-queue slots 2 x 48 B, shadow slot 48 B, hit 8 B),
-    // so the default 512M paths take ~86 GB of the 288 GB HBM (a 1080p frame
-    // up to 256 spp, a 4K frame's 64 spp, is one chunk; frames of the split
-    // path share one copy); np stays below 2^31 for 32-bit queue indices.
-    // Per full C5 frame (4K, 1024 spp) 256M / 512M / 1G paths per chunk:
-    // 4,113 / 4,016 / 4,088 ms (profiles/r5_ab_chunk.txt): half the launches
-    // and their tails.
-#ifndef RR_CHUNK_MPATHS
-#define RR_CHUNK_MPATHS 512
-#endif
-    constexpr long kChunkPaths = (long)RR_CHUNK_MPATHS << 20;
-    const long target = kChunkPaths;
-    long c = target / std::max(1, fs.W * fs.H);
-    if (c < 1) c = 1;
-    if (c > fs.spp) c = fs.spp;
-    return (int)c;
-}
-
-// The chunk a frame renders with: choose_spp_chunk, lowered when the path
-// state of that many paths (168 B each, DevPaths::ensure_paths) would not fit
-// in 85 % of the device memory free now plus what this context's path buffers
-// already hold — a smaller GPU, or several ranks sharing one, gets more chunks
-// instead of RR_ENOMEM. Chunking changes no bit of the image
-// (test_chunking_and_determinism); an explicit spp_per_chunk is kept as asked.
-int fit_spp_chunk(const FrameSetup& fs, const DevPaths& p) {
-    const int c = choose_spp_chunk(fs);
-    if (fs.spp_per_chunk > 0) return c;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void)hipGetLastError();
-        return c;
-    }
-    constexpr size_t kPathStateBytes = 168;
-    const double usable = 0.85 * ((double)free_b + (double)p.cap * kPathStateBytes);
-    const double npix = std::max(1.0, (double)fs.W * fs.H);
-    // ensure_paths' slack: a persistent grid's threads + 1/64 of the paths
-    const double slack = (double)std::max(p.grid_blocks, 256 * 8) * kBlock;  // 8: kMaxBlocksPerCu
-    const long fit = (long)((usable / kPathStateBytes - slack) / (1.0 + 1.0 / 64.0) / npix);
-    return (int)std::max<long>(1, std::min<long>(c, fit));
-}
-
-// The device JPEG transform's table: dct | qinv luma | qinv chroma.
-void jpeg_device_table(int quality, float out[192]) {
-    JpegTables t;
-    jpeg_tables(quality, t);
-    std::memcpy(out, t.dct, sizeof t.dct);
-    std::memcpy(out + 64, t.qinv_l, sizeof t.qinv_l);
-    std::memcpy(out + 128, t.qinv_c, sizeof t.qinv_c);
-}
-
-// Device JPEG encode of an RGBA8 frame (transform into f.jpeg_coeffs +
-// Huffman coding) into the slot's pinned stream buffer, on stream st with f's
-// scratch. The slot's colour mode decides the file: RR_COLOR_BW a one-component one.
-void enqueue_jpeg_device(rr_ctx* c, FrameSlot& sl, DevFrame& f, hipStream_t st, const uint8_t* d_rgba, int W, int H,
-                         const float* d_tab) {
-    const bool grey = sl.color_mode == RR_COLOR_BW;
-    if (!c->jpeg_huff.ptr) {
-        quiesce(c);
-        uint32_t h[4 * 256];
-        jpeg_huff_tables(h);
-        c->jpeg_huff.ensure(4 * 256);
-        RR_HIP(hipMemcpy(c->jpeg_huff.ptr, h, sizeof h, hipMemcpyHostToDevice));
-    }
-    const size_t mcuy = jpeg_mcu_rows(H, grey);
-    const size_t nblocks = jpeg_block_count(W, H, grey);
-    f.jpeg_coeffs.ensure(jpeg_coeff_count(W, H, grey));
-    f.jpeg_blk.ensure(2 * nblocks + 2 * mcuy);
-    f.jpeg_scratch.ensure(mcuy * jpeg_row_scratch_words(W, grey));
-    sl.host_jpeg.ensure(jpeg_stream_max_bytes(W, H, grey) + 16);
-    void* dev_host = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, sl.host_jpeg.ptr, 0));
-    uint32_t* blk = f.jpeg_blk.ptr;
-    JpegDevBufs b{blk, blk + nblocks, blk + 2 * nblocks, blk + 2 * nblocks + mcuy, f.jpeg_scratch.ptr};
-    jpeg_encode_device(d_rgba, W, H, grey, d_tab, c->jpeg_huff.ptr, f.jpeg_coeffs.ptr, b, static_cast<uint8_t*>(dev_host),
-                       st);
-}
-
-// The file of a device-coded JPEG frame: host-built header + the device stream.
-void jpeg_file_bytes(const FrameSlot& sl, std::vector<uint8_t>& data) {
-    uint64_t len = 0;
-    std::memcpy(&len, sl.host_jpeg.ptr, sizeof len);
-    if (len + 16 > sl.host_jpeg.cap) throw std::runtime_error("device JPEG stream overflow");
-    jpeg_header_bytes(sl.fs.W, sl.fs.H, sl.quality, data, sl.color_mode == RR_COLOR_BW);
-    data.insert(data.end(), sl.host_jpeg.ptr + 16, sl.host_jpeg.ptr + 16 + len);
-}
-
-// The 16-bit path's sRGB table on the device. Written once, before the first
-// kernel that reads it is enqueued, and never again.
-static_assert(kSrgb16LutSize == kSrgb16N, "host table and device read agree on the interval count");
-void ensure_srgb16(rr_ctx* c) {
-    if (c->srgb16_lut.ptr) return;
-    std::vector<float> lut(kSrgb16LutSize + 2);
-    build_srgb16_lut(lut.data());
-    c->srgb16_lut.ensure(lut.size());
-    RR_HIP(hipMemcpy(c->srgb16_lut.ptr, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
-}
-
-// The plan of a deflate-coded frame. A size outside the coder's range is
-// refused, never rerouted: there is no other coder that writes the same file.
-int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p) {
-    const bool ok = k == Coder::Png8    ? png_plan(W, H, C, p)
-                    : k == Coder::Png16 ? png16_plan(W, H, C, p)
-                    : k == Coder::Exr32 ? exr32_plan(W, H, C, p)
-                                        : exr_plan(W, H, C, p);
-    if (ok) return RR_OK;
-    const char* name = k == Coder::Png8    ? "PNG"
-                       : k == Coder::Png16 ? "16-bit PNG"
-                       : k == Coder::Exr32 ? "32-bit EXR"
-                                           : "EXR";
-    return fail(RR_EINVAL, std::string("image size outside the device ") + name + " encoder's range");
-}
-
-// The formats' encode calls as enqueue_deflate's `launch`. film: sums, scaled
-// by inv_spp. C: the file's channels (FrameSlot::color_mode).
-// compression: the frame's resolved setting (rr_set_png_compression): LEGACY the
-// Sub front end, 0 .. 100 the adaptive one with a filter type per row of the
-// H rows in f's png_ftype (the device coders have one effort level).
-auto launch_png8(DevFrame& f, const uint8_t* d_rgba, int C, int compression, int H) {
-    uint8_t* ftype = nullptr;
-    if (compression >= 0) {
-        f.png_ftype.ensure((size_t)H);
-        ftype = f.png_ftype.ptr;
-    }
-    return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        if (ftype) png_encode_device_adaptive(d_rgba, C, p, scratch, ftype, out, tab, st);
-        else png_encode_device(d_rgba, C, p, scratch, out, tab, st);
-    };
-}
-// view_transform, look and gamma are the resolved ones (the Filmic family and
-// a look only with the context's LUTs for them).
-// compression as for launch_png8; the adaptive front end also takes the raw
-// scanlines, 2C W H bytes (less than the plan's stream, which is below 2 GB), in df's png_raw.
-auto launch_png16(rr_ctx* c, DevFrame& df, const float4* d_film, float inv_spp, float exposure_scale, int view_transform,
-                  int look, float gamma, int C, int compression, int W, int H) {
-    if (view_transform >= VIEW_FILMIC && !c->filmic.ready) throw std::runtime_error("Filmic view transform without LUTs");
-    ensure_srgb16(c);
-    const Png16Front f{d_film, inv_spp, exposure_scale, view_transform, c->srgb16_lut.ptr,
-                       view_args(c, view_transform, look, gamma)};
-    uint8_t *ftype = nullptr, *raw = nullptr;
-    if (compression >= 0) {
-        df.png_ftype.ensure((size_t)H);
-        df.png_raw.ensure((size_t)2 * (size_t)C * (size_t)W * (size_t)H);
-        ftype = df.png_ftype.ptr;
-        raw = df.png_raw.ptr;
-    }
-    return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        if (ftype) png16_encode_device_adaptive(f, C, p, scratch, raw, ftype, out, tab, st);
-        else png16_encode_device(f, C, p, scratch, out, tab, st);
-    };
-}
-// full: FLOAT channels (Coder::Exr32), else HALF
-auto launch_exr(const float4* d_film, float inv_spp, bool alpha_one, bool full, int C) {
-    return [=](const DeflatePlan& p, uint32_t* scratch, uint8_t* out, uint32_t* tab, hipStream_t st) {
-        if (full) exr32_encode_device(d_film, inv_spp, alpha_one, C, p, scratch, out, tab, st);
-        else exr_encode_device(d_film, inv_spp, alpha_one, C, p, scratch, out, tab, st);
-    };
-}
-
-// Device deflate of one frame into the slot's pinned stream buffer and band
-// table, on stream st with f's scratch and profiler.
-template <class Launch>
-void enqueue_deflate(FrameSlot& sl, DevFrame& f, hipStream_t st, const DeflatePlan& p, Launch launch) {
-    DeflateOut& o = sl.deflate;
-    o.plan = p;
-    f.deflate_scratch.ensure(deflate_scratch_words(p));
-    o.stream.ensure((p.own_stream ? exr_stream_max_bytes(p) : deflate_stream_max_bytes(p)) + 32);
-    o.tab.ensure((size_t)p.nbands * (p.own_stream ? 4 : 2) * sizeof(uint32_t));
-    void *dev_host = nullptr, *dev_tab = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
-    RR_HIP(hipHostGetDevicePointer(&dev_tab, o.tab.ptr, 0));
-    f.prof.begin(st, RR_K_PNG);
-    launch(p, f.deflate_scratch.ptr, static_cast<uint8_t*>(dev_host), static_cast<uint32_t*>(dev_tab), st);
-    f.prof.end(st);
-}
-
-// The file of a deflate-coded frame: the host-built container of format k
-// around the device stream. C: the channels the stream was coded with.
-void deflate_file_bytes(const DeflateOut& o, Coder k, int C, std::vector<uint8_t>& data) {
-    const DeflatePlan& p = o.plan;
-    const uint32_t* tab = reinterpret_cast<const uint32_t*>(o.tab.ptr);
-    uint64_t len = 0;
-    std::memcpy(&len, o.stream.ptr, sizeof len);
-    // one stream: its bound counts the 4 bytes of Adler-32 the host adds
-    if (len > o.stream.cap || len + 16 + (p.own_stream ? 0 : 4) > o.stream.cap)
-        throw std::runtime_error("device deflate stream overflow");
-    switch (k) {
-    case Coder::Png8:
-    case Coder::Png16:
-        png_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Png16 ? 16 : 8,
-                        C == 4 ? 6 : C == 3 ? 2 : 0);
-        break;
-    case Coder::Exr:
-    case Coder::Exr32:
-        if (!exr_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Exr32 ? 2 : 1,
-                             C))
-            throw std::runtime_error("device EXR chunk table does not match its stream");
-        break;
-    default:
-        throw std::runtime_error("not a deflate-coded frame");
-    }
-}
-
-// Enqueue the device part of one frame on its slot's stream, with the slot's
-// device state (no host synchronisation): LBVH (if needed), wavefront, tonemap,
-// optionally the JPEG transform, and the asynchronous copies of the slot's outputs.
-void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
-    set_device(c);
-    rr_scene* s = sl.scene;
-    const FrameSetup& fs = sl.fs;
-    FrameRun& r = sl.r;
-    r = FrameRun{};
-    r.W = fs.W;
-    r.H = fs.H;
-    for (auto& e : sl.ev)
-        if (!e) RR_HIP(hipEventCreate(&e));
-    if (sl.build_scene != s) {  // products of another scene (or none): start this scene's set afresh
-        sl.build.release();
-        sl.build_scene = s;
-    }
-    FrameOpts opts;
-    opts.count_traversal = (fs.flags & RR_FLAG_COUNT_TRAVERSAL) != 0;
-    opts.force_wavefront = (fs.flags & RR_FLAG_WAVEFRONT) != 0;
-    sl.tiles = frame_uses_tiles(make_consts(fs, s->mesh.n_tris), opts.force_wavefront);
-    // A k_tiles frame following a k_tiles frame does not wait for it: k_tiles
-    // and its helper kernels touch only the slot's state and read-only tables,
-    // and the frame builds into the slot's own products, so frame N+1's build
-    // and launch fill the CUs that frame N's tail and its JPEG kernels leave
-    // idle. Any other frame shares the wavefront queues of DevPaths and the
-    // scene's products, and waits for the previous frame's device work.
-    hipStream_t st = sl.stream;
-    DevFrame& f = sl.dev;
-    DevBuild& build = sl.tiles ? sl.build : s->build;
-    FrameSlot* prev = c->last_enqueued;
-    // (the deflate coder reads its slot's rgba8 / film and writes slot buffers
-    // only, so the next frame waits for the image, ev[5], not for the coder)
-    if (prev && prev != &sl && !(sl.tiles && prev->tiles))
-        RR_HIP(hipStreamWaitEvent(st, device_deflate(prev->coder) ? prev->ev[5] : prev->ev[2], 0));
-    c->last_enqueued = &sl;
-    // a k_tiles frame enqueued while another k_tiles frame is pending overlaps
-    // it: whole-tile work units (render_frame_device); a frame rendered alone
-    // (rr_render_frame, the first of a batch) slices its tiles by sample group.
-    // Scheduling only: both give the same bits.
-    bool pending_tiles = false;
-    for (auto& o : c->slots)
-        if (&o != &sl && o.busy && o.tiles) pending_tiles = true;
-    opts.tile_whole = sl.tiles && pending_tiles;
-    f.prof.reset((fs.flags & RR_FLAG_PROFILE_KERNELS) != 0);
-    RR_HIP(hipEventRecord(sl.ev[0], st));
-    {
-        hipEvent_t& se = c->start_ring[sl.ticket % rr_ctx::kStartRing];
-        if (!se) RR_HIP(hipEventCreate(&se));
-        RR_HIP(hipEventRecord(se, st));
-    }
-    r.rebuilt = prepare_frame(c, s, build, f, st, fs, sl.host_upload);
-    RR_HIP(hipEventRecord(sl.ev[1], st));
-    FrameConsts k = make_consts(fs, s->mesh.n_tris);
-    r.spp_chunk = fit_spp_chunk(fs, c->paths);
-    r.chunks = (fs.spp + r.spp_chunk - 1) / r.spp_chunk;
-    k.spp_chunk = r.spp_chunk;
-    k.div_spp = FastDiv::make((uint32_t)k.spp_chunk);
-    render_frame_device(s->mesh, build, c->paths, f, k, r.chunks, opts, st);
-    r.tile_slices = f.tile_slices;
-    // the Filmic family, a display gamma or a dither: film -> view settings -> rgba8 (overwrites the kernels' tonemap)
-    if (view_needs_pass(fs.view_transform, fs.gamma, fs.dither)) {
-        f.prof.begin(st, RR_K_ACCUM);
-        view_device(view_args(c, fs.view_transform, fs.look, fs.gamma, fs.dither), k, c->paths.srgb_lut.ptr,
-                    f.film.ptr, reinterpret_cast<uchar4*>(f.rgba8.ptr), st);
-        f.prof.end(st);
-    }
-    RR_HIP(hipEventRecord(sl.ev[4], st));
-    const size_t npix = (size_t)fs.W * fs.H;
-    if (sl.coder == Coder::Jpeg) {
-        if (c->jpeg_tab_quality != sl.quality) {
-            quiesce(c);
-            float tab[192];
-            jpeg_device_table(sl.quality, tab);
-            c->jpeg_tab.ensure(192);
-            RR_HIP(hipMemcpy(c->jpeg_tab.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
-            c->jpeg_tab_quality = sl.quality;
-        }
-        enqueue_jpeg_device(c, sl, f, st, f.rgba8.ptr, fs.W, fs.H, c->jpeg_tab.ptr);
-    }
-    if (device_deflate(sl.coder)) {
-        RR_HIP(hipEventRecord(sl.ev[5], st));
-        const DeflatePlan& plan = sl.deflate.plan;  // rr_frame_submit's
-        const float4* film = f.film.ptr;
-        if (sl.coder == Coder::Png8)
-            enqueue_deflate(sl, f, st, plan, launch_png8(f, f.rgba8.ptr, sl.color_mode, sl.png_compression, fs.H));
-        else if (sl.coder == Coder::Png16)  // the film again, through exposure and view transform, at 16 bits
-            enqueue_deflate(sl, f, st, plan,
-                            launch_png16(c, f, film, k.inv_spp, k.exposure_scale, fs.view_transform, fs.look, fs.gamma,
-                                         sl.color_mode, sl.png_compression, fs.W, fs.H));
-        else  // the film's means: the product finish_frame forms, no view transform
-            enqueue_deflate(sl, f, st, plan,
-                            launch_exr(film, 1.0f / (float)fs.spp, true, sl.coder == Coder::Exr32, sl.color_mode));
-    }
-    RR_HIP(hipEventRecord(sl.ev[2], st));
-    // the outputs' device-to-host copies follow on the slot's own stream: the
-    // next frames run on the other slots' streams, so nothing waits for them
-    if (sl.coder == Coder::HostRgba) {
-        sl.host_rgba.ensure(npix * 4);
-        RR_HIP(hipMemcpyAsync(sl.host_rgba.ptr, f.rgba8.ptr, npix * 4, hipMemcpyDeviceToHost, st));
-    }
-    const int cpc = counters_per_chunk(fs.max_bounces);
-    const size_t nctr = (size_t)cpc * r.chunks;
-    sl.host_counters.ensure(nctr * sizeof(int32_t));
-    RR_HIP(hipMemcpyAsync(sl.host_counters.ptr, f.counters.ptr, nctr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (sl.film_out)
-        RR_HIP(hipMemcpyAsync(sl.film_out, f.film.ptr, npix * sizeof(float4), hipMemcpyDeviceToHost, st));
-    RR_HIP(hipEventRecord(sl.ev[3], st));
-    if (opts.count_traversal) {  // measurement mode: read the traversal counters now
-        RR_HIP(hipStreamSynchronize(st));
-        RR_HIP(hipMemcpy(r.trav, f.trav_counts.ptr, sizeof r.trav, hipMemcpyDeviceToHost));
-    }
-}
-
-// Wait for a slot's device work and collect its timings and counters.
-void finish_frame(rr_ctx* c, FrameSlot& sl) {
-    set_device(c);
-    FrameRun& r = sl.r;
-    const FrameSetup& fs = sl.fs;
-    RR_HIP(hipEventSynchronize(sl.ev[3]));
-    RR_HIP(hipEventElapsedTime(&r.build_ms, sl.ev[0], sl.ev[1]));
-    RR_HIP(hipEventElapsedTime(&r.trace_ms, sl.ev[1], sl.ev[4]));
-    RR_HIP(hipEventElapsedTime(&r.readback_ms, sl.ev[4], sl.ev[3]));
-    RR_HIP(hipEventElapsedTime(&r.render_ms, sl.ev[0], sl.ev[4]));
-    RR_HIP(hipEventElapsedTime(&r.device_ms, sl.ev[0], sl.ev[2]));
-    const int cpc = counters_per_chunk(fs.max_bounces);
-    r.counters.assign(reinterpret_cast<const int32_t*>(sl.host_counters.ptr),
-                      reinterpret_cast<const int32_t*>(sl.host_counters.ptr) + (size_t)cpc * r.chunks);
-    sl.dev.prof.collect(r.kernel_ms, r.kernel_launches);
-    sl.dev.prof.reset(false);
-    if (sl.film_out) {  // film holds sums; report the mean
-        const size_t npix = (size_t)fs.W * fs.H;
-        const float inv = 1.0f / (float)fs.spp;
-        for (size_t i = 0; i < npix; ++i) {
-            float* f = sl.film_out + 4 * i;
-            f[0] = f[0] * inv;
-            f[1] = f[1] * inv;
-            f[2] = f[2] * inv;
-            f[3] = 1.0f;
-        }
-    }
-}
-
-void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int n_tris) {
-    if (!st) return;
-    std::memset(st, 0, sizeof *st);
-    st->width = fs.W;
-    st->height = fs.H;
-    st->spp = fs.spp;
-    st->chunks = r.chunks;
-    st->camera_rays = (uint64_t)fs.W * fs.H * fs.spp;
-    st->view_transform = fs.view_transform;
-    const int cpc = counters_per_chunk(fs.max_bounces);
-    uint64_t drops = 0, ext_traced = 0, sh_traced = 0;
-    for (int c = 0; c < r.chunks; ++c) {
-        // pair b: {paths entering bounce b+1, shadow rays of bounce b} (wavefront.hip, tiles.hip)
-        const int32_t* q = &r.counters[(size_t)cpc * c];
-        st->camera_rays_traced += (uint64_t)(uint32_t)q[camera_traced_slot(fs.max_bounces)];
-        drops += (uint64_t)(uint32_t)q[drops_slot(fs.max_bounces)];
-        if (r.tile_slices > 0) {  // k_tiles: the traversed ones are counted; the rest escaped
-            ext_traced += (uint64_t)(uint32_t)q[escaped_slot(fs.max_bounces)];
-            sh_traced += (uint64_t)(uint32_t)q[escaped_slot(fs.max_bounces) + 1];
-        }
-        for (int b = 0; b < fs.max_bounces; ++b) st->extension_rays += (uint64_t)q[2 * b];
-        for (int b = 0; b <= fs.max_bounces; ++b) st->shadow_rays += (uint64_t)q[2 * b + 1];
-        st->primary_continued += (uint64_t)q[0];
-        st->primary_shadow += (uint64_t)q[1];
-    }
-    for (int k = 0; k < RR_K_CLASSES; ++k) {
-        st->kernel_ms[k] = r.kernel_ms[k];
-        st->kernel_launches[k] = r.kernel_launches[k];
-    }
-    for (int k = 0; k < 3; ++k) {
-        st->trav_nodes[k] = r.trav[2 * k];
-        st->trav_tris[k] = r.trav[2 * k + 1];
-    }
-    {
-        // k_tiles<count>: sums over waves of shader-clock and 100 MHz real-time ticks
-        const unsigned long long* w = r.trav;
-        st->kernel_clock_ghz = w[7] ? 0.1 * (double)w[6] / (double)w[7] : 0.0;
-        const unsigned long long t0 = ~w[10], t1 = w[11];
-        st->kernel_wave_fill = (w[8] && t1 > t0) ? (double)w[9] / (double)w[8] / (double)(t1 - t0) : 0.0;
-        const unsigned long long e1 = w[12], x0 = ~w[13];
-        st->kernel_entry_spread = (w[8] && t1 > t0 && e1 >= t0) ? (double)(e1 - t0) / (double)(t1 - t0) : 0.0;
-        st->kernel_exit_spread = (w[8] && t1 > t0 && t1 >= x0) ? (double)(t1 - x0) / (double)(t1 - t0) : 0.0;
-    }
-    st->stack_drops = (int32_t)std::min<uint64_t>(drops, 0x7fffffffull);
-    if (r.tile_slices > 0) {
-        st->extension_rays_escaped = st->extension_rays - std::min(ext_traced, st->extension_rays);
-        st->shadow_rays_escaped = st->shadow_rays - std::min(sh_traced, st->shadow_rays);
-    }
-    st->build_ms = r.rebuilt ? r.build_ms : 0.0;
-    st->trace_ms = r.trace_ms;
-    st->readback_ms = r.readback_ms;
-    st->bvh_rebuilt = r.rebuilt ? 1 : 0;
-    st->tile_slices = r.tile_slices;
-    st->n_triangles = n_tris;
-}
-
-// mode: a colour mode as rr_set_color_mode takes it, 0 the format's own layout.
-// compression ("PNG"): LEGACY, or 0 .. 100 (rr_set_png_compression).
-int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,
-              uint64_t* bytes, int mode = 0, int compression = RR_PNG_COMPRESSION_LEGACY) {
-    if (!out_path || !format) return fail(RR_EINVAL, "out_path and format are required");
-    const std::string fmt(format);
-    std::vector<uint8_t> data;
-    std::string ext;
-    if (fmt == "JPEG") {
-        if (quality < 1 || quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
-        if (!encode_jpeg(rgba, W, H, quality, data, 0, resolve_color_mode(mode, true) == RR_COLOR_BW))
-            return fail(RR_EINVAL, "JPEG encode failed");
-        ext = ".jpg";
-    } else if (fmt == "PNG") {
-        const bool adaptive = compression >= 0;
-        if (!encode_png(rgba, W, H, data, adaptive ? png_zlib_level(compression) : 1, 0, resolve_color_mode(mode, false),
-                        adaptive))
-            return fail(RR_EIO, "PNG encode failed");
-        ext = ".png";
-    } else {
-        return fail(RR_ENOTSUP, "unsupported output format '" + fmt + "' (JPEG and PNG are supported)");
-    }
-    const std::string path = std::string(out_path) + ext;
-    if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
-    if (bytes) *bytes = data.size();
-    return RR_OK;
-}
-
-// BVH width the frame kernels traverse for this scene (2: LDS-resident fused
-// path, 4: split path from HBM).
-int frame_hier_of(rr_scene* s, const FrameSetup& fs) { return frame_hier(fs, s->mesh.n_tris); }
-
-FrameSlot* slot_for(rr_ctx* c, uint64_t ticket) { return &c->slots[ticket % RR_MAX_FRAMES_IN_FLIGHT]; }
-
-bool idle(rr_ctx* c) { return c->next_complete == c->next_ticket; }
-
-// The body of the deflate formats' inspection entry points: an image of the
-// caller's through format k's coder (the home set's scratch, slot 0's pinned outputs), the file's bytes to `out` if
-// `cap` suffices. make(device image) gives enqueue_deflate's launch.
-template <class Make>
-int debug_deflate_device(rr_ctx* c, Coder k, int C, int w, int h, const void* pixels, size_t bytes, uint8_t* out,
-                         uint64_t cap, uint64_t* len, Make make) {
-    DeflatePlan plan;
-    const int rc = plan_or_refuse(k, C, w, h, plan);
-    if (rc != RR_OK) return rc;
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        DevBuf<uint8_t> img;
-        img.ensure(bytes);
-        RR_HIP(hipMemcpy(img.ptr, pixels, bytes, hipMemcpyHostToDevice));
-        FrameSlot& sl = c->slots[0];
-        enqueue_deflate(sl, c->home, c->stream, plan, make(img.ptr));
-        RR_HIP(hipStreamSynchronize(c->stream));
-        img.release();
-        std::vector<uint8_t> data;
-        deflate_file_bytes(sl.deflate, k, C, data);
-        *len = data.size();
-        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
-        return RR_OK;
-    });
-}
-
-// The body of the JPEG inspection entry points: an RGBA8 image of the caller's
-// through the device JPEG coder (the home set's scratch, slot 0's pinned
-// output) in colour mode `mode` (resolved).
-int debug_jpeg_device(rr_ctx* c, int mode, const uint8_t* rgba8, int32_t w, int32_t h, int32_t quality, uint8_t* out,
-                      uint64_t cap, uint64_t* len) {
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        hipStream_t st = c->stream;
-        DevBuf<uint8_t> img;
-        img.ensure((size_t)w * h * 4);
-        RR_HIP(hipMemcpy(img.ptr, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice));
-        float tab[192];
-        jpeg_device_table(quality, tab);
-        DevBuf<float> dtab;
-        dtab.ensure(192);
-        RR_HIP(hipMemcpy(dtab.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
-        c->jpeg_tab_quality = -1;  // the context's cached table is not this one's
-        FrameSlot& sl = c->slots[0];
-        sl.fs.W = w;
-        sl.fs.H = h;
-        sl.quality = quality;
-        sl.color_mode = mode;
-        enqueue_jpeg_device(c, sl, c->home, st, img.ptr, w, h, dtab.ptr);
-        RR_HIP(hipStreamSynchronize(st));
-        std::vector<uint8_t> data;
-        jpeg_file_bytes(sl, data);
-        *len = data.size();
-        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
-        img.release();
-        dtab.release();
-        return RR_OK;
-    });
-}
+// rr_set_*: a refused value is RR_EINVAL and changes nothing.
+int setter_result(bool ok, const std::string& err) { return ok ? RR_OK : fail(RR_EINVAL, err); }
 
 }  // namespace
 
@@ -1043,61 +75,12 @@ int rr_create(int device_ordinal, rr_ctx** out) {
         if (device_ordinal < 0 || device_ordinal >= n)
             return fail(RR_ENODEV, "device ordinal " + std::to_string(device_ordinal) + " out of range (" +
                                        std::to_string(n) + " visible)");
-        int png_depth = 0;
-        if (const char* d = getenv("RR_PNG_DEPTH")) {  // as rr_set_png_depth
-            const std::string v(d);
-            if (v == "8") png_depth = 8;
-            else if (v == "16") png_depth = 16;
-            else if (!v.empty() && v != "0") return fail(RR_EINVAL, "RR_PNG_DEPTH must be 0, 8 or 16, got '" + v + "'");
-        }
-        int exr_depth = 0;
-        if (const char* d = getenv("RR_EXR_DEPTH")) {  // as rr_set_exr_depth
-            const std::string v(d);
-            if (v == "16") exr_depth = 16;
-            else if (v == "32") exr_depth = 32;
-            else if (!v.empty() && v != "0") return fail(RR_EINVAL, "RR_EXR_DEPTH must be 0, 16 or 32, got '" + v + "'");
-        }
-        int color_mode = 0;
-        if (const char* d = getenv("RR_COLOR_MODE")) {  // as rr_set_color_mode
-            const std::string v(d);
-            if (v == "BW") color_mode = RR_COLOR_BW;
-            else if (v == "RGB") color_mode = RR_COLOR_RGB;
-            else if (v == "RGBA") color_mode = RR_COLOR_RGBA;
-            else if (!v.empty()) return fail(RR_EINVAL, "RR_COLOR_MODE must be BW, RGB or RGBA, got '" + v + "'");
-        }
-        int look = -1;
-        if (const char* d = getenv("RR_LOOK")) {  // as rr_set_look
-            look = *d ? look_id(d) : -1;
-            if (*d && look < 0) return fail(RR_EINVAL, std::string("RR_LOOK: unknown look '") + d + "'");
-        }
-        float gamma = 0.f;
-        if (const char* d = getenv("RR_DISPLAY_GAMMA")) {  // as rr_set_display_gamma
-            char* end = nullptr;
-            const double v = *d ? std::strtod(d, &end) : 0.0;
-            if (*d && (end == d || *end || !(v >= 0.0) || v > (double)kGammaMax))
-                return fail(RR_EINVAL, std::string("RR_DISPLAY_GAMMA must be 0 or in (0, 5], got '") + d + "'");
-            gamma = (float)v;
-        }
-        int png_compression = RR_PNG_COMPRESSION_LEGACY;
-        if (const char* d = getenv("RR_PNG_COMPRESSION")) {  // as rr_set_png_compression: a number, or "scene"
-            char* end = nullptr;
-            const long v = *d ? std::strtol(d, &end, 10) : 0;
-            if (std::string(d) == "scene") png_compression = RR_PNG_COMPRESSION_SCENE;
-            else if (*d && (end == d || *end || v < 0 || v > 100))
-                return fail(RR_EINVAL, std::string("RR_PNG_COMPRESSION must be 0 .. 100 or 'scene', got '") + d + "'");
-            else if (*d) png_compression = (int)v;
-        }
-        float dither = 0.f;
-        if (const char* d = getenv("RR_DITHER")) {  // as rr_set_dither: a number, or "scene"
-            char* end = nullptr;
-            const double v = *d ? std::strtod(d, &end) : 0.0;
-            if (std::string(d) == "scene") dither = RR_DITHER_SCENE;
-            else if (*d && (end == d || *end || !(v >= 0.0) || v > (double)kDitherMax))
-                return fail(RR_EINVAL, std::string("RR_DITHER must be in [0, 2] or 'scene', got '") + d + "'");
-            else dither = (float)v;
-        }
+        OutputSettings settings;
+        std::string err;
+        if (!settings_from_env(settings, err)) return fail(RR_EINVAL, err);
         std::unique_ptr<rr_ctx> c(new rr_ctx());
         c->device = device_ordinal;
+        c->settings = settings;
         set_device(c.get());
         // One stream per slot and no other, so that each gets a hardware queue
         // of its own (GPU_MAX_HW_QUEUES is 4, and the process's null stream
@@ -1112,18 +95,10 @@ int rr_create(int device_ordinal, rr_ctx** out) {
             // a broken LUT directory does not fail the context: Filmic frames fall
             // back to Standard and carry the reason in rr_last_warning
             FilmicLuts l;
-            std::string err;
-            if (*d && load_filmic_luts(d, l, err)) c->filmic.upload(l, d);
-            else if (*d) c->ctx_warning = "RR_OCIO_DIR: " + err;
+            std::string lut_err;
+            if (*d && load_filmic_luts(d, l, lut_err)) c->filmic.upload(l, d);
+            else if (*d) c->ctx_warning = "RR_OCIO_DIR: " + lut_err;
         }
-        if (const char* d = getenv("RR_DEVICE_PNG")) c->device_png = std::string(d) == "1";
-        c->png_depth = png_depth;
-        c->exr_depth = exr_depth;
-        c->color_mode = color_mode;
-        c->look = look;
-        c->gamma = gamma;
-        c->dither = dither;
-        c->png_compression = png_compression;
         *out = c.release();
         return RR_OK;
     });
@@ -1197,16 +172,10 @@ void rr_scene_free(rr_scene* s) {
 
 int rr_scene_resolution(rr_scene* s, const rr_render_params* p, int32_t* w, int32_t* h) {
     if (!s) return fail(RR_EINVAL, "scene is NULL");
-    return guarded([&] {
-        rr_render_params d;
-        rr_render_params_default(&d);
-        const RenderDesc& r = s->desc.render;
-        const int W = (p && p->width > 0) ? p->width : (r.resx * r.percent) / 100;
-        const int H = (p && p->height > 0) ? p->height : (r.resy * r.percent) / 100;
-        if (w) *w = W;
-        if (h) *h = H;
-        return RR_OK;
-    });
+    const RenderDesc& r = s->desc.render;
+    if (w) *w = (p && p->width > 0) ? p->width : (r.resx * r.percent) / 100;
+    if (h) *h = (p && p->height > 0) ? p->height : (r.resy * r.percent) / 100;
+    return RR_OK;
 }
 
 int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* params, const char* out_path,
@@ -1217,9 +186,9 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
     if (format && std::string(format) != "JPEG" && std::string(format) != "PNG" &&
         std::string(format) != "OPEN_EXR")
         return fail(RR_ENOTSUP, std::string("unsupported output format '") + format + "'");
-    const bool jpeg = out_path && std::string(format) == "JPEG";
-    const bool exr = out_path && std::string(format) == "OPEN_EXR";
-    if (jpeg && (jpeg_quality < 1 || jpeg_quality > 100)) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
+    const FrameOutput fo = resolve_output(c->settings, s->desc.render, format, out_path != nullptr, jpeg_quality);
+    if (fo.coder == Coder::Jpeg && (jpeg_quality < 1 || jpeg_quality > 100))
+        return fail(RR_EINVAL, "jpeg_quality must be 1..100");
     FrameSlot* sl = slot_for(c, c->next_ticket);
     if (sl->busy) return fail(RR_EBUSY, "too many frames in flight (complete the oldest first)");
     return guarded([&] {
@@ -1234,24 +203,12 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->tm.started_rendering_at = unix_now();
         sl->scene = s;
         sl->out_path = out_path ? out_path : "";
-        sl->quality = jpeg_quality;
-        if (!out_path) sl->coder = Coder::None;
-        else if (jpeg) sl->coder = Coder::Jpeg;
-        else if (exr)  // HALF unless the context, or at 0 the scene, asks for FLOAT channels
-            sl->coder = (c->exr_depth ? c->exr_depth : s->desc.render.exr_depth) == 32 ? Coder::Exr32 : Coder::Exr;
-        // "PNG". 16 bits per sample: always the device coder (there is no host one)
-        else if ((c->png_depth ? c->png_depth : s->desc.render.color_depth) == 16) sl->coder = Coder::Png16;
-        else sl->coder = c->device_png ? Coder::Png8 : Coder::HostRgba;
-        // the context's mode, at 0 the scene's, at 0 again the format's own layout
-        sl->color_mode = resolve_color_mode(c->color_mode ? c->color_mode : s->desc.render.color_mode, jpeg);
-        // the context's setting, at SCENE the scene's (-1, legacy, where it has no field)
-        sl->png_compression =
-            c->png_compression == RR_PNG_COMPRESSION_SCENE ? s->desc.render.png_compression : c->png_compression;
-        if (device_deflate(sl->coder)) {
-            const int rc = plan_or_refuse(sl->coder, sl->color_mode, sl->fs.W, sl->fs.H, sl->deflate.plan);
+        sl->out = fo;
+        if (device_deflate(fo.coder)) {
+            const int rc = plan_or_refuse(fo.coder, fo.color_mode, sl->fs.W, sl->fs.H, sl->coded.deflate.plan);
             if (rc != RR_OK) return rc;
         }
-        if (sl->coder == Coder::Png16) {
+        if (fo.coder == Coder::Png16) {
             set_device(c);
             ensure_srgb16(c);
         }
@@ -1272,55 +229,22 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
     if (ticket != c->next_complete) return fail(RR_EINVAL, "frames must be completed in submission order");
     FrameSlot* sl = slot_for(c, ticket);
     if (!sl->busy || sl->ticket != ticket) return fail(RR_EINVAL, "unknown ticket");
-    auto release = [&] {
-        sl->busy = false;
-        c->next_complete = ticket + 1;
-    };
     const int rc = guarded([&] {
         finish_frame(c, *sl);
         const FrameSetup& fs = sl->fs;
-        const FrameRun& r = sl->r;
-        const double t_sync = unix_now();
-        // Render span from the device's own clock. The frame's device work
-        // starts at its start event: for a frame submitted to an idle context
-        // that is the submit time; otherwise the previous completed frame's
-        // device start plus the device clock's difference between the two
-        // start events (start_ring). Frames in flight together overlap on the
-        // device, but the worker's records are consecutive (traces.py
-        // not_before, performance.rs): the render span starts when the
-        // previous frame's ended, or at the device start if later, and ends
-        // at the frame's own end event (ev4: build, trace, view transform),
-        // so the spans of overlapped frames add up to at most the wall time
-        // they took. The device JPEG coder, the copies and the file write
-        // after ev4 are "saving" (Blender's write_still).
-        constexpr int K = rr_ctx::kStartRing;
-        double dev_start = std::max(sl->submit_at, c->gpu_free_at);
-        if (!sl->anchor && c->chain_ticket && c->chain_ticket + 1 == ticket && c->start_ring[ticket % K]) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, c->start_ring[c->chain_ticket % K], c->start_ring[ticket % K]) == hipSuccess)
-                dev_start = c->chain_unix + ms * 1e-3;
-        }
-        dev_start = std::min(std::max(dev_start, sl->submit_at), t_sync);
-        c->chain_ticket = ticket;
-        c->chain_unix = dev_start;
-        sl->tm.started_rendering_at = std::min(std::max(dev_start, c->last_render_end), t_sync);
-        sl->tm.finished_rendering_at =
-            std::min(std::max(dev_start + r.render_ms * 1e-3, sl->tm.started_rendering_at), t_sync);
-        sl->tm.file_saving_started_at = sl->tm.finished_rendering_at;
-        c->last_render_end = sl->tm.finished_rendering_at;
-        c->gpu_free_at = std::min(dev_start + r.device_ms * 1e-3, t_sync);
+        const FrameOutput& fo = sl->out;
+        set_render_span(c, *sl, unix_now());
         uint64_t bytes = 0;
         const auto t_enc = std::chrono::steady_clock::now();
-        if (sl->coder == Coder::Jpeg || device_deflate(sl->coder)) {  // the host's container + the device-coded stream
+        if (fo.coder == Coder::Jpeg || device_deflate(fo.coder)) {  // the host's container + the device-coded stream
             std::vector<uint8_t> data;
-            if (sl->coder == Coder::Jpeg) jpeg_file_bytes(*sl, data);
-            else deflate_file_bytes(sl->deflate, sl->coder, sl->color_mode, data);
-            const std::string path = sl->out_path + coder_ext(sl->coder);
+            coded_file_bytes(sl->coded, fo, data);
+            const std::string path = sl->out_path + coder_ext(fo.coder);
             bytes = data.size();
             if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
-        } else if (sl->coder == Coder::HostRgba) {  // a submitted frame's: "PNG" by the host coder
-            const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), "PNG", sl->quality, &bytes,
-                                    sl->color_mode, sl->png_compression);
+        } else if (fo.coder == Coder::HostRgba) {  // a submitted frame's: "PNG" by the host coder
+            const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), "PNG", fo.quality, &bytes,
+                                    fo.color_mode, fo.png_compression);
             if (e != RR_OK) return e;
         }
         const double enc_ms = ms_since(t_enc);
@@ -1328,7 +252,7 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
         if (timing) *timing = sl->tm;
         c->frame_warning = sl->view_warning;
         if (stats) {
-            fill_stats(stats, fs, r, sl->scene->mesh.n_tris);
+            fill_stats(stats, fs, sl->r, sl->scene->mesh.n_tris);
             stats->view_transform_substituted = sl->view_substituted ? 1 : 0;
             stats->anim_ms = sl->anim_ms;
             stats->encode_ms = enc_ms;
@@ -1337,7 +261,8 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
         }
         return RR_OK;
     });
-    release();
+    sl->busy = false;
+    c->next_complete = ticket + 1;
     return rc;
 }
 
@@ -1373,7 +298,8 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         sl->view_substituted = !sl->view_warning.empty();
         sl->scene = s;
         sl->out_path.clear();
-        sl->coder = Coder::HostRgba;
+        sl->out = FrameOutput{};
+        sl->out.coder = Coder::HostRgba;  // the 8-bit image to the host; no file
         sl->film_out = film;
         sl->ticket = c->next_ticket;
         enqueue_frame(c, *sl);
@@ -1397,100 +323,11 @@ int rr_encode_image(const uint8_t* rgba8, int32_t w, int32_t h, const char* out_
     return guarded([&] { return do_encode(rgba8, w, h, out_path, format, quality, bytes); });
 }
 
-int rr_debug_jpeg_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, int32_t quality, uint8_t* out,
-                         uint64_t cap, uint64_t* len) {
-    if (!c || !rgba8 || !len || w <= 0 || h <= 0 || w > 65535 || h > 65535) return fail(RR_EINVAL, "bad arguments");
-    if (quality < 1 || quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
-    return debug_jpeg_device(c, RR_COLOR_RGB, rgba8, w, h, quality, out, cap, len);
-}
-
-int rr_set_device_png(rr_ctx* c, int32_t on) {
-    if (!c) return fail(RR_EINVAL, "NULL ctx");
-    c->device_png = on != 0;  // read when a frame is submitted; frames in flight keep their choice
-    return RR_OK;
-}
-
-int rr_debug_png_device(rr_ctx* c, const uint8_t* rgba8, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
-                        uint64_t* len) {
-    if (!c || !rgba8 || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    return debug_deflate_device(c, Coder::Png8, 4, w, h, rgba8, (size_t)w * h * 4, out, cap, len, [&](const void* img) {
-        return launch_png8(c->home, static_cast<const uint8_t*>(img), 4, png_compression_of(c), h);
-    });
-}
-
-int rr_debug_exr_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
-                        uint64_t* len) {
-    if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    return debug_deflate_device(c, Coder::Exr, 4, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
-                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false, false, 4); });
-}
-
-int rr_set_exr_depth(rr_ctx* c, int32_t depth) {
-    if (!c) return fail(RR_EINVAL, "NULL ctx");
-    if (depth != 0 && depth != 16 && depth != 32)
-        return fail(RR_EINVAL, "EXR depth must be 0 (the scene's), 16 or 32");
-    c->exr_depth = depth;  // read when a frame is submitted; frames in flight keep their choice
-    return RR_OK;
-}
-
-int rr_debug_exr32_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, uint8_t* out, uint64_t cap,
-                          uint64_t* len) {
-    if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    return debug_deflate_device(c, Coder::Exr32, 4, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
-                                [](const void* img) { return launch_exr(static_cast<const float4*>(img), 1.0f, false, true, 4); });
-}
-
-int rr_set_png_depth(rr_ctx* c, int32_t depth) {
-    if (!c) return fail(RR_EINVAL, "NULL ctx");
-    if (depth != 0 && depth != 8 && depth != 16) return fail(RR_EINVAL, "PNG depth must be 0 (the scene's), 8 or 16");
-    c->png_depth = depth;  // read when a frame is submitted; frames in flight keep their choice
-    return RR_OK;
-}
-
-int rr_debug_png16_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int32_t view_transform,
-                          float exposure_scale, uint8_t* out, uint64_t cap, uint64_t* len) {
-    if (!c || !rgba || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    int look = 0;
-    float gamma = 1.f;
-    if (const int rc = debug_view_settings(c, view_transform, look, gamma)) return rc;
-    return debug_deflate_device(c, Coder::Png16, 4, w, h, rgba, (size_t)w * h * sizeof(float4), out, cap, len,
-                                [&](const void* img) {
-                                    return launch_png16(c, c->home, static_cast<const float4*>(img), 1.0f,
-                                                        exposure_scale, view_transform, look, gamma, 4,
-                                                        png_compression_of(c), w, h);
-                                });
-}
-
-int rr_set_look(rr_ctx* c, const char* name) {
-    if (!c) return fail(RR_EINVAL, "NULL ctx");
-    const int id = (name && *name) ? look_id(name) : -1;
-    if (name && *name && id < 0) return fail(RR_EINVAL, std::string("unknown look '") + name + "'");
-    c->look = id;  // read when a frame is submitted; frames in flight keep theirs
-    return RR_OK;
-}
-
-int rr_set_display_gamma(rr_ctx* c, float gamma) {
-    if (!c) return fail(RR_EINVAL, "NULL ctx");
-    if (!(gamma >= 0.f) || gamma > kGammaMax)
-        return fail(RR_EINVAL, "display gamma must be 0 (the scene's) or above 0 and at most 5");
-    c->gamma = gamma;  // read when a frame is submitted; frames in flight keep theirs
-    return RR_OK;
-}
-
-int rr_set_dither(rr_ctx* c, float intensity) {
-    if (!c) return fail(RR_EINVAL, "NULL ctx");
-    if (intensity != RR_DITHER_SCENE && (!(intensity >= 0.f) || intensity > kDitherMax))
-        return fail(RR_EINVAL, "dither intensity must be in [0, 2], or RR_DITHER_SCENE (the scene's)");
-    c->dither = intensity;  // read when a frame is submitted; frames in flight keep theirs
-    return RR_OK;
-}
-
-int rr_set_png_compression(rr_ctx* c, int32_t percent) {
-    if (!c) return fail(RR_EINVAL, "NULL ctx");
-    if (!valid_png_compression(percent))
-        return fail(RR_EINVAL, "PNG compression must be 0 .. 100, RR_PNG_COMPRESSION_LEGACY or RR_PNG_COMPRESSION_SCENE");
-    c->png_compression = percent;  // read when a frame is submitted; frames in flight keep theirs
-    return RR_OK;
+int rr_encode_image_mode(const uint8_t* rgba8, int32_t w, int32_t h, const char* out_path, const char* format,
+                         int32_t quality, int32_t color_mode, uint64_t* bytes) {
+    if (!rgba8 || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad image");
+    if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
+    return guarded([&] { return do_encode(rgba8, w, h, out_path, format, quality, bytes, color_mode); });
 }
 
 int rr_encode_image_png(const uint8_t* rgba8, int32_t w, int32_t h, const char* out_path, int32_t color_mode,
@@ -1502,450 +339,55 @@ int rr_encode_image_png(const uint8_t* rgba8, int32_t w, int32_t h, const char* 
     return guarded([&] { return do_encode(rgba8, w, h, out_path, "PNG", 90, bytes, color_mode, compression); });
 }
 
-int rr_debug_png_filters(const uint8_t* raw, int32_t row_bytes, int32_t rows, int32_t bpp, uint8_t* types) {
-    if (!raw || !types || row_bytes <= 0 || rows <= 0 || bpp < 1 || bpp > 8) return fail(RR_EINVAL, "bad arguments");
-    for (int32_t y = 0; y < rows; ++y) {
-        const uint8_t* cur = raw + (size_t)y * (size_t)row_bytes;
-        types[y] = (uint8_t)png_pick_row(cur, y ? cur - row_bytes : nullptr, (size_t)row_bytes, (size_t)bpp, (size_t)rows);
-    }
+// The settings (settings.hpp has their values): read when a frame is
+// submitted; frames in flight keep their choice.
+
+int rr_set_device_png(rr_ctx* c, int32_t on) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    set_device_png(c->settings, on != 0);
     return RR_OK;
 }
 
-int rr_debug_scene_png_compression(rr_scene* s, int32_t* compression) {
-    if (!s || !compression) return fail(RR_EINVAL, "NULL argument");
-    *compression = s->desc.render.png_compression;
-    return RR_OK;
+int rr_set_png_depth(rr_ctx* c, int32_t depth) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_png_depth(c->settings, depth, err), err);
 }
 
-int rr_debug_sin_fixed(const float* in, uint64_t n, float* out) {
-    if ((!in || !out) && n) return fail(RR_EINVAL, "NULL array");
-    sin_fixed_host(in, (size_t)n, out);
-    return RR_OK;
-}
-
-int rr_debug_dither_noise(int32_t w, int32_t h, float* out) {
-    if (!out || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    dither_noise_host(w, h, out);
-    return RR_OK;
-}
-
-int rr_debug_view_device(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int32_t view_transform,
-                         float exposure_scale, uint8_t* rgba8_out) {
-    if (!c || !rgba || !rgba8_out || w <= 0 || h <= 0 || (int64_t)w * h > (int64_t)1 << 28)
-        return fail(RR_EINVAL, "bad arguments");
-    int look = 0;
-    float gamma = 1.f;
-    if (const int rc = debug_view_settings(c, view_transform, look, gamma)) return rc;
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        const size_t npix = (size_t)w * h;
-        if (!c->srgb_uploaded) {  // the 8-bit path's table (prepare_frame uploads it with a frame)
-            quiesce(c);
-            std::vector<float> lut(kSrgbLutSize + 1);
-            build_srgb_lut(lut.data());
-            c->paths.srgb_lut.ensure(lut.size());
-            RR_HIP(hipMemcpy(c->paths.srgb_lut.ptr, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
-            c->srgb_uploaded = true;
-        }
-        DevBuf<float4> img;
-        DevBuf<uchar4> q;
-        img.ensure(npix);
-        q.ensure(npix);
-        RR_HIP(hipMemcpy(img.ptr, rgba, npix * sizeof(float4), hipMemcpyHostToDevice));
-        FrameConsts k{};
-        k.W = w;
-        k.H = h;
-        k.npix = (int)npix;
-        k.inv_spp = 1.0f;
-        k.exposure_scale = exposure_scale;
-        k.view_transform = view_transform;
-        k.div_w = FastDiv::make((uint32_t)w);
-        // the context's dither; none where it leaves the intensity to a scene
-        const float dither = c->dither > 0.f ? c->dither : 0.f;
-        view_device(view_args(c, view_transform, look, gamma, dither), k, c->paths.srgb_lut.ptr, img.ptr, q.ptr,
-                    c->stream);
-        RR_HIP(hipStreamSynchronize(c->stream));
-        RR_HIP(hipMemcpy(rgba8_out, q.ptr, npix * 4, hipMemcpyDeviceToHost));
-        img.release();
-        q.release();
-        return RR_OK;
-    });
-}
-
-int rr_debug_display_gamma(const float* in, uint64_t n, float gamma, float* out) {
-    if ((!in || !out) && n) return fail(RR_EINVAL, "NULL array");
-    if (!(gamma > 0.f) || gamma > kGammaMax) return fail(RR_EINVAL, "display gamma must be above 0 and at most 5");
-    display_gamma_host(in, (size_t)n, gamma, out);
-    return RR_OK;
-}
-
-int rr_debug_scene_view(rr_scene* s, int32_t* view_transform, char* look, int32_t cap, float* gamma) {
-    if (!s) return fail(RR_EINVAL, "scene is NULL");
-    const RenderDesc& r = s->desc.render;
-    if (view_transform) *view_transform = r.view_transform;
-    const char* name = kLooks[r.look].name;
-    if (look && cap > (int32_t)std::strlen(name)) std::strcpy(look, name);
-    if (gamma) *gamma = (float)r.gamma;
-    return RR_OK;
+int rr_set_exr_depth(rr_ctx* c, int32_t depth) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_exr_depth(c->settings, depth, err), err);
 }
 
 int rr_set_color_mode(rr_ctx* c, int32_t mode) {
     if (!c) return fail(RR_EINVAL, "NULL ctx");
-    if (!valid_color_mode(mode))
-        return fail(RR_EINVAL, "colour mode must be RR_COLOR_SCENE (0), RR_COLOR_BW (1), RR_COLOR_RGB (3) or RR_COLOR_RGBA (4)");
-    c->color_mode = mode;  // read when a frame is submitted; frames in flight keep their choice
-    return RR_OK;
+    std::string err;
+    return setter_result(set_color_mode(c->settings, mode, err), err);
 }
 
-int rr_encode_image_mode(const uint8_t* rgba8, int32_t w, int32_t h, const char* out_path, const char* format,
-                         int32_t quality, int32_t color_mode, uint64_t* bytes) {
-    if (!rgba8 || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad image");
-    if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
-    return guarded([&] { return do_encode(rgba8, w, h, out_path, format, quality, bytes, color_mode); });
+int rr_set_look(rr_ctx* c, const char* name) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_look(c->settings, name, err), err);
 }
 
-int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t color_mode, const void* image,
-                           int32_t image_is_float, int32_t w, int32_t h, int32_t view_transform, float exposure_scale,
-                           int32_t jpeg_quality, uint8_t* out, uint64_t cap, uint64_t* len) {
-    if (!c || !format || !image || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
-    if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
-    const std::string fmt(format);
-    const bool jpeg = fmt == "JPEG";
-    const int C = resolve_color_mode(color_mode, jpeg);
-    if (jpeg) {
-        if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "JPEG takes an RGBA8 image at depth 8");
-        if (w > 65535 || h > 65535) return fail(RR_EINVAL, "image size outside the JPEG format's range");
-        if (jpeg_quality < 1 || jpeg_quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
-        return debug_jpeg_device(c, C, static_cast<const uint8_t*>(image), w, h, jpeg_quality, out, cap, len);
-    }
-    if (fmt == "PNG" && (depth == 0 || depth == 8)) {
-        if (image_is_float) return fail(RR_EINVAL, "8-bit PNG takes an RGBA8 image");
-        return debug_deflate_device(c, Coder::Png8, C, w, h, image, (size_t)w * h * 4, out, cap, len,
-                                    [&](const void* img) {
-                                        return launch_png8(c->home, static_cast<const uint8_t*>(img), C,
-                                                           png_compression_of(c), h);
-                                    });
-    }
-    if (!image_is_float) return fail(RR_EINVAL, "16-bit PNG and OPEN_EXR take a float RGBA image");
-    const size_t bytes = (size_t)w * h * sizeof(float4);
-    if (fmt == "PNG" && depth == 16) {
-        int look = 0;
-        float gamma = 1.f;
-        if (const int rc = debug_view_settings(c, view_transform, look, gamma)) return rc;
-        return debug_deflate_device(c, Coder::Png16, C, w, h, image, bytes, out, cap, len, [&](const void* img) {
-            return launch_png16(c, c->home, static_cast<const float4*>(img), 1.0f, exposure_scale, view_transform, look,
-                                gamma, C, png_compression_of(c), w, h);
-        });
-    }
-    if (fmt == "OPEN_EXR" && (depth == 0 || depth == 16 || depth == 32)) {
-        const bool full = depth == 32;
-        // A = 1, as in a rendered frame's file
-        return debug_deflate_device(c, full ? Coder::Exr32 : Coder::Exr, C, w, h, image, bytes, out, cap, len,
-                                    [&](const void* img) {
-                                        return launch_exr(static_cast<const float4*>(img), 1.0f, true, full, C);
-                                    });
-    }
-    return fail(RR_EINVAL, "no such format and depth: '" + fmt + "' at " + std::to_string(depth));
+int rr_set_display_gamma(rr_ctx* c, float gamma) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_display_gamma(c->settings, gamma, err), err);
 }
 
-int rr_debug_srgb16_table(float* table, int32_t cap, int32_t* n) {
-    if (!n) return fail(RR_EINVAL, "n is NULL");
-    *n = kSrgb16LutSize + 1;
-    if (table && cap >= *n) {
-        std::vector<float> lut(kSrgb16LutSize + 2);
-        build_srgb16_lut(lut.data());
-        std::memcpy(table, lut.data(), (size_t)*n * sizeof(float));
-    }
-    return RR_OK;
+int rr_set_dither(rr_ctx* c, float intensity) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_dither(c->settings, intensity, err), err);
 }
 
-int rr_debug_scene_mesh(rr_scene* s, float* tri_local9, int32_t* tri_object) {
-    if (!s) return fail(RR_EINVAL, "scene is NULL");
-    const size_t n = s->desc.tri_obj.size();
-    if (tri_local9)
-        for (size_t i = 0; i < n; ++i)
-            for (int k = 0; k < 3; ++k)
-                for (int a = 0; a < 3; ++a) tri_local9[9 * i + 3 * k + a] = s->desc.tri_local[12 * i + 4 * k + a];
-    if (tri_object && n) std::memcpy(tri_object, s->desc.tri_obj.data(), n * sizeof(int32_t));
-    return RR_OK;
-}
-
-int rr_debug_counts(rr_scene* s, int32_t* nt, int32_t* nl, int32_t* nm, int32_t* no) {
-    if (!s) return fail(RR_EINVAL, "scene is NULL");
-    int lights = 0;
-    for (auto& o : s->desc.objects) lights += o.type == OBJ_LIGHT;
-    if (nt) *nt = (int32_t)s->desc.tri_obj.size();
-    if (nl) *nl = lights;
-    if (nm) *nm = (int32_t)s->desc.materials.size();
-    if (no) *no = (int32_t)s->desc.objects.size();
-    return RR_OK;
-}
-
-int rr_debug_frame_state(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* params, float* tris_world,
-                         int32_t* tri_material, float* camera, float* lights, float* materials, float* world,
-                         int32_t* render_ints, float* render_floats) {
-    if (!s) return fail(RR_EINVAL, "NULL scene");
-    if (!c && tris_world) return fail(RR_EINVAL, "world triangles need a device context");
-    return guarded([&] {
-        FrameSetup fs = setup_frame(s->desc, frame, params);
-        if (c) resolve_view(c, fs);  // render_ints[5]: the transform a frame on c is rendered with
-        const int n = s->mesh.n_tris;
-        if (c) {  // host-only queries (c == NULL) skip the device part
-            if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-            set_device(c);
-            PinnedBuf staging;
-            prepare_frame(c, s, s->build, c->home, c->stream, fs, staging);
-            RR_HIP(hipStreamSynchronize(c->stream));
-        }
-        if (tris_world && n > 0) {
-            std::vector<float4> w((size_t)3 * n);
-            RR_HIP(hipMemcpyAsync(w.data(), s->build.tri_world.ptr, w.size() * sizeof(float4), hipMemcpyDeviceToHost,
-                                  c->stream));
-            RR_HIP(hipStreamSynchronize(c->stream));
-            for (size_t i = 0; i < w.size(); ++i) {
-                tris_world[3 * i] = w[i].x;
-                tris_world[3 * i + 1] = w[i].y;
-                tris_world[3 * i + 2] = w[i].z;
-            }
-        }
-        if (c) RR_HIP(hipStreamSynchronize(c->stream));
-        if (tri_material) std::memcpy(tri_material, s->desc.tri_mat.data(), n * sizeof(int32_t));
-        if (camera) std::memcpy(camera, fs.cam, sizeof fs.cam);
-        if (lights && !fs.lights.empty()) std::memcpy(lights, fs.lights.data(), fs.lights.size() * sizeof(float));
-        if (materials) std::memcpy(materials, fs.materials.data(), fs.materials.size() * sizeof(float));
-        if (world) std::memcpy(world, fs.world, sizeof fs.world);
-        if (render_ints) {
-            const int32_t ri[RR_RENDER_INTS] = {fs.W, fs.H, fs.spp, fs.max_bounces, (int32_t)fs.seed,
-                                               fs.view_transform, choose_spp_chunk(fs), frame_hier_of(s, fs),
-                                               fs.max_diffuse, fs.max_glossy};
-            std::memcpy(render_ints, ri, sizeof ri);
-        }
-        if (render_floats) {
-            const float rf[RR_RENDER_FLOATS] = {fs.clamp_indirect, fs.filter_width, fs.exposure_scale, 0.f};
-            std::memcpy(render_floats, rf, sizeof rf);
-        }
-        return RR_OK;
-    });
-}
-
-int rr_debug_bvh(rr_ctx* c, rr_scene* s, int32_t frame, uint32_t* keys, uint32_t* order, int32_t* children,
-                 float* boxes) {
-    return rr_debug_bvh_hier(c, s, frame, 0, keys, order, children, boxes);
-}
-
-int rr_debug_bvh_hier(rr_ctx* c, rr_scene* s, int32_t frame, int32_t hier, uint32_t* keys, uint32_t* order,
-                      int32_t* children, float* boxes) {
-    if (!c || !s) return fail(RR_EINVAL, "NULL ctx or scene");
-    if (hier != 0 && hier != kHierLbvh && hier != kHierPloc) return fail(RR_EINVAL, "hier must be 0, 2 or 3");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        FrameSetup fs = setup_frame(s->desc, frame, nullptr);
-        set_device(c);
-        PinnedBuf staging;
-        prepare_frame(c, s, s->build, c->home, c->stream, fs, staging, hier);
-        const DevBuild& d = s->build;
-        const int n = s->mesh.n_tris;
-        hipStream_t st = c->stream;
-        if (n > 0) {
-            if (keys) RR_HIP(hipMemcpyAsync(keys, d.keys[0].ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            if (order) RR_HIP(hipMemcpyAsync(order, d.vals[0].ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            const int ni = n > 1 ? n - 1 : 1;
-            std::vector<BvhNode> nodes((size_t)ni);
-            RR_HIP(hipMemcpyAsync(nodes.data(), d.nodes.ptr, ni * sizeof(BvhNode), hipMemcpyDeviceToHost, st));
-            RR_HIP(hipStreamSynchronize(st));
-            for (int i = 0; i < ni; ++i) {
-                const float* f = reinterpret_cast<const float*>(&nodes[i]);
-                if (boxes) std::memcpy(boxes + 12 * i, f, 12 * sizeof(float));
-                if (children) {
-                    children[2 * i] = nodes[i].d.x;
-                    children[2 * i + 1] = nodes[i].d.y;
-                }
-            }
-        }
-        RR_HIP(hipStreamSynchronize(st));
-        return RR_OK;
-    });
-}
-
-int rr_debug_qbvh(rr_ctx* c, rr_scene* s, int32_t frame, int32_t* nq, int32_t* children, uint32_t* nodes16,
-                  int32_t* tri_orig) {
-    if (!c || !s || !nq) return fail(RR_EINVAL, "NULL ctx, scene or nq");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        FrameSetup fs = setup_frame(s->desc, frame, nullptr);
-        set_device(c);
-        PinnedBuf staging;
-        prepare_frame(c, s, s->build, c->home, c->stream, fs, staging, kHierQWide);
-        const DevBuild& d = s->build;
-        hipStream_t st = c->stream;
-        const int n = s->mesh.n_tris;
-        *nq = 0;
-        if (n > 0) {
-            const uint32_t cnt = (uint32_t)d.nq;
-            *nq = (int32_t)cnt;
-            if (children || nodes16) {
-                std::vector<QNode6> nodes(cnt);
-                RR_HIP(hipMemcpyAsync(nodes.data(), d.qnodes.ptr, cnt * sizeof(QNode6), hipMemcpyDeviceToHost, st));
-                RR_HIP(hipStreamSynchronize(st));
-                for (uint32_t i = 0; i < cnt; ++i) {
-                    const QNode6& q = nodes[i];
-                    if (children) {  // the implicit references, spelled out (unused slots: 0x7fffffff)
-                        const uint32_t eb = (uint32_t)f2i(q.org.w);
-                        for (int k = 0; k < kQWidth; ++k) {
-                            const uint32_t lox = k < 4 ? (q.a.z >> (8 * k)) & 255u : (q.c.x >> (8 * (k - 4))) & 255u;
-                            const uint32_t hix = k < 4 ? (q.b.y >> (8 * k)) & 255u : (q.c.y >> (16 + 8 * (k - 4))) & 255u;
-                            const bool unused = lox == 255u && hix == 0u && !((eb >> (24 + k)) & 1u);
-                            children[kQWidth * (size_t)i + k] = unused ? 0x7fffffff : q6_ref(q, k);
-                        }
-                    }
-                    if (nodes16) std::memcpy(nodes16 + 16 * (size_t)i, &q, sizeof(QNode6));
-                }
-            }
-            if (tri_orig) {  // original id of each position of the hierarchy's triangle array
-                std::vector<TriPack> tp((size_t)n);
-                RR_HIP(hipMemcpyAsync(tp.data(), d.tris.ptr, (size_t)n * sizeof(TriPack), hipMemcpyDeviceToHost, st));
-                RR_HIP(hipStreamSynchronize(st));
-                for (int i = 0; i < n; ++i) tri_orig[i] = f2i(tp[(size_t)i].p0.w);
-            }
-        }
-        return RR_OK;
-    });
-}
-
-int rr_debug_trace(rr_ctx* c, rr_scene* s, int32_t frame, int32_t bvh_width, int32_t n, const float* rays,
-                   float* hits, int32_t* prims, uint8_t* occluded) {
-    if (!c || !s || n < 0 || (n > 0 && !rays)) return fail(RR_EINVAL, "bad arguments");
-    if (bvh_width < 0 || bvh_width == 1 || bvh_width > 7)
-        return fail(RR_EINVAL, "hierarchy must be 0 (frame's), 2 (LBVH), 3 (PLOC), 4 (6-wide), 5 (6-wide, packets) "
-                               "6 (6-wide, one LDS stack entry) or 7 (6-wide, beam packets)");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        FrameSetup fs = setup_frame(s->desc, frame, nullptr);
-        set_device(c);
-        PinnedBuf staging;
-        const int hier = bvh_width >= 5 ? kHierQWide : (bvh_width ? bvh_width : frame_hier_of(s, fs));
-        prepare_frame(c, s, s->build, c->home, c->stream, fs, staging, hier);
-        const int width = bvh_width >= 5 ? bvh_width : (hier == kHierQWide ? 4 : 2);
-        hipStream_t st = c->stream;
-        DevBuf<float4> dr, dh;
-        DevBuf<int32_t> dp;
-        DevBuf<uint8_t> dq;
-        const size_t m = n > 0 ? (size_t)n : 1;
-        dr.ensure(2 * m);
-        dh.ensure(m);
-        dp.ensure(m);
-        dq.ensure(m);
-        if (n > 0) RR_HIP(hipMemcpyAsync(dr.ptr, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice, st));
-        trace_batch_device(s->mesh, s->build, c->paths, c->home, n, dr.ptr, dh.ptr, dp.ptr, dq.ptr, st, width);
-        std::vector<float4> h(m);
-        if (n > 0) {
-            RR_HIP(hipMemcpyAsync(h.data(), dh.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, st));
-            if (prims) RR_HIP(hipMemcpyAsync(prims, dp.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            if (occluded) RR_HIP(hipMemcpyAsync(occluded, dq.ptr, n, hipMemcpyDeviceToHost, st));
-        }
-        RR_HIP(hipStreamSynchronize(st));
-        if (hits)
-            for (int i = 0; i < n; ++i) {
-                hits[4 * i] = h[i].x;
-                hits[4 * i + 1] = h[i].y;
-                hits[4 * i + 2] = h[i].z;
-                hits[4 * i + 3] = 0.0f;
-            }
-        dr.release(); dh.release(); dp.release(); dq.release();
-        return RR_OK;
-    });
-}
-
-int rr_debug_tile_costs(rr_ctx* c, int32_t capacity, uint32_t* costs, int32_t* order, int32_t* n_tiles,
-                        uint64_t* unit_log, int32_t unit_capacity) {
-    if (!c || capacity < 0 || !n_tiles || (capacity > 0 && (!costs || !order)) || unit_capacity < 0 ||
-        (unit_capacity > 0 && !unit_log))
-        return fail(RR_EINVAL, "bad arguments");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        *n_tiles = 0;
-        const FrameSlot* sl = c->last_enqueued;
-        if (!sl || !sl->tiles) return RR_OK;  // no tile frame yet
-        set_device(c);
-        const DevFrame& f = sl->dev;
-        const size_t n = std::min(f.tile_cost.cap, f.tile_order.cap);
-        *n_tiles = (int32_t)n;
-        const size_t m = std::min<size_t>(n, (size_t)capacity);
-        if (m > 0) {
-            // the cost buffer is longer than the order's: behind the frame's tile costs it holds, per tile, the
-            // samples a counting launch's covered body ran (tiles.hip); a caller with room gets those words too
-            const size_t mc = std::min<size_t>(f.tile_cost.cap, (size_t)capacity);
-            RR_HIP(hipMemcpy(costs, f.tile_cost.ptr, mc * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            RR_HIP(hipMemcpy(order, f.tile_order.ptr, m * sizeof(int32_t), hipMemcpyDeviceToHost));
-        }
-        const size_t nu = std::min<size_t>((size_t)unit_capacity, kUnitLog);
-        if (nu > 0) {
-            std::memset(unit_log, 0, 2 * nu * sizeof(uint64_t));
-            // only the launch that wrote it (a counting frame): an older frame's log stays unreported
-            if (f.unit_logged && f.trav_counts.cap >= (size_t)(kTravWords + 2 * kUnitLog))
-                RR_HIP(hipMemcpy(unit_log, f.trav_counts.ptr + kTravWords, 2 * nu * sizeof(uint64_t),
-                                 hipMemcpyDeviceToHost));
-        }
-        return RR_OK;
-    });
-}
-
-int rr_debug_fastmath_check(rr_ctx* c, uint32_t lo, uint64_t n, uint64_t* counts5) {
-    if (!c || !counts5 || n > (1ull << 32) - lo) return fail(RR_EINVAL, "bad arguments");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        hipStream_t st = c->stream;
-        DevBuf<unsigned long long> d;
-        d.ensure(5);
-        fastmath_check_device(lo, n, d.ptr, st);
-        RR_HIP(hipMemcpyAsync(counts5, d.ptr, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        RR_HIP(hipStreamSynchronize(st));
-        d.release();
-        return RR_OK;
-    });
-}
-
-int rr_debug_bsdf_sample(rr_ctx* c, const float* mat12, const float* n3, const float* wo3, int32_t n,
-                         const float* u, float* wi3, float* f3, float* pdf, int32_t* ok) {
-    if (!c || !mat12 || !n3 || !wo3 || n < 0 || (n > 0 && (!u || !wi3 || !f3 || !pdf || !ok)))
-        return fail(RR_EINVAL, "bad arguments");
-    return guarded([&] {
-        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
-        set_device(c);
-        hipStream_t st = c->stream;
-        const size_t m = n > 0 ? (size_t)n : 1;
-        DevBuf<float> dm, du, dw, df, dp, dl;
-        DevBuf<int32_t> dk;
-        float lut[kMatLutFloatsPerMat];
-        build_material_lut(mat12, lut);
-        dl.ensure(kMatLutFloatsPerMat);
-        RR_HIP(hipMemcpyAsync(dl.ptr, lut, sizeof lut, hipMemcpyHostToDevice, st));
-        dm.ensure(RR_MAT_FLOATS);
-        du.ensure(3 * m); dw.ensure(3 * m); df.ensure(3 * m); dp.ensure(m); dk.ensure(m);
-        RR_HIP(hipMemcpyAsync(dm.ptr, mat12, RR_MAT_FLOATS * sizeof(float), hipMemcpyHostToDevice, st));
-        if (n > 0) RR_HIP(hipMemcpyAsync(du.ptr, u, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-        bsdf_batch_device(dm.ptr, dl.ptr, n3, wo3, n, du.ptr, dw.ptr, df.ptr, dp.ptr, dk.ptr, st);
-        if (n > 0) {
-            RR_HIP(hipMemcpyAsync(wi3, dw.ptr, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-            RR_HIP(hipMemcpyAsync(f3, df.ptr, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-            RR_HIP(hipMemcpyAsync(pdf, dp.ptr, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-            RR_HIP(hipMemcpyAsync(ok, dk.ptr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        }
-        RR_HIP(hipStreamSynchronize(st));
-        RR_HIP(hipStreamSynchronize(st));
-        dm.release(); du.release(); dw.release(); df.release(); dp.release(); dk.release(); dl.release();
-        return RR_OK;
-    });
-}
-
-int rr_debug_object_matrix(rr_scene* s, int32_t obj, double frame, double* m16) {
-    if (!s || !m16) return fail(RR_EINVAL, "NULL argument");
-    return guarded([&] {
-        object_matrix(s->desc, obj, frame, m16);
-        return RR_OK;
-    });
+int rr_set_png_compression(rr_ctx* c, int32_t percent) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_png_compression(c->settings, percent, err), err);
 }
 
 }  // extern "C"

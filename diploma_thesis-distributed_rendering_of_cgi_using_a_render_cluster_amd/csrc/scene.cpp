@@ -11,7 +11,7 @@
 #include <stdexcept>
 
 #include "json.hpp"
-#include "view.hpp"
+#include "looks.hpp"
 
 namespace rr {
 
@@ -671,7 +671,7 @@ SceneDesc load_scene(const std::string& path) {
         // The Filmic family ("Filmic" with its looks, "Filmic Log", "False
         // Color") is applied through Blender's OCIO LUTs when the context has
         // them (rr_set_ocio_config); otherwise the frame falls back and says
-        // so (rr_frame_stats.view_transform_substituted; rr_api.cpp
+        // so (rr_frame_stats.view_transform_substituted; frame.cpp
         // resolve_view). Any other view renders as Standard with the same flag
         // and a warning naming it, and a look this renderer does not know is
         // ignored the same way: the job still renders, and the substitution is

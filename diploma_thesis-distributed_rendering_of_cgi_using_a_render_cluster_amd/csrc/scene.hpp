@@ -115,7 +115,7 @@ struct RenderDesc {
     int color_mode = 0;   // RR_COLOR_BW / RGB / RGBA, 0: no field (rr_set_color_mode 0 takes it)
     int view_transform = VIEW_STANDARD;
     std::string view_transform_name = "Standard";
-    int look = 0;        // view.hpp kLooks id of render.look (0 None; rr_set_look NULL takes it)
+    int look = 0;        // looks.hpp kLooks id of render.look (0 None; rr_set_look NULL takes it)
     double gamma = 1.0;  // render.gamma, in (0, 5] (rr_set_display_gamma 0 takes it)
     double dither_intensity = 0.0;  // render.dither_intensity, in [0, 2] (rr_set_dither RR_DITHER_SCENE takes it)
     int png_compression = -1;  // render.png_compression, 0 .. 100; -1: no field (rr_set_png_compression SCENE takes it)
@@ -123,7 +123,7 @@ struct RenderDesc {
     // frame's warning ("" when there is nothing): a view transform this
     // renderer does not know (rendered as Standard), a look it does not know
     // (ignored). What a context cannot apply for want of a LUT is noted when
-    // the frame is submitted (rr_api.cpp resolve_view).
+    // the frame is submitted (frame.cpp resolve_view).
     std::string view_note;
     uint32_t seed = 0;
     int spp_per_chunk = 0;

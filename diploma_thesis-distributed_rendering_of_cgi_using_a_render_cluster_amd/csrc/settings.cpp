@@ -1,0 +1,213 @@
+// Output settings: their ranges, their environment spellings, and the file a
+// frame gets from them. See settings.hpp.
+#include "settings.hpp"
+
+#include <cstdlib>
+
+#include "looks.hpp"
+#include "scene.hpp"
+
+namespace rr {
+
+bool set_png_depth(OutputSettings& s, int depth, std::string& err) {
+    if (depth != 0 && depth != 8 && depth != 16) {
+        err = "PNG depth must be 0 (the scene's), 8 or 16";
+        return false;
+    }
+    s.png_depth = depth;
+    return true;
+}
+
+bool set_exr_depth(OutputSettings& s, int depth, std::string& err) {
+    if (depth != 0 && depth != 16 && depth != 32) {
+        err = "EXR depth must be 0 (the scene's), 16 or 32";
+        return false;
+    }
+    s.exr_depth = depth;
+    return true;
+}
+
+bool valid_color_mode(int mode) {
+    return mode == RR_COLOR_SCENE || mode == RR_COLOR_BW || mode == RR_COLOR_RGB || mode == RR_COLOR_RGBA;
+}
+
+bool set_color_mode(OutputSettings& s, int mode, std::string& err) {
+    if (!valid_color_mode(mode)) {
+        err = "colour mode must be RR_COLOR_SCENE (0), RR_COLOR_BW (1), RR_COLOR_RGB (3) or RR_COLOR_RGBA (4)";
+        return false;
+    }
+    s.color_mode = mode;
+    return true;
+}
+
+bool set_look(OutputSettings& s, const char* name, std::string& err) {
+    const int id = (name && *name) ? look_id(name) : -1;
+    if (name && *name && id < 0) {
+        err = std::string("unknown look '") + name + "'";
+        return false;
+    }
+    s.look = id;
+    return true;
+}
+
+bool set_display_gamma(OutputSettings& s, double gamma, std::string& err) {
+    if (!(gamma >= 0.0) || gamma > (double)kGammaMax) {
+        err = "display gamma must be 0 (the scene's) or above 0 and at most 5";
+        return false;
+    }
+    s.gamma = (float)gamma;
+    return true;
+}
+
+bool set_dither(OutputSettings& s, double intensity, std::string& err) {
+    if (intensity != (double)RR_DITHER_SCENE && (!(intensity >= 0.0) || intensity > (double)kDitherMax)) {
+        err = "dither intensity must be in [0, 2], or RR_DITHER_SCENE (the scene's)";
+        return false;
+    }
+    s.dither = (float)intensity;
+    return true;
+}
+
+bool valid_png_compression(int v) { return v >= RR_PNG_COMPRESSION_SCENE && v <= 100; }
+
+bool set_png_compression(OutputSettings& s, int percent, std::string& err) {
+    if (!valid_png_compression(percent)) {
+        err = "PNG compression must be 0 .. 100, RR_PNG_COMPRESSION_LEGACY or RR_PNG_COMPRESSION_SCENE";
+        return false;
+    }
+    s.png_compression = percent;
+    return true;
+}
+
+namespace {
+
+// A whole text as one number, as strtol / strtod read it.
+bool whole_long(const char* t, long& v) {
+    char* end = nullptr;
+    v = std::strtol(t, &end, 10);
+    return end != t && !*end;
+}
+bool whole_double(const char* t, double& v) {
+    char* end = nullptr;
+    v = std::strtod(t, &end);
+    return end != t && !*end;
+}
+
+// The text of one variable through its setter. The spellings: "" is the
+// setting's default; a depth is "0", "8", "16", "32" and no other way of
+// writing those numbers; a colour mode is its Blender name; the values that
+// rr.h gives a negative constant are spelled "scene" (and LEGACY ""), never as
+// that number.
+bool apply_text(OutputSettings& s, const std::string& var, const char* t, std::string& err) {
+    const std::string v(t);
+    long n = 0;
+    double x = 0.0;
+    if (var == "RR_DEVICE_PNG") {
+        set_device_png(s, v == "1");
+        return true;
+    }
+    if (var == "RR_PNG_DEPTH" || var == "RR_EXR_DEPTH") {
+        if (v.empty()) n = 0;
+        else if (!whole_long(t, n) || std::to_string(n) != v) {
+            err = "not a depth";
+            return false;
+        }
+        const int d = n == (long)(int)n ? (int)n : -1;
+        return var == "RR_PNG_DEPTH" ? set_png_depth(s, d, err) : set_exr_depth(s, d, err);
+    }
+    if (var == "RR_COLOR_MODE") {
+        if (v.empty()) return set_color_mode(s, RR_COLOR_SCENE, err);
+        if (v == "BW") return set_color_mode(s, RR_COLOR_BW, err);
+        if (v == "RGB") return set_color_mode(s, RR_COLOR_RGB, err);
+        if (v == "RGBA") return set_color_mode(s, RR_COLOR_RGBA, err);
+        err = "colour mode must be BW, RGB or RGBA";
+        return false;
+    }
+    if (var == "RR_LOOK") return set_look(s, t, err);
+    if (var == "RR_DISPLAY_GAMMA") {
+        if (v.empty()) return set_display_gamma(s, 0.0, err);
+        if (!whole_double(t, x)) {
+            err = "not a number";
+            return false;
+        }
+        return set_display_gamma(s, x, err);
+    }
+    if (var == "RR_DITHER") {
+        if (v.empty()) return set_dither(s, 0.0, err);
+        if (v == "scene") return set_dither(s, (double)RR_DITHER_SCENE, err);
+        if (!whole_double(t, x) || x == (double)RR_DITHER_SCENE) {
+            err = "not a number in [0, 2] or 'scene'";
+            return false;
+        }
+        return set_dither(s, x, err);
+    }
+    if (var == "RR_PNG_COMPRESSION") {
+        if (v.empty()) return true;  // the context's own (LEGACY on a new one)
+        if (v == "scene") return set_png_compression(s, RR_PNG_COMPRESSION_SCENE, err);
+        if (!whole_long(t, n) || n != (long)(int)n || n == RR_PNG_COMPRESSION_LEGACY || n == RR_PNG_COMPRESSION_SCENE) {
+            err = "not a number in 0 .. 100 or 'scene'";
+            return false;
+        }
+        return set_png_compression(s, (int)n, err);
+    }
+    err = "not an output setting";
+    return false;
+}
+
+constexpr const char* kEnvVars[] = {"RR_PNG_DEPTH",     "RR_EXR_DEPTH",       "RR_COLOR_MODE", "RR_LOOK",
+                                    "RR_DISPLAY_GAMMA", "RR_PNG_COMPRESSION", "RR_DITHER",     "RR_DEVICE_PNG"};
+
+}  // namespace
+
+bool setting_from_text(OutputSettings& s, const std::string& var, const char* text, std::string& err) {
+    std::string why;
+    if (apply_text(s, var, text, why)) return true;
+    err = var + "='" + text + "': " + why;
+    return false;
+}
+
+bool settings_from_env(OutputSettings& s, std::string& err) {
+    OutputSettings t = s;
+    for (const char* var : kEnvVars)
+        if (const char* text = std::getenv(var))
+            if (!setting_from_text(t, var, text, err)) return false;
+    s = t;
+    return true;
+}
+
+const char* coder_ext(Coder k) {
+    return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : ".png";
+}
+
+int resolve_color_mode(int mode, bool jpeg) {
+    if (mode == 0) return jpeg ? RR_COLOR_RGB : RR_COLOR_RGBA;
+    return (jpeg && mode == RR_COLOR_RGBA) ? RR_COLOR_RGB : mode;
+}
+
+FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const char* format, bool has_path,
+                           int jpeg_quality) {
+    const bool jpeg = has_path && std::string(format) == "JPEG";
+    const bool exr = has_path && std::string(format) == "OPEN_EXR";
+    FrameOutput o;
+    if (!has_path) o.coder = Coder::None;
+    else if (jpeg) o.coder = Coder::Jpeg;
+    else if (exr)  // HALF unless the context, or at 0 the scene, asks for FLOAT channels
+        o.coder = (s.exr_depth ? s.exr_depth : r.exr_depth) == 32 ? Coder::Exr32 : Coder::Exr;
+    // "PNG". 16 bits per sample: always the device coder (there is no host one)
+    else if ((s.png_depth ? s.png_depth : r.color_depth) == 16) o.coder = Coder::Png16;
+    else o.coder = s.device_png ? Coder::Png8 : Coder::HostRgba;
+    // the context's mode, at 0 the scene's, at 0 again the format's own layout
+    o.color_mode = resolve_color_mode(s.color_mode ? s.color_mode : r.color_mode, jpeg);
+    // the context's setting, at SCENE the scene's (-1, legacy, where it has no field)
+    o.png_compression = s.png_compression == RR_PNG_COMPRESSION_SCENE ? r.png_compression : s.png_compression;
+    o.quality = jpeg_quality;
+    return o;
+}
+
+int png_compression_of(const OutputSettings& s) {
+    return s.png_compression >= 0 ? s.png_compression : RR_PNG_COMPRESSION_LEGACY;
+}
+
+float dither_of(const OutputSettings& s) { return s.dither > 0.f ? s.dither : 0.f; }
+
+}  // namespace rr

@@ -1,0 +1,103 @@
+// The output settings of a context (rr_set_* / the RR_* environment variables)
+// and what file they give a frame. Host code only, no HIP header: the checks
+// of tests/cpp/settings_check.cpp link settings.cpp and nothing else.
+//
+// A setting's valid values are stated once, in its setter. rr_set_* calls the
+// setter; settings_from_env parses a variable's text and calls the same one.
+#pragma once
+
+#include <string>
+
+#include "rr.h"
+
+namespace rr {
+
+struct RenderDesc;  // scene.hpp
+
+struct OutputSettings {
+    // 8-bit "PNG" frames are coded on the device (rr_set_device_png / RR_DEVICE_PNG)
+    bool device_png = false;
+    // bit depth of "PNG" frames (rr_set_png_depth / RR_PNG_DEPTH): 0 the scene's, 8, 16
+    int png_depth = 0;
+    // channel type of "OPEN_EXR" frames (rr_set_exr_depth / RR_EXR_DEPTH): 0 the scene's, 16 HALF, 32 FLOAT
+    int exr_depth = 0;
+    // colour mode of the files (rr_set_color_mode / RR_COLOR_MODE): 0 the scene's, else RR_COLOR_BW / RGB / RGBA
+    int color_mode = 0;
+    // look of Filmic frames (rr_set_look / RR_LOOK): a looks.hpp kLooks id, -1 the scene's
+    int look = -1;
+    // compression of "PNG" files (rr_set_png_compression / RR_PNG_COMPRESSION): LEGACY, SCENE or 0 .. 100
+    int png_compression = RR_PNG_COMPRESSION_LEGACY;
+    // display gamma (rr_set_display_gamma / RR_DISPLAY_GAMMA): 0 the scene's
+    float gamma = 0.f;
+    // dither of the 8-bit image (rr_set_dither / RR_DITHER): an intensity in [0, 2], RR_DITHER_SCENE the scene's
+    float dither = 0.f;
+};
+
+// The setters. false + err for a value outside the setting's range, which
+// changes nothing. Settings are read when a frame is submitted; frames in
+// flight keep theirs.
+inline void set_device_png(OutputSettings& s, bool on) { s.device_png = on; }
+bool set_png_depth(OutputSettings& s, int depth, std::string& err);
+bool set_exr_depth(OutputSettings& s, int depth, std::string& err);
+bool set_color_mode(OutputSettings& s, int mode, std::string& err);
+bool set_look(OutputSettings& s, const char* name, std::string& err);  // NULL or "": the scene's
+bool set_display_gamma(OutputSettings& s, double gamma, std::string& err);
+bool set_dither(OutputSettings& s, double intensity, std::string& err);
+bool set_png_compression(OutputSettings& s, int percent, std::string& err);
+
+bool valid_color_mode(int mode);
+// rr_set_png_compression's values: LEGACY, SCENE or a percentage.
+bool valid_png_compression(int v);
+
+// One variable's text (RR_PNG_DEPTH, RR_EXR_DEPTH, RR_COLOR_MODE, RR_LOOK,
+// RR_DISPLAY_GAMMA, RR_PNG_COMPRESSION, RR_DITHER, RR_DEVICE_PNG) through its
+// setter. A refusal's err names the variable and quotes the text.
+bool setting_from_text(OutputSettings& s, const std::string& var, const char* text, std::string& err);
+// Every variable that is set, in the order above. false + err: s is unchanged.
+bool settings_from_env(OutputSettings& s, std::string& err);
+
+// Who codes a frame's output. HostRgba: the 8-bit image comes back to the host
+// (rr_render_frame_to_memory; a "PNG" file from the host's zlib threads where a
+// path is given). Jpeg ... Exr32: coded on the device, the file written from the
+// slot's pinned stream. Png8: "PNG" with rr_set_device_png; Png16: "PNG" at 16
+// bits per sample, for which there is no host coder. Exr: "OPEN_EXR" with HALF
+// channels; Exr32: with FLOAT channels (rr_set_exr_depth).
+enum class Coder { None, HostRgba, Jpeg, Png8, Png16, Exr, Exr32 };
+
+// The formats behind the deflate coder (deflate.hip): their coder reads only
+// its slot's rgba8 / film and writes slot buffers only.
+inline bool device_deflate(Coder k) {
+    return k == Coder::Png8 || k == Coder::Png16 || k == Coder::Exr || k == Coder::Exr32;
+}
+
+const char* coder_ext(Coder k);
+
+// The channels a frame's file holds (rr_set_color_mode), which is also the
+// resolved mode's value: RR_COLOR_BW 1, RR_COLOR_RGB 3, RR_COLOR_RGBA 4. mode 0:
+// the format's layout before there was a setting (JPEG three components, PNG
+// and OPEN_EXR four channels). JPEG has no alpha: RGBA resolves to RGB, as in
+// Blender.
+int resolve_color_mode(int mode, bool jpeg);
+
+// The file of one frame, resolved when the frame is submitted.
+struct FrameOutput {
+    Coder coder = Coder::None;
+    int color_mode = RR_COLOR_RGBA;                    // the file's channels (resolve_color_mode)
+    int png_compression = RR_PNG_COMPRESSION_LEGACY;   // LEGACY, or 0 .. 100
+    int quality = 0;                                   // JPEG
+};
+
+// What a frame of a scene with render settings r is written as on a context
+// with settings s. format: "JPEG", "PNG" or "OPEN_EXR" (checked by the
+// caller); without a path there is no file (Coder::None).
+FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const char* format, bool has_path,
+                           int jpeg_quality);
+
+// The PNG compression of an image that comes with no scene (the inspection
+// entry points): the context's, SCENE meaning legacy.
+int png_compression_of(const OutputSettings& s);
+// The dither of such an image: the context's; none where it leaves the
+// intensity to a scene.
+float dither_of(const OutputSettings& s);
+
+}  // namespace rr

@@ -554,7 +554,7 @@ RR_D TileOrder uniform_order(TileOrder t) {
 
 // Per-lane ray counts of the tile kernel, reduced once per wave at exit into
 // the chunk-0 counter pairs: {0, 1} = bounce 0, {2, 3} = all later bounces
-// (rr_api.cpp fill_stats sums the pairs); tail = the chunk's words from
+// (frame.cpp fill_stats sums the pairs); tail = the chunk's words from
 // camera_traced_slot on: [0] camera rays traced, [2] / [3] continuations /
 // shadow rays traversed (the out-of-line traversals; the other continuations
 // and shadow rays left a hull side and were resolved without a traversal,

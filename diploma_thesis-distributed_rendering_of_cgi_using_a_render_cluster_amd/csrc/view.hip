@@ -227,25 +227,6 @@ bool load_filmic_luts(const std::string& dir, FilmicLuts& out, std::string& err)
     return true;
 }
 
-int look_id(const std::string& name) {
-    const std::string prefix = "Filmic - ";
-    const std::string n = name.rfind(prefix, 0) == 0 ? name.substr(prefix.size()) : name;
-    for (int id = 0; id < kNumLooks; ++id)
-        if (n == kLooks[id].name) return id;
-    return -1;
-}
-
-const char* view_name(int view_transform) {
-    switch (view_transform) {
-    case RR_VIEW_STANDARD: return "Standard";
-    case RR_VIEW_RAW: return "Raw";
-    case RR_VIEW_FILMIC: return "Filmic";
-    case RR_VIEW_FILMIC_LOG: return "Filmic Log";
-    case RR_VIEW_FALSE_COLOR: return "False Color";
-    default: return "?";
-    }
-}
-
 namespace {
 
 void upload_cube(const std::vector<float>& src, int n, DevBuf<float4>& dst) {

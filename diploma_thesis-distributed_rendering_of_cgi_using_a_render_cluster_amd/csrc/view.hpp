@@ -38,39 +38,12 @@
 #include <vector>
 
 #include "device.hpp"
+#include "looks.hpp"
 
 namespace rr {
 
-// Blender 3.6's looks of the Filmic view and the 1D curve each puts in the
-// base curve's place. file nullptr: the base curve itself (no extra file).
-// A look's id is its index here; 0 is "None".
-struct LookDef {
-    const char* name;
-    const char* file;
-};
-constexpr int kNumLooks = 8;
-constexpr LookDef kLooks[kNumLooks] = {
-    {"None", nullptr},
-    {"Very High Contrast", "filmic_to_1.20_1-00.spi1d"},
-    {"High Contrast", "filmic_to_0.99_1-0075.spi1d"},
-    {"Medium High Contrast", "filmic_to_0-85_1-011.spi1d"},
-    {"Medium Contrast", nullptr},  // filmic_to_0-70_1-03.spi1d, the base curve
-    {"Medium Low Contrast", "filmic_to_0-60_1-04.spi1d"},
-    {"Low Contrast", "filmic_to_0-48_1-09.spi1d"},
-    {"Very Low Contrast", "filmic_to_0-35_1-30.spi1d"},
-};
-constexpr const char* kFalseColorFile = "filmic_false_color.spi3d";
-// Blender's range of view_settings.gamma
-constexpr float kGammaMax = 5.0f;
-// Blender's range of image_settings.dither_intensity: [0, kDitherMax]
-constexpr float kDitherMax = 2.0f;
-
-// The id of a look by its name, with or without Blender's "Filmic - " prefix;
-// -1 for a name that is not in kLooks.
-int look_id(const std::string& name);
-// Blender's name of a view transform this renderer knows ("Standard", ...,
-// "False Color").
-const char* view_name(int view_transform);
+// The looks table (kLooks, look_id), view_name, kFalseColorFile, kGammaMax and
+// kDitherMax are host data of their own: looks.hpp.
 
 // A 1D LUT as parsed from its file (host).
 struct Curve1 {
