@@ -922,7 +922,7 @@ void build_ploc(const DevMesh& mesh, DevBuild& s, hipStream_t st) {
 // unit geometric normal (the same norm3(cross3(e1, e2)) shade() computes
 // from the triangle record, contraction off: the same bits) and the material
 // id, one 16 B read per shading point instead of the 48 B record and a cross
-// product (paths.hpp shade(), RR_SHADE_NRM).
+// product (paths.hpp shade(), GlobalView::nrm).
 __global__ __launch_bounds__(kBlock) void k_tri_nrm(const TriPack* __restrict__ tris, int n, float4* __restrict__ out) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;

@@ -177,7 +177,6 @@ struct DevPaths {
     DevBuf<float4> sh_o, sh_d, sh_c;           // segmented shadow queue
     DevBuf<float2> hits;                       // split path: (t, leaf index) per queue entry
     DevBuf<uint32_t> qctr;                     // split path: grouped queue append counters
-    DevBuf<uint32_t> perm;                     // split path, RR_RAY_SORT: queue position -> slot (k_sort_queue)
     DevBuf<float4> film_part;  // open sample group's partial sum between chunks (k_accumulate)
     DevBuf<float> filter_table;
     DevBuf<float> srgb_lut;

@@ -59,20 +59,18 @@ struct SceneView {
     FloatP lut;  // material tables (kMatLutStride floats per material, build_material_lut)
     lds_f4w* cam = nullptr;  // LDS scenes, camera kernels: 3 float4 per triangle (stage_camera)
     // unit geometric normal + material per triangle: LDS scenes' staged copy
-    // (shading kernels), HBM scenes' DevBuild::tnrm (RR_SHADE_NRM) — one
+    // (shading kernels), HBM scenes' DevBuild::tnrm (null: none built) — one
     // member for both, so the LDS view passed to k_tiles' out-of-line calls
     // stays the size it was
     typename std::conditional<std::is_same<FloatP, lds_float*>::value, lds_f4w*, const float4*>::type nrm = nullptr;
     lds_f4w* matd = nullptr;  // LDS scenes, shading kernels: each material with its derived terms (kMatDF4)
     lds_f4w* onb = nullptr;   // LDS scenes, shading kernels: make_onb of both sides' normals (kOnbF4 per triangle)
 };
-// RR_SHADE_NRM (default): the split path's shading reads each hit triangle's
-// normal and material from DevBuild::tnrm (16 B) instead of its 48 B record
-// and a cross product: shading per 02 / 03 / C5 frame slice 11.34 / 11.49 /
-// 9.18 -> 10.77 / 10.85 / 8.61 ms (profiles/r5_ab_spec.txt).
-#ifndef RR_SHADE_NRM
-#define RR_SHADE_NRM 1
-#endif
+// The split path's shading reads each hit triangle's normal and material from
+// DevBuild::tnrm (16 B, GlobalView::nrm) instead of its 48 B record and a
+// cross product: shading per 02 / 03 / C5 frame slice 11.34 / 11.49 / 9.18 ->
+// 10.77 / 10.85 / 8.61 ms (profiles/r5_ab_spec.txt). shade() still takes the
+// record where a caller has no such table and passes null.
 using GlobalView = SceneView<const BvhNode*, const TriPack*, const float*>;
 using LdsView = SceneView<lds_node*, lds_tri*, lds_float*>;
 
@@ -263,7 +261,7 @@ __device__ __forceinline__ void shade(const FC& fc, int bounce, const View& v, f
         // table offsets become 24-bit multiplies (full rate) instead of
         // v_mul_lo_u32 / v_mad_u64_u32
         __builtin_assume(mid >= 0 && mid < 4096);
-    } else if (RR_SHADE_NRM && v.nrm) {
+    } else if (v.nrm) {
         const float4 nm = v.nrm[h.idx];  // k_tri_nrm: the same normal, precomputed
         N = xyz(nm);
         mid = f2i(nm.w);

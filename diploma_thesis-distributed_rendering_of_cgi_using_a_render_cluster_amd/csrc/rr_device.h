@@ -144,7 +144,7 @@ constexpr int kLdsStack = RR_LDS_STACK;
 constexpr int kSpillStack = kStackCap - kLdsStack;
 // The split path's trace kernels (round 6): 8 LDS entries per lane, 32 KB per
 // 1,024-thread block, leave 48 KB for the top of the hierarchy (768 nodes,
-// wavefront.hip kTopNodes) at two blocks per CU; against 12 entries and 512
+// split_kernels.hpp kTopNodes) at two blocks per CU; against 12 entries and 512
 // nodes: C5 frame slices -1.0 % (extension walks -1.8 %), 02 / 03 unchanged;
 // 10 / 640 no better, 6 / 896 level, 4 / 1,024 +5 % (spills;
 // profiles/r6_ab_lds_top.txt).
@@ -152,9 +152,10 @@ constexpr int kSpillStack = kStackCap - kLdsStack;
 #define RR_TRACE_LDS_STACK 8
 #endif
 constexpr int kTraceLdsStack = RR_TRACE_LDS_STACK;
-// entries per lane of the spill area (DevPaths::spill): what the stack with
-// the fewest LDS entries needs to reach kStackCap
-constexpr int kSpillLane = kStackCap - (kTraceLdsStack < kLdsStack ? kTraceLdsStack : kLdsStack);
+// entries per lane of the spill area (DevFrame::spill): what the stack with
+// the fewest LDS entries needs to reach kStackCap. That is rr_debug_trace
+// width 6, one LDS entry (TravStackT asserts that no stack needs more).
+constexpr int kSpillLane = kStackCap - 1;
 constexpr int kDimsPerBounce = 8;   // RNG dimensions consumed per bounce
 constexpr int kRrStartBounce = 3;   // Russian roulette from this bounce on
 
@@ -617,9 +618,12 @@ RR_D TriPack load_tri(lds_tri* p, int i) {
 }
 // kB: the threads per block of the kernel that owns the stack; kL: its LDS
 // entries per lane (rr_debug_trace width 6 runs the 6-wide walk with 1, so
-// nearly every entry lives in the HBM part); kS: its HBM entries per lane.
-template <int kB = kBlock, int kL = kLdsStack, int kS = kSpillStack>
+// nearly every entry lives in the HBM part); kS: its HBM entries per lane, the
+// rest of the oracle's capacity.
+template <int kB = kBlock, int kL = kLdsStack, int kS = kStackCap - kL>
 struct TravStackT {
+    static_assert(kL + kS == kStackCap, "a traversal stack holds the oracle's ORC_MAXDEPTH entries");
+    static_assert(kS <= kSpillLane, "the spill area has kSpillLane rows per lane");
     // Bases only: the lane's slots are recomputed from threadIdx/blockIdx at each
     // push/pop, so no per-lane pointer stays live in VGPRs across a kernel's
     // ray loop.
@@ -650,7 +654,7 @@ struct TravStackT {
         if (sp < kL) return lds[sp * kB + (int)threadIdx.x];
         return spill[(sp - kL) * spill_stride + (int)(blockIdx.x * kB + threadIdx.x)];
     }
-    // Grouped entries of the 6-wide walk (RR_STACK_GROUP): one entry per node
+    // Grouped entries of the 6-wide walk: one entry per node
     // for all the internal children it leaves for later, first child index << 6
     // | the mask of their ranks among the node's internal children (internal
     // children are consecutive nodes: child of rank k = first + k). pop_group
@@ -685,13 +689,11 @@ RR_D uint32_t q6_rank_mask(uint32_t rest, uint32_t imask) {
     }
     return r;
 }
-// RR_STACK_GROUP (default): the 6-wide walks push one grouped entry per node
-// (pop_group) instead of one entry per child: per 02 / 03 / C5 frame slice
-// 80.5 / 86.7 / 69.6 -> 79.0 / 85.5 / 69.3 ms (profiles/r5_ab_walk.txt). The
-// oracle's walk keeps the same entries, so both stacks fill (and drop) alike.
-#ifndef RR_STACK_GROUP
-#define RR_STACK_GROUP 1
-#endif
+// The 6-wide walk pushes one grouped entry per node (pop_group) instead of one
+// entry per child: per 02 / 03 / C5 frame slice 80.5 / 86.7 / 69.6 -> 79.0 /
+// 85.5 / 69.3 ms (profiles/r5_ab_walk.txt; the per-child push loop was removed
+// with its switch, pop() stays for the BVH2 walk). The oracle's walk keeps the
+// same entries, so both stacks fill (and drop) alike.
 using TravStack = TravStackT<kBlock>;
 
 RR_D lds_int* lds_slot(int* shared_elem) {
@@ -705,10 +707,11 @@ struct TravCount {
 
 // Resumable traversal of one ray: start() then step() until it returns true.
 // Near child first (left on ties); leaf children are intersected as soon as
-// their box passes. The fused path kernels run it to completion per lane
-// (traverse() below); the split trace kernels of large scenes interleave
-// step() with lane refill (wavefront.hip trace_refill), which changes only the
-// schedule, never the visited nodes, so the hits are identical.
+// their box passes. The tile kernel runs it to completion per lane
+// (traverse() below); the split trace kernels of large scenes interleave the
+// step() of the 6-wide walk (TravStateQ6D) with lane refill (split_kernels.hpp
+// trace_refill), which changes only the schedule, never the visited nodes, so
+// the hits are identical.
 // nodes / tris: global or LDS pointers (paths.hpp SceneView).
 // The largest |coordinate| of a BVH2's scene box (its root's two child boxes).
 RR_D float scene_radius(const BvhNode& r) {
@@ -864,7 +867,7 @@ RR_D uint32_t q6_box_hits(const QNode6& n, float3 o, float3 iq, float tmin, floa
 
 // q6_box_hits that keeps only the nearest hit internal child (ties: lower
 // slot) instead of every entry distance: six fewer live registers in the
-// per-lane walk (TravStateQ6); best = -1 when no internal child is hit.
+// per-lane walk (TravStateQ6D); best = -1 when no internal child is hit.
 // kNearest false (any-hit rays): the lowest hit internal slot instead. An
 // any-hit walk opens every node whose box meets [tmin, tmax] until its first
 // hit (the bound never shrinks), so the order decides nothing but the speed:
@@ -921,20 +924,14 @@ struct Q6Nodes {
     lds_f4w* top;  // nodes [0, n_top): 4 float4 each (QNode6 layout)
     int n_top;
 };
-RR_D uint4 f4_bits(float4 v) {
-    return make_uint4((uint32_t)f2i(v.x), (uint32_t)f2i(v.y), (uint32_t)f2i(v.z), (uint32_t)f2i(v.w));
-}
-// RR_FLAT_TOP (default): per 02 / 03 / C5 frame slice 78.5 / 85.0 / 69.1 ->
-// 78.4 / 84.8 / 68.7 ms (profiles/r5_ab_lds.txt; the branchy form measured
-// within 0.5 % of it, and the 4 x 16 B of a node arrive either way).
-#ifndef RR_FLAT_TOP
-#define RR_FLAT_TOP 1
-#endif
 RR_D QNode6 q6_load(const Q6Nodes& n, int i) {
-#if RR_FLAT_TOP
     // one generic (flat) pointer for both copies: a wave whose lanes read
     // both takes one set of loads, not the two branches in turn (where the LDS
-    // reads waited for the HBM loads, whose registers they reuse)
+    // reads waited for the HBM loads, whose registers they reuse). Against a
+    // branch per copy (ds_read / global_load), per 02 / 03 / C5 frame slice
+    // 78.5 / 85.0 / 69.1 -> 78.4 / 84.8 / 68.7 ms (profiles/r5_ab_lds.txt:
+    // within 0.5 %, the 4 x 16 B of a node arrive either way); the branchy
+    // form was removed with its switch.
     typedef uint32_t u4v __attribute__((ext_vector_type(4)));
     const u4v* top_g = (const u4v*)(const rr_f4v*)n.top;
     const u4v* q = i < n.n_top ? top_g + 4 * i : reinterpret_cast<const u4v*>(n.g + i);
@@ -945,86 +942,19 @@ RR_D QNode6 q6_load(const Q6Nodes& n, int i) {
     r.b = make_uint4(w2.x, w2.y, w2.z, w2.w);
     r.c = make_uint4(w3.x, w3.y, w3.z, w3.w);
     return r;
-#endif
-    if (i < n.n_top) {
-        const lds_f4w* q = n.top + 4 * i;
-        QNode6 r;
-        r.org = lds_ld4(q);
-        r.a = f4_bits(lds_ld4(q + 1));
-        r.b = f4_bits(lds_ld4(q + 2));
-        r.c = f4_bits(lds_ld4(q + 3));
-        return r;
-    }
-    return q6_load(n.g, i);
 }
 
 // Resumable traversal of the quantised 6-wide hierarchy (same contract as
-// TravState), box tests by q6_box_best. Leaf children whose boxes pass are
-// intersected at once in slot order; the nearest hit internal child (any-hit
-// rays: the lowest hit internal slot) is visited next and the others are
-// pushed in descending slot order.
-// oracle/rr_oracle.c trace4() is the same walk.
-template <bool kAnyHit, bool kCount = false>
-struct TravStateQ6 {
-    float3 o, iq;
-    Shear sh;
-    float tmin;
-    Hit h;
-    int node;
-    // (no scene radius, unlike TravState::start: the margins are per node, q6_planes)
-    RR_D void start(float3 o_, float3 d_, float tmin_, float tmax_) {
-        o = o_;
-        sh = make_shear(d_);
-        tmin = tmin_;
-        h.t = tmax_;
-        h.u = h.v = 0.0f;
-        h.idx = -1;
-        h.orig = -1;
-        iq = rcp3(d_);
-        node = 0;
-    }
-    template <typename NodeSrc, typename TriP, typename Stack>
-    RR_D bool step(const NodeSrc& nodes, TriP tris, Stack& st, TravCount& cnt) {
-        if (kCount) ++cnt.nodes;
-        const float tcur = h.t;
-        const auto nd = q6_load(nodes, node);
-        const uint32_t imask = q6_inner(nd);
-        int best;
-        const uint32_t hm = q6_box_best<!kAnyHit>(nd, o, iq, tmin, tcur, imask, best);
-        uint32_t leaves = hm & ~imask;
-        const uint32_t inner = hm & imask;
-        // passing leaves in slot order; the loop runs as often as the lane with
-        // the most leaves needs, not once per slot
-        while (leaves) {
-            const int c = __builtin_ctz(leaves);
-            leaves &= leaves - 1;
-            const int ti = q6_first_leaf(nd) + c - __builtin_popcount(imask & ((1u << c) - 1u));
-            if (kCount) ++cnt.tris;
-            leaf_test(load_tri(tris, ti), ti, sh, o, tmin, h);
-            if (kAnyHit && h.idx >= 0) return true;
-        }
-        if (!inner) {
-            if (st.sp == 0) return true;
-            node = RR_STACK_GROUP ? st.pop_group() : st.pop();
-            return false;
-        }
-        // nearest hit child next (ties: lower slot, q6_box_best); the other hit
-        // children are pushed in descending slot order (so they pop in slot order)
-        const uint32_t rest = inner & ~(1u << best);
-        const int base = q6_first_inner(nd);
-#if RR_STACK_GROUP
-        if (rest) st.push((int)(((uint32_t)base << 6) | q6_rank_mask(rest, imask)));
-#else
-#pragma unroll
-        for (int c = kQWidth - 1; c >= 0; --c)
-            if ((rest >> c) & 1u) st.push(base + __builtin_popcount(imask & ((1u << c) - 1u)));
-#endif
-        node = base + __builtin_popcount(imask & ((1u << best) - 1u));
-        return false;
-    }
-};
-
-// TravStateQ6 with postponed leaf tests (Aila & Laine 2009, "while-while"):
+// TravState: start() then step() by the lanes that still have a ray until it
+// returns true), box tests by q6_box_best. The leaf children a ray enters are
+// intersected in slot order before its next node visit; the nearest hit
+// internal child (any-hit rays: the lowest hit internal slot; ties: the lower
+// slot) is visited next and the others are pushed as one grouped entry, so
+// that they pop in slot order. oracle/rr_oracle.c trace4() is the same walk
+// with the leaf tests at once: the same nodes, stack entries and hits. (No
+// scene radius, unlike TravState::start: the margins are per node, q6_planes.)
+//
+// The leaf tests are postponed (Aila & Laine 2009, "while-while"):
 // a node visit records the leaf children its ray enters (slot mask, the node's
 // first leaf triangle and internal-slot mask) instead of testing them, and the
 // lane then waits; the wave runs its leaf tests together, one triangle per
@@ -1036,6 +966,13 @@ struct TravStateQ6 {
 // bound every box test uses is the same as with immediate tests: the same
 // nodes are visited, the same triangles tested, only in another interleaving
 // across lanes, and the accept rule makes the hit the same (bit-exact).
+// Leaf phase once 12 of the lanes have leaves pending. Per frame slice against
+// testing leaves at once (02 / 03 at 64 spp, C5 at 16 spp, two interleaved
+// rounds, profiles/r5_ab_leaf_defer.txt): 87.4 / 94.8 / 73.0 -> 82.7 / 89.1 /
+// 70.3 ms (extension and shadow traversal -6 to -9 %); a phase threshold of
+// 4 / 8 / 16 / 24 / 32 / 48 lanes: 86.6 / 83.6 / 82.5 / 85.2 / 91.1 / 118.6 ms
+// on 02. The walk that tested leaves at once was removed with its switch; the
+// debug walks (rr_debug_trace widths 4 and 6) run this one too.
 #ifndef RR_LEAF_PHASE
 #define RR_LEAF_PHASE 12
 #endif
@@ -1096,18 +1033,14 @@ struct TravStateQ6D {
                 node = -1;
                 return lmask == 0u;
             }
-            node = RR_STACK_GROUP ? st.pop_group() : st.pop();
+            node = st.pop_group();
             return false;
         }
+        // nearest hit child next (ties: lower slot, q6_box_best); the other hit
+        // children as one grouped entry (they pop in slot order)
         const uint32_t rest = inner & ~(1u << best);
         const int base = q6_first_inner(nd);
-#if RR_STACK_GROUP
         if (rest) st.push((int)(((uint32_t)base << 6) | q6_rank_mask(rest, imask)));
-#else
-#pragma unroll
-        for (int c = kQWidth - 1; c >= 0; --c)
-            if ((rest >> c) & 1u) st.push(base + __builtin_popcount(imask & ((1u << c) - 1u)));
-#endif
         node = base + __builtin_popcount(imask & ((1u << best) - 1u));
         return false;
     }

@@ -17,17 +17,13 @@
 #include "paths.hpp"
 
 // The split path's kernels are compiled into this unit too, ahead of the tile
-// code, and never launched from it (seven dead kernels in its code object).
-// They are here for one reason: k_tiles' helpers are all force-inlined, in the
-// order the front end emits them, and shade<GlobalView> of k_shade_extend is
-// what emits them ahead of k_tiles. Without it the four k_tiles come out with
-// other scheduling (whole-tile variants 4 % shorter, counting sliced variant
-// 512 instead of 496 B of scratch; profiles/tiles_split.md). Dropping this
-// include is a change of k_tiles' code and wants its own measurement.
-#define RR_TILES_TU 1
+// code, and never launched from it: shade<GlobalView> of k_shade_extend emits
+// k_tiles' force-inlined helpers ahead of it, and without that the four
+// k_tiles come out with other scheduling (profiles/tiles_split.md). Dropping
+// this include is a change of k_tiles' code and wants its own measurement.
 #pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // those kernels, unused here (the parent's suppression)
-#include "wavefront.hip"
+#pragma clang diagnostic ignored "-Wunused-function"  // those kernels, unused here
+#include "split_kernels.hpp"
 #pragma clang diagnostic pop
 
 namespace rr {

@@ -6,8 +6,9 @@
 
 tiles.hip gets the extra flags of its translation unit (-fno-slp-vectorize);
 the environment variable TILES_TUFLAGS, named as the Makefile's variable,
-replaces them. Its rows for the split path's kernels are the unused copies
-that unit carries (see tiles.hip); the ones that run are wavefront.hip's.
+replaces them. Both units include the split path's kernels
+(split_kernels.hpp); tiles.hip's rows for them are the unused copies that unit
+carries (see tiles.hip), and the ones that run are wavefront.hip's.
 
 Compiles each file device-only with the Makefile's device flags into /tmp and
 prints one line per kernel: VGPRs, AGPRs, VGPR spills, SGPR spills, scratch
