@@ -1,5 +1,5 @@
 // The coders of a frame's file: the dispatch to the device coders (jpeg.hip,
-// png.hip, png16.hip, exr.hip), the host-built files around their streams, and
+// png.hip, png16.hip, exr.hip, tga.hip), the host-built files around their streams, and
 // the host coders of an RGBA8 image. See frame.hpp.
 #include <cerrno>
 #include <cstring>
@@ -46,7 +46,37 @@ int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p) {
     return fail(RR_EINVAL, std::string("image size outside the device ") + name + " encoder's range");
 }
 
+int plan_or_refuse(const FrameOutput& fo, int W, int H, TgaPlan& p) {
+    if (tga_plan(W, H, fo.color_mode, !fo.tga_raw, p)) return RR_OK;
+    return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
+}
+
 namespace {
+
+// Device TARGA encode of an RGBA8 image into o's pinned stream, by o.plan.
+void enqueue_tga(const CoderInput& in, DevFrame& f, hipStream_t st, TgaOut& o) {
+    const TgaPlan& p = o.plan;
+    if (p.W != in.W || p.H != in.H) throw std::runtime_error("TARGA plan of another image");
+    f.tga_scratch.ensure(tga_scratch_words(p));
+    o.stream.ensure(tga_stream_bytes(p));
+    void* dev_host = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
+    f.prof.begin(st, RR_K_PNG);
+    tga_encode_device(in.rgba8, p, f.tga_scratch.ptr, static_cast<uint8_t*>(dev_host), st);
+    f.prof.end(st);
+}
+
+// The file of a device-coded TARGA image: host-built header + the device body.
+void tga_file_bytes(const TgaOut& o, std::vector<uint8_t>& data) {
+    const TgaPlan& p = o.plan;
+    uint64_t len = 0;
+    std::memcpy(&len, o.stream.ptr, sizeof len);
+    if (len > p.body_cap || len + 16 > o.stream.cap || (!p.rle && len != p.body_cap))
+        throw std::runtime_error("device TARGA stream overflow");
+    tga_header_bytes(p.W, p.H, p.C, p.rle, data);
+    data.insert(data.end(), o.stream.ptr + 16, o.stream.ptr + 16 + len);
+}
+
 
 // Device JPEG encode of an RGBA8 image (transform into f.jpeg_coeffs + Huffman
 // coding) into o's pinned stream. grey: a one-component file (RR_COLOR_BW).
@@ -119,6 +149,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
     const Coder k = fo.coder;
     const int C = fo.color_mode;
     if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o.jpeg);
+    if (k == Coder::Tga) return enqueue_tga(in, f, st, o.tga);
     if (!device_deflate(k)) throw std::runtime_error("no device coder for this output");
     // the front ends' own buffers. "PNG" at compression 0 .. 100: a filter type
     // per row of the H rows, and at 16 bits the raw scanlines, 2C W H bytes
@@ -169,6 +200,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
 
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data) {
     if (fo.coder == Coder::Jpeg) jpeg_file_bytes(o.jpeg, data);
+    else if (fo.coder == Coder::Tga) tga_file_bytes(o.tga, data);
     else deflate_file_bytes(o.deflate, fo.coder, fo.color_mode, data);
 }
 
@@ -189,8 +221,13 @@ int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const cha
                         adaptive))
             return fail(RR_EIO, "PNG encode failed");
         ext = ".png";
+    } else if (fmt == "TARGA" || fmt == "TARGA_RAW") {
+        if (!encode_tga(rgba, W, H, resolve_color_mode(mode, false), fmt == "TARGA", data))
+            return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
+        ext = ".tga";
     } else {
-        return fail(RR_ENOTSUP, "unsupported output format '" + fmt + "' (JPEG and PNG are supported)");
+        return fail(RR_ENOTSUP,
+                    "unsupported output format '" + fmt + "' (JPEG, PNG, TARGA and TARGA_RAW are supported)");
     }
     const std::string path = std::string(out_path) + ext;
     if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));

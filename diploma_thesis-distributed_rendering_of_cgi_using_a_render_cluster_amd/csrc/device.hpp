@@ -212,6 +212,8 @@ struct DevFrame {
     // PNG frames with the adaptive filter (rr_set_png_compression): a filter type per image row, and at 16 bits
     // the raw big-endian scanlines (png16.hip k_png16_raw); grow-only, untouched by legacy frames
     DevBuf<uint8_t> png_ftype, png_raw;
+    // TARGA frames (tga.hip): the dense body, and for run-length coded ones the per-pixel records; grow-only
+    DevBuf<uint32_t> tga_scratch;
     // written by render_frame_device, about the frame it enqueued
     int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log (trav_counts)

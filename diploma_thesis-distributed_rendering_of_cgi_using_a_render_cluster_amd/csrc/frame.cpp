@@ -280,10 +280,11 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     DevFrame& f = sl.dev;
     DevBuild& build = sl.tiles ? sl.build : s->build;
     FrameSlot* prev = c->last_enqueued;
-    // (the deflate coder reads its slot's rgba8 / film and writes slot buffers
-    // only, so the next frame waits for the image, ev[5], not for the coder)
+    // (the deflate coder and the TARGA packer read their slot's rgba8 / film and
+    // write slot buffers only, so the next frame waits for the image, ev[5], not
+    // for the coder)
     if (prev && prev != &sl && !(sl.tiles && prev->tiles))
-        RR_HIP(hipStreamWaitEvent(st, device_deflate(prev->out.coder) ? prev->ev[5] : prev->ev[2], 0));
+        RR_HIP(hipStreamWaitEvent(st, slot_coder(prev->out.coder) ? prev->ev[5] : prev->ev[2], 0));
     c->last_enqueued = &sl;
     // a k_tiles frame enqueued while another k_tiles frame is pending overlaps
     // it: whole-tile work units (render_frame_device); a frame rendered alone
@@ -319,7 +320,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     RR_HIP(hipEventRecord(sl.ev[4], st));
     const size_t npix = (size_t)fs.W * fs.H;
     const Coder coder = sl.out.coder;
-    if (coder == Coder::Jpeg || device_deflate(coder)) {
+    if (coder == Coder::Jpeg || slot_coder(coder)) {
         CoderInput in;
         in.rgba8 = f.rgba8.ptr;
         in.film = f.film.ptr;
@@ -332,7 +333,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
             RR_HIP(hipEventRecord(sl.ev[5], st));
             // Png16: the film again, through exposure and view transform, at 16
             // bits; OPEN_EXR: the film's means, the product finish_frame forms,
-            // no view transform
+            // no view transform; TARGA reads rgba8 and none of these
             in.inv_spp = k.inv_spp;
             in.exposure_scale = k.exposure_scale;
             in.view_transform = fs.view_transform;

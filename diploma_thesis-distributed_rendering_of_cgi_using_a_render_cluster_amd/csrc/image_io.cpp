@@ -10,6 +10,7 @@
 
 #include "grey.h"
 #include "png_filter.h"
+#include "tga_rule.h"
 
 #include <zlib.h>
 
@@ -666,6 +667,69 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
         src += len;
     }
     return src == n;
+}
+
+// ------------------------------------------------------------- TARGA ------
+void tga_header_bytes(int W, int H, int C, bool rle, std::vector<uint8_t>& out) {
+    out.clear();
+    out.push_back(0);                                          // no image id
+    out.push_back(0);                                          // no colour map
+    out.push_back((uint8_t)((C == 1 ? 3 : 2) + (rle ? 8 : 0)));  // 2 true colour, 3 grey, + 8 run-length coded
+    for (int k = 0; k < 5; ++k) out.push_back(0);              // colour map specification
+    put_le(out, 0, 2);                                         // x origin
+    put_le(out, 0, 2);                                         // y origin
+    put_le(out, (uint32_t)W, 2);
+    put_le(out, (uint32_t)H, 2);
+    out.push_back((uint8_t)(8 * C));                           // bits a pixel
+    out.push_back(C == 4 ? 8 : 0);                             // alpha bits; bit 5 clear: bottom-left origin
+}
+
+bool encode_tga(const uint8_t* rgba, int W, int H, int C, bool rle, std::vector<uint8_t>& out) {
+    const uint64_t bound = tga_body_max_bytes(W, H, C, rle);
+    if (!rgba || bound == 0) return false;
+    tga_header_bytes(W, H, C, rle, out);
+    out.reserve(out.size() + (size_t)bound);
+    std::vector<uint8_t> row((size_t)W * C);
+    const size_t c = (size_t)C;
+    for (int y = H - 1; y >= 0; --y) {  // bottom row first
+        const uint8_t* src = rgba + (size_t)y * W * 4;
+        for (int x = 0; x < W; ++x) {
+            const uint8_t* p = src + 4 * (size_t)x;
+            uint8_t* q = row.data() + c * x;
+            if (C == 1) {
+                q[0] = (uint8_t)grey8(p[0], p[1], p[2]);
+            } else {
+                q[0] = p[2], q[1] = p[1], q[2] = p[0];
+                if (C == 4) q[3] = p[3];
+            }
+        }
+        if (!rle) {
+            out.insert(out.end(), row.begin(), row.end());
+            continue;
+        }
+        // a stretch of n pixels from pixel `from`: packets of 128, then the remainder
+        auto put_stretch = [&](size_t from, size_t n, bool run) {
+            for (size_t at = 0; at < n; at += kTgaPacket) {
+                const size_t count = std::min<size_t>(kTgaPacket, n - at);
+                out.push_back((uint8_t)tga_packet_header(run, (uint32_t)count));
+                const uint8_t* px = row.data() + c * (from + at);
+                out.insert(out.end(), px, px + c * (run ? 1 : count));
+            }
+        };
+        size_t lit = 0;  // first pixel of the open literal stretch
+        for (size_t x = 0; x < (size_t)W;) {
+            size_t e = x + 1;  // the maximal run [x, e)
+            while (e < (size_t)W && std::memcmp(row.data() + c * e, row.data() + c * x, c) == 0) ++e;
+            if (e - x >= tga_min_run(C)) {
+                put_stretch(lit, x - lit, false);
+                put_stretch(x, e - x, true);
+                lit = e;
+            }
+            x = e;
+        }
+        put_stretch(lit, (size_t)W - lit, false);
+    }
+    return out.size() - kTgaHeaderBytes <= bound;
 }
 
 bool write_file(const std::string& path, const std::vector<uint8_t>& data) {

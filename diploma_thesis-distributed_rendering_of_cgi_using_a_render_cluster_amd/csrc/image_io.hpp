@@ -60,6 +60,15 @@ void png_wrap_stream(int W, int H, const uint8_t* z, size_t n, const uint32_t* b
 // not add up to n, or a chunk's size is not what its scanlines allow.
 bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
                      std::vector<uint8_t>& out, int pixel_type = 1, int channels = 4);
+// A TARGA file of the RGBA8 image (tga_rule.h): the 18-byte header (no id, no
+// colour map, type 2 true colour or 3 grey, + 8 run-length coded, bottom-left
+// origin, 8 C bits a pixel, 8 alpha bits for C = 4) and the body, rows bottom
+// first, pixels B, G, R(, A) or the grey code of grey.h; rle: packets by the
+// rule of tga_rule.h ("TARGA"), else the plain bytes ("TARGA_RAW"). No footer.
+// false: W or H above 65535, C not 1, 3 or 4, or a body of 2 GB and more.
+// tga.hip writes the same bytes.
+bool encode_tga(const uint8_t* rgba, int W, int H, int C, bool rle, std::vector<uint8_t>& out);
+void tga_header_bytes(int W, int H, int C, bool rle, std::vector<uint8_t>& out);
 bool write_file(const std::string& path, const std::vector<uint8_t>& data);
 
 }  // namespace rr

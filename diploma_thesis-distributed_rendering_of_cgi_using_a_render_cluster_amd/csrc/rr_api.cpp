@@ -183,9 +183,9 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
     if (!c || !s || !ticket) return fail(RR_EINVAL, "NULL ctx, scene or ticket");
     if (s->ctx && s->ctx != c) return fail(RR_EINVAL, "scene belongs to another context");
     if (out_path && !format) return fail(RR_EINVAL, "format is required when out_path is given");
-    if (format && std::string(format) != "JPEG" && std::string(format) != "PNG" &&
-        std::string(format) != "OPEN_EXR")
-        return fail(RR_ENOTSUP, std::string("unsupported output format '") + format + "'");
+    if (format && !known_format(format))
+        return fail(RR_ENOTSUP, std::string("unsupported output format '") + format +
+                                    "' (JPEG, PNG, OPEN_EXR, TARGA and TARGA_RAW are supported)");
     const FrameOutput fo = resolve_output(c->settings, s->desc.render, format, out_path != nullptr, jpeg_quality);
     if (fo.coder == Coder::Jpeg && (jpeg_quality < 1 || jpeg_quality > 100))
         return fail(RR_EINVAL, "jpeg_quality must be 1..100");
@@ -206,6 +206,10 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->out = fo;
         if (device_deflate(fo.coder)) {
             const int rc = plan_or_refuse(fo.coder, fo.color_mode, sl->fs.W, sl->fs.H, sl->coded.deflate.plan);
+            if (rc != RR_OK) return rc;
+        }
+        if (fo.coder == Coder::Tga) {
+            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.tga.plan);
             if (rc != RR_OK) return rc;
         }
         if (fo.coder == Coder::Png16) {
@@ -236,7 +240,7 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
         set_render_span(c, *sl, unix_now());
         uint64_t bytes = 0;
         const auto t_enc = std::chrono::steady_clock::now();
-        if (fo.coder == Coder::Jpeg || device_deflate(fo.coder)) {  // the host's container + the device-coded stream
+        if (fo.coder == Coder::Jpeg || slot_coder(fo.coder)) {  // the host's container + the device-coded stream
             std::vector<uint8_t> data;
             coded_file_bytes(sl->coded, fo, data);
             const std::string path = sl->out_path + coder_ext(fo.coder);

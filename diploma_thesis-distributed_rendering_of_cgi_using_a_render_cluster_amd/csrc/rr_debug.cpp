@@ -32,11 +32,11 @@ int debug_view_settings(const rr_ctx* c, int view, int& look, float& gamma) {
 }
 
 // The body of the coders' entry points: a w x h image of the caller's (RGBA8
-// for Jpeg and Png8, float RGBA means for the others) through coder k in C
+// for Jpeg, Png8 and Tga, float RGBA means for the others) through coder k in C
 // channels, with the context's PNG compression; the file's bytes to `out` if
 // `cap` suffices. alpha_one, view_transform, exposure_scale: CoderInput's.
 int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, bool alpha_one, int view_transform,
-                 float exposure_scale, int quality, uint8_t* out, uint64_t cap, uint64_t* len) {
+                 float exposure_scale, int quality, uint8_t* out, uint64_t cap, uint64_t* len, bool tga_raw = false) {
     CoderInput in;
     in.W = w;
     in.H = h;
@@ -47,11 +47,14 @@ int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, boo
         if (const int rc = debug_view_settings(c, view_transform, in.look, in.gamma)) return rc;
     if (device_deflate(k))
         if (const int rc = plan_or_refuse(k, C, w, h, c->home_coded.deflate.plan)) return rc;
-    const FrameOutput fo{k, C, png_compression_of(c->settings), quality};
+    const FrameOutput fo{k, C, png_compression_of(c->settings), quality, tga_raw};
+    if (k == Coder::Tga)
+        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.tga.plan)) return rc;
     return guarded([&] {
         if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
         set_device(c);
-        const size_t bytes = (size_t)w * h * (k == Coder::Jpeg || k == Coder::Png8 ? 4 : sizeof(float4));
+        const bool bytes8 = k == Coder::Jpeg || k == Coder::Png8 || k == Coder::Tga;
+        const size_t bytes = (size_t)w * h * (bytes8 ? 4 : sizeof(float4));
         DevBuf<uint8_t> img;
         img.ensure(bytes);
         RR_HIP(hipMemcpy(img.ptr, image, bytes, hipMemcpyHostToDevice));
@@ -125,13 +128,17 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
     } else if (fmt == "PNG" && (depth == 0 || depth == 8)) {
         if (image_is_float) return fail(RR_EINVAL, "8-bit PNG takes an RGBA8 image");
         k = Coder::Png8;
+    } else if (fmt == "TARGA" || fmt == "TARGA_RAW") {  // 8 bits a channel and no other depth
+        if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "TARGA takes an RGBA8 image at depth 8");
+        k = Coder::Tga;
     } else {
         if (!image_is_float) return fail(RR_EINVAL, "16-bit PNG and OPEN_EXR take a float RGBA image");
         if (fmt == "PNG" && depth == 16) k = Coder::Png16;
         else if (fmt == "OPEN_EXR" && (depth == 0 || depth == 16 || depth == 32)) k = depth == 32 ? Coder::Exr32 : Coder::Exr;
         else return fail(RR_EINVAL, "no such format and depth: '" + fmt + "' at " + std::to_string(depth));
     }
-    return debug_encode(c, k, C, image, w, h, true, view_transform, exposure_scale, jpeg_quality, out, cap, len);
+    return debug_encode(c, k, C, image, w, h, true, view_transform, exposure_scale, jpeg_quality, out, cap, len,
+                        fmt == "TARGA_RAW");
 }
 
 int rr_debug_png_filters(const uint8_t* raw, int32_t row_bytes, int32_t rows, int32_t bpp, uint8_t* types) {

@@ -175,8 +175,13 @@ bool settings_from_env(OutputSettings& s, std::string& err) {
     return true;
 }
 
+bool known_format(const char* format) {
+    const std::string f(format ? format : "");
+    return f == "JPEG" || f == "PNG" || f == "OPEN_EXR" || f == "TARGA" || f == "TARGA_RAW";
+}
+
 const char* coder_ext(Coder k) {
-    return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : ".png";
+    return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : k == Coder::Tga ? ".tga" : ".png";
 }
 
 int resolve_color_mode(int mode, bool jpeg) {
@@ -188,9 +193,13 @@ FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const c
                            int jpeg_quality) {
     const bool jpeg = has_path && std::string(format) == "JPEG";
     const bool exr = has_path && std::string(format) == "OPEN_EXR";
+    const bool tga_raw = has_path && std::string(format) == "TARGA_RAW";
+    const bool tga = tga_raw || (has_path && std::string(format) == "TARGA");
     FrameOutput o;
+    o.tga_raw = tga_raw;
     if (!has_path) o.coder = Coder::None;
     else if (jpeg) o.coder = Coder::Jpeg;
+    else if (tga) o.coder = Coder::Tga;  // 8 bits a channel: the depth settings do not apply
     else if (exr)  // HALF unless the context, or at 0 the scene, asks for FLOAT channels
         o.coder = (s.exr_depth ? s.exr_depth : r.exr_depth) == 32 ? Coder::Exr32 : Coder::Exr;
     // "PNG". 16 bits per sample: always the device coder (there is no host one)

@@ -119,6 +119,17 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "rr-blender-shim: no project file on the command line\n");
         return 1;
     }
+    // the extension write_still appends; a format nobody writes is an error, as in the library
+    const std::string ext = fmt == "JPEG"                             ? ".jpg"
+                            : fmt == "PNG"                            ? ".png"
+                            : fmt == "OPEN_EXR"                       ? ".exr"
+                            : (fmt == "TARGA" || fmt == "TARGA_RAW") ? ".tga"
+                                                                      : "";
+    if (ext.empty()) {
+        std::fprintf(stderr, "rr-blender-shim: unsupported output format '%s'\n", fmt.c_str());
+        std::printf("Error: unsupported output format '%s'\n", fmt.c_str());
+        return 1;
+    }
     std::string scene_path = project;
     if (ends_with(project, ".blend")) scene_path = project.substr(0, project.size() - 6) + ".rrscene";
     std::printf("rr-blender-shim (MI355X renderer, ABI %d)\n", rr_abi_version());
@@ -149,7 +160,6 @@ int main(int argc, char** argv) {
         rr_destroy(ctx);
         return 1;
     }
-    const std::string ext = fmt == "PNG" ? ".png" : fmt == "OPEN_EXR" ? ".exr" : ".jpg";
     std::printf("Fra:%ld Mem:0M | Rendered %d x %d, %d spp, %.3f ms device\n", frame, st.width, st.height, st.spp,
                 st.build_ms + st.trace_ms);
     std::printf("Saved: '%s%s'\n", out_path.c_str(), ext.c_str());

@@ -79,7 +79,7 @@ class FrameStats(ctypes.Structure):
 
 RR_FLAG_PROFILE_KERNELS, RR_FLAG_COUNT_TRAVERSAL, RR_FLAG_WAVEFRONT = 1, 2, 4
 KERNEL_CLASSES = ["build", "primary", "extend", "shadow", "accumulate", "shade", "tiles"]
-RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR)
+RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR) or the TARGA packer
 
 
 # Every symbol include/rr.h declares (checked by tests/test_abi.py).
@@ -612,8 +612,9 @@ class RenderContext:
     def encode_device(self, fmt: str, image: np.ndarray, depth: int = 0, color_mode=0, view_transform: int = 0,
                       exposure_scale: float = 1.0, quality: int = 90) -> bytes:
         """rr_debug_encode_device: the file bytes of an (H, W, 4) image coded on the
-        device as `fmt` ("JPEG", "PNG", "OPEN_EXR") at `depth` in `color_mode`.
-        uint8 images for JPEG and 8-bit PNG, float32 means for the others."""
+        device as `fmt` ("JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW") at `depth`
+        in `color_mode`. uint8 images for JPEG, 8-bit PNG and TARGA, float32 means
+        for the others."""
         is_float = image.dtype != np.uint8
         image = np.ascontiguousarray(image, dtype=np.float32 if is_float else np.uint8)
         h, w = image.shape[:2]

@@ -93,7 +93,7 @@ typedef struct rr_render_params {
 #define RR_K_ACCUM 4     /* film accumulate + tonemap */
 #define RR_K_SHADE 5     /* split path (large scenes): shading kernels; PRIMARY/EXTEND then time traversal only */
 #define RR_K_TILES 6     /* LDS-resident scenes: k_tiles, every sample of an 8x8 pixel tile run to completion + film + tonemap */
-#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR): all its kernels, one event pair per frame */
+#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), or the TARGA packer: all its kernels, one event pair per frame */
 #define RR_K_CLASSES 8
 
 /* The five timestamps the reference recovers from Blender's stdout
@@ -200,8 +200,9 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *  - frame_index: the frame to evaluate (Blender frame number, scene.frame_set).
  *  - out_path: output path WITHOUT extension, '#' runs already substituted
  *    (render-timing-script.py:69-78,82); the library appends ".jpg" / ".png"
- *    / ".exr" as Blender's write_still does with R_EXTENSION. NULL: render only.
- *  - format: "JPEG", "PNG" or "OPEN_EXR" (job output_file_format,
+ *    / ".exr" / ".tga" as Blender's write_still does with R_EXTENSION. NULL:
+ *    render only.
+ *  - format: "JPEG", "PNG", "OPEN_EXR", "TARGA" or "TARGA_RAW" (job output_file_format,
  *    shared/src/jobs/mod.rs:80, handed to image_settings.file_format,
  *    render-timing-script.py:83-92). "OPEN_EXR": the film's mean linear
  *    radiance before any view transform (alpha = 1) as A, B, G, R channels,
@@ -212,8 +213,17 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *    render.exr_depth says 32. Coded on the GPU (exr.hip); there is no host
  *    EXR encoder. RR_EINVAL for a width above 2^19 (HALF) or 2^18 (FLOAT), or
  *    a frame of 2 GB and more.
+ *    "TARGA" / "TARGA_RAW": the 8-bit image (view settings and dither
+ *    applied) as an 18-byte header (type 2 true colour or 3 grey, + 8 for
+ *    "TARGA"; bottom-left origin) and the rows bottom first, pixels B, G, R, A
+ *    (rr_set_color_mode RGB: B, G, R; BW: the grey code), alpha 255;
+ *    "TARGA" in run-length packets that never cross a row (the project's own
+ *    choice of packets; any reader returns the same pixels), "TARGA_RAW"
+ *    plain. No footer. Always 8 bits a channel: rr_set_png_depth and the
+ *    scene's colour depth do not apply. Coded on the GPU (tga.hip).
+ *    RR_EINVAL for a width or height above 65535 or a body of 2 GB and more.
  *  - jpeg_quality: 1..100 (the reference script forces 90, :84); ignored for
- *    "PNG" and "OPEN_EXR".
+ *    every other format.
  *  - timing / stats: optional outputs (may be NULL). */
 int rr_render_frame(rr_ctx* ctx, rr_scene* scene, int32_t frame_index,
                     const rr_render_params* params, const char* out_path,
@@ -259,8 +269,10 @@ int rr_scene_resolution(rr_scene* scene, const rr_render_params* params,
                         int32_t* width, int32_t* height);
 
 /* Encode an RGBA8 image (rows top to bottom) to `path` + extension.
- * Host encoder used by rr_render_frame; exported for tests. "JPEG" and "PNG"
- * only: "OPEN_EXR" needs the float film and is RR_ENOTSUP here. */
+ * Host encoder used by rr_render_frame; exported for tests. "JPEG", "PNG",
+ * "TARGA" and "TARGA_RAW" (four channels, as "PNG"; RR_EINVAL for a width or
+ * height above 65535 or a body of 2 GB and more): "OPEN_EXR" needs the float
+ * film and is RR_ENOTSUP here. */
 int rr_encode_image(const uint8_t* rgba8, int32_t width, int32_t height,
                     const char* out_path_no_ext, const char* format,
                     int32_t jpeg_quality, uint64_t* bytes_written);
@@ -383,10 +395,10 @@ int rr_encode_image_mode(const uint8_t* rgba8, int32_t width, int32_t height,
 
 /* Encode an image of the caller's with the device coder of a format, depth and
  * colour mode, through the enqueue, wrap and file code rendered frames take.
- * format "JPEG" (depth 8) and "PNG" at depth 8 take an RGBA8 image
- * (image_is_float 0); "PNG" at depth 16 and "OPEN_EXR" at depth 16 (HALF) or 32
+ * format "JPEG" (depth 8), "PNG" at depth 8 and "TARGA" / "TARGA_RAW" (depth 8
+ * and no other) take an RGBA8 image (image_is_float 0); "PNG" at depth 16 and "OPEN_EXR" at depth 16 (HALF) or 32
  * (FLOAT) take width * height * 4 floats (image_is_float 1) as means, spp = 1,
- * alpha 1. depth 0: 8 for PNG, 16 for OPEN_EXR. view_transform and
+ * alpha 1. depth 0: 8 for PNG and TARGA, 16 for OPEN_EXR. view_transform and
  * exposure_scale: 16-bit PNG only, as for rr_debug_png16_device; jpeg_quality:
  * JPEG only. A size outside the coder's range is RR_EINVAL before anything is
  * launched. *len receives the file size; the bytes are copied to out if
