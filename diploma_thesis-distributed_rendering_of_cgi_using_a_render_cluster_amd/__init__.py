@@ -16,7 +16,7 @@ from .naming import EXTENSIONS, format_hash_frame_placeholders, job_output_files
     output_path_without_extension
 from .native import (LIB_PATH, SHIM_PATH, EXPORTS, FrameState, FrameStats, FrameTiming, RenderContext,
                      RenderParams, RRError, Scene, default_params, display_gamma, dither_noise, encode_image,
-                     encode_image_mode, encode_image_png, lib, png_filters, sin_fixed)
+                     encode_image_mode, encode_image_png, hdr_host, lib, png_filters, sin_fixed)
 from .runner import (BackendRunner, FrameQueueRemoveResult, PendingFrame, RenderError, WorkerAutomaticQueue,
                      WorkerFrameState)
 from .traces import FrameRenderTime, WorkerTrace, WorkerTraceBuilder, raw_trace_document, save_raw_traces, \

@@ -1,5 +1,5 @@
 // The coders of a frame's file: the dispatch to the device coders (jpeg.hip,
-// png.hip, png16.hip, exr.hip, tga.hip), the host-built files around their streams, and
+// png.hip, png16.hip, exr.hip, tga.hip, hdr.hip), the host-built files around their streams, and
 // the host coders of an RGBA8 image. See frame.hpp.
 #include <cerrno>
 #include <cstring>
@@ -51,7 +51,36 @@ int plan_or_refuse(const FrameOutput& fo, int W, int H, TgaPlan& p) {
     return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
 }
 
+int plan_or_refuse(const FrameOutput& fo, int W, int H, HdrPlan& p) {
+    if (hdr_plan(W, H, fo.color_mode, p)) return RR_OK;
+    return fail(RR_EINVAL, "image size outside the HDR coder's range (a body bound below 2 GB)");
+}
+
 namespace {
+
+// Device HDR encode of a film into o's pinned stream, by o.plan.
+void enqueue_hdr(const CoderInput& in, DevFrame& f, hipStream_t st, HdrOut& o) {
+    const HdrPlan& p = o.plan;
+    if (p.W != in.W || p.H != in.H) throw std::runtime_error("HDR plan of another image");
+    f.hdr_scratch.ensure(hdr_scratch_words(p));
+    o.stream.ensure(hdr_stream_bytes(p));
+    void* dev_host = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
+    f.prof.begin(st, RR_K_PNG);
+    hdr_encode_device(in.film, in.inv_spp, p, f.hdr_scratch.ptr, static_cast<uint8_t*>(dev_host), st);
+    f.prof.end(st);
+}
+
+// The file of a device-coded HDR image: host-built header + the device body.
+void hdr_file_bytes(const HdrOut& o, std::vector<uint8_t>& data) {
+    const HdrPlan& p = o.plan;
+    uint64_t len = 0;
+    std::memcpy(&len, o.stream.ptr, sizeof len);
+    if (len > p.body_cap || len + 16 > o.stream.cap || (p.flat && len != p.body_cap))
+        throw std::runtime_error("device HDR stream overflow");
+    hdr_header_bytes(p.W, p.H, data);
+    data.insert(data.end(), o.stream.ptr + 16, o.stream.ptr + 16 + len);
+}
 
 // Device TARGA encode of an RGBA8 image into o's pinned stream, by o.plan.
 void enqueue_tga(const CoderInput& in, DevFrame& f, hipStream_t st, TgaOut& o) {
@@ -150,6 +179,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
     const int C = fo.color_mode;
     if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o.jpeg);
     if (k == Coder::Tga) return enqueue_tga(in, f, st, o.tga);
+    if (k == Coder::Hdr) return enqueue_hdr(in, f, st, o.hdr);
     if (!device_deflate(k)) throw std::runtime_error("no device coder for this output");
     // the front ends' own buffers. "PNG" at compression 0 .. 100: a filter type
     // per row of the H rows, and at 16 bits the raw scanlines, 2C W H bytes
@@ -201,6 +231,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data) {
     if (fo.coder == Coder::Jpeg) jpeg_file_bytes(o.jpeg, data);
     else if (fo.coder == Coder::Tga) tga_file_bytes(o.tga, data);
+    else if (fo.coder == Coder::Hdr) hdr_file_bytes(o.hdr, data);
     else deflate_file_bytes(o.deflate, fo.coder, fo.color_mode, data);
 }
 
@@ -225,9 +256,14 @@ int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const cha
         if (!encode_tga(rgba, W, H, resolve_color_mode(mode, false), fmt == "TARGA", data))
             return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
         ext = ".tga";
+    } else if (fmt == "OPEN_EXR" || fmt == "HDR") {
+        return fail(RR_ENOTSUP, "unsupported output format '" + fmt +
+                                    "' for an RGBA8 image: it needs the float film (JPEG, PNG, TARGA and TARGA_RAW "
+                                    "are supported here)");
     } else {
-        return fail(RR_ENOTSUP,
-                    "unsupported output format '" + fmt + "' (JPEG, PNG, TARGA and TARGA_RAW are supported)");
+        return fail(RR_ENOTSUP, "unsupported output format '" + fmt +
+                                    "' (JPEG, PNG, TARGA and TARGA_RAW are supported here; OPEN_EXR and HDR need "
+                                    "the float film)");
     }
     const std::string path = std::string(out_path) + ext;
     if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));

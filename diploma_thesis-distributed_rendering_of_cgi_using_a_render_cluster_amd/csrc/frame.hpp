@@ -14,6 +14,7 @@
 
 #include "deflate.hpp"
 #include "device.hpp"
+#include "hdr.hpp"
 #include "rr.h"
 #include "scene.hpp"
 #include "settings.hpp"
@@ -67,12 +68,20 @@ struct TgaOut {
     rr::TgaPlan plan{};
 };
 
+// The same for a device-coded HDR body (hdr.hpp); the host puts the text header
+// in front.
+struct HdrOut {
+    PinnedBuf stream;
+    rr::HdrPlan plan{};
+};
+
 // Where the device coders write: a frame slot has one, and the context one
 // more for the inspection entry points.
 struct CodedOut {
     JpegOut jpeg;
     DeflateOut deflate;
     TgaOut tga;
+    HdrOut hdr;
 };
 
 struct FrameRun {
@@ -95,7 +104,7 @@ struct FrameSlot {
     uint64_t ticket = 0;
     // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
     // work done, 3 outputs on the host (after their copies), 5 (device PNG,
-    // EXR and TARGA frames) before the slot's coder: the state shared between frames is free
+    // EXR, TARGA and HDR frames) before the slot's coder: the state shared between frames is free
     hipEvent_t ev[6] = {};
     // The slot's frames run on its own stream and write only its own device
     // state, so a k_tiles frame runs on the GPU beside the other slots'
@@ -251,7 +260,7 @@ void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int
 
 // ---- the device coders (coders.cpp) ----------------------------------------
 
-// The image a coder reads. rgba8: Jpeg, Png8 and Tga; film: Png16, Exr and Exr32,
+// The image a coder reads. rgba8: Jpeg, Png8 and Tga; film: Png16, Exr, Exr32 and Hdr,
 // W x H float4 sums scaled by inv_spp. exposure_scale, view_transform, look
 // and gamma (resolved: resolve_view, or an inspection call's own check): Png16,
 // which takes the film through exposure and view transform again at 16 bits.
@@ -276,6 +285,9 @@ int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p);
 // The same for a TARGA image (Coder::Tga): W or H above 65535 and a body of
 // 2 GB and more are refused.
 int plan_or_refuse(const FrameOutput& fo, int W, int H, TgaPlan& p);
+// The same for an HDR image (Coder::Hdr): a body bound of 2 GB and more is
+// refused.
+int plan_or_refuse(const FrameOutput& fo, int W, int H, HdrPlan& p);
 
 // The 16-bit path's sRGB table on the device. Written once, before the first
 // kernel that reads it is enqueued, and never again.
@@ -284,11 +296,12 @@ void ensure_srgb16(rr_ctx* c);
 // with every stream idle when the quality changes.
 void ensure_jpeg_table(rr_ctx* c, int quality);
 
-// Enqueue the device coder that `fo` names (Jpeg ... Tga) on stream st, with
+// Enqueue the device coder that `fo` names (Jpeg ... Hdr) on stream st, with
 // f's scratch and profiler, into o's pinned buffers. fo.color_mode: the file's
 // channels; fo.png_compression ("PNG"): LEGACY the Sub front end, 0 .. 100 the
 // adaptive one (the device coders have one effort level). A deflate format
-// codes by o.deflate.plan, a TARGA one by o.tga.plan (plan_or_refuse).
+// codes by o.deflate.plan, a TARGA one by o.tga.plan, an HDR one by o.hdr.plan
+// (plan_or_refuse).
 void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o);
 
 // The file of a device-coded image, once its stream is on the host: the
@@ -296,7 +309,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data);
 
 // The host coders: an RGBA8 image as a "JPEG", "PNG", "TARGA" or "TARGA_RAW"
-// file at out_path + its extension. mode: a colour mode as rr_set_color_mode takes it, 0 the format's
+// file at out_path + its extension ("OPEN_EXR" and "HDR" need the float film: RR_ENOTSUP). mode: a colour mode as rr_set_color_mode takes it, 0 the format's
 // own layout. compression ("PNG"): LEGACY, or 0 .. 100 (rr_set_png_compression).
 int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,
               uint64_t* bytes, int mode = 0, int compression = RR_PNG_COMPRESSION_LEGACY);

@@ -9,6 +9,7 @@
 #include "image_io.hpp"
 
 #include "grey.h"
+#include "hdr_rule.h"
 #include "png_filter.h"
 #include "tga_rule.h"
 
@@ -730,6 +731,73 @@ bool encode_tga(const uint8_t* rgba, int W, int H, int C, bool rle, std::vector<
         put_stretch(lit, (size_t)W - lit, false);
     }
     return out.size() - kTgaHeaderBytes <= bound;
+}
+
+// --------------------------------------------------------------- HDR ------
+void hdr_header_bytes(int W, int H, std::vector<uint8_t>& out) {
+    const std::string text =
+        "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y " + std::to_string(H) + " +X " + std::to_string(W) + "\n";
+    out.assign(text.begin(), text.end());
+}
+
+bool encode_hdr(const float* rgba, int W, int H, int C, std::vector<uint8_t>& out) {
+    const uint64_t bound = hdr_body_max_bytes(W, H);
+    if (!rgba || bound == 0 || (C != 1 && C != 3)) return false;
+    hdr_header_bytes(W, H, out);
+    const size_t head = out.size();
+    out.reserve(head + (size_t)bound);
+    auto bits = [](float v) {
+        uint32_t u;
+        std::memcpy(&u, &v, sizeof u);
+        return u;
+    };
+    std::vector<uint8_t> quads((size_t)W * 4), plane((size_t)W);
+    for (int y = 0; y < H; ++y) {  // top row first
+        const float* src = rgba + (size_t)y * W * 4;
+        for (int x = 0; x < W; ++x) {
+            const float* p = src + 4 * (size_t)x;
+            uint32_t q;
+            if (C == 1) {
+                const uint32_t l = bits(luma709(p[0], p[1], p[2]));
+                q = hdr_quad(l, l, l);
+            } else {
+                q = hdr_quad(bits(p[0]), bits(p[1]), bits(p[2]));
+            }
+            for (int k = 0; k < 4; ++k) quads[4 * (size_t)x + k] = (uint8_t)(q >> (8 * k));
+        }
+        if (hdr_row_flat(W)) {
+            out.insert(out.end(), quads.begin(), quads.end());
+            continue;
+        }
+        const uint8_t marker[4] = {2, 2, (uint8_t)(W >> 8), (uint8_t)W};
+        out.insert(out.end(), marker, marker + 4);
+        for (int k = 0; k < 4; ++k) {
+            for (int x = 0; x < W; ++x) plane[(size_t)x] = quads[4 * (size_t)x + k];
+            // a stretch of n bytes from byte `from`: packets of 127 (runs) or 128 (literals), then the remainder
+            auto put_stretch = [&](size_t from, size_t n, bool run) {
+                const size_t cap = run ? kHdrRunPacket : kHdrLitPacket;
+                for (size_t at = 0; at < n; at += cap) {
+                    const size_t count = std::min(cap, n - at);
+                    out.push_back((uint8_t)hdr_packet_header(run, (uint32_t)count));
+                    const uint8_t* b = plane.data() + from + at;
+                    out.insert(out.end(), b, b + (run ? 1 : count));
+                }
+            };
+            size_t lit = 0;  // first byte of the open literal stretch
+            for (size_t x = 0; x < (size_t)W;) {
+                size_t e = x + 1;  // the maximal run [x, e)
+                while (e < (size_t)W && plane[e] == plane[x]) ++e;
+                if (e - x >= kHdrMinRun) {
+                    put_stretch(lit, x - lit, false);
+                    put_stretch(x, e - x, true);
+                    lit = e;
+                }
+                x = e;
+            }
+            put_stretch(lit, (size_t)W - lit, false);
+        }
+    }
+    return out.size() - head <= bound;
 }
 
 bool write_file(const std::string& path, const std::vector<uint8_t>& data) {

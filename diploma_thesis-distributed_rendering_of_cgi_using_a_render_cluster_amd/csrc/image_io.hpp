@@ -69,6 +69,15 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
 // tga.hip writes the same bytes.
 bool encode_tga(const uint8_t* rgba, int W, int H, int C, bool rle, std::vector<uint8_t>& out);
 void tga_header_bytes(int W, int H, int C, bool rle, std::vector<uint8_t>& out);
+// A Radiance RGBE file ("HDR") of W x H float RGBA means (alpha ignored), by
+// the rules of hdr_rule.h: the text header "#?RADIANCE\nFORMAT=32-bit_rle_rgbe
+// \n\n-Y <H> +X <W>\n" and the rows top first, each the marker bytes and the
+// four planes in packets, or flat quads where the width says so. C = 3: the
+// quads of R, G, B; C = 1: of the Rec.709 luma (grey.h luma709) in all three.
+// The rule is stated as a plain walk over the runs: hdr.hip writes the same
+// bytes from ballots. false: C not 1 or 3, or a body bound of 2 GB and more.
+bool encode_hdr(const float* rgba, int W, int H, int C, std::vector<uint8_t>& out);
+void hdr_header_bytes(int W, int H, std::vector<uint8_t>& out);
 bool write_file(const std::string& path, const std::vector<uint8_t>& data);
 
 }  // namespace rr

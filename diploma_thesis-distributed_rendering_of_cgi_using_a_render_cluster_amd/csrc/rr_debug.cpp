@@ -8,6 +8,7 @@
 
 #include "api_util.hpp"
 #include "frame.hpp"
+#include "image_io.hpp"
 #include "png_filter.h"
 
 using namespace rr;
@@ -50,6 +51,8 @@ int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, boo
     const FrameOutput fo{k, C, png_compression_of(c->settings), quality, tga_raw};
     if (k == Coder::Tga)
         if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.tga.plan)) return rc;
+    if (k == Coder::Hdr)
+        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.hdr.plan)) return rc;
     return guarded([&] {
         if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
         set_device(c);
@@ -117,8 +120,8 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
     if (!c || !format || !image || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
     if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
     const std::string fmt(format);
-    const bool jpeg = fmt == "JPEG";
-    const int C = resolve_color_mode(color_mode, jpeg);
+    const bool jpeg = fmt == "JPEG", hdr = fmt == "HDR";
+    const int C = resolve_color_mode(color_mode, jpeg || hdr);
     Coder k = Coder::None;
     if (jpeg) {
         if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "JPEG takes an RGBA8 image at depth 8");
@@ -131,6 +134,9 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
     } else if (fmt == "TARGA" || fmt == "TARGA_RAW") {  // 8 bits a channel and no other depth
         if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "TARGA takes an RGBA8 image at depth 8");
         k = Coder::Tga;
+    } else if (hdr) {  // the film's floats and no other depth
+        if (!image_is_float || (depth != 0 && depth != 32)) return fail(RR_EINVAL, "HDR takes a float RGBA image at depth 32");
+        k = Coder::Hdr;
     } else {
         if (!image_is_float) return fail(RR_EINVAL, "16-bit PNG and OPEN_EXR take a float RGBA image");
         if (fmt == "PNG" && depth == 16) k = Coder::Png16;
@@ -139,6 +145,20 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
     }
     return debug_encode(c, k, C, image, w, h, true, view_transform, exposure_scale, jpeg_quality, out, cap, len,
                         fmt == "TARGA_RAW");
+}
+
+int rr_debug_hdr_host(const float* rgba, int32_t w, int32_t h, int32_t color_mode, uint8_t* out, uint64_t cap,
+                      uint64_t* bytes) {
+    if (!rgba || !bytes || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
+    return guarded([&] {
+        std::vector<uint8_t> data;
+        if (!encode_hdr(rgba, w, h, resolve_color_mode(color_mode, true), data))
+            return fail(RR_EINVAL, "image size outside the HDR coder's range (a body bound below 2 GB)");
+        *bytes = data.size();
+        if (out && cap >= *bytes) std::memcpy(out, data.data(), data.size());
+        return RR_OK;
+    });
 }
 
 int rr_debug_png_filters(const uint8_t* raw, int32_t row_bytes, int32_t rows, int32_t bpp, uint8_t* types) {

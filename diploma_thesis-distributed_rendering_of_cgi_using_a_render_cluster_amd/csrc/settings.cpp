@@ -177,16 +177,17 @@ bool settings_from_env(OutputSettings& s, std::string& err) {
 
 bool known_format(const char* format) {
     const std::string f(format ? format : "");
-    return f == "JPEG" || f == "PNG" || f == "OPEN_EXR" || f == "TARGA" || f == "TARGA_RAW";
+    return f == "JPEG" || f == "PNG" || f == "OPEN_EXR" || f == "TARGA" || f == "TARGA_RAW" || f == "HDR";
 }
 
 const char* coder_ext(Coder k) {
+    if (k == Coder::Hdr) return ".hdr";
     return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : k == Coder::Tga ? ".tga" : ".png";
 }
 
-int resolve_color_mode(int mode, bool jpeg) {
-    if (mode == 0) return jpeg ? RR_COLOR_RGB : RR_COLOR_RGBA;
-    return (jpeg && mode == RR_COLOR_RGBA) ? RR_COLOR_RGB : mode;
+int resolve_color_mode(int mode, bool no_alpha) {
+    if (mode == 0) return no_alpha ? RR_COLOR_RGB : RR_COLOR_RGBA;
+    return (no_alpha && mode == RR_COLOR_RGBA) ? RR_COLOR_RGB : mode;
 }
 
 FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const char* format, bool has_path,
@@ -195,18 +196,20 @@ FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const c
     const bool exr = has_path && std::string(format) == "OPEN_EXR";
     const bool tga_raw = has_path && std::string(format) == "TARGA_RAW";
     const bool tga = tga_raw || (has_path && std::string(format) == "TARGA");
+    const bool hdr = has_path && std::string(format) == "HDR";
     FrameOutput o;
     o.tga_raw = tga_raw;
     if (!has_path) o.coder = Coder::None;
     else if (jpeg) o.coder = Coder::Jpeg;
     else if (tga) o.coder = Coder::Tga;  // 8 bits a channel: the depth settings do not apply
+    else if (hdr) o.coder = Coder::Hdr;  // RGBE quads of the film's means: nor do they here
     else if (exr)  // HALF unless the context, or at 0 the scene, asks for FLOAT channels
         o.coder = (s.exr_depth ? s.exr_depth : r.exr_depth) == 32 ? Coder::Exr32 : Coder::Exr;
     // "PNG". 16 bits per sample: always the device coder (there is no host one)
     else if ((s.png_depth ? s.png_depth : r.color_depth) == 16) o.coder = Coder::Png16;
     else o.coder = s.device_png ? Coder::Png8 : Coder::HostRgba;
     // the context's mode, at 0 the scene's, at 0 again the format's own layout
-    o.color_mode = resolve_color_mode(s.color_mode ? s.color_mode : r.color_mode, jpeg);
+    o.color_mode = resolve_color_mode(s.color_mode ? s.color_mode : r.color_mode, jpeg || hdr);
     // the context's setting, at SCENE the scene's (-1, legacy, where it has no field)
     o.png_compression = s.png_compression == RR_PNG_COMPRESSION_SCENE ? r.png_compression : s.png_compression;
     o.quality = jpeg_quality;

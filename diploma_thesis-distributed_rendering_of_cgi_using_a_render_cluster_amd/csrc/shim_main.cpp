@@ -124,6 +124,7 @@ int main(int argc, char** argv) {
                             : fmt == "PNG"                            ? ".png"
                             : fmt == "OPEN_EXR"                       ? ".exr"
                             : (fmt == "TARGA" || fmt == "TARGA_RAW") ? ".tga"
+                            : fmt == "HDR"                            ? ".hdr"
                                                                       : "";
     if (ext.empty()) {
         std::fprintf(stderr, "rr-blender-shim: unsupported output format '%s'\n", fmt.c_str());

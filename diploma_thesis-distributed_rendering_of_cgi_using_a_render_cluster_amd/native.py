@@ -79,7 +79,7 @@ class FrameStats(ctypes.Structure):
 
 RR_FLAG_PROFILE_KERNELS, RR_FLAG_COUNT_TRAVERSAL, RR_FLAG_WAVEFRONT = 1, 2, 4
 KERNEL_CLASSES = ["build", "primary", "extend", "shadow", "accumulate", "shade", "tiles"]
-RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR) or the TARGA packer
+RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer or the HDR coder
 
 
 # Every symbol include/rr.h declares (checked by tests/test_abi.py).
@@ -98,6 +98,7 @@ EXPORTS = [
     "rr_set_look", "rr_set_display_gamma", "rr_debug_view_device", "rr_debug_display_gamma", "rr_debug_scene_view",
     "rr_set_dither", "rr_debug_dither_noise", "rr_debug_sin_fixed",
     "rr_set_png_compression", "rr_encode_image_png", "rr_debug_png_filters", "rr_debug_scene_png_compression",
+    "rr_debug_hdr_host",
 ]
 
 # rr_set_png_compression's values beside 0 .. 100 (include/rr.h)
@@ -211,6 +212,7 @@ def lib() -> ctypes.CDLL:
         "rr_encode_image_png": (c_int, [u8p, i32, i32, ctypes.c_char_p, i32, i32, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_png_filters": (c_int, [u8p, i32, i32, i32, u8p]),
         "rr_debug_scene_png_compression": (c_int, [P, i32p]),
+        "rr_debug_hdr_host": (c_int, [f32p, i32, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
         "rr_debug_fastmath_check": (c_int, [P, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -612,9 +614,11 @@ class RenderContext:
     def encode_device(self, fmt: str, image: np.ndarray, depth: int = 0, color_mode=0, view_transform: int = 0,
                       exposure_scale: float = 1.0, quality: int = 90) -> bytes:
         """rr_debug_encode_device: the file bytes of an (H, W, 4) image coded on the
-        device as `fmt` ("JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW") at `depth`
-        in `color_mode`. uint8 images for JPEG, 8-bit PNG and TARGA, float32 means
-        for the others."""
+        device as `fmt` ("JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW", "HDR") at
+        `depth` in `color_mode`. uint8 images for JPEG, 8-bit PNG and TARGA, float32
+        means for the others; "HDR" at depth 0 or 32 and no other."""
+        if fmt == "HDR" and (image.dtype == np.uint8 or int(depth) not in (0, 32)):
+            raise RRError(RR_EINVAL, "HDR takes a float image at depth 0 or 32")
         is_float = image.dtype != np.uint8
         image = np.ascontiguousarray(image, dtype=np.float32 if is_float else np.uint8)
         h, w = image.shape[:2]
@@ -758,6 +762,20 @@ def encode_image_png(rgba: np.ndarray, out_path_no_ext: str, color_mode=0, compr
                                      color_mode_value(color_mode), png_compression_value(compression),
                                      ctypes.byref(nbytes)))
     return nbytes.value
+
+
+def hdr_host(rgba: np.ndarray, color_mode=0) -> bytes:
+    """rr_debug_hdr_host: the Radiance RGBE file ("HDR") the host coder makes of an
+    (H, W, 4) float32 image of means in `color_mode` ("BW", or "RGB" / "RGBA" / 0
+    for RGB). No context and no device: the reference for the device coder's bytes."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+    h, w = rgba.shape[:2]
+    args = (_ptr(rgba, ctypes.c_float), w, h, color_mode_value(color_mode))
+    n = ctypes.c_uint64()
+    _check(lib().rr_debug_hdr_host(*args, None, 0, ctypes.byref(n)))
+    out = np.zeros(n.value, np.uint8)
+    _check(lib().rr_debug_hdr_host(*args, _ptr(out, ctypes.c_uint8), out.size, ctypes.byref(n)))
+    return out[:n.value].tobytes()
 
 
 def png_filters(raw: np.ndarray, bpp: int) -> np.ndarray:

@@ -47,7 +47,8 @@ class BackendRunner:
         logic alone pass a stand-in with the same methods (no rendering).
         device_png: "PNG" jobs are coded on the device (rr_set_device_png).
         "OPEN_EXR" jobs (ZIP files of the linear film) always are, and so are
-        "TARGA" and "TARGA_RAW" jobs (8-bit .tga files, run-length coded or plain).
+        "TARGA" and "TARGA_RAW" jobs (8-bit .tga files, run-length coded or plain)
+        and "HDR" jobs (Radiance RGBE .hdr files of the linear film).
         png_depth: bits per sample of "PNG" jobs (rr_set_png_depth): 8, 16, or 0
         for each scene's own render.color_depth; 16-bit frames are always coded
         on the device.

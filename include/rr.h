@@ -93,7 +93,7 @@ typedef struct rr_render_params {
 #define RR_K_ACCUM 4     /* film accumulate + tonemap */
 #define RR_K_SHADE 5     /* split path (large scenes): shading kernels; PRIMARY/EXTEND then time traversal only */
 #define RR_K_TILES 6     /* LDS-resident scenes: k_tiles, every sample of an 8x8 pixel tile run to completion + film + tonemap */
-#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), or the TARGA packer: all its kernels, one event pair per frame */
+#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer or the HDR coder: all its kernels, one event pair per frame */
 #define RR_K_CLASSES 8
 
 /* The five timestamps the reference recovers from Blender's stdout
@@ -200,9 +200,9 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *  - frame_index: the frame to evaluate (Blender frame number, scene.frame_set).
  *  - out_path: output path WITHOUT extension, '#' runs already substituted
  *    (render-timing-script.py:69-78,82); the library appends ".jpg" / ".png"
- *    / ".exr" / ".tga" as Blender's write_still does with R_EXTENSION. NULL:
- *    render only.
- *  - format: "JPEG", "PNG", "OPEN_EXR", "TARGA" or "TARGA_RAW" (job output_file_format,
+ *    / ".exr" / ".tga" / ".hdr" as Blender's write_still does with
+ *    R_EXTENSION. NULL: render only.
+ *  - format: "JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW" or "HDR" (job output_file_format,
  *    shared/src/jobs/mod.rs:80, handed to image_settings.file_format,
  *    render-timing-script.py:83-92). "OPEN_EXR": the film's mean linear
  *    radiance before any view transform (alpha = 1) as A, B, G, R channels,
@@ -222,6 +222,19 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *    plain. No footer. Always 8 bits a channel: rr_set_png_depth and the
  *    scene's colour depth do not apply. Coded on the GPU (tga.hip).
  *    RR_EINVAL for a width or height above 65535 or a body of 2 GB and more.
+ *    "HDR": a Radiance RGBE file of the values a FLOAT "OPEN_EXR" file of the
+ *    frame holds (the film's means; no view transform, look, display gamma or
+ *    dither; the depth settings and the PNG compression do not apply). The
+ *    header "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y <H> +X <W>\n", then the
+ *    rows top first: for a width of 8 .. 32767 the bytes 2, 2, W >> 8, W & 255
+ *    and the R, G, B and E planes, each run-length coded on its own (run
+ *    packets of at most 127, literal packets of at most 128 bytes, runs from 4
+ *    bytes); any other width flat quads. No alpha: RGBA and no mode write RGB;
+ *    BW writes R = G = B = the Rec.709 luma of the means. Quads truncate, by
+ *    integer shifts of the floats' bits; the rule and the packets are the
+ *    project's own (csrc/hdr_rule.h) and unpinned against Blender's files: any
+ *    reader returns the same quads from either packing. Coded on the GPU
+ *    (hdr.hip). RR_EINVAL for a body bound of 2 GB and more.
  *  - jpeg_quality: 1..100 (the reference script forces 90, :84); ignored for
  *    every other format.
  *  - timing / stats: optional outputs (may be NULL). */
@@ -271,8 +284,8 @@ int rr_scene_resolution(rr_scene* scene, const rr_render_params* params,
 /* Encode an RGBA8 image (rows top to bottom) to `path` + extension.
  * Host encoder used by rr_render_frame; exported for tests. "JPEG", "PNG",
  * "TARGA" and "TARGA_RAW" (four channels, as "PNG"; RR_EINVAL for a width or
- * height above 65535 or a body of 2 GB and more): "OPEN_EXR" needs the float
- * film and is RR_ENOTSUP here. */
+ * height above 65535 or a body of 2 GB and more): "OPEN_EXR" and "HDR" need the
+ * float film and are RR_ENOTSUP here. */
 int rr_encode_image(const uint8_t* rgba8, int32_t width, int32_t height,
                     const char* out_path_no_ext, const char* format,
                     int32_t jpeg_quality, uint64_t* bytes_written);
@@ -396,9 +409,10 @@ int rr_encode_image_mode(const uint8_t* rgba8, int32_t width, int32_t height,
 /* Encode an image of the caller's with the device coder of a format, depth and
  * colour mode, through the enqueue, wrap and file code rendered frames take.
  * format "JPEG" (depth 8), "PNG" at depth 8 and "TARGA" / "TARGA_RAW" (depth 8
- * and no other) take an RGBA8 image (image_is_float 0); "PNG" at depth 16 and "OPEN_EXR" at depth 16 (HALF) or 32
- * (FLOAT) take width * height * 4 floats (image_is_float 1) as means, spp = 1,
- * alpha 1. depth 0: 8 for PNG and TARGA, 16 for OPEN_EXR. view_transform and
+ * and no other) take an RGBA8 image (image_is_float 0); "PNG" at depth 16, "OPEN_EXR" at depth 16 (HALF) or 32
+ * (FLOAT) and "HDR" (depth 32 and no other) take width * height * 4 floats
+ * (image_is_float 1) as means, spp = 1, alpha 1. depth 0: 8 for PNG and TARGA,
+ * 16 for OPEN_EXR, 32 for HDR. view_transform and
  * exposure_scale: 16-bit PNG only, as for rr_debug_png16_device; jpeg_quality:
  * JPEG only. A size outside the coder's range is RR_EINVAL before anything is
  * launched. *len receives the file size; the bytes are copied to out if
@@ -407,6 +421,15 @@ int rr_debug_encode_device(rr_ctx* ctx, const char* format, int32_t depth, int32
                            const void* image, int32_t image_is_float, int32_t width, int32_t height,
                            int32_t view_transform, float exposure_scale, int32_t jpeg_quality,
                            uint8_t* out, uint64_t cap, uint64_t* len);
+
+/* The host "HDR" coder (no context, no device needed), the reference for the
+ * device coder's bytes: the Radiance RGBE file of width * height * 4 floats
+ * taken as means (alpha ignored), in color_mode (RR_COLOR_SCENE and
+ * RR_COLOR_RGBA: RGB; RR_COLOR_BW: R = G = B = luma). *bytes receives the file
+ * size; the bytes are copied to out if cap >= *bytes. RR_EINVAL for a body
+ * bound of 2 GB and more. Exported for tests. */
+int rr_debug_hdr_host(const float* rgba, int32_t width, int32_t height, int32_t color_mode,
+                      uint8_t* out, uint64_t cap, uint64_t* bytes);
 
 /* The sRGB table of the 16-bit PNG path (host only, no device needed): *n
  * receives the number of floats (intervals + 1), which are copied to table if
