@@ -1,5 +1,5 @@
 // The coders of a frame's file: the dispatch to the device coders (jpeg.hip,
-// png.hip, png16.hip, exr.hip, tga.hip, hdr.hip), the host-built files around their streams, and
+// png.hip, png16.hip, exr.hip, tga.hip, hdr.hip, iris.hip), the host-built files around their streams, and
 // the host coders of an RGBA8 image. See frame.hpp.
 #include <cerrno>
 #include <cstring>
@@ -56,7 +56,41 @@ int plan_or_refuse(const FrameOutput& fo, int W, int H, HdrPlan& p) {
     return fail(RR_EINVAL, "image size outside the HDR coder's range (a body bound below 2 GB)");
 }
 
+static const char* const kIrisRange =
+    "image size outside the IRIS format's range (65535 x 65535, a body bound below 2 GB)";
+
+int plan_or_refuse(const FrameOutput& fo, int W, int H, IrisPlan& p) {
+    if (iris_plan(W, H, fo.color_mode, p)) return RR_OK;
+    return fail(RR_EINVAL, kIrisRange);
+}
+
 namespace {
+
+// Device IRIS encode of an RGBA8 image into o's pinned stream, by o.plan.
+void enqueue_iris(const CoderInput& in, DevFrame& f, hipStream_t st, IrisOut& o) {
+    const IrisPlan& p = o.plan;
+    if (p.W != in.W || p.H != in.H) throw std::runtime_error("IRIS plan of another image");
+    f.iris_scratch.ensure(iris_scratch_words(p));
+    o.stream.ensure(iris_stream_bytes(p));
+    void* dev_host = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
+    f.prof.begin(st, RR_K_PNG);
+    iris_encode_device(in.rgba8, p, f.iris_scratch.ptr, static_cast<uint8_t*>(dev_host), st);
+    f.prof.end(st);
+}
+
+// The file of a device-coded IRIS image: host-built header + the device body
+// (the tables and the coded row-planes, each at least its terminator).
+void iris_file_bytes(const IrisOut& o, std::vector<uint8_t>& data) {
+    const IrisPlan& p = o.plan;
+    uint64_t len = 0;
+    std::memcpy(&len, o.stream.ptr, sizeof len);
+    const uint64_t planes = (uint64_t)p.H * (uint64_t)p.C;
+    if (len > p.body_cap || len + 16 > o.stream.cap || len < 8 * planes + 3 * planes)
+        throw std::runtime_error("device IRIS stream overflow");
+    iris_header_bytes(p.W, p.H, p.C, data);
+    data.insert(data.end(), o.stream.ptr + 16, o.stream.ptr + 16 + len);
+}
 
 // Device HDR encode of a film into o's pinned stream, by o.plan.
 void enqueue_hdr(const CoderInput& in, DevFrame& f, hipStream_t st, HdrOut& o) {
@@ -180,6 +214,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
     if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o.jpeg);
     if (k == Coder::Tga) return enqueue_tga(in, f, st, o.tga);
     if (k == Coder::Hdr) return enqueue_hdr(in, f, st, o.hdr);
+    if (k == Coder::Iris) return enqueue_iris(in, f, st, o.iris);
     if (!device_deflate(k)) throw std::runtime_error("no device coder for this output");
     // the front ends' own buffers. "PNG" at compression 0 .. 100: a filter type
     // per row of the H rows, and at 16 bits the raw scanlines, 2C W H bytes
@@ -232,6 +267,7 @@ void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint
     if (fo.coder == Coder::Jpeg) jpeg_file_bytes(o.jpeg, data);
     else if (fo.coder == Coder::Tga) tga_file_bytes(o.tga, data);
     else if (fo.coder == Coder::Hdr) hdr_file_bytes(o.hdr, data);
+    else if (fo.coder == Coder::Iris) iris_file_bytes(o.iris, data);
     else deflate_file_bytes(o.deflate, fo.coder, fo.color_mode, data);
 }
 
@@ -256,14 +292,17 @@ int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const cha
         if (!encode_tga(rgba, W, H, resolve_color_mode(mode, false), fmt == "TARGA", data))
             return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
         ext = ".tga";
+    } else if (fmt == "IRIS") {
+        if (!encode_iris(rgba, W, H, resolve_color_mode(mode, false), data)) return fail(RR_EINVAL, kIrisRange);
+        ext = ".rgb";
     } else if (fmt == "OPEN_EXR" || fmt == "HDR") {
         return fail(RR_ENOTSUP, "unsupported output format '" + fmt +
-                                    "' for an RGBA8 image: it needs the float film (JPEG, PNG, TARGA and TARGA_RAW "
-                                    "are supported here)");
+                                    "' for an RGBA8 image: it needs the float film (JPEG, PNG, TARGA, TARGA_RAW and "
+                                    "IRIS are supported here)");
     } else {
         return fail(RR_ENOTSUP, "unsupported output format '" + fmt +
-                                    "' (JPEG, PNG, TARGA and TARGA_RAW are supported here; OPEN_EXR and HDR need "
-                                    "the float film)");
+                                    "' (JPEG, PNG, TARGA, TARGA_RAW and IRIS are supported here; OPEN_EXR and HDR "
+                                    "need the float film)");
     }
     const std::string path = std::string(out_path) + ext;
     if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));

@@ -216,6 +216,8 @@ struct DevFrame {
     DevBuf<uint32_t> tga_scratch;
     // HDR frames (hdr.hip): the quads, and for coded rows the per-byte records and the dense body; grow-only
     DevBuf<uint32_t> hdr_scratch;
+    // IRIS frames (iris.hip): the dense body (tables and coded row-planes) and the per-byte records; grow-only
+    DevBuf<uint32_t> iris_scratch;
     // written by render_frame_device, about the frame it enqueued
     int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log (trav_counts)

@@ -15,6 +15,7 @@
 #include "deflate.hpp"
 #include "device.hpp"
 #include "hdr.hpp"
+#include "iris.hpp"
 #include "rr.h"
 #include "scene.hpp"
 #include "settings.hpp"
@@ -75,6 +76,13 @@ struct HdrOut {
     rr::HdrPlan plan{};
 };
 
+// The same for a device-coded IRIS body (iris.hpp): the tables and the coded
+// row-planes; the host puts the 512-byte header in front.
+struct IrisOut {
+    PinnedBuf stream;
+    rr::IrisPlan plan{};
+};
+
 // Where the device coders write: a frame slot has one, and the context one
 // more for the inspection entry points.
 struct CodedOut {
@@ -82,6 +90,7 @@ struct CodedOut {
     DeflateOut deflate;
     TgaOut tga;
     HdrOut hdr;
+    IrisOut iris;
 };
 
 struct FrameRun {
@@ -104,7 +113,7 @@ struct FrameSlot {
     uint64_t ticket = 0;
     // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
     // work done, 3 outputs on the host (after their copies), 5 (device PNG,
-    // EXR, TARGA and HDR frames) before the slot's coder: the state shared between frames is free
+    // EXR, TARGA, HDR and IRIS frames) before the slot's coder: the state shared between frames is free
     hipEvent_t ev[6] = {};
     // The slot's frames run on its own stream and write only its own device
     // state, so a k_tiles frame runs on the GPU beside the other slots'
@@ -260,7 +269,7 @@ void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int
 
 // ---- the device coders (coders.cpp) ----------------------------------------
 
-// The image a coder reads. rgba8: Jpeg, Png8 and Tga; film: Png16, Exr, Exr32 and Hdr,
+// The image a coder reads. rgba8: Jpeg, Png8, Tga and Iris; film: Png16, Exr, Exr32 and Hdr,
 // W x H float4 sums scaled by inv_spp. exposure_scale, view_transform, look
 // and gamma (resolved: resolve_view, or an inspection call's own check): Png16,
 // which takes the film through exposure and view transform again at 16 bits.
@@ -288,6 +297,9 @@ int plan_or_refuse(const FrameOutput& fo, int W, int H, TgaPlan& p);
 // The same for an HDR image (Coder::Hdr): a body bound of 2 GB and more is
 // refused.
 int plan_or_refuse(const FrameOutput& fo, int W, int H, HdrPlan& p);
+// The same for an IRIS image (Coder::Iris): W or H above 65535 and a body
+// bound of 2 GB and more are refused.
+int plan_or_refuse(const FrameOutput& fo, int W, int H, IrisPlan& p);
 
 // The 16-bit path's sRGB table on the device. Written once, before the first
 // kernel that reads it is enqueued, and never again.
@@ -296,19 +308,19 @@ void ensure_srgb16(rr_ctx* c);
 // with every stream idle when the quality changes.
 void ensure_jpeg_table(rr_ctx* c, int quality);
 
-// Enqueue the device coder that `fo` names (Jpeg ... Hdr) on stream st, with
+// Enqueue the device coder that `fo` names (Jpeg ... Iris) on stream st, with
 // f's scratch and profiler, into o's pinned buffers. fo.color_mode: the file's
 // channels; fo.png_compression ("PNG"): LEGACY the Sub front end, 0 .. 100 the
 // adaptive one (the device coders have one effort level). A deflate format
-// codes by o.deflate.plan, a TARGA one by o.tga.plan, an HDR one by o.hdr.plan
-// (plan_or_refuse).
+// codes by o.deflate.plan, a TARGA one by o.tga.plan, an HDR one by o.hdr.plan,
+// an IRIS one by o.iris.plan (plan_or_refuse).
 void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o);
 
 // The file of a device-coded image, once its stream is on the host: the
 // host-built header or container around it.
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data);
 
-// The host coders: an RGBA8 image as a "JPEG", "PNG", "TARGA" or "TARGA_RAW"
+// The host coders: an RGBA8 image as a "JPEG", "PNG", "TARGA", "TARGA_RAW" or "IRIS"
 // file at out_path + its extension ("OPEN_EXR" and "HDR" need the float film: RR_ENOTSUP). mode: a colour mode as rr_set_color_mode takes it, 0 the format's
 // own layout. compression ("PNG"): LEGACY, or 0 .. 100 (rr_set_png_compression).
 int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,

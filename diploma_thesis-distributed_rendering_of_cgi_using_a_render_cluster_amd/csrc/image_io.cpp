@@ -10,6 +10,7 @@
 
 #include "grey.h"
 #include "hdr_rule.h"
+#include "iris_rule.h"
 #include "png_filter.h"
 #include "tga_rule.h"
 
@@ -798,6 +799,69 @@ bool encode_hdr(const float* rgba, int W, int H, int C, std::vector<uint8_t>& ou
         }
     }
     return out.size() - head <= bound;
+}
+
+// -------------------------------------------------------------- IRIS ------
+void iris_header_bytes(int W, int H, int C, std::vector<uint8_t>& out) {
+    out.assign(kIrisHeaderBytes, 0);  // name, colour map id 0 and the rest of the header stay 0
+    auto put_be16 = [&](size_t at, uint32_t v) { out[at] = (uint8_t)(v >> 8), out[at + 1] = (uint8_t)v; };
+    put_be16(0, 474);                // the magic number
+    out[2] = 1;                      // run-length coded
+    out[3] = 1;                      // a byte a channel
+    put_be16(4, C == 1 ? 2 : 3);     // dimension
+    put_be16(6, (uint32_t)W);
+    put_be16(8, (uint32_t)H);
+    put_be16(10, (uint32_t)C);
+    out[19] = 255;                   // pixmin 0 at 12, pixmax 255 at 16
+}
+
+bool encode_iris(const uint8_t* rgba, int W, int H, int C, std::vector<uint8_t>& out) {
+    const uint64_t bound = iris_body_max_bytes(W, H, C);
+    if (!rgba || bound == 0) return false;
+    iris_header_bytes(W, H, C, out);
+    const size_t n = (size_t)H * (size_t)C;
+    out.reserve(out.size() + (size_t)bound);
+    out.resize(out.size() + (size_t)iris_table_bytes((uint64_t)H, (uint64_t)C), 0);
+    auto put_be32 = [&](size_t at, uint64_t v) {
+        for (int k = 0; k < 4; ++k) out[at + (size_t)k] = (uint8_t)(v >> (8 * (3 - k)));
+    };
+    std::vector<uint8_t> plane((size_t)W);
+    for (int f = 0; f < H; ++f) {  // file row f: bottom row first
+        const uint8_t* src = rgba + (size_t)(H - 1 - f) * W * 4;
+        for (int z = 0; z < C; ++z) {
+            for (int x = 0; x < W; ++x) {
+                const uint8_t* p = src + 4 * (size_t)x;
+                plane[(size_t)x] = C == 1 ? (uint8_t)grey8(p[0], p[1], p[2]) : p[z];
+            }
+            const size_t start = out.size();
+            // a stretch of n bytes from byte `from`: packets of 127, then the remainder
+            auto put_stretch = [&](size_t from, size_t len, bool run) {
+                for (size_t at = 0; at < len; at += kIrisPacket) {
+                    const size_t count = std::min<size_t>(kIrisPacket, len - at);
+                    out.push_back((uint8_t)iris_packet_header(run, (uint32_t)count));
+                    const uint8_t* b = plane.data() + from + at;
+                    out.insert(out.end(), b, b + (run ? 1 : count));
+                }
+            };
+            size_t lit = 0;  // first byte of the open literal stretch
+            for (size_t x = 0; x < (size_t)W;) {
+                size_t e = x + 1;  // the maximal run [x, e)
+                while (e < (size_t)W && plane[e] == plane[x]) ++e;
+                if (e - x >= kIrisMinRun) {
+                    put_stretch(lit, x - lit, false);
+                    put_stretch(x, e - x, true);
+                    lit = e;
+                }
+                x = e;
+            }
+            put_stretch(lit, (size_t)W - lit, false);
+            out.push_back(0);  // the terminator
+            const size_t entry = (size_t)f + (size_t)z * (size_t)H;
+            put_be32(kIrisHeaderBytes + 4 * entry, start);
+            put_be32(kIrisHeaderBytes + 4 * (n + entry), out.size() - start);
+        }
+    }
+    return out.size() - kIrisHeaderBytes <= bound;
 }
 
 bool write_file(const std::string& path, const std::vector<uint8_t>& data) {

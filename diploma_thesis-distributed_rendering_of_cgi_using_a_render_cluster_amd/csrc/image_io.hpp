@@ -78,6 +78,16 @@ void tga_header_bytes(int W, int H, int C, bool rle, std::vector<uint8_t>& out);
 // bytes from ballots. false: C not 1 or 3, or a body bound of 2 GB and more.
 bool encode_hdr(const float* rgba, int W, int H, int C, std::vector<uint8_t>& out);
 void hdr_header_bytes(int W, int H, std::vector<uint8_t>& out);
+// A Silicon Graphics image file ("IRIS", .rgb) of the RGBA8 image, by the rules
+// of iris_rule.h, every number big-endian: the 512-byte header (magic 474,
+// run-length coded, a byte a channel, dimension 2 for C = 1 else 3, W, H, C,
+// pixmin 0, pixmax 255, no name, colour map id 0), the start and the length
+// table, and the row-planes in packets, rows bottom first, channels R, G, B(, A)
+// or the grey code of grey.h. The rule is stated as a plain walk over the runs:
+// iris.hip writes the same bytes from ballots. false: W or H above 65535, C not
+// 1, 3 or 4, or a body bound of 2 GB and more.
+bool encode_iris(const uint8_t* rgba, int W, int H, int C, std::vector<uint8_t>& out);
+void iris_header_bytes(int W, int H, int C, std::vector<uint8_t>& out);
 bool write_file(const std::string& path, const std::vector<uint8_t>& data);
 
 }  // namespace rr

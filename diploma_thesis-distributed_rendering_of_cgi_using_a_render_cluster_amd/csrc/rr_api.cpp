@@ -185,7 +185,7 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
     if (out_path && !format) return fail(RR_EINVAL, "format is required when out_path is given");
     if (format && !known_format(format))
         return fail(RR_ENOTSUP, std::string("unsupported output format '") + format +
-                                    "' (JPEG, PNG, OPEN_EXR, TARGA, TARGA_RAW and HDR are supported)");
+                                    "' (JPEG, PNG, OPEN_EXR, TARGA, TARGA_RAW, HDR and IRIS are supported)");
     const FrameOutput fo = resolve_output(c->settings, s->desc.render, format, out_path != nullptr, jpeg_quality);
     if (fo.coder == Coder::Jpeg && (jpeg_quality < 1 || jpeg_quality > 100))
         return fail(RR_EINVAL, "jpeg_quality must be 1..100");
@@ -214,6 +214,10 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         }
         if (fo.coder == Coder::Hdr) {
             const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.hdr.plan);
+            if (rc != RR_OK) return rc;
+        }
+        if (fo.coder == Coder::Iris) {
+            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.iris.plan);
             if (rc != RR_OK) return rc;
         }
         if (fo.coder == Coder::Png16) {

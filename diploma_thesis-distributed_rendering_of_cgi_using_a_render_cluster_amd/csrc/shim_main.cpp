@@ -125,6 +125,7 @@ int main(int argc, char** argv) {
                             : fmt == "OPEN_EXR"                       ? ".exr"
                             : (fmt == "TARGA" || fmt == "TARGA_RAW") ? ".tga"
                             : fmt == "HDR"                            ? ".hdr"
+                            : fmt == "IRIS"                           ? ".rgb"
                                                                       : "";
     if (ext.empty()) {
         std::fprintf(stderr, "rr-blender-shim: unsupported output format '%s'\n", fmt.c_str());

@@ -79,7 +79,7 @@ class FrameStats(ctypes.Structure):
 
 RR_FLAG_PROFILE_KERNELS, RR_FLAG_COUNT_TRAVERSAL, RR_FLAG_WAVEFRONT = 1, 2, 4
 KERNEL_CLASSES = ["build", "primary", "extend", "shadow", "accumulate", "shade", "tiles"]
-RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer or the HDR coder
+RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer, the HDR or the IRIS coder
 
 
 # Every symbol include/rr.h declares (checked by tests/test_abi.py).
@@ -614,9 +614,9 @@ class RenderContext:
     def encode_device(self, fmt: str, image: np.ndarray, depth: int = 0, color_mode=0, view_transform: int = 0,
                       exposure_scale: float = 1.0, quality: int = 90) -> bytes:
         """rr_debug_encode_device: the file bytes of an (H, W, 4) image coded on the
-        device as `fmt` ("JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW", "HDR") at
-        `depth` in `color_mode`. uint8 images for JPEG, 8-bit PNG and TARGA, float32
-        means for the others; "HDR" at depth 0 or 32 and no other."""
+        device as `fmt` ("JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW", "HDR",
+        "IRIS") at `depth` in `color_mode`. uint8 images for JPEG, 8-bit PNG, TARGA
+        and IRIS, float32 means for the others; "HDR" at depth 0 or 32 and no other."""
         if fmt == "HDR" and (image.dtype == np.uint8 or int(depth) not in (0, 32)):
             raise RRError(RR_EINVAL, "HDR takes a float image at depth 0 or 32")
         is_float = image.dtype != np.uint8

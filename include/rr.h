@@ -93,7 +93,7 @@ typedef struct rr_render_params {
 #define RR_K_ACCUM 4     /* film accumulate + tonemap */
 #define RR_K_SHADE 5     /* split path (large scenes): shading kernels; PRIMARY/EXTEND then time traversal only */
 #define RR_K_TILES 6     /* LDS-resident scenes: k_tiles, every sample of an 8x8 pixel tile run to completion + film + tonemap */
-#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer or the HDR coder: all its kernels, one event pair per frame */
+#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer, the HDR or the IRIS coder: all its kernels, one event pair per frame */
 #define RR_K_CLASSES 8
 
 /* The five timestamps the reference recovers from Blender's stdout
@@ -200,9 +200,9 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *  - frame_index: the frame to evaluate (Blender frame number, scene.frame_set).
  *  - out_path: output path WITHOUT extension, '#' runs already substituted
  *    (render-timing-script.py:69-78,82); the library appends ".jpg" / ".png"
- *    / ".exr" / ".tga" / ".hdr" as Blender's write_still does with
+ *    / ".exr" / ".tga" / ".hdr" / ".rgb" as Blender's write_still does with
  *    R_EXTENSION. NULL: render only.
- *  - format: "JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW" or "HDR" (job output_file_format,
+ *  - format: "JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW", "HDR" or "IRIS" (job output_file_format,
  *    shared/src/jobs/mod.rs:80, handed to image_settings.file_format,
  *    render-timing-script.py:83-92). "OPEN_EXR": the film's mean linear
  *    radiance before any view transform (alpha = 1) as A, B, G, R channels,
@@ -235,6 +235,23 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *    project's own (csrc/hdr_rule.h) and unpinned against Blender's files: any
  *    reader returns the same quads from either packing. Coded on the GPU
  *    (hdr.hip). RR_EINVAL for a body bound of 2 GB and more.
+ *    "IRIS": a Silicon Graphics image file (.rgb) of the 8-bit image that
+ *    "TARGA" takes (view settings and dither applied; always 8 bits a channel:
+ *    the depth settings and the PNG compression do not apply), every number
+ *    big-endian: a 512-byte header (magic 474, run-length coded, a byte a
+ *    channel, dimension 2 for one channel else 3, W, H, C, pixmin 0, pixmax
+ *    255, the rest 0), a start and a length table of H C uint32 entries each
+ *    (entry y + z H: file row y of channel z, its offset in the file and its
+ *    coded bytes), then the coded row-planes, file row 0 (the image's bottom
+ *    row) first and within a row channel 0 .. C - 1. Channels R, G, B, A with
+ *    alpha 255 (rr_set_color_mode RGB: R, G, B; BW: the grey code). A run
+ *    packet is the byte n and a value, a literal packet 0x80 | n and n bytes,
+ *    n at most 127, runs from 3 equal bytes; a 0 byte ends every row-plane.
+ *    Packets and the order of the row-planes are the project's own choice
+ *    (csrc/iris_rule.h), unpinned against Blender's files: any reader goes
+ *    through the tables and returns the same pixels. Coded on the GPU
+ *    (iris.hip). RR_EINVAL for a width or height above 65535 or a body bound
+ *    (tables and row-planes at their longest) of 2 GB and more.
  *  - jpeg_quality: 1..100 (the reference script forces 90, :84); ignored for
  *    every other format.
  *  - timing / stats: optional outputs (may be NULL). */
@@ -283,9 +300,9 @@ int rr_scene_resolution(rr_scene* scene, const rr_render_params* params,
 
 /* Encode an RGBA8 image (rows top to bottom) to `path` + extension.
  * Host encoder used by rr_render_frame; exported for tests. "JPEG", "PNG",
- * "TARGA" and "TARGA_RAW" (four channels, as "PNG"; RR_EINVAL for a width or
- * height above 65535 or a body of 2 GB and more): "OPEN_EXR" and "HDR" need the
- * float film and are RR_ENOTSUP here. */
+ * "TARGA", "TARGA_RAW" and "IRIS" (four channels, as "PNG"; RR_EINVAL for a width
+ * or height above 65535 or a body of 2 GB and more): "OPEN_EXR" and "HDR" need
+ * the float film and are RR_ENOTSUP here. */
 int rr_encode_image(const uint8_t* rgba8, int32_t width, int32_t height,
                     const char* out_path_no_ext, const char* format,
                     int32_t jpeg_quality, uint64_t* bytes_written);
@@ -408,10 +425,10 @@ int rr_encode_image_mode(const uint8_t* rgba8, int32_t width, int32_t height,
 
 /* Encode an image of the caller's with the device coder of a format, depth and
  * colour mode, through the enqueue, wrap and file code rendered frames take.
- * format "JPEG" (depth 8), "PNG" at depth 8 and "TARGA" / "TARGA_RAW" (depth 8
+ * format "JPEG" (depth 8), "PNG" at depth 8 and "TARGA" / "TARGA_RAW" / "IRIS" (depth 8
  * and no other) take an RGBA8 image (image_is_float 0); "PNG" at depth 16, "OPEN_EXR" at depth 16 (HALF) or 32
  * (FLOAT) and "HDR" (depth 32 and no other) take width * height * 4 floats
- * (image_is_float 1) as means, spp = 1, alpha 1. depth 0: 8 for PNG and TARGA,
+ * (image_is_float 1) as means, spp = 1, alpha 1. depth 0: 8 for PNG, TARGA and IRIS,
  * 16 for OPEN_EXR, 32 for HDR. view_transform and
  * exposure_scale: 16-bit PNG only, as for rr_debug_png16_device; jpeg_quality:
  * JPEG only. A size outside the coder's range is RR_EINVAL before anything is
