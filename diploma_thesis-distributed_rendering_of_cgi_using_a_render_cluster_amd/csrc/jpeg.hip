@@ -273,13 +273,15 @@ __global__ __launch_bounds__(kJpegThreads) void k_jpeg_emit(const int16_t* __res
     const int z = blk[c_zigzag[t]];
     const uint64_t nz = __ballot(z != 0 && t > 0);
     const bool luma = (b % B) < 4;
+    // The DC difference and its table entry are formed by every lane (the same
+    // addresses across the wave) ahead of the lanes' own symbols; lane 0 codes it.
+    const int p = dc_pred_block<B>(b);
+    const int diff = blk[0] - (p >= 0 ? coeffs[(size_t)(gb - b + p) * 64] : 0);
+    const int n = cat_bits(diff);
+    const uint32_t e = huff[(luma ? 0 : 512) + n];
     uint64_t str = 0ull;
     int len;
     if (t == 0) {  // DC difference
-        const int p = dc_pred_block<B>(b);
-        const int diff = z - (p >= 0 ? coeffs[(size_t)(gb - b + p) * 64] : 0);
-        const int n = cat_bits(diff);
-        const uint32_t e = huff[(luma ? 0 : 512) + n];
         const int cl = (int)(e >> 16);
         str = ((uint64_t)(e & 0xFFFFu) << (64 - cl)) | (n ? (uint64_t)mag_bits(diff, n) << (64 - cl - n) : 0ull);
         len = cl + n;
