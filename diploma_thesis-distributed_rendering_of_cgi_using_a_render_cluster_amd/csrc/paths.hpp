@@ -234,6 +234,18 @@ struct EmitCont {
     RR_D void operator()(float3, float3, float3, uint32_t, bool, float3&) const {}
 };
 
+// Lights behind the hit's surface: shade_covered(), the
+// shading of k_tiles' tiles that one triangle covers, asks light_behind
+// (rr_device.h) before it draws a point on a point / disk light, and where
+// that holds skips the draw and the cosN test it could only fail: nothing
+// added, out.shadow false, as without the rule. shade() does not ask: with
+// the rule in its LdsView instantiation as well (k_tiles' general body and
+// tiles_continue) the whole-tile kernel ran slower than without any rule
+// (measured, code removed: profiles/light_facing.md).
+#ifndef RR_LIGHT_FACING
+#define RR_LIGHT_FACING 1  // 0: the rule compiled out (tiles.hip as before it: the reference of tests and A/B runs)
+#endif
+
 // FC: FrameConsts or ShadeConsts (the fields shade() reads: world,
 // clamp_indirect, the bounce caps, n_lights).
 template <typename View, typename Shadow = EmitShadow, typename FC = FrameConsts, typename Cont = EmitCont>
@@ -485,53 +497,59 @@ __device__ __forceinline__ void shade_covered(const FC& fc, int bounce, const Ld
         };
         float3 wi, Li;
         float dist;
+        bool away = false;  // the light lies behind the side seen: nothing to draw
         if (lt(0) == 0.0f) {  // point / disk light
             const float3 lp = mk3(lt(1), lt(2), lt(3));
             const float radius = lt(7);
-            const float3 I = mk3(lt(8), lt(9), lt(10));
-            const float3 tl = sub3(lp, P);
-            const float dl2 = dot3(tl, tl);
-            if (radius > 0.0f) {
-                float sl, rl;
-                sqrt_rcp_any(dl2, sl, rl);
-                const float3 wl = scl3(tl, rl);
-                float3 b1, b2;
-                make_onb(wl, b1, b2);
-                float dx, dy;
-                float u1, u2;
-                rng2(key, dim0 + 1u, u1, u2);
-                concentric_disk(u1, u2, dx, dy);
-                dx = dx * radius;
-                dy = dy * radius;
-                const float3 sp = madd3(madd3(lp, b1, dx), b2, dy);
-                const float3 ts = sub3(sp, P);
-                const float ds2 = dot3(ts, ts);
-                float id;
-                sqrt_rcp_any(ds2, dist, id);
-                wi = scl3(ts, id);
-                const float cl = fabsf(dot3(wl, wi));
-                Li = scl3(I, cl * id * id);
-            } else {
-                float id;
-                sqrt_rcp_any(dl2, dist, id);
-                wi = scl3(tl, id);
-                Li = scl3(I, 1.0f / dl2);
+            if constexpr (RR_LIGHT_FACING != 0) away = light_behind(N, P, lp, radius);
+            if (!away) {
+                const float3 I = mk3(lt(8), lt(9), lt(10));
+                const float3 tl = sub3(lp, P);
+                const float dl2 = dot3(tl, tl);
+                if (radius > 0.0f) {
+                    float sl, rl;
+                    sqrt_rcp_any(dl2, sl, rl);
+                    const float3 wl = scl3(tl, rl);
+                    float3 b1, b2;
+                    make_onb(wl, b1, b2);
+                    float dx, dy;
+                    float u1, u2;
+                    rng2(key, dim0 + 1u, u1, u2);
+                    concentric_disk(u1, u2, dx, dy);
+                    dx = dx * radius;
+                    dy = dy * radius;
+                    const float3 sp = madd3(madd3(lp, b1, dx), b2, dy);
+                    const float3 ts = sub3(sp, P);
+                    const float ds2 = dot3(ts, ts);
+                    float id;
+                    sqrt_rcp_any(ds2, dist, id);
+                    wi = scl3(ts, id);
+                    const float cl = fabsf(dot3(wl, wi));
+                    Li = scl3(I, cl * id * id);
+                } else {
+                    float id;
+                    sqrt_rcp_any(dl2, dist, id);
+                    wi = scl3(tl, id);
+                    Li = scl3(I, 1.0f / dl2);
+                }
             }
         } else {  // sun: delta direction, irradiance
             wi = mk3(-lt(4), -lt(5), -lt(6));
             dist = kFltMax;
             Li = mk3(lt(8), lt(9), lt(10));
         }
-        const float cosN = dot3(N, wi);
-        if (cosN > 0.0f) {
-            float pdf;
-            const float3 f = bsdf_eval_v(m, lut, vw, N, wo, wi, pdf);  // f * cosN
-            const float k = (float)fc.n_lights;
-            float3 c = mk3(T.x * f.x * k * Li.x, T.y * f.y * k * Li.y, T.z * f.z * k * Li.z);
-            if (bounce > 0) c = clamp_contrib(c, fc.clamp_indirect);
-            if (max3f(c) > 0.0f) {
-                out.shadow = true;
-                if (esc || !trace_shadow(Po, wi, dist)) add_to(L, c);
+        if (!away) {  // else every cosN the branch could compute is <= 0 (light_behind)
+            const float cosN = dot3(N, wi);
+            if (cosN > 0.0f) {
+                float pdf;
+                const float3 f = bsdf_eval_v(m, lut, vw, N, wo, wi, pdf);  // f * cosN
+                const float k = (float)fc.n_lights;
+                float3 c = mk3(T.x * f.x * k * Li.x, T.y * f.y * k * Li.y, T.z * f.z * k * Li.z);
+                if (bounce > 0) c = clamp_contrib(c, fc.clamp_indirect);
+                if (max3f(c) > 0.0f) {
+                    out.shadow = true;
+                    if (esc || !trace_shadow(Po, wi, dist)) add_to(L, c);
+                }
             }
         }
     }

@@ -355,6 +355,55 @@ RR_HD float3 offset_ray(float3 p, float3 n) {
     return mk3(offset_axis(p.x, n.x), offset_axis(p.y, n.y), offset_axis(p.z, n.z));
 }
 
+// Whether a point / disk light (position lp, `radius`) lies wholly behind the
+// shading point P's surface (N: the unit shading normal after the flip), so
+// far that no direction wi the light branch of shade() can form has a computed
+// cosN = dot3(N, wi) above 0: the branch's `cosN > 0.0f` would discard its
+// draw, and a caller may skip the draw (the RNG is counter-based: a draw not
+// taken shifts no other). True only then; false says nothing. The branch
+// draws on a disk only where `radius > 0.0f`; every other value (zero,
+// negative, NaN: the scene loader passes the file's number on) is its plain
+// point light, and so it is here: below, `radius` stands for max(radius, 0).
+// The rule, with m = |lp|_1 + |P|_1 and k = kLightMargin:
+//     dot3(N, lp - P) <= -(radius (1 + kLightSlack + k) + k m)
+// i.e. the centre's height over the plane is below -(radius (1 + slack) +
+// margin) with the margin k (m + radius) relative to the coordinates.
+//
+// Bound (u = 2^-24, finite inputs, |N|_2 <= 1 + 2^-20). The branch forms
+// sp = fl(fl(lp + b1 dx) + b2 dy), ts = fl(sp - P), wi = fl(ts id), id > 0, and
+// cosN = dot3(N, wi). Write sp = lp + delta + eta with delta = b1 dx + b2 dy
+// (the computed b1, b2, dx, dy, combined exactly) and eta the two fmaf
+// roundings, |eta_k| <= 2.1 u (|lp_k| + 1.01 radius).
+//   * slack: |delta| <= radius (1 + 2^-16). (dx, dy) = fl(radius x disk point)
+//     with |disk point| <= 1 + 2^-20 (sincos_small: sin^2 + cos^2 = 1 to a few
+//     u); b1, b2 are make_onb of wl = fl(tl rl), |wl| = 1 to a few u, so
+//     |b1|, |b2| <= 1 + 2^-18 and |b1 . b2| <= 2^-18. kLightSlack = 2^-10 is
+//     2^6 times that.
+//   * margin: with H = N . (lp - P) exact, the computed left side differs from
+//     H by at most 4.2 u m (the subtraction, three accumulations), the computed
+//     right side from its exact value by a factor within 1 -+ 7 u, and
+//     N . (sp - P) <= H + |N| |delta| + 2.1 u (m + 3.1 radius). The roundings of
+//     ts and wi and the accumulations of dot3(N, wi) move id^-1 cosN by at most
+//     5 u (m + 3.1 radius) more. All of it is below 12 u (m + 3.1 radius) <
+//     2^-18.7 (m + radius): kLightMargin = 2^-10 is 2^8 times the worst case and
+//     more than 2^10 times the usual rounding.
+// So when the rule holds, N . (sp - P) <= -0.98 k (m + radius) for every sp,
+// and since |sp - P| <= m + 1.01 radius the exact dot(N, wi) <= -k / 2 = -2^-11
+// (kLightBehindCos), against an error of dot3 below 2^-21: cosN < 0. Radius 0:
+// sp = lp, wi = fl(tl id), the same bound without delta and eta. NaNs compare
+// false. tests/test_light_facing_bound.py restates the rule and the branch in
+// float32 and checks -k / 4 over 2^20 configurations. About 14 VALU, three of
+// them the subtraction the branch makes anyway.
+constexpr float kLightSlack = 0x1p-10f;
+constexpr float kLightMargin = 0x1p-10f;
+constexpr float kLightBehindCos = -0.5f * kLightMargin;
+RR_HD bool light_behind(float3 N, float3 P, float3 lp, float radius) {
+    const float r = fmaxf(radius, 0.0f);  // the branch's `radius > 0.0f`: any other value, a NaN too, is the point light
+    const float h = dot3(N, sub3(lp, P));
+    const float m = (fabsf(lp.x) + fabsf(lp.y) + fabsf(lp.z)) + (fabsf(P.x) + fabsf(P.y) + fabsf(P.z));
+    return h <= -fmaf(kLightMargin, m, r * (1.0f + kLightSlack + kLightMargin));
+}
+
 // Piecewise-linear table read, u in [0,1] (t: global or LDS pointer).
 template <typename FloatP>
 RR_HD float table_lerp(FloatP t, int n, float u) {
