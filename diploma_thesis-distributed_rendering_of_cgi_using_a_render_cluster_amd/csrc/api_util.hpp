@@ -12,6 +12,7 @@
 namespace rr {
 
 inline thread_local std::string g_err;  // rr_last_error
+inline thread_local std::string g_warn;  // rr_last_warning(NULL): the thread's last host encode (rr_encode_image)
 
 inline int fail(int code, const std::string& msg) {
     g_err = msg;

@@ -1,5 +1,5 @@
 // The coders of a frame's file: the dispatch to the device coders (jpeg.hip,
-// png.hip, png16.hip, exr.hip, tga.hip, hdr.hip, iris.hip), the host-built files around their streams, and
+// png.hip, png16.hip, exr.hip, tga.hip, hdr.hip, iris.hip, webp.hip), the host-built files around their streams, and
 // the host coders of an RGBA8 image. See frame.hpp.
 #include <cerrno>
 #include <cstring>
@@ -64,7 +64,44 @@ int plan_or_refuse(const FrameOutput& fo, int W, int H, IrisPlan& p) {
     return fail(RR_EINVAL, kIrisRange);
 }
 
+static const char* const kWebpRange =
+    "image size outside the WEBP format's range (16384 x 16384, a payload bound below 2 GB)";
+
+int plan_or_refuse(const FrameOutput& fo, int W, int H, WebpPlan& p) {
+    if (webp_plan(W, H, fo.color_mode, p)) return RR_OK;
+    return fail(RR_EINVAL, kWebpRange);
+}
+
+std::string webp_quality_warning(int quality) {
+    if (quality >= 100) return "";
+    return "WEBP at quality " + std::to_string(quality) +
+           ": lossy WEBP is not built, the file is lossless (as at quality 100)";
+}
+
 namespace {
+
+// Device WEBP encode of an RGBA8 image into o's pinned stream, by o.plan.
+void enqueue_webp(const CoderInput& in, DevFrame& f, hipStream_t st, WebpOut& o) {
+    const WebpPlan& p = o.plan;
+    if (p.W != in.W || p.H != in.H) throw std::runtime_error("WEBP plan of another image");
+    f.webp_scratch.ensure(webp_scratch_words(p));
+    o.stream.ensure(webp_stream_bytes(p));
+    void* dev_host = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
+    f.prof.begin(st, RR_K_PNG);
+    webp_encode_device(in.rgba8, p, f.webp_scratch.ptr, static_cast<uint8_t*>(dev_host), st);
+    f.prof.end(st);
+}
+
+// The file of a device-coded WEBP image: the host-built RIFF and chunk headers
+// around the device's payload (at least the 5 bytes of signature and sizes).
+void webp_file_bytes(const WebpOut& o, std::vector<uint8_t>& data) {
+    const WebpPlan& p = o.plan;
+    uint64_t len = 0;
+    std::memcpy(&len, o.stream.ptr, sizeof len);
+    if (len > p.body_cap || len + 16 > o.stream.cap || len < 5) throw std::runtime_error("device WEBP stream overflow");
+    webp_wrap_stream(o.stream.ptr + 16, (size_t)len, data);
+}
 
 // Device IRIS encode of an RGBA8 image into o's pinned stream, by o.plan.
 void enqueue_iris(const CoderInput& in, DevFrame& f, hipStream_t st, IrisOut& o) {
@@ -215,6 +252,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
     if (k == Coder::Tga) return enqueue_tga(in, f, st, o.tga);
     if (k == Coder::Hdr) return enqueue_hdr(in, f, st, o.hdr);
     if (k == Coder::Iris) return enqueue_iris(in, f, st, o.iris);
+    if (k == Coder::Webp) return enqueue_webp(in, f, st, o.webp);
     if (!device_deflate(k)) throw std::runtime_error("no device coder for this output");
     // the front ends' own buffers. "PNG" at compression 0 .. 100: a filter type
     // per row of the H rows, and at 16 bits the raw scanlines, 2C W H bytes
@@ -268,6 +306,7 @@ void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint
     else if (fo.coder == Coder::Tga) tga_file_bytes(o.tga, data);
     else if (fo.coder == Coder::Hdr) hdr_file_bytes(o.hdr, data);
     else if (fo.coder == Coder::Iris) iris_file_bytes(o.iris, data);
+    else if (fo.coder == Coder::Webp) webp_file_bytes(o.webp, data);
     else deflate_file_bytes(o.deflate, fo.coder, fo.color_mode, data);
 }
 
@@ -295,14 +334,17 @@ int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const cha
     } else if (fmt == "IRIS") {
         if (!encode_iris(rgba, W, H, resolve_color_mode(mode, false), data)) return fail(RR_EINVAL, kIrisRange);
         ext = ".rgb";
+    } else if (fmt == "WEBP") {  // lossless at every quality: the caller flags one below 100
+        if (!encode_webp(rgba, W, H, resolve_color_mode(mode, false), data)) return fail(RR_EINVAL, kWebpRange);
+        ext = ".webp";
     } else if (fmt == "OPEN_EXR" || fmt == "HDR") {
         return fail(RR_ENOTSUP, "unsupported output format '" + fmt +
-                                    "' for an RGBA8 image: it needs the float film (JPEG, PNG, TARGA, TARGA_RAW and "
-                                    "IRIS are supported here)");
+                                    "' for an RGBA8 image: it needs the float film (JPEG, PNG, TARGA, TARGA_RAW, "
+                                    "IRIS and WEBP are supported here)");
     } else {
         return fail(RR_ENOTSUP, "unsupported output format '" + fmt +
-                                    "' (JPEG, PNG, TARGA, TARGA_RAW and IRIS are supported here; OPEN_EXR and HDR "
-                                    "need the float film)");
+                                    "' (JPEG, PNG, TARGA, TARGA_RAW, IRIS and WEBP are supported here; OPEN_EXR and "
+                                    "HDR need the float film)");
     }
     const std::string path = std::string(out_path) + ext;
     if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));

@@ -218,6 +218,8 @@ struct DevFrame {
     DevBuf<uint32_t> hdr_scratch;
     // IRIS frames (iris.hip): the dense body (tables and coded row-planes) and the per-byte records; grow-only
     DevBuf<uint32_t> iris_scratch;
+    // WEBP frames (webp.hip): the payload, the residuals and per-pixel records, counts, codes and row offsets; grow-only
+    DevBuf<uint32_t> webp_scratch;
     // written by render_frame_device, about the frame it enqueued
     int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log (trav_counts)

@@ -280,7 +280,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     DevFrame& f = sl.dev;
     DevBuild& build = sl.tiles ? sl.build : s->build;
     FrameSlot* prev = c->last_enqueued;
-    // (the deflate coder, the TARGA packer, the HDR and the IRIS coder read their
+    // (the deflate coder, the TARGA packer, the HDR, the IRIS and the WEBP coder read their
     // slot's rgba8 / film and write slot buffers only, so the next frame waits
     // for the image, ev[5], not for the coder)
     if (prev && prev != &sl && !(sl.tiles && prev->tiles))
@@ -333,7 +333,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
             RR_HIP(hipEventRecord(sl.ev[5], st));
             // Png16: the film again, through exposure and view transform, at 16
             // bits; OPEN_EXR and HDR: the film's means, the product finish_frame
-            // forms, no view transform; TARGA and IRIS read rgba8 and none of these
+            // forms, no view transform; TARGA, IRIS and WEBP read rgba8 and none of these
             in.inv_spp = k.inv_spp;
             in.exposure_scale = k.exposure_scale;
             in.view_transform = fs.view_transform;

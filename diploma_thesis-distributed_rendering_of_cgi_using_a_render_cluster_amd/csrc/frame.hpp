@@ -21,6 +21,7 @@
 #include "settings.hpp"
 #include "tga.hpp"
 #include "view.hpp"
+#include "webp.hpp"
 
 namespace rr {
 
@@ -85,12 +86,20 @@ struct IrisOut {
 
 // Where the device coders write: a frame slot has one, and the context one
 // more for the inspection entry points.
+// The same for a device-coded WEBP payload (webp.hpp): the VP8L bit stream; the
+// host puts the RIFF and chunk headers in front and the pad byte behind.
+struct WebpOut {
+    PinnedBuf stream;
+    rr::WebpPlan plan{};
+};
+
 struct CodedOut {
     JpegOut jpeg;
     DeflateOut deflate;
     TgaOut tga;
     HdrOut hdr;
     IrisOut iris;
+    WebpOut webp;
 };
 
 struct FrameRun {
@@ -113,7 +122,7 @@ struct FrameSlot {
     uint64_t ticket = 0;
     // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
     // work done, 3 outputs on the host (after their copies), 5 (device PNG,
-    // EXR, TARGA, HDR and IRIS frames) before the slot's coder: the state shared between frames is free
+    // EXR, TARGA, HDR, IRIS and WEBP frames) before the slot's coder: the state shared between frames is free
     hipEvent_t ev[6] = {};
     // The slot's frames run on its own stream and write only its own device
     // state, so a k_tiles frame runs on the GPU beside the other slots'
@@ -131,6 +140,7 @@ struct FrameSlot {
     PinnedBuf host_rgba, host_counters, host_upload;
     CodedOut coded;  // the device-coded file's stream; a deflate frame's plan is made when the frame is submitted
     rr::FrameSetup fs;
+    std::string quality_warning;    // a WEBP frame below quality 100: lossless all the same
     bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
     std::string view_warning;
     double submit_at = 0.0;         // UNIX time when the device work was enqueued
@@ -269,7 +279,7 @@ void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int
 
 // ---- the device coders (coders.cpp) ----------------------------------------
 
-// The image a coder reads. rgba8: Jpeg, Png8, Tga and Iris; film: Png16, Exr, Exr32 and Hdr,
+// The image a coder reads. rgba8: Jpeg, Png8, Tga, Iris and Webp; film: Png16, Exr, Exr32 and Hdr,
 // W x H float4 sums scaled by inv_spp. exposure_scale, view_transform, look
 // and gamma (resolved: resolve_view, or an inspection call's own check): Png16,
 // which takes the film through exposure and view transform again at 16 bits.
@@ -300,6 +310,12 @@ int plan_or_refuse(const FrameOutput& fo, int W, int H, HdrPlan& p);
 // The same for an IRIS image (Coder::Iris): W or H above 65535 and a body
 // bound of 2 GB and more are refused.
 int plan_or_refuse(const FrameOutput& fo, int W, int H, IrisPlan& p);
+// The same for a WEBP image (Coder::Webp): W or H above 16384 and a payload
+// bound of 2 GB and more are refused.
+int plan_or_refuse(const FrameOutput& fo, int W, int H, WebpPlan& p);
+// What a WEBP file of this quality is flagged with (rr_last_warning): "" at 100
+// and above, else that the file is lossless, as lossy WEBP is not built.
+std::string webp_quality_warning(int quality);
 
 // The 16-bit path's sRGB table on the device. Written once, before the first
 // kernel that reads it is enqueued, and never again.
@@ -308,19 +324,19 @@ void ensure_srgb16(rr_ctx* c);
 // with every stream idle when the quality changes.
 void ensure_jpeg_table(rr_ctx* c, int quality);
 
-// Enqueue the device coder that `fo` names (Jpeg ... Iris) on stream st, with
+// Enqueue the device coder that `fo` names (Jpeg ... Webp) on stream st, with
 // f's scratch and profiler, into o's pinned buffers. fo.color_mode: the file's
 // channels; fo.png_compression ("PNG"): LEGACY the Sub front end, 0 .. 100 the
 // adaptive one (the device coders have one effort level). A deflate format
 // codes by o.deflate.plan, a TARGA one by o.tga.plan, an HDR one by o.hdr.plan,
-// an IRIS one by o.iris.plan (plan_or_refuse).
+// an IRIS one by o.iris.plan, a WEBP one by o.webp.plan (plan_or_refuse).
 void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o);
 
 // The file of a device-coded image, once its stream is on the host: the
 // host-built header or container around it.
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data);
 
-// The host coders: an RGBA8 image as a "JPEG", "PNG", "TARGA", "TARGA_RAW" or "IRIS"
+// The host coders: an RGBA8 image as a "JPEG", "PNG", "TARGA", "TARGA_RAW", "IRIS" or "WEBP"
 // file at out_path + its extension ("OPEN_EXR" and "HDR" need the float film: RR_ENOTSUP). mode: a colour mode as rr_set_color_mode takes it, 0 the format's
 // own layout. compression ("PNG"): LEGACY, or 0 .. 100 (rr_set_png_compression).
 int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,

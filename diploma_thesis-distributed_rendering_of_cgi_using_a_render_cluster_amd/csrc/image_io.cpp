@@ -13,6 +13,7 @@
 #include "iris_rule.h"
 #include "png_filter.h"
 #include "tga_rule.h"
+#include "webp_rule.h"
 
 #include <zlib.h>
 
@@ -862,6 +863,243 @@ bool encode_iris(const uint8_t* rgba, int W, int H, int C, std::vector<uint8_t>&
         }
     }
     return out.size() - kIrisHeaderBytes <= bound;
+}
+
+// -------------------------------------------------------------- WEBP ------
+namespace {
+
+// An LSB-first bit stream appended to a byte vector.
+struct WebpBits {
+    std::vector<uint8_t>& out;
+    uint64_t acc = 0;
+    int n = 0;
+    void put(uint32_t v, int nb) {  // the low nb <= 32 bits of v
+        acc |= (uint64_t)v << n;
+        n += nb;
+        for (; n >= 8; n -= 8, acc >>= 8) out.push_back((uint8_t)acc);
+    }
+    void flush() {
+        if (n > 0) out.push_back((uint8_t)acc);
+        acc = 0, n = 0;
+    }
+    // A simple code of k = 1 or 2 symbols, s0 < s1 < 256.
+    void simple(int k, uint32_t s0, uint32_t s1) {
+        put(1u, 1);
+        put((uint32_t)(k - 1), 1);
+        put(s0 > 1u ? 1u : 0u, 1);
+        put(s0, s0 > 1u ? 8 : 1);
+        if (k == 2) put(s1, 8);
+    }
+};
+
+// Code lengths (<= maxbits) of an alphabet with at least two nonzero counts:
+// deflate.hip's build_lengths, step for step. Symbols ranked by (count, index),
+// the tree by the two-queue merge, depths capped, the Kraft sum repaired by
+// moving leaves down, lengths handed out by rank.
+void webp_lengths(const uint32_t* freq, int n, int maxbits, uint8_t* lens) {
+    std::vector<int> order;
+    for (int s = 0; s < n; ++s) {
+        lens[s] = 0;
+        if (freq[s]) order.push_back(s);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return freq[a] < freq[b]; });
+    const int nu = (int)order.size();
+    std::vector<uint32_t> iw((size_t)nu);
+    std::vector<int> lpar((size_t)nu), ipar((size_t)nu), idepth((size_t)nu);
+    int li = 0, ii = 0, ni = 0;
+    for (int k = 0; k + 1 < nu; ++k) {
+        uint32_t w = 0;
+        for (int pick = 0; pick < 2; ++pick) {
+            if (li < nu && (ii >= ni || freq[order[(size_t)li]] <= iw[(size_t)ii])) {
+                w += freq[order[(size_t)li]];
+                lpar[(size_t)li++] = ni;
+            } else {
+                w += iw[(size_t)ii];
+                ipar[(size_t)ii++] = ni;
+            }
+        }
+        iw[(size_t)ni++] = w;
+    }
+    int count[33] = {};
+    if (ni > 0) idepth[(size_t)ni - 1] = 0;
+    for (int k = ni - 2; k >= 0; --k) idepth[(size_t)k] = idepth[(size_t)ipar[(size_t)k]] + 1;
+    for (int i = 0; i < nu; ++i) count[std::min(idepth[(size_t)lpar[(size_t)i]] + 1, maxbits)] += 1;
+    uint32_t total = 0;
+    for (int i = maxbits; i >= 1; --i) total += (uint32_t)count[i] << (maxbits - i);
+    while (total > (1u << maxbits)) {
+        count[maxbits] -= 1;
+        for (int i = maxbits - 1; i >= 1; --i)
+            if (count[i]) {
+                count[i] -= 1;
+                count[i + 1] += 2;
+                break;
+            }
+        total -= 1;
+    }
+    int j = nu;
+    for (int i = 1; i <= maxbits; ++i)
+        for (int l = count[i]; l > 0; --l) lens[order[(size_t)--j]] = (uint8_t)i;
+}
+
+// Canonical codes of lens[0 .. n), bit-reversed for the LSB-first stream:
+// code | length << 16, as deflate.hip's assign_codes.
+void webp_assign_codes(const uint8_t* lens, int n, uint32_t* codes) {
+    uint32_t next[17];
+    int count[17] = {};
+    for (int s = 0; s < n; ++s) count[lens[s]] += 1;
+    count[0] = 0;
+    uint32_t code = 0;
+    next[0] = 0;
+    for (int i = 1; i <= 16; ++i) {
+        code = (code + (uint32_t)count[i - 1]) << 1;
+        next[i] = code;
+    }
+    for (int s = 0; s < n; ++s) {
+        const int l = lens[s];
+        uint32_t c = l ? next[l]++ : 0u, r = 0;
+        for (int k = 0; k < l; ++k) r |= ((c >> k) & 1u) << (l - 1 - k);
+        codes[s] = l ? (r | (uint32_t)l << 16) : 0u;
+    }
+}
+
+// One alphabet's code into the header and the table (code | length << 16).
+void webp_write_code(WebpBits& b, const uint32_t* freq, int n, uint32_t* codes) {
+    uint32_t nu = 0, lo = 0, hi = 0;
+    for (int s = 0; s < n; ++s)
+        if (freq[s]) {
+            if (!nu++) lo = (uint32_t)s;
+            hi = (uint32_t)s;
+        }
+    for (int s = 0; s < n; ++s) codes[s] = 0u;
+    if (nu == 0u || (nu <= 2u && hi < 256u)) {
+        b.simple(nu == 2u ? 2 : 1, lo, hi);
+        if (nu == 2u) codes[lo] = 0u | 1u << 16, codes[hi] = 1u | 1u << 16;
+        return;
+    }
+    std::vector<uint8_t> lens((size_t)n);
+    webp_lengths(freq, n, kWebpMaxBits, lens.data());
+    uint32_t clfreq[19] = {}, clcode[19] = {};
+    uint8_t cllen[19] = {};
+    for (int s = 0; s < n; ++s) clfreq[lens[(size_t)s]] += 1u;
+    int cu = 0;
+    for (int k = 0; k < 19; ++k)
+        if (clfreq[k]) ++cu, cllen[k] = 1;  // its only used symbol: length 1, and its uses take no bits
+    if (cu >= 2) {
+        webp_lengths(clfreq, 19, kWebpClMaxBits, cllen);
+        webp_assign_codes(cllen, 19, clcode);
+    }
+    webp_assign_codes(lens.data(), n, codes);
+    b.put(0u, 1);
+    b.put(19u - 4u, 4);
+    for (int k = 0; k < 19; ++k) b.put(cllen[webp_cl_order(k)], 3);
+    b.put(0u, 1);  // every symbol's length follows
+    for (int s = 0; s < n; ++s) {
+        const uint32_t c = clcode[lens[(size_t)s]];
+        b.put(c & 0xFFFFu, (int)(c >> 16));
+    }
+}
+
+}  // namespace
+
+void webp_wrap_stream(const uint8_t* payload, size_t len, std::vector<uint8_t>& out) {
+    const size_t pad = len & 1u;
+    out.clear();
+    out.reserve(kWebpRiffBytes + len + pad);
+    auto put_le32 = [&](uint64_t v) {
+        for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(v >> (8 * k)));
+    };
+    out.insert(out.end(), {'R', 'I', 'F', 'F'});
+    put_le32(4 + 8 + len + pad);
+    out.insert(out.end(), {'W', 'E', 'B', 'P', 'V', 'P', '8', 'L'});
+    put_le32(len);
+    out.insert(out.end(), payload, payload + len);
+    if (pad) out.push_back(0);
+}
+
+bool encode_webp(const uint8_t* rgba, int W, int H, int C, std::vector<uint8_t>& out) {
+    const uint64_t bound = webp_body_max_bytes(W, H, C);
+    if (!rgba || bound == 0) return false;
+    const size_t n = (size_t)W * (size_t)H;
+    std::vector<uint32_t> resid(n);
+    auto pixel = [&](size_t i) {
+        uint32_t v;
+        std::memcpy(&v, rgba + 4 * i, 4);  // little-endian host: R in the low byte
+        return webp_pixel(v, C);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t pred = i % (size_t)W ? pixel(i - 1) : i ? pixel(i - (size_t)W) : kWebpFirstPrediction;
+        resid[i] = webp_sub(pixel(i), pred);
+    }
+    // the rule as a plain walk over the rows' stretches: lit(residual), copy(length)
+    auto walk = [&](auto&& lit, auto&& copy) {
+        for (int y = 0; y < H; ++y) {
+            const uint32_t* row = resid.data() + (size_t)y * (size_t)W;
+            for (int x = 0; x < W;) {
+                if (x == 0 || row[x] != row[x - 1]) {
+                    lit(row[x++]);
+                    continue;
+                }
+                int e = x + 1;  // the stretch [x, e)
+                while (e < W && row[e] == row[e - 1]) ++e;
+                while (x < e) {
+                    const uint32_t m = std::min<uint32_t>(kWebpMaxCopy, (uint32_t)(e - x));
+                    if (m >= kWebpMinRun) copy(m);
+                    else
+                        for (uint32_t k = 0; k < m; ++k) lit(row[x + (int)k]);
+                    x += (int)m;
+                }
+            }
+        }
+    };
+    std::vector<uint32_t> freq((size_t)kWebpSyms, 0u), codes((size_t)kWebpSyms, 0u);
+    walk(
+        [&](uint32_t v) {
+            freq[(size_t)kWebpGreen + ((v >> 8) & 255u)] += 1u;
+            freq[(size_t)kWebpRed + ((v >> 16) & 255u)] += 1u;
+            freq[(size_t)kWebpBlue + (v & 255u)] += 1u;
+            freq[(size_t)kWebpAlpha + (v >> 24)] += 1u;
+        },
+        [&](uint32_t len) {
+            uint32_t sym, nb, extra;
+            webp_prefix(len, sym, nb, extra);
+            freq[(size_t)kWebpGreen + 256 + sym] += 1u;
+            freq[(size_t)kWebpDist + kWebpDistSym] += 1u;
+        });
+    std::vector<uint8_t> body;
+    WebpBits b{body};
+    b.put(0x2Fu, 8);
+    b.put((uint32_t)(W - 1), 14);
+    b.put((uint32_t)(H - 1), 14);
+    b.put(C == 4 ? 1u : 0u, 1);  // alpha_is_used
+    b.put(0u, 3);                // version
+    b.put(1u, 1), b.put(2u, 2);  // a transform: subtract-green
+    b.put(1u, 1), b.put(0u, 2);  // a transform: predictor
+    b.put(kWebpBlockBits - 2u, 3);
+    b.put(0u, 1);                // its sub-image: no colour cache
+    b.simple(1, 1u, 0u);         // green: mode 1 in every block
+    for (int a = 1; a < kWebpAlphabets; ++a) b.simple(1, 0u, 0u);
+    b.put(0u, 1);                // no more transforms
+    b.put(0u, 1), b.put(0u, 1);  // the image: no colour cache, no meta prefix codes
+    for (int a = 0; a < kWebpAlphabets; ++a)
+        webp_write_code(b, freq.data() + webp_base(a), webp_size(a), codes.data() + webp_base(a));
+    auto code = [&](size_t s) { b.put(codes[s] & 0xFFFFu, (int)(codes[s] >> 16)); };
+    walk(
+        [&](uint32_t v) {
+            code((size_t)kWebpGreen + ((v >> 8) & 255u));
+            code((size_t)kWebpRed + ((v >> 16) & 255u));
+            code((size_t)kWebpBlue + (v & 255u));
+            code((size_t)kWebpAlpha + (v >> 24));
+        },
+        [&](uint32_t len) {
+            uint32_t sym, nb, extra;
+            webp_prefix(len, sym, nb, extra);
+            code((size_t)kWebpGreen + 256 + sym);
+            b.put(extra, (int)nb);
+            code((size_t)kWebpDist + kWebpDistSym);
+        });
+    b.flush();
+    webp_wrap_stream(body.data(), body.size(), out);
+    return body.size() <= bound;
 }
 
 bool write_file(const std::string& path, const std::vector<uint8_t>& data) {

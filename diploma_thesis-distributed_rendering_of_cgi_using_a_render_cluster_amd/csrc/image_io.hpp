@@ -88,6 +88,18 @@ void hdr_header_bytes(int W, int H, std::vector<uint8_t>& out);
 // 1, 3 or 4, or a body bound of 2 GB and more.
 bool encode_iris(const uint8_t* rgba, int W, int H, int C, std::vector<uint8_t>& out);
 void iris_header_bytes(int W, int H, int C, std::vector<uint8_t>& out);
+// A lossless WebP file ("WEBP", .webp) of the RGBA8 image, by the rules of
+// webp_rule.h: a RIFF container with one VP8L chunk, subtract-green, the
+// left-neighbour predictor, copies at distance 1 of at least kWebpMinRun equal
+// residuals, five prefix codes. C = 4: the pixels as they are, alpha hint 1;
+// C = 3: alpha 255, hint 0; C = 1: the grey code of grey.h in R, G and B. The
+// rule is stated as a plain walk over the stretches: webp.hip writes the same
+// bytes from ballots and scans. false: W or H outside 1 .. 16384, C not 1, 3 or
+// 4, or a payload bound of 2 GB and more.
+bool encode_webp(const uint8_t* rgba, int W, int H, int C, std::vector<uint8_t>& out);
+// The file around a VP8L payload: "RIFF", the size, "WEBP", "VP8L", the
+// payload's size, the payload, and a 0 byte if its size is odd.
+void webp_wrap_stream(const uint8_t* payload, size_t len, std::vector<uint8_t>& out);
 bool write_file(const std::string& path, const std::vector<uint8_t>& data);
 
 }  // namespace rr

@@ -39,12 +39,17 @@ void rr_render_params_default(rr_render_params* p) {
     p->max_glossy_bounces = -1;
 }
 
+// The warning of a host encode, which has no context: rr_last_warning(NULL).
+static void set_encode_warning(const char* format, int quality) {
+    g_warn = format && std::string(format) == "WEBP" ? webp_quality_warning(quality) : "";
+}
+
 int32_t rr_abi_version(void) { return RR_ABI_VERSION; }
 
 const char* rr_last_error(rr_ctx*) { return g_err.c_str(); }
 
 const char* rr_last_warning(rr_ctx* c) {
-    if (!c) return "";
+    if (!c) return g_warn.c_str();
     c->warning = c->ctx_warning;
     if (!c->frame_warning.empty()) c->warning += (c->warning.empty() ? "" : "; ") + c->frame_warning;
     return c->warning.c_str();
@@ -185,7 +190,7 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
     if (out_path && !format) return fail(RR_EINVAL, "format is required when out_path is given");
     if (format && !known_format(format))
         return fail(RR_ENOTSUP, std::string("unsupported output format '") + format +
-                                    "' (JPEG, PNG, OPEN_EXR, TARGA, TARGA_RAW, HDR and IRIS are supported)");
+                                    "' (JPEG, PNG, OPEN_EXR, TARGA, TARGA_RAW, HDR, IRIS and WEBP are supported)");
     const FrameOutput fo = resolve_output(c->settings, s->desc.render, format, out_path != nullptr, jpeg_quality);
     if (fo.coder == Coder::Jpeg && (jpeg_quality < 1 || jpeg_quality > 100))
         return fail(RR_EINVAL, "jpeg_quality must be 1..100");
@@ -219,6 +224,12 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         if (fo.coder == Coder::Iris) {
             const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.iris.plan);
             if (rc != RR_OK) return rc;
+        }
+        sl->quality_warning.clear();
+        if (fo.coder == Coder::Webp) {
+            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.webp.plan);
+            if (rc != RR_OK) return rc;
+            sl->quality_warning = webp_quality_warning(fo.quality);
         }
         if (fo.coder == Coder::Png16) {
             set_device(c);
@@ -263,6 +274,8 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
         sl->tm.file_saving_finished_at = unix_now();
         if (timing) *timing = sl->tm;
         c->frame_warning = sl->view_warning;
+        if (!sl->quality_warning.empty())
+            c->frame_warning += (c->frame_warning.empty() ? "" : "; ") + sl->quality_warning;
         if (stats) {
             fill_stats(stats, fs, sl->r, sl->scene->mesh.n_tris);
             stats->view_transform_substituted = sl->view_substituted ? 1 : 0;
@@ -310,6 +323,7 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         sl->view_substituted = !sl->view_warning.empty();
         sl->scene = s;
         sl->out_path.clear();
+        sl->quality_warning.clear();
         sl->out = FrameOutput{};
         sl->out.coder = Coder::HostRgba;  // the 8-bit image to the host; no file
         sl->film_out = film;
@@ -332,6 +346,7 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
 int rr_encode_image(const uint8_t* rgba8, int32_t w, int32_t h, const char* out_path, const char* format,
                     int32_t quality, uint64_t* bytes) {
     if (!rgba8 || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad image");
+    set_encode_warning(format, quality);
     return guarded([&] { return do_encode(rgba8, w, h, out_path, format, quality, bytes); });
 }
 
@@ -339,6 +354,7 @@ int rr_encode_image_mode(const uint8_t* rgba8, int32_t w, int32_t h, const char*
                          int32_t quality, int32_t color_mode, uint64_t* bytes) {
     if (!rgba8 || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad image");
     if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
+    set_encode_warning(format, quality);
     return guarded([&] { return do_encode(rgba8, w, h, out_path, format, quality, bytes, color_mode); });
 }
 

@@ -33,7 +33,7 @@ int debug_view_settings(const rr_ctx* c, int view, int& look, float& gamma) {
 }
 
 // The body of the coders' entry points: a w x h image of the caller's (RGBA8
-// for Jpeg, Png8, Tga and Iris, float RGBA means for the others) through coder k in C
+// for Jpeg, Png8, Tga, Iris and Webp, float RGBA means for the others) through coder k in C
 // channels, with the context's PNG compression; the file's bytes to `out` if
 // `cap` suffices. alpha_one, view_transform, exposure_scale: CoderInput's.
 int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, bool alpha_one, int view_transform,
@@ -55,10 +55,15 @@ int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, boo
         if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.hdr.plan)) return rc;
     if (k == Coder::Iris)
         if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.iris.plan)) return rc;
+    if (k == Coder::Webp) {
+        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.webp.plan)) return rc;
+        c->frame_warning = webp_quality_warning(quality);  // flagged as a frame's file is
+    }
     return guarded([&] {
         if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
         set_device(c);
-        const bool bytes8 = k == Coder::Jpeg || k == Coder::Png8 || k == Coder::Tga || k == Coder::Iris;
+        const bool bytes8 = k == Coder::Jpeg || k == Coder::Png8 || k == Coder::Tga || k == Coder::Iris ||
+                            k == Coder::Webp;
         const size_t bytes = (size_t)w * h * (bytes8 ? 4 : sizeof(float4));
         DevBuf<uint8_t> img;
         img.ensure(bytes);
@@ -139,6 +144,9 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
     } else if (fmt == "IRIS") {  // the same
         if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "IRIS takes an RGBA8 image at depth 8");
         k = Coder::Iris;
+    } else if (fmt == "WEBP") {  // the same; jpeg_quality below 100 is flagged (rr_last_warning), the file lossless
+        if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "WEBP takes an RGBA8 image at depth 8");
+        k = Coder::Webp;
     } else if (hdr) {  // the film's floats and no other depth
         if (!image_is_float || (depth != 0 && depth != 32)) return fail(RR_EINVAL, "HDR takes a float RGBA image at depth 32");
         k = Coder::Hdr;

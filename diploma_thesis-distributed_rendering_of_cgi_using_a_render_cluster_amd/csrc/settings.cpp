@@ -178,12 +178,13 @@ bool settings_from_env(OutputSettings& s, std::string& err) {
 bool known_format(const char* format) {
     const std::string f(format ? format : "");
     return f == "JPEG" || f == "PNG" || f == "OPEN_EXR" || f == "TARGA" || f == "TARGA_RAW" || f == "HDR" ||
-           f == "IRIS";
+           f == "IRIS" || f == "WEBP";
 }
 
 const char* coder_ext(Coder k) {
     if (k == Coder::Hdr) return ".hdr";
     if (k == Coder::Iris) return ".rgb";
+    if (k == Coder::Webp) return ".webp";
     return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : k == Coder::Tga ? ".tga" : ".png";
 }
 
@@ -200,6 +201,7 @@ FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const c
     const bool tga = tga_raw || (has_path && std::string(format) == "TARGA");
     const bool hdr = has_path && std::string(format) == "HDR";
     const bool iris = has_path && std::string(format) == "IRIS";
+    const bool webp = has_path && std::string(format) == "WEBP";
     FrameOutput o;
     o.tga_raw = tga_raw;
     if (!has_path) o.coder = Coder::None;
@@ -207,6 +209,7 @@ FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const c
     else if (tga) o.coder = Coder::Tga;  // 8 bits a channel: the depth settings do not apply
     else if (hdr) o.coder = Coder::Hdr;  // RGBE quads of the film's means: nor do they here
     else if (iris) o.coder = Coder::Iris;  // 8 bits a channel, as TARGA; it has alpha: RGBA stays RGBA
+    else if (webp) o.coder = Coder::Webp;  // the same; lossless at every quality
     else if (exr)  // HALF unless the context, or at 0 the scene, asks for FLOAT channels
         o.coder = (s.exr_depth ? s.exr_depth : r.exr_depth) == 32 ? Coder::Exr32 : Coder::Exr;
     // "PNG". 16 bits per sample: always the device coder (there is no host one)

@@ -64,8 +64,9 @@ bool settings_from_env(OutputSettings& s, std::string& err);
 // channels; Exr32: with FLOAT channels (rr_set_exr_depth). Tga: "TARGA" and
 // "TARGA_RAW" (FrameOutput::tga_raw), always 8 bits a channel. Hdr: "HDR",
 // Radiance RGBE quads of the film's means. Iris: "IRIS", a run-length coded
-// Silicon Graphics .rgb file of the 8-bit image.
-enum class Coder { None, HostRgba, Jpeg, Png8, Png16, Exr, Exr32, Tga, Hdr, Iris };
+// Silicon Graphics .rgb file of the 8-bit image. Webp: "WEBP", a lossless WebP
+// file (VP8L) of the 8-bit image.
+enum class Coder { None, HostRgba, Jpeg, Png8, Png16, Exr, Exr32, Tga, Hdr, Iris, Webp };
 
 // The formats behind the deflate coder (deflate.hip): their coder reads only
 // its slot's rgba8 / film and writes slot buffers only.
@@ -75,10 +76,10 @@ inline bool device_deflate(Coder k) {
 
 // The coders that read only their slot's rgba8 / film and write slot buffers
 // only: the deflate formats, the TARGA packer (tga.hip), the HDR coder
-// (hdr.hip) and the IRIS coder (iris.hip). The next frame waits for such a
-// frame's image, not for its coder.
+// (hdr.hip), the IRIS coder (iris.hip) and the WEBP coder (webp.hip). The next
+// frame waits for such a frame's image, not for its coder.
 inline bool slot_coder(Coder k) {
-    return device_deflate(k) || k == Coder::Tga || k == Coder::Hdr || k == Coder::Iris;
+    return device_deflate(k) || k == Coder::Tga || k == Coder::Hdr || k == Coder::Iris || k == Coder::Webp;
 }
 
 // The output formats a frame can be submitted with.
@@ -89,7 +90,7 @@ const char* coder_ext(Coder k);
 // The channels a frame's file holds (rr_set_color_mode), which is also the
 // resolved mode's value: RR_COLOR_BW 1, RR_COLOR_RGB 3, RR_COLOR_RGBA 4. mode 0:
 // the format's layout before there was a setting (JPEG three components, PNG
-// OPEN_EXR, TARGA and IRIS four channels). JPEG and HDR have no alpha (no_alpha):
+// OPEN_EXR, TARGA, IRIS and WEBP four channels). JPEG and HDR have no alpha (no_alpha):
 // RGBA resolves to RGB, as in Blender, and mode 0 is RGB.
 int resolve_color_mode(int mode, bool no_alpha);
 
@@ -104,9 +105,9 @@ struct FrameOutput {
 
 // What a frame of a scene with render settings r is written as on a context
 // with settings s. format: "JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW",
-// "HDR" or "IRIS" (known_format, checked by the caller); without a path there
-// is no file (Coder::None). A TARGA and an IRIS file are 8 bits a channel and an
-// HDR file RGBE quads whatever the depth settings.
+// "HDR", "IRIS" or "WEBP" (known_format, checked by the caller); without a path
+// there is no file (Coder::None). A TARGA, an IRIS and a WEBP file are 8 bits a
+// channel and an HDR file RGBE quads whatever the depth settings.
 FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const char* format, bool has_path,
                            int jpeg_quality);
 

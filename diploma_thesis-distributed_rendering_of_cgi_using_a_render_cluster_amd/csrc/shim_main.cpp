@@ -126,6 +126,7 @@ int main(int argc, char** argv) {
                             : (fmt == "TARGA" || fmt == "TARGA_RAW") ? ".tga"
                             : fmt == "HDR"                            ? ".hdr"
                             : fmt == "IRIS"                           ? ".rgb"
+                            : fmt == "WEBP"                           ? ".webp"
                                                                       : "";
     if (ext.empty()) {
         std::fprintf(stderr, "rr-blender-shim: unsupported output format '%s'\n", fmt.c_str());

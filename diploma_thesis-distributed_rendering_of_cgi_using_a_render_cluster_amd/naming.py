@@ -6,12 +6,12 @@ substitution) and the path assembly of BlenderJobRunner::render_frame
 output_file_name_format), plus Blender's write_still extension (R_EXTENSION is
 set in the 01 project): ".jpg" for JPEG, ".png" for PNG,
 ".exr" for OPEN_EXR, ".tga" for TARGA and TARGA_RAW, ".hdr" for HDR, ".rgb"
-for IRIS.
+for IRIS, ".webp" for WEBP.
 """
 from __future__ import annotations
 
 EXTENSIONS = {"JPEG": ".jpg", "PNG": ".png", "OPEN_EXR": ".exr", "TARGA": ".tga", "TARGA_RAW": ".tga", "HDR": ".hdr",
-              "IRIS": ".rgb"}
+              "IRIS": ".rgb", "WEBP": ".webp"}
 
 
 def format_hash_frame_placeholders(raw_file_path: str, frame_number: int) -> str:

@@ -79,7 +79,7 @@ class FrameStats(ctypes.Structure):
 
 RR_FLAG_PROFILE_KERNELS, RR_FLAG_COUNT_TRAVERSAL, RR_FLAG_WAVEFRONT = 1, 2, 4
 KERNEL_CLASSES = ["build", "primary", "extend", "shadow", "accumulate", "shade", "tiles"]
-RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer, the HDR or the IRIS coder
+RR_K_PNG = 7  # FrameStats.kernel_ms index of the device deflate coder (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer, the HDR, the IRIS or the WEBP coder
 
 
 # Every symbol include/rr.h declares (checked by tests/test_abi.py).
@@ -615,8 +615,10 @@ class RenderContext:
                       exposure_scale: float = 1.0, quality: int = 90) -> bytes:
         """rr_debug_encode_device: the file bytes of an (H, W, 4) image coded on the
         device as `fmt` ("JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW", "HDR",
-        "IRIS") at `depth` in `color_mode`. uint8 images for JPEG, 8-bit PNG, TARGA
-        and IRIS, float32 means for the others; "HDR" at depth 0 or 32 and no other."""
+        "IRIS", "WEBP") at `depth` in `color_mode`. uint8 images for JPEG, 8-bit PNG,
+        TARGA, IRIS and WEBP, float32 means for the others; "HDR" at depth 0 or 32 and
+        no other. `quality`: JPEG's; a "WEBP" file is lossless at every quality, and
+        one below 100 is flagged (last_warning)."""
         if fmt == "HDR" and (image.dtype == np.uint8 or int(depth) not in (0, 32)):
             raise RRError(RR_EINVAL, "HDR takes a float image at depth 0 or 32")
         is_float = image.dtype != np.uint8
@@ -740,6 +742,12 @@ def encode_image(rgba: np.ndarray, out_path_no_ext: str, fmt: str, quality: int 
     _check(lib().rr_encode_image(_ptr(rgba, ctypes.c_uint8), w, h, out_path_no_ext.encode(), fmt.encode(),
                                  int(quality), ctypes.byref(nbytes)))
     return nbytes.value
+
+
+def last_host_warning() -> str:
+    """rr_last_warning without a context: the warning of this thread's last
+    encode_image / encode_image_mode ("WEBP" below quality 100), "" if none."""
+    return lib().rr_last_warning(None).decode("utf-8", "replace")
 
 
 def encode_image_mode(rgba: np.ndarray, out_path_no_ext: str, fmt: str, quality: int = 90, color_mode=0) -> int:

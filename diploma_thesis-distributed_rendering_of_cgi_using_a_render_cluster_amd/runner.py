@@ -48,8 +48,9 @@ class BackendRunner:
         device_png: "PNG" jobs are coded on the device (rr_set_device_png).
         "OPEN_EXR" jobs (ZIP files of the linear film) always are, and so are
         "TARGA" and "TARGA_RAW" jobs (8-bit .tga files, run-length coded or plain)
-        "HDR" jobs (Radiance RGBE .hdr files of the linear film) and "IRIS" jobs
-        (8-bit Silicon Graphics .rgb files, run-length coded).
+        "HDR" jobs (Radiance RGBE .hdr files of the linear film), "IRIS" jobs
+        (8-bit Silicon Graphics .rgb files, run-length coded) and "WEBP" jobs
+        (8-bit lossless WebP files; a quality below 100 is flagged, not honoured).
         png_depth: bits per sample of "PNG" jobs (rr_set_png_depth): 8, 16, or 0
         for each scene's own render.color_depth; 16-bit frames are always coded
         on the device.

@@ -93,7 +93,7 @@ typedef struct rr_render_params {
 #define RR_K_ACCUM 4     /* film accumulate + tonemap */
 #define RR_K_SHADE 5     /* split path (large scenes): shading kernels; PRIMARY/EXTEND then time traversal only */
 #define RR_K_TILES 6     /* LDS-resident scenes: k_tiles, every sample of an 8x8 pixel tile run to completion + film + tonemap */
-#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer, the HDR or the IRIS coder: all its kernels, one event pair per frame */
+#define RR_K_PNG 7       /* device deflate coder of the frame's format (PNG with rr_set_device_png, 16-bit PNG, or OPEN_EXR), the TARGA packer, the HDR, the IRIS or the WEBP coder: all its kernels, one event pair per frame */
 #define RR_K_CLASSES 8
 
 /* The five timestamps the reference recovers from Blender's stdout
@@ -200,9 +200,9 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *  - frame_index: the frame to evaluate (Blender frame number, scene.frame_set).
  *  - out_path: output path WITHOUT extension, '#' runs already substituted
  *    (render-timing-script.py:69-78,82); the library appends ".jpg" / ".png"
- *    / ".exr" / ".tga" / ".hdr" / ".rgb" as Blender's write_still does with
+ *    / ".exr" / ".tga" / ".hdr" / ".rgb" / ".webp" as Blender's write_still does with
  *    R_EXTENSION. NULL: render only.
- *  - format: "JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW", "HDR" or "IRIS" (job output_file_format,
+ *  - format: "JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW", "HDR", "IRIS" or "WEBP" (job output_file_format,
  *    shared/src/jobs/mod.rs:80, handed to image_settings.file_format,
  *    render-timing-script.py:83-92). "OPEN_EXR": the film's mean linear
  *    radiance before any view transform (alpha = 1) as A, B, G, R channels,
@@ -252,8 +252,25 @@ int rr_scene_load(rr_ctx* ctx, const char* scene_path, rr_scene** out);
  *    through the tables and returns the same pixels. Coded on the GPU
  *    (iris.hip). RR_EINVAL for a width or height above 65535 or a body bound
  *    (tables and row-planes at their longest) of 2 GB and more.
- *  - jpeg_quality: 1..100 (the reference script forces 90, :84); ignored for
- *    every other format.
+ *    "WEBP": a lossless WebP file (.webp) of the same 8-bit image: a RIFF
+ *    container with one VP8L chunk, always 8 bits a channel. The payload, an
+ *    LSB-first bit stream: byte 0x2F, W - 1 and H - 1 in 14 bits each, the
+ *    alpha hint (1 with four channels: rr_set_color_mode RGBA or none; RGB:
+ *    alpha 255, hint 0; BW: the grey code in R, G and B, hint 0), version 0;
+ *    the subtract-green transform; the predictor transform with mode 1 (the
+ *    left neighbour) in every block; no colour cache, no meta prefix codes;
+ *    five prefix codes; literals, and copies of 3 .. 4096 equal residuals at
+ *    distance 1 within a row. Pinned: the pixels, which libwebp returns
+ *    exactly, and the bytes against a restatement of the writer. The run rule
+ *    and the single predictor mode are the project's own (csrc/webp_rule.h):
+ *    any reader returns the same pixels. Blender writes lossy VP8 below quality
+ *    100: that is not built. jpeg_quality below 100 gives the same lossless
+ *    file and sets rr_last_warning, naming the quality; the frame does not
+ *    fail. Coded on the GPU (webp.hip). RR_EINVAL for a width or height above
+ *    16384 or a payload bound (60 bits a pixel and the header) of 2 GB and
+ *    more.
+ *  - jpeg_quality: 1..100 (the reference script forces 90, :84); "WEBP": below
+ *    100 flagged, see above; ignored for every other format.
  *  - timing / stats: optional outputs (may be NULL). */
 int rr_render_frame(rr_ctx* ctx, rr_scene* scene, int32_t frame_index,
                     const rr_render_params* params, const char* out_path,
@@ -300,9 +317,11 @@ int rr_scene_resolution(rr_scene* scene, const rr_render_params* params,
 
 /* Encode an RGBA8 image (rows top to bottom) to `path` + extension.
  * Host encoder used by rr_render_frame; exported for tests. "JPEG", "PNG",
- * "TARGA", "TARGA_RAW" and "IRIS" (four channels, as "PNG"; RR_EINVAL for a width
- * or height above 65535 or a body of 2 GB and more): "OPEN_EXR" and "HDR" need
- * the float film and are RR_ENOTSUP here. */
+ * "TARGA", "TARGA_RAW", "IRIS" (four channels, as "PNG"; RR_EINVAL for a width
+ * or height above 65535 or a body of 2 GB and more) and "WEBP" (four channels;
+ * RR_EINVAL above 16384; lossless, and a jpeg_quality below 100 sets the
+ * warning rr_last_warning(NULL) returns on this thread until the next host
+ * encode): "OPEN_EXR" and "HDR" need the float film and are RR_ENOTSUP here. */
 int rr_encode_image(const uint8_t* rgba8, int32_t width, int32_t height,
                     const char* out_path_no_ext, const char* format,
                     int32_t jpeg_quality, uint64_t* bytes_written);
@@ -425,10 +444,10 @@ int rr_encode_image_mode(const uint8_t* rgba8, int32_t width, int32_t height,
 
 /* Encode an image of the caller's with the device coder of a format, depth and
  * colour mode, through the enqueue, wrap and file code rendered frames take.
- * format "JPEG" (depth 8), "PNG" at depth 8 and "TARGA" / "TARGA_RAW" / "IRIS" (depth 8
+ * format "JPEG" (depth 8), "PNG" at depth 8 and "TARGA" / "TARGA_RAW" / "IRIS" / "WEBP" (depth 8
  * and no other) take an RGBA8 image (image_is_float 0); "PNG" at depth 16, "OPEN_EXR" at depth 16 (HALF) or 32
  * (FLOAT) and "HDR" (depth 32 and no other) take width * height * 4 floats
- * (image_is_float 1) as means, spp = 1, alpha 1. depth 0: 8 for PNG, TARGA and IRIS,
+ * (image_is_float 1) as means, spp = 1, alpha 1. depth 0: 8 for PNG, TARGA, IRIS and WEBP,
  * 16 for OPEN_EXR, 32 for HDR. view_transform and
  * exposure_scale: 16-bit PNG only, as for rr_debug_png16_device; jpeg_quality:
  * JPEG only. A size outside the coder's range is RR_EINVAL before anything is
@@ -459,7 +478,8 @@ const char* rr_last_error(rr_ctx* ctx);
 
 /* Warning of ctx's last completed frame ("" if none), e.g. a Filmic view
  * transform rendered as Standard because no OCIO LUTs are configured. Valid
- * until the next call on ctx. */
+ * until the next call on ctx. ctx NULL: the warning of this thread's last host
+ * encode (rr_encode_image, rr_encode_image_mode), "" if none. */
 const char* rr_last_warning(rr_ctx* ctx);
 
 /* Blender colour-management directory (datafiles/colormanagement: config.ocio
