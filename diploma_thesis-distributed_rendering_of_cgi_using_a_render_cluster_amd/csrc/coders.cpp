@@ -46,30 +46,27 @@ int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p) {
     return fail(RR_EINVAL, std::string("image size outside the device ") + name + " encoder's range");
 }
 
-int plan_or_refuse(const FrameOutput& fo, int W, int H, TgaPlan& p) {
-    if (tga_plan(W, H, fo.color_mode, !fo.tga_raw, p)) return RR_OK;
-    return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
-}
-
-int plan_or_refuse(const FrameOutput& fo, int W, int H, HdrPlan& p) {
-    if (hdr_plan(W, H, fo.color_mode, p)) return RR_OK;
-    return fail(RR_EINVAL, "image size outside the HDR coder's range (a body bound below 2 GB)");
-}
-
 static const char* const kIrisRange =
     "image size outside the IRIS format's range (65535 x 65535, a body bound below 2 GB)";
-
-int plan_or_refuse(const FrameOutput& fo, int W, int H, IrisPlan& p) {
-    if (iris_plan(W, H, fo.color_mode, p)) return RR_OK;
-    return fail(RR_EINVAL, kIrisRange);
-}
-
 static const char* const kWebpRange =
     "image size outside the WEBP format's range (16384 x 16384, a payload bound below 2 GB)";
 
-int plan_or_refuse(const FrameOutput& fo, int W, int H, WebpPlan& p) {
-    if (webp_plan(W, H, fo.color_mode, p)) return RR_OK;
-    return fail(RR_EINVAL, kWebpRange);
+int plan_or_refuse(const FrameOutput& fo, int W, int H, BodyOut& o) {
+    const int C = fo.color_mode;
+    switch (fo.coder) {
+    case Coder::Tga:
+        if (tga_plan(W, H, C, !fo.tga_raw, o.tga)) return RR_OK;
+        return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
+    case Coder::Hdr:
+        if (hdr_plan(W, H, C, o.hdr)) return RR_OK;
+        return fail(RR_EINVAL, "image size outside the HDR coder's range (a body bound below 2 GB)");
+    case Coder::Iris:
+        return iris_plan(W, H, C, o.iris) ? RR_OK : fail(RR_EINVAL, kIrisRange);
+    case Coder::Webp:
+        return webp_plan(W, H, C, o.webp) ? RR_OK : fail(RR_EINVAL, kWebpRange);
+    default:
+        return RR_OK;  // no body coder: nothing to plan
+    }
 }
 
 std::string webp_quality_warning(int quality) {
@@ -80,103 +77,77 @@ std::string webp_quality_warning(int quality) {
 
 namespace {
 
-// Device WEBP encode of an RGBA8 image into o's pinned stream, by o.plan.
-void enqueue_webp(const CoderInput& in, DevFrame& f, hipStream_t st, WebpOut& o) {
-    const WebpPlan& p = o.plan;
-    if (p.W != in.W || p.H != in.H) throw std::runtime_error("WEBP plan of another image");
-    f.webp_scratch.ensure(webp_scratch_words(p));
-    o.stream.ensure(webp_stream_bytes(p));
+// Device encode by a body coder (TARGA, HDR, IRIS, WEBP) into o's pinned
+// stream, by the format's plan p: launch(scratch, host_out) enqueues it.
+template <class Plan, class Launch>
+void enqueue_body(const char* name, const Plan& p, size_t scratch_words, const CoderInput& in, DevFrame& f,
+                  hipStream_t st, BodyOut& o, Launch launch) {
+    if (p.W != in.W || p.H != in.H) throw std::runtime_error(std::string(name) + " plan of another image");
+    f.body_scratch.ensure(scratch_words);
+    o.stream.ensure(body_stream_bytes(p.body_cap));
     void* dev_host = nullptr;
     RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
     f.prof.begin(st, RR_K_PNG);
-    webp_encode_device(in.rgba8, p, f.webp_scratch.ptr, static_cast<uint8_t*>(dev_host), st);
+    launch(f.body_scratch.ptr, static_cast<uint8_t*>(dev_host));
     f.prof.end(st);
 }
 
-// The file of a device-coded WEBP image: the host-built RIFF and chunk headers
-// around the device's payload (at least the 5 bytes of signature and sizes).
-void webp_file_bytes(const WebpOut& o, std::vector<uint8_t>& data) {
-    const WebpPlan& p = o.plan;
+void enqueue_body(Coder k, const CoderInput& in, DevFrame& f, hipStream_t st, BodyOut& o) {
+    if (k == Coder::Tga)
+        enqueue_body("TARGA", o.tga, tga_scratch_words(o.tga), in, f, st, o, [&](uint32_t* scratch, uint8_t* out) {
+            tga_encode_device(in.rgba8, o.tga, scratch, out, st);
+        });
+    else if (k == Coder::Hdr)
+        enqueue_body("HDR", o.hdr, hdr_scratch_words(o.hdr), in, f, st, o, [&](uint32_t* scratch, uint8_t* out) {
+            hdr_encode_device(in.film, in.inv_spp, o.hdr, scratch, out, st);
+        });
+    else if (k == Coder::Iris)
+        enqueue_body("IRIS", o.iris, iris_scratch_words(o.iris), in, f, st, o, [&](uint32_t* scratch, uint8_t* out) {
+            iris_encode_device(in.rgba8, o.iris, scratch, out, st);
+        });
+    else
+        enqueue_body("WEBP", o.webp, webp_scratch_words(o.webp), in, f, st, o, [&](uint32_t* scratch, uint8_t* out) {
+            webp_encode_device(in.rgba8, o.webp, scratch, out, st);
+        });
+}
+
+// The checked length of the body in o's stream: within the plan's bound
+// body_cap and the stream, and at least min_len (an exact length: body_cap).
+uint64_t body_stream_len(const BodyOut& o, const char* name, uint32_t body_cap, uint64_t min_len) {
     uint64_t len = 0;
     std::memcpy(&len, o.stream.ptr, sizeof len);
-    if (len > p.body_cap || len + 16 > o.stream.cap || len < 5) throw std::runtime_error("device WEBP stream overflow");
-    webp_wrap_stream(o.stream.ptr + 16, (size_t)len, data);
+    if (len > body_cap || len + 16 > o.stream.cap || len < min_len)
+        throw std::runtime_error(std::string("device ") + name + " stream overflow");
+    return len;
 }
 
-// Device IRIS encode of an RGBA8 image into o's pinned stream, by o.plan.
-void enqueue_iris(const CoderInput& in, DevFrame& f, hipStream_t st, IrisOut& o) {
-    const IrisPlan& p = o.plan;
-    if (p.W != in.W || p.H != in.H) throw std::runtime_error("IRIS plan of another image");
-    f.iris_scratch.ensure(iris_scratch_words(p));
-    o.stream.ensure(iris_stream_bytes(p));
-    void* dev_host = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
-    f.prof.begin(st, RR_K_PNG);
-    iris_encode_device(in.rgba8, p, f.iris_scratch.ptr, static_cast<uint8_t*>(dev_host), st);
-    f.prof.end(st);
+// The file of a device-coded TARGA, HDR, IRIS or WEBP image: the host-built
+// header + the device body. What a body holds at least: a raw TARGA and a flat
+// HDR body their exact length; IRIS the tables and every coded row-plane a
+// packet and its terminator; WEBP the 5 bytes of signature and sizes, inside
+// the host-built RIFF and chunk headers.
+void body_file_bytes(const BodyOut& o, Coder k, std::vector<uint8_t>& data) {
+    const uint8_t* body = o.stream.ptr + 16;
+    if (k == Coder::Tga) {
+        const TgaPlan& p = o.tga;
+        const uint64_t len = body_stream_len(o, "TARGA", p.body_cap, p.rle ? 0 : p.body_cap);
+        tga_header_bytes(p.W, p.H, p.C, p.rle, data);
+        data.insert(data.end(), body, body + len);
+    } else if (k == Coder::Hdr) {
+        const HdrPlan& p = o.hdr;
+        const uint64_t len = body_stream_len(o, "HDR", p.body_cap, p.flat ? p.body_cap : 0);
+        hdr_header_bytes(p.W, p.H, data);
+        data.insert(data.end(), body, body + len);
+    } else if (k == Coder::Iris) {
+        const IrisPlan& p = o.iris;
+        const uint64_t planes = (uint64_t)p.H * (uint64_t)p.C;
+        const uint64_t len = body_stream_len(o, "IRIS", p.body_cap, 8 * planes + 3 * planes);
+        iris_header_bytes(p.W, p.H, p.C, data);
+        data.insert(data.end(), body, body + len);
+    } else {
+        webp_wrap_stream(body, (size_t)body_stream_len(o, "WEBP", o.webp.body_cap, 5), data);
+    }
 }
-
-// The file of a device-coded IRIS image: host-built header + the device body
-// (the tables and the coded row-planes, each at least its terminator).
-void iris_file_bytes(const IrisOut& o, std::vector<uint8_t>& data) {
-    const IrisPlan& p = o.plan;
-    uint64_t len = 0;
-    std::memcpy(&len, o.stream.ptr, sizeof len);
-    const uint64_t planes = (uint64_t)p.H * (uint64_t)p.C;
-    if (len > p.body_cap || len + 16 > o.stream.cap || len < 8 * planes + 3 * planes)
-        throw std::runtime_error("device IRIS stream overflow");
-    iris_header_bytes(p.W, p.H, p.C, data);
-    data.insert(data.end(), o.stream.ptr + 16, o.stream.ptr + 16 + len);
-}
-
-// Device HDR encode of a film into o's pinned stream, by o.plan.
-void enqueue_hdr(const CoderInput& in, DevFrame& f, hipStream_t st, HdrOut& o) {
-    const HdrPlan& p = o.plan;
-    if (p.W != in.W || p.H != in.H) throw std::runtime_error("HDR plan of another image");
-    f.hdr_scratch.ensure(hdr_scratch_words(p));
-    o.stream.ensure(hdr_stream_bytes(p));
-    void* dev_host = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
-    f.prof.begin(st, RR_K_PNG);
-    hdr_encode_device(in.film, in.inv_spp, p, f.hdr_scratch.ptr, static_cast<uint8_t*>(dev_host), st);
-    f.prof.end(st);
-}
-
-// The file of a device-coded HDR image: host-built header + the device body.
-void hdr_file_bytes(const HdrOut& o, std::vector<uint8_t>& data) {
-    const HdrPlan& p = o.plan;
-    uint64_t len = 0;
-    std::memcpy(&len, o.stream.ptr, sizeof len);
-    if (len > p.body_cap || len + 16 > o.stream.cap || (p.flat && len != p.body_cap))
-        throw std::runtime_error("device HDR stream overflow");
-    hdr_header_bytes(p.W, p.H, data);
-    data.insert(data.end(), o.stream.ptr + 16, o.stream.ptr + 16 + len);
-}
-
-// Device TARGA encode of an RGBA8 image into o's pinned stream, by o.plan.
-void enqueue_tga(const CoderInput& in, DevFrame& f, hipStream_t st, TgaOut& o) {
-    const TgaPlan& p = o.plan;
-    if (p.W != in.W || p.H != in.H) throw std::runtime_error("TARGA plan of another image");
-    f.tga_scratch.ensure(tga_scratch_words(p));
-    o.stream.ensure(tga_stream_bytes(p));
-    void* dev_host = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
-    f.prof.begin(st, RR_K_PNG);
-    tga_encode_device(in.rgba8, p, f.tga_scratch.ptr, static_cast<uint8_t*>(dev_host), st);
-    f.prof.end(st);
-}
-
-// The file of a device-coded TARGA image: host-built header + the device body.
-void tga_file_bytes(const TgaOut& o, std::vector<uint8_t>& data) {
-    const TgaPlan& p = o.plan;
-    uint64_t len = 0;
-    std::memcpy(&len, o.stream.ptr, sizeof len);
-    if (len > p.body_cap || len + 16 > o.stream.cap || (!p.rle && len != p.body_cap))
-        throw std::runtime_error("device TARGA stream overflow");
-    tga_header_bytes(p.W, p.H, p.C, p.rle, data);
-    data.insert(data.end(), o.stream.ptr + 16, o.stream.ptr + 16 + len);
-}
-
 
 // Device JPEG encode of an RGBA8 image (transform into f.jpeg_coeffs + Huffman
 // coding) into o's pinned stream. grey: a one-component file (RR_COLOR_BW).
@@ -249,10 +220,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
     const Coder k = fo.coder;
     const int C = fo.color_mode;
     if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o.jpeg);
-    if (k == Coder::Tga) return enqueue_tga(in, f, st, o.tga);
-    if (k == Coder::Hdr) return enqueue_hdr(in, f, st, o.hdr);
-    if (k == Coder::Iris) return enqueue_iris(in, f, st, o.iris);
-    if (k == Coder::Webp) return enqueue_webp(in, f, st, o.webp);
+    if (device_body(k)) return enqueue_body(k, in, f, st, o.body);
     if (!device_deflate(k)) throw std::runtime_error("no device coder for this output");
     // the front ends' own buffers. "PNG" at compression 0 .. 100: a filter type
     // per row of the H rows, and at 16 bits the raw scanlines, 2C W H bytes
@@ -303,10 +271,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
 
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data) {
     if (fo.coder == Coder::Jpeg) jpeg_file_bytes(o.jpeg, data);
-    else if (fo.coder == Coder::Tga) tga_file_bytes(o.tga, data);
-    else if (fo.coder == Coder::Hdr) hdr_file_bytes(o.hdr, data);
-    else if (fo.coder == Coder::Iris) iris_file_bytes(o.iris, data);
-    else if (fo.coder == Coder::Webp) webp_file_bytes(o.webp, data);
+    else if (device_body(fo.coder)) body_file_bytes(o.body, fo.coder, data);
     else deflate_file_bytes(o.deflate, fo.coder, fo.color_mode, data);
 }
 

@@ -212,14 +212,9 @@ struct DevFrame {
     // PNG frames with the adaptive filter (rr_set_png_compression): a filter type per image row, and at 16 bits
     // the raw big-endian scanlines (png16.hip k_png16_raw); grow-only, untouched by legacy frames
     DevBuf<uint8_t> png_ftype, png_raw;
-    // TARGA frames (tga.hip): the dense body, and for run-length coded ones the per-pixel records; grow-only
-    DevBuf<uint32_t> tga_scratch;
-    // HDR frames (hdr.hip): the quads, and for coded rows the per-byte records and the dense body; grow-only
-    DevBuf<uint32_t> hdr_scratch;
-    // IRIS frames (iris.hip): the dense body (tables and coded row-planes) and the per-byte records; grow-only
-    DevBuf<uint32_t> iris_scratch;
-    // WEBP frames (webp.hip): the payload, the residuals and per-pixel records, counts, codes and row offsets; grow-only
-    DevBuf<uint32_t> webp_scratch;
+    // TARGA, HDR, IRIS and WEBP frames (tga.hip, hdr.hip, iris.hip, webp.hip): the dense body and the coder's
+    // records, carved by the coder's *_carve; grow-only. A frame writes one file, so the four share it
+    DevBuf<uint32_t> body_scratch;
     // written by render_frame_device, about the frame it enqueued
     int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log (trav_counts)

@@ -62,44 +62,30 @@ struct JpegOut {
     bool grey = false;
 };
 
-// The pinned output of a device-coded TARGA body, [uint64 length][8 B pad]
-// [bytes] (tga.hpp). The plan is made before the coder is enqueued
-// (plan_or_refuse); the file's header is built from it.
-struct TgaOut {
+// The pinned output of a device-coded TARGA, HDR or IRIS body or WEBP payload,
+// [uint64 length][8 B pad][bytes] (tga.hpp, hdr.hpp, iris.hpp, webp.hpp), of
+// body_stream_bytes. A frame writes one file, so the four share the stream. The
+// format's plan is made before the coder is enqueued (plan_or_refuse); the host
+// builds the file's header (WEBP: the RIFF and chunk headers and the pad byte)
+// from it.
+struct BodyOut {
     PinnedBuf stream;
-    rr::TgaPlan plan{};
+    rr::TgaPlan tga{};
+    rr::HdrPlan hdr{};
+    rr::IrisPlan iris{};
+    rr::WebpPlan webp{};
 };
 
-// The same for a device-coded HDR body (hdr.hpp); the host puts the text header
-// in front.
-struct HdrOut {
-    PinnedBuf stream;
-    rr::HdrPlan plan{};
-};
-
-// The same for a device-coded IRIS body (iris.hpp): the tables and the coded
-// row-planes; the host puts the 512-byte header in front.
-struct IrisOut {
-    PinnedBuf stream;
-    rr::IrisPlan plan{};
-};
+// The pinned stream of a body of at most body_cap bytes: 16 + the body rounded
+// up to 16.
+inline size_t body_stream_bytes(uint32_t body_cap) { return 16 + ((size_t)body_cap + 15) / 16 * 16; }
 
 // Where the device coders write: a frame slot has one, and the context one
 // more for the inspection entry points.
-// The same for a device-coded WEBP payload (webp.hpp): the VP8L bit stream; the
-// host puts the RIFF and chunk headers in front and the pad byte behind.
-struct WebpOut {
-    PinnedBuf stream;
-    rr::WebpPlan plan{};
-};
-
 struct CodedOut {
     JpegOut jpeg;
     DeflateOut deflate;
-    TgaOut tga;
-    HdrOut hdr;
-    IrisOut iris;
-    WebpOut webp;
+    BodyOut body;
 };
 
 struct FrameRun {
@@ -301,18 +287,10 @@ struct CoderInput {
 // range is refused (RR_EINVAL), never rerouted: there is no other coder that
 // writes the same file.
 int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p);
-// The same for a TARGA image (Coder::Tga): W or H above 65535 and a body of
-// 2 GB and more are refused.
-int plan_or_refuse(const FrameOutput& fo, int W, int H, TgaPlan& p);
-// The same for an HDR image (Coder::Hdr): a body bound of 2 GB and more is
-// refused.
-int plan_or_refuse(const FrameOutput& fo, int W, int H, HdrPlan& p);
-// The same for an IRIS image (Coder::Iris): W or H above 65535 and a body
-// bound of 2 GB and more are refused.
-int plan_or_refuse(const FrameOutput& fo, int W, int H, IrisPlan& p);
-// The same for a WEBP image (Coder::Webp): W or H above 16384 and a payload
-// bound of 2 GB and more are refused.
-int plan_or_refuse(const FrameOutput& fo, int W, int H, WebpPlan& p);
+// The same for the image of a body coder (fo.coder: Tga, Hdr, Iris or Webp),
+// into that format's plan of o. Refused: a TARGA or IRIS side above 65535, a
+// WEBP side above 16384, and a body bound of 2 GB and more.
+int plan_or_refuse(const FrameOutput& fo, int W, int H, BodyOut& o);
 // What a WEBP file of this quality is flagged with (rr_last_warning): "" at 100
 // and above, else that the file is lossless, as lossy WEBP is not built.
 std::string webp_quality_warning(int quality);
@@ -328,8 +306,8 @@ void ensure_jpeg_table(rr_ctx* c, int quality);
 // f's scratch and profiler, into o's pinned buffers. fo.color_mode: the file's
 // channels; fo.png_compression ("PNG"): LEGACY the Sub front end, 0 .. 100 the
 // adaptive one (the device coders have one effort level). A deflate format
-// codes by o.deflate.plan, a TARGA one by o.tga.plan, an HDR one by o.hdr.plan,
-// an IRIS one by o.iris.plan, a WEBP one by o.webp.plan (plan_or_refuse).
+// codes by o.deflate.plan, a TARGA, HDR, IRIS or WEBP one by its plan in o.body
+// (plan_or_refuse).
 void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o);
 
 // The file of a device-coded image, once its stream is on the host: the

@@ -2,16 +2,16 @@
 // slot's film, so only the file's bytes cross PCIe and the host writes the text
 // header (image_io hdr_header_bytes). See hdr.hpp, and hdr_rule.h for the RGBE
 // rule and the scanline rule, which the host encoder (image_io encode_hdr)
-// states as a walk over the runs and the kernels below as bit operations on
-// ballots.
+// states as a walk over the runs and the device packer (rle_device.hpp) as bit
+// operations on ballots.
 //
 // Coded rows (8 <= W <= 32767): k_hdr_quad (a thread per pixel: the quad of the
 // film's means, one word) -> k_hdr_size (a workgroup per row and plane: every
 // byte's offset in its coded plane and its packet's header byte, the plane's
 // length) -> k_hdr_scan (a row is 4 marker bytes and its four planes: the rows'
 // offsets, the body's length) -> k_hdr_emit (a thread per plane byte stores its
-// byte, one lane a row the marker) -> k_hdr_gather (the dense body to pinned
-// host memory, 16 bytes a thread). Flat rows: k_hdr_quad -> k_hdr_gather, the
+// byte, one lane a row the marker) -> k_body_gather (the dense body to pinned
+// host memory, 16 bytes a thread). Flat rows: k_hdr_quad -> k_body_gather, the
 // quads are the body. Integers only after k_hdr_quad, no atomics, no workgroup
 // waits for another; order comes from the launches. Same film -> same bytes.
 #include <hip/hip_runtime.h>
@@ -20,14 +20,16 @@
 #include "grey.h"
 #include "hdr.hpp"
 #include "hdr_rule.h"
+#include "rle_device.hpp"
+#include "wg_scan.hpp"
 
 namespace rr {
 
 namespace {
 
-constexpr int kThreads = kHdrChunk;
-constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kRecWrites = 1u << 30, kRecFirst = 1u << 31, kRecOffset = kRecWrites - 1u;
+static_assert(kHdrChunk == kBodyChunk, "the packer's step");
+constexpr int kThreads = kBodyChunk;
+constexpr int kWaves = kBodyWaves;
 static_assert(hdr_plane_max_bytes(kHdrCodedMaxW) <= kRecOffset, "a plane offset fits the record");
 
 // A thread per pixel: the RGBE quad of the film's means, the products formed
@@ -50,123 +52,21 @@ __global__ __launch_bounds__(kThreads) void k_hdr_quad(const float4* __restrict_
     }
 }
 
-// eq(j) of hdr_rule.h in a plane of W bytes: byte `sh8` / 8 of the row's quads.
-__device__ __forceinline__ bool hdr_eq(const uint32_t* __restrict__ row, int sh8, int j, int W) {
-    if (j <= 0 || j >= W) return false;
-    return (((row[j] ^ row[j - 1]) >> sh8) & 255u) == 0u;
-}
-
-__device__ __forceinline__ int top_bit(uint64_t m) { return 63 - __builtin_clzll(m); }
-
-// One workgroup per row y and plane pl, kHdrChunk bytes a step, one a lane.
-// Per step: the eq bits as one ballot word a wave, with three bits of the step
-// before and four of the step after (ew); from a lane's eight bits
-// eq(i - 3 .. i + 4) its kind (the four three-in-a-row windows that cover it),
-// whether a stretch starts at i and at i + 1; the stretch starts as ballot
-// words (sw), whose highest set bit at or below a lane is its stretch's first
-// byte, found across the step's words and else carried from the steps before
-// (`carry`); the position in the stretch modulo 127 (runs) or 128 (literals)
-// says "first of its packet"; ballots of "first" and "writes its byte" (fw,
-// pw) give the byte offset by population counts, with the bytes of the steps
-// before carried in `base`. A packet's last byte knows its count and stores
-// the header byte at the packet's first byte.
+// One workgroup per row y and plane pl: rle_pack_row over the plane's bytes,
+// byte pl of the row's quads.
 __global__ __launch_bounds__(kThreads) void k_hdr_size(const uint32_t* __restrict__ quad, int W, int H,
                                                        uint32_t* __restrict__ rec, uint8_t* __restrict__ hdr,
                                                        uint32_t* __restrict__ plane_bytes) {
-    __shared__ uint64_t ew[kWaves + 2], sw[kWaves], fw[kWaves], pw[kWaves];
     const int y = blockIdx.x, pl = blockIdx.y;
     if (y >= H || pl >= 4) return;
     const uint32_t* __restrict__ row = quad + (size_t)y * (size_t)W;
     const int sh8 = 8 * pl;
-    const size_t at0 = ((size_t)y * 4 + (size_t)pl) * (size_t)W;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int carry = 0;      // first byte of the stretch open at the step's start
-    uint32_t base = 0;  // bytes of the coded plane before the step
-    for (int c0 = 0; c0 < W; c0 += kThreads) {
-        const int i = c0 + t;
-        const bool valid = i < W;
-        const uint64_t e = __ballot(hdr_eq(row, sh8, i, W));
-        if (lane == 0) ew[1 + w] = e;
-        if (w == 0) {  // eq(c0 - 3 .. c0 - 1)
-            const uint64_t b = __ballot(lane >= 61 && hdr_eq(row, sh8, c0 - 64 + lane, W));
-            if (lane == 0) ew[0] = b;
-        }
-        if (w == kWaves - 1) {  // eq(c0 + 256 .. c0 + 259)
-            const uint64_t b = __ballot(lane < 4 && hdr_eq(row, sh8, c0 + kThreads + lane, W));
-            if (lane == 0) ew[kWaves + 1] = b;
-        }
-        __syncthreads();
-        // bit k of win: eq(i - 3 + k)
-        const int pos = 61 + t, word = pos >> 6, sh = pos & 63;
-        const uint32_t win = (uint32_t)((ew[word] >> sh) | (sh ? ew[word + 1] << (64 - sh) : 0ull)) & 0xFFu;
-        const bool run = hdr_in_run(win >> 1);
-        const bool start = i == 0 || hdr_stretch_start(win & 0x7Fu);
-        const bool next_starts = i + 1 >= W || hdr_stretch_start(win >> 1);
-        const uint64_t s = __ballot(valid && start);
-        if (lane == 0) sw[w] = s;
-        __syncthreads();
-        int first_px = carry;
-        {
-            const uint64_t m = sw[w] & (~0ull >> (63 - lane));
-            if (m) {
-                first_px = c0 + 64 * w + top_bit(m);
-            } else {
-                for (int k = w - 1; k >= 0; --k)
-                    if (sw[k]) {
-                        first_px = c0 + 64 * k + top_bit(sw[k]);
-                        break;
-                    }
-            }
-        }
-        for (int k = kWaves - 1; k >= 0; --k)  // the same for every lane
-            if (sw[k]) {
-                carry = c0 + 64 * k + top_bit(sw[k]);
-                break;
-            }
-        const uint32_t q = (uint32_t)(i - first_px) % (run ? kHdrRunPacket : kHdrLitPacket);
-        const bool first = valid && q == 0u;
-        const bool writes = valid && (!run || q == 0u);
-        const uint64_t fb = __ballot(first), pb = __ballot(writes);
-        if (lane == 0) {
-            fw[w] = fb;
-            pw[w] = pb;
-        }
-        __syncthreads();
-        uint32_t off = base;
-        for (int k = 0; k < kWaves; ++k) {
-            const uint32_t n = (uint32_t)__popcll(pw[k]) + (uint32_t)__popcll(fw[k]);
-            if (k < w) off += n;
-            base += n;
-        }
-        const uint64_t below = (1ull << lane) - 1ull;
-        off += (uint32_t)__popcll(pw[w] & below) + (uint32_t)__popcll(fw[w] & below);
-        if (valid) {
-            rec[at0 + (size_t)i] = off | (writes ? kRecWrites : 0u) | (first ? kRecFirst : 0u);
-            if (q == (run ? kHdrRunPacket : kHdrLitPacket) - 1u || next_starts)
-                hdr[at0 + (size_t)(i - (int)q)] = (uint8_t)hdr_packet_header(run, q + 1u);
-        }
-    }
-    if (t == 0) plane_bytes[4 * (size_t)y + (size_t)pl] = base;
-}
-
-// Exclusive scan of one value a thread over the workgroup; returns the total.
-__device__ uint32_t hdr_wg_scan(uint32_t& v, uint32_t* lds_waves) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) lds_waves[w] = inc;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int k = 0; k < kWaves; ++k) {
-        if (k < w) before += lds_waves[k];
-        total += lds_waves[k];
-    }
-    v = before + inc - v;
-    __syncthreads();
-    return total;
+    const auto eq = [row, sh8, W](int j) {
+        if (j <= 0 || j >= W) return false;
+        return (((row[j] ^ row[j - 1]) >> sh8) & 255u) == 0u;
+    };
+    const uint32_t bytes = rle_pack_row<HdrRle>(eq, W, rec, hdr, ((size_t)y * 4 + (size_t)pl) * (size_t)W);
+    if (threadIdx.x == 0) plane_bytes[4 * (size_t)y + (size_t)pl] = bytes;
 }
 
 // A row's length is 4 plus its four planes: the rows' offsets in the body and
@@ -182,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void k_hdr_scan(int H, const uint32_t* __
             const uint4 p = *reinterpret_cast<const uint4*>(plane_bytes + 4 * (size_t)r);
             v = 4u + p.x + p.y + p.z + p.w;
         }
-        const uint32_t sum = hdr_wg_scan(v, ws);
+        const uint32_t sum = wg_exclusive_scan<kWaves>(v, ws);
         if (r < H) row_off[r] = base + v;
         base += sum;
     }
@@ -222,22 +122,6 @@ __global__ __launch_bounds__(kThreads) void k_hdr_emit(const uint32_t* __restric
     body[pos] = (uint8_t)(quad[(size_t)y * (size_t)W + (size_t)x] >> (8 * pl));
 }
 
-// The dense body to pinned host memory: [uint64 length][8 B pad][bytes], 16
-// bytes a thread (the body's buffer and the stream are whole 16-byte units).
-// A length above cap (never, by the rule) is reported as it is and the copy
-// stops at cap: the host refuses it.
-__global__ __launch_bounds__(kThreads) void k_hdr_gather(const uint8_t* __restrict__ body,
-                                                         const uint32_t* __restrict__ total, uint32_t cap,
-                                                         uint8_t* __restrict__ host) {
-    const uint32_t len = total[0];
-    const uint64_t o = 16ull * ((uint64_t)blockIdx.x * kThreads + threadIdx.x);
-    if (o == 0) *reinterpret_cast<uint4*>(host) = make_uint4(len, 0u, 0u, 0u);
-    if (o >= (uint64_t)min(len, cap)) return;
-    *reinterpret_cast<uint4*>(host + 16 + o) = *reinterpret_cast<const uint4*>(body + o);
-}
-
-inline size_t up16(size_t n) { return (n + 15) / 16 * 16; }
-
 }  // namespace
 
 bool hdr_plan(int W, int H, int C, HdrPlan& p) {
@@ -248,29 +132,22 @@ bool hdr_plan(int W, int H, int C, HdrPlan& p) {
 
 HdrBufs hdr_carve(const HdrPlan& p, uint32_t* base) {
     HdrBufs b{};
-    size_t at = 0;  // in 32-bit words; every part starts 16-byte aligned
-    auto take = [&](size_t bytes) {
-        uint32_t* r = base ? base + at : nullptr;
-        at += up16(bytes) / 4;
-        return r;
-    };
+    Carver c{base};
     const size_t npix = (size_t)p.W * (size_t)p.H;
-    b.quad = take(up16(npix * 4) + 16);
-    b.total = take(16);
+    b.quad = c.take(up16(npix * 4) + 16);
+    b.total = c.take(16);
     if (!p.flat) {
-        b.body = reinterpret_cast<uint8_t*>(take(up16(p.body_cap) + 16));
-        b.rec = take(npix * 16);
-        b.plane_bytes = take((size_t)p.H * 16);
-        b.row_off = take((size_t)p.H * 4);
-        b.hdr = reinterpret_cast<uint8_t*>(take(npix * 4));
+        b.body = reinterpret_cast<uint8_t*>(c.take(up16(p.body_cap) + 16));
+        b.rec = c.take(npix * 16);
+        b.plane_bytes = c.take((size_t)p.H * 16);
+        b.row_off = c.take((size_t)p.H * 4);
+        b.hdr = reinterpret_cast<uint8_t*>(c.take(npix * 4));
     }
-    b.words = at;
+    b.words = c.words;
     return b;
 }
 
 size_t hdr_scratch_words(const HdrPlan& p) { return hdr_carve(p, nullptr).words; }
-
-size_t hdr_stream_bytes(const HdrPlan& p) { return 16 + up16(p.body_cap); }
 
 void hdr_encode_device(const float4* d_film, float inv_spp, const HdrPlan& p, uint32_t* scratch, uint8_t* host_out,
                        hipStream_t st) {
@@ -291,9 +168,7 @@ void hdr_encode_device(const float4* d_film, float inv_spp, const HdrPlan& p, ui
                                                                                  b.body);
         body = b.body;
     }
-    const size_t units = up16(p.body_cap) / 16;
-    k_hdr_gather<<<dim3((unsigned)((units + kThreads - 1) / kThreads)), kThreads, 0, st>>>(body, b.total, p.body_cap,
-                                                                                           host_out);
+    body_gather(body, b.total, p.body_cap, host_out, st);
     RR_HIP(hipGetLastError());
 }
 

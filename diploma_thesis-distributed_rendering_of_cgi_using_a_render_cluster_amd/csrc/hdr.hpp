@@ -43,10 +43,9 @@ struct HdrBufs {
 };
 HdrBufs hdr_carve(const HdrPlan& p, uint32_t* base);  // base nullptr: only `words`
 size_t hdr_scratch_words(const HdrPlan& p);
-size_t hdr_stream_bytes(const HdrPlan& p);  // the pinned stream: 16 + the body rounded up to 16
 
 // Enqueues the coder on st: host_out (device-visible pinned memory of
-// hdr_stream_bytes) gets the stream. Reads the film, writes scratch and host_out.
+// body_stream_bytes(p.body_cap)) gets the stream. Reads the film, writes scratch and host_out.
 void hdr_encode_device(const float4* d_film, float inv_spp, const HdrPlan& p, uint32_t* scratch, uint8_t* host_out,
                        hipStream_t st);
 

@@ -20,37 +20,31 @@
 // W < 8 or W > 32767 is flat: W quads R, G, B, E and nothing else. Every other
 // row is the bytes 2, 2, W >> 8, W & 255 and then the R, the G, the B and the E
 // plane, W bytes each, coded on its own; packets never cross a plane or a row.
-// Within a plane:
-//  1. The plane is cut into maximal runs of equal consecutive bytes.
-//  2. A run of at least 4 bytes (Radiance's MINRUN) is a run stretch; a run of
-//     3 saves nothing once the literals around it are split.
-//  3. The bytes between run stretches, and between a run stretch and an end of
-//     the plane, form literal stretches.
-//  4. A run stretch of n bytes is n / 127 packets of 127, then one of the
-//     remainder if there is one (it may be shorter than 4; count 1 is legal);
-//     a literal stretch n / 128 packets of 128, then the remainder. A run
-//     packet is the byte 128 + count and the value, a literal packet the byte
-//     count and count bytes.
+// Within a plane the packets follow the shared rule of rle_rule.h with the
+// numbers of HdrRle:
+//  - a run of at least 4 bytes (Radiance's MINRUN) is a run stretch; a run of
+//    3 saves nothing once the literals around it are split;
+//  - a run packet stands for at most 127 bytes (a stretch's last may be
+//    shorter than 4; count 1 is legal), a literal packet holds at most 128. A
+//    run packet is the byte 128 + count and the value, a literal packet the
+//    byte count and count bytes.
 // A plane is longest when all of it is literal: W + ceil(W / 128) bytes.
 // Radiance's own encoder picks its packets differently (a greedy serial scan
 // with a special case for short runs); every decoder returns the same quads
 // from either.
 //
 // With eq(j) = "byte j equals byte j - 1" (false for j <= 0 and j >= W), byte
-// i lies in a run stretch when one of the four windows of three consecutive
-// eq bits that cover it, eq(i - 2 .. i) to eq(i + 1 .. i + 3), is all set; a
-// stretch starts at i when i = 0, when i's kind differs from i - 1's, or when
-// i is in a run stretch and !eq(i) (the next run).
+// i lies in a run stretch (rle_in_run) when one of the four windows of three
+// consecutive eq bits that cover it, eq(i - 2 .. i) to eq(i + 1 .. i + 3), is
+// all set.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIP__)
-#define RR_HDR_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define RR_HDR_HD inline
-#endif
+#include "rle_rule.h"
+
+#define RR_HDR_HD RR_RLE_HD
 
 namespace rr {
 
@@ -110,18 +104,11 @@ RR_HDR_HD uint64_t hdr_body_max_bytes(int W, int H) {
     return n < (1ull << 31) ? n : 0;
 }
 
-// Whether byte i is in a run stretch, from eq(i - 2 + k) in bit k of `e`
-// (k = 0 .. 5: eq(i - 2) .. eq(i + 3)).
-RR_HDR_HD bool hdr_in_run(uint32_t e) { return (e & (e >> 1) & (e >> 2) & 0xFu) != 0u; }
-
-// Whether a stretch starts at byte i > 0, from eq(i - 3 + k) in bit k of `e`
-// (k = 0 .. 6: eq(i - 3) .. eq(i + 3)).
-RR_HDR_HD bool hdr_stretch_start(uint32_t e) {
-    const bool run = hdr_in_run(e >> 1), before = hdr_in_run(e & 0x3Fu);
-    return run != before || (run && !((e >> 3) & 1u));
-}
-
-// The header byte of a packet of `count` bytes.
-RR_HDR_HD uint32_t hdr_packet_header(bool run, uint32_t count) { return (run ? 128u : 0u) + count; }
+// The numbers of the packet rule for a plane's bytes.
+struct HdrRle {
+    static constexpr uint32_t kMinRun = kHdrMinRun, kRunPacket = kHdrRunPacket, kLitPacket = kHdrLitPacket;
+    static constexpr uint32_t kElemBytes = 1;
+    static RR_HDR_HD uint32_t header(bool run, uint32_t count) { return (run ? 128u : 0u) + count; }
+};
 
 }  // namespace rr

@@ -672,6 +672,42 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
     return src == n;
 }
 
+// ------------------------------------------------- run-length packets ------
+namespace {
+
+// The packets of one row of W elements, T::kElemBytes bytes each, by the rule
+// of rle_rule.h with T's numbers, appended to out. Stated as a walk over the
+// maximal runs; the device packer (rle_device.hpp) states it as window
+// functions on eq bits and writes the same bytes.
+template <class T>
+void rle_pack_row(const uint8_t* row, size_t W, std::vector<uint8_t>& out) {
+    constexpr size_t c = T::kElemBytes;
+    // a stretch of n elements from element `from`: packets of the kind's cap, then the remainder
+    auto put_stretch = [&](size_t from, size_t n, bool run) {
+        const size_t cap = rle_packet_cap<T>(run);
+        for (size_t at = 0; at < n; at += cap) {
+            const size_t count = std::min(cap, n - at);
+            out.push_back((uint8_t)T::header(run, (uint32_t)count));
+            const uint8_t* el = row + c * (from + at);
+            out.insert(out.end(), el, el + c * (run ? 1 : count));
+        }
+    };
+    size_t lit = 0;  // first element of the open literal stretch
+    for (size_t x = 0; x < W;) {
+        size_t e = x + 1;  // the maximal run [x, e)
+        while (e < W && std::memcmp(row + c * e, row + c * x, c) == 0) ++e;
+        if (e - x >= T::kMinRun) {
+            put_stretch(lit, x - lit, false);
+            put_stretch(x, e - x, true);
+            lit = e;
+        }
+        x = e;
+    }
+    put_stretch(lit, W - lit, false);
+}
+
+}  // namespace
+
 // ------------------------------------------------------------- TARGA ------
 void tga_header_bytes(int W, int H, int C, bool rle, std::vector<uint8_t>& out) {
     out.clear();
@@ -710,27 +746,9 @@ bool encode_tga(const uint8_t* rgba, int W, int H, int C, bool rle, std::vector<
             out.insert(out.end(), row.begin(), row.end());
             continue;
         }
-        // a stretch of n pixels from pixel `from`: packets of 128, then the remainder
-        auto put_stretch = [&](size_t from, size_t n, bool run) {
-            for (size_t at = 0; at < n; at += kTgaPacket) {
-                const size_t count = std::min<size_t>(kTgaPacket, n - at);
-                out.push_back((uint8_t)tga_packet_header(run, (uint32_t)count));
-                const uint8_t* px = row.data() + c * (from + at);
-                out.insert(out.end(), px, px + c * (run ? 1 : count));
-            }
-        };
-        size_t lit = 0;  // first pixel of the open literal stretch
-        for (size_t x = 0; x < (size_t)W;) {
-            size_t e = x + 1;  // the maximal run [x, e)
-            while (e < (size_t)W && std::memcmp(row.data() + c * e, row.data() + c * x, c) == 0) ++e;
-            if (e - x >= tga_min_run(C)) {
-                put_stretch(lit, x - lit, false);
-                put_stretch(x, e - x, true);
-                lit = e;
-            }
-            x = e;
-        }
-        put_stretch(lit, (size_t)W - lit, false);
+        if (C == 1) rle_pack_row<TgaRle<1>>(row.data(), (size_t)W, out);
+        else if (C == 3) rle_pack_row<TgaRle<3>>(row.data(), (size_t)W, out);
+        else rle_pack_row<TgaRle<4>>(row.data(), (size_t)W, out);
     }
     return out.size() - kTgaHeaderBytes <= bound;
 }
@@ -775,28 +793,7 @@ bool encode_hdr(const float* rgba, int W, int H, int C, std::vector<uint8_t>& ou
         out.insert(out.end(), marker, marker + 4);
         for (int k = 0; k < 4; ++k) {
             for (int x = 0; x < W; ++x) plane[(size_t)x] = quads[4 * (size_t)x + k];
-            // a stretch of n bytes from byte `from`: packets of 127 (runs) or 128 (literals), then the remainder
-            auto put_stretch = [&](size_t from, size_t n, bool run) {
-                const size_t cap = run ? kHdrRunPacket : kHdrLitPacket;
-                for (size_t at = 0; at < n; at += cap) {
-                    const size_t count = std::min(cap, n - at);
-                    out.push_back((uint8_t)hdr_packet_header(run, (uint32_t)count));
-                    const uint8_t* b = plane.data() + from + at;
-                    out.insert(out.end(), b, b + (run ? 1 : count));
-                }
-            };
-            size_t lit = 0;  // first byte of the open literal stretch
-            for (size_t x = 0; x < (size_t)W;) {
-                size_t e = x + 1;  // the maximal run [x, e)
-                while (e < (size_t)W && plane[e] == plane[x]) ++e;
-                if (e - x >= kHdrMinRun) {
-                    put_stretch(lit, x - lit, false);
-                    put_stretch(x, e - x, true);
-                    lit = e;
-                }
-                x = e;
-            }
-            put_stretch(lit, (size_t)W - lit, false);
+            rle_pack_row<HdrRle>(plane.data(), (size_t)W, out);
         }
     }
     return out.size() - head <= bound;
@@ -835,27 +832,7 @@ bool encode_iris(const uint8_t* rgba, int W, int H, int C, std::vector<uint8_t>&
                 plane[(size_t)x] = C == 1 ? (uint8_t)grey8(p[0], p[1], p[2]) : p[z];
             }
             const size_t start = out.size();
-            // a stretch of n bytes from byte `from`: packets of 127, then the remainder
-            auto put_stretch = [&](size_t from, size_t len, bool run) {
-                for (size_t at = 0; at < len; at += kIrisPacket) {
-                    const size_t count = std::min<size_t>(kIrisPacket, len - at);
-                    out.push_back((uint8_t)iris_packet_header(run, (uint32_t)count));
-                    const uint8_t* b = plane.data() + from + at;
-                    out.insert(out.end(), b, b + (run ? 1 : count));
-                }
-            };
-            size_t lit = 0;  // first byte of the open literal stretch
-            for (size_t x = 0; x < (size_t)W;) {
-                size_t e = x + 1;  // the maximal run [x, e)
-                while (e < (size_t)W && plane[e] == plane[x]) ++e;
-                if (e - x >= kIrisMinRun) {
-                    put_stretch(lit, x - lit, false);
-                    put_stretch(x, e - x, true);
-                    lit = e;
-                }
-                x = e;
-            }
-            put_stretch(lit, (size_t)W - lit, false);
+            rle_pack_row<IrisRle>(plane.data(), (size_t)W, out);
             out.push_back(0);  // the terminator
             const size_t entry = (size_t)f + (size_t)z * (size_t)H;
             put_be32(kIrisHeaderBytes + 4 * entry, start);

@@ -41,10 +41,9 @@ struct IrisBufs {
 };
 IrisBufs iris_carve(const IrisPlan& p, uint32_t* base);  // base nullptr: only `words`
 size_t iris_scratch_words(const IrisPlan& p);
-size_t iris_stream_bytes(const IrisPlan& p);  // the pinned stream: 16 + the body rounded up to 16
 
 // Enqueues the coder on st: host_out (device-visible pinned memory of
-// iris_stream_bytes) gets the stream. Reads d_rgba, writes scratch and host_out.
+// body_stream_bytes(p.body_cap)) gets the stream. Reads d_rgba, writes scratch and host_out.
 void iris_encode_device(const uint8_t* d_rgba, const IrisPlan& p, uint32_t* scratch, uint8_t* host_out,
                         hipStream_t st);
 

@@ -11,15 +11,13 @@
 // its coded bytes, terminator included. The coded row-planes are contiguous:
 // file row 0 first, within a row channel 0 .. C - 1.
 //
-// The packet rule. No packet crosses a row-plane. Within a row-plane:
-//  1. It is cut into maximal runs of equal consecutive bytes.
-//  2. A run of at least 3 bytes is a run stretch.
-//  3. The bytes between run stretches, and between a run stretch and an end of
-//     the row-plane, form literal stretches (runs of 2 included).
-//  4. A stretch of n bytes is n / 127 packets of 127, then one of the remainder
-//     if there is one. A run packet is the byte count and the value, a literal
-//     packet the byte 0x80 | count and count bytes.
-//  5. After the last packet comes one 0 byte, the terminator.
+// The packet rule. No packet crosses a row-plane. Within a row-plane the
+// packets follow the shared rule of rle_rule.h with the numbers of IrisRle:
+//  - a run of at least 3 bytes is a run stretch (runs of 2 are literals);
+//  - a packet stands for at most 127 bytes: the count has 7 bits. A run packet
+//    is the byte count and the value, a literal packet the byte 0x80 | count
+//    and count bytes;
+//  - after the last packet comes one 0 byte, the terminator.
 // A row-plane is longest when all of it is literal: W + ceil(W / 127) + 1 bytes.
 // UNPINNED: the rule is the project's own and is not pinned against Blender's
 // files. Blender's writer, quoted from memory with no Blender to check it
@@ -28,21 +26,18 @@
 // returns the same pixels from either; the bytes of the files may differ.
 //
 // With eq(j) = "byte j equals byte j - 1" (false for j <= 0 and j >= W), byte i
-// lies in a run stretch when one of the three windows of two consecutive eq
-// bits that cover it is all set:
+// lies in a run stretch (rle_in_run) when one of the three windows of two
+// consecutive eq bits that cover it is all set:
 //   eq(i - 1) & eq(i) | eq(i) & eq(i + 1) | eq(i + 1) & eq(i + 2)
-// and a stretch starts at i when i = 0, when i's kind differs from i - 1's, or
-// when i is in a run stretch and !eq(i) (the next run). Integers only.
+// Integers only.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIP__)
-#define RR_IRIS_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define RR_IRIS_HD inline
-#endif
+#include "rle_rule.h"
+
+#define RR_IRIS_HD RR_RLE_HD
 
 namespace rr {
 
@@ -66,18 +61,11 @@ RR_IRIS_HD uint64_t iris_body_max_bytes(int W, int H, int C) {
     return bound < (1ull << 31) ? bound : 0;
 }
 
-// Whether byte i is in a run stretch, from eq(i - 2 + k) in bit k of `e`
-// (k = 1 .. 4: eq(i - 1) .. eq(i + 2); bit 0 is not read).
-RR_IRIS_HD bool iris_in_run(uint32_t e) { return (e & (e >> 1) & 0xEu) != 0u; }
-
-// Whether a stretch starts at byte i > 0, from eq(i - 3 + k) in bit k of `e`
-// (k = 1 .. 5: eq(i - 2) .. eq(i + 2)).
-RR_IRIS_HD bool iris_stretch_start(uint32_t e) {
-    const bool run = iris_in_run(e >> 1), before = iris_in_run(e);
-    return run != before || (run && !((e >> 3) & 1u));
-}
-
-// The header byte of a packet of `count` bytes, 1 .. 127.
-RR_IRIS_HD uint32_t iris_packet_header(bool run, uint32_t count) { return (run ? 0u : 0x80u) | count; }
+// The numbers of the packet rule for a row-plane's bytes (count: 1 .. 127).
+struct IrisRle {
+    static constexpr uint32_t kMinRun = kIrisMinRun, kRunPacket = kIrisPacket, kLitPacket = kIrisPacket;
+    static constexpr uint32_t kElemBytes = 1;
+    static RR_IRIS_HD uint32_t header(bool run, uint32_t count) { return (run ? 0u : 0x80u) | count; }
+};
 
 }  // namespace rr

@@ -213,24 +213,12 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
             const int rc = plan_or_refuse(fo.coder, fo.color_mode, sl->fs.W, sl->fs.H, sl->coded.deflate.plan);
             if (rc != RR_OK) return rc;
         }
-        if (fo.coder == Coder::Tga) {
-            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.tga.plan);
-            if (rc != RR_OK) return rc;
-        }
-        if (fo.coder == Coder::Hdr) {
-            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.hdr.plan);
-            if (rc != RR_OK) return rc;
-        }
-        if (fo.coder == Coder::Iris) {
-            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.iris.plan);
+        if (device_body(fo.coder)) {
+            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.body);
             if (rc != RR_OK) return rc;
         }
         sl->quality_warning.clear();
-        if (fo.coder == Coder::Webp) {
-            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.webp.plan);
-            if (rc != RR_OK) return rc;
-            sl->quality_warning = webp_quality_warning(fo.quality);
-        }
+        if (fo.coder == Coder::Webp) sl->quality_warning = webp_quality_warning(fo.quality);
         if (fo.coder == Coder::Png16) {
             set_device(c);
             ensure_srgb16(c);

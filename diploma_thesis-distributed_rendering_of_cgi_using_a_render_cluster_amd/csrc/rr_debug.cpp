@@ -49,16 +49,9 @@ int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, boo
     if (device_deflate(k))
         if (const int rc = plan_or_refuse(k, C, w, h, c->home_coded.deflate.plan)) return rc;
     const FrameOutput fo{k, C, png_compression_of(c->settings), quality, tga_raw};
-    if (k == Coder::Tga)
-        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.tga.plan)) return rc;
-    if (k == Coder::Hdr)
-        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.hdr.plan)) return rc;
-    if (k == Coder::Iris)
-        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.iris.plan)) return rc;
-    if (k == Coder::Webp) {
-        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.webp.plan)) return rc;
-        c->frame_warning = webp_quality_warning(quality);  // flagged as a frame's file is
-    }
+    if (device_body(k))
+        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.body)) return rc;
+    if (k == Coder::Webp) c->frame_warning = webp_quality_warning(quality);  // flagged as a frame's file is
     return guarded([&] {
         if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
         set_device(c);

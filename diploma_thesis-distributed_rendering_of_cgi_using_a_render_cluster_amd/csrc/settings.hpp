@@ -74,13 +74,17 @@ inline bool device_deflate(Coder k) {
     return k == Coder::Png8 || k == Coder::Png16 || k == Coder::Exr || k == Coder::Exr32;
 }
 
-// The coders that read only their slot's rgba8 / film and write slot buffers
-// only: the deflate formats, the TARGA packer (tga.hip), the HDR coder
-// (hdr.hip), the IRIS coder (iris.hip) and the WEBP coder (webp.hip). The next
-// frame waits for such a frame's image, not for its coder.
-inline bool slot_coder(Coder k) {
-    return device_deflate(k) || k == Coder::Tga || k == Coder::Hdr || k == Coder::Iris || k == Coder::Webp;
+// The body coders: the TARGA packer (tga.hip), the HDR coder (hdr.hip), the
+// IRIS coder (iris.hip) and the WEBP coder (webp.hip), which form a dense body
+// in the slot's scratch and gather it into the slot's pinned stream.
+inline bool device_body(Coder k) {
+    return k == Coder::Tga || k == Coder::Hdr || k == Coder::Iris || k == Coder::Webp;
 }
+
+// The coders that read only their slot's rgba8 / film and write slot buffers
+// only: the deflate formats and the body coders. The next frame waits for such
+// a frame's image, not for its coder.
+inline bool slot_coder(Coder k) { return device_deflate(k) || device_body(k); }
 
 // The output formats a frame can be submitted with.
 bool known_format(const char* format);

@@ -40,10 +40,9 @@ struct TgaBufs {
 };
 TgaBufs tga_carve(const TgaPlan& p, uint32_t* base);  // base nullptr: only `words`
 size_t tga_scratch_words(const TgaPlan& p);
-size_t tga_stream_bytes(const TgaPlan& p);  // the pinned stream: 16 + the body rounded up to 16
 
 // Enqueues the coder on st: host_out (device-visible pinned memory of
-// tga_stream_bytes) gets the stream. Reads d_rgba, writes scratch and host_out.
+// body_stream_bytes(p.body_cap)) gets the stream. Reads d_rgba, writes scratch and host_out.
 void tga_encode_device(const uint8_t* d_rgba, const TgaPlan& p, uint32_t* scratch, uint8_t* host_out, hipStream_t st);
 
 }  // namespace rr

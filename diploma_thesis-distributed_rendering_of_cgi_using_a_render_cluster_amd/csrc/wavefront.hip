@@ -129,7 +129,7 @@ void DevFrame::release() {
     prof.release();
     jpeg_coeffs.release(); jpeg_blk.release(); jpeg_scratch.release(); deflate_scratch.release();
     png_ftype.release(); png_raw.release();
-    tga_scratch.release(); hdr_scratch.release(); iris_scratch.release(); webp_scratch.release();
+    body_scratch.release();
 }
 
 namespace {

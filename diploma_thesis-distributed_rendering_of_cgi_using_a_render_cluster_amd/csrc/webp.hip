@@ -14,7 +14,7 @@
 // (a row's bits) -> k_webp_scan (the rows' offsets, the payload's length) ->
 // k_webp_zero (the words the tokens go to) -> k_webp_emit (a thread per pixel
 // ORs its token in at its row's offset + the scan of the tokens before it) ->
-// k_webp_gather (the dense payload to pinned host memory, 16 bytes a thread).
+// k_body_gather (the dense payload to pinned host memory, 16 bytes a thread).
 // Integer sums and ORs only, so nothing depends on the order of arrival: same
 // image -> same bytes. No workgroup waits for another; order comes from the
 // launches.
@@ -22,6 +22,7 @@
 
 #include "device.hpp"
 #include "prefix_code.hpp"
+#include "rle_device.hpp"
 #include "webp.hpp"
 #include "webp_rule.h"
 #include "wg_scan.hpp"
@@ -30,8 +31,9 @@ namespace rr {
 
 namespace {
 
-constexpr int kThreads = kWebpChunk;
-constexpr int kWaves = kThreads / 64;
+static_assert(kWebpChunk == kBodyChunk, "the shared step");
+constexpr int kThreads = kBodyChunk;
+constexpr int kWaves = kBodyWaves;
 static_assert(kThreads == kCodeThreads, "build_lengths strides by the workgroup");
 constexpr int kMaxRowGroups = 512;  // workgroups of the row kernels: each takes every kMaxRowGroups-th row
 // The header's words: its longest form, rounded up to whole 16-byte units.
@@ -51,8 +53,6 @@ __global__ __launch_bounds__(kThreads) void k_webp_residual(const uint32_t* __re
                                              : kWebpFirstPrediction;
     resid[i] = webp_sub(webp_pixel(rgba[i], C), pred);
 }
-
-__device__ __forceinline__ int top_bit(uint64_t m) { return 63 - __builtin_clzll(m); }
 
 // eq(j) of webp_rule.h in a row of W residuals.
 __device__ __forceinline__ bool webp_eq(const uint32_t* __restrict__ row, int j, int W) {
@@ -369,22 +369,6 @@ __global__ __launch_bounds__(kThreads) void k_webp_emit(const uint32_t* __restri
     }
 }
 
-// The dense payload to pinned host memory: [uint64 length][8 B pad][bytes], 16
-// bytes a thread (the payload's buffer and the stream are whole 16-byte units).
-// A length above cap (never, by the bound) is reported as it is and the copy
-// stops at cap: the host refuses it.
-__global__ __launch_bounds__(kThreads) void k_webp_gather(const uint8_t* __restrict__ body,
-                                                          const uint32_t* __restrict__ meta, uint32_t cap,
-                                                          uint8_t* __restrict__ host) {
-    const uint32_t len = meta[1];
-    const uint64_t o = 16ull * ((uint64_t)blockIdx.x * kThreads + threadIdx.x);
-    if (o == 0) *reinterpret_cast<uint4*>(host) = make_uint4(len, 0u, 0u, 0u);
-    if (o >= (uint64_t)min(len, cap)) return;
-    *reinterpret_cast<uint4*>(host + 16 + o) = *reinterpret_cast<const uint4*>(body + o);
-}
-
-inline size_t up16(size_t n) { return (n + 15) / 16 * 16; }
-
 // The payload buffer's bytes: the bound in whole 16-byte units and two more,
 // and at least the header's words.
 inline size_t body_bytes(const WebpPlan& p) {
@@ -402,28 +386,21 @@ bool webp_plan(int W, int H, int C, WebpPlan& p) {
 
 WebpBufs webp_carve(const WebpPlan& p, uint32_t* base) {
     WebpBufs b{};
-    size_t at = 0;  // in 32-bit words; every part starts 16-byte aligned
-    auto take = [&](size_t bytes) {
-        uint32_t* r = base ? base + at : nullptr;
-        at += up16(bytes) / 4;
-        return r;
-    };
+    Carver c{base};
     const size_t n = (size_t)p.W * (size_t)p.H;
-    b.body = take(body_bytes(p));
-    b.hist = take((size_t)kWebpSyms * 4);
-    b.codes = take((size_t)kWebpSyms * 4);
-    b.meta = take(16);
-    b.row_off = reinterpret_cast<uint64_t*>(take((size_t)p.H * 8));
-    b.row_bits = take((size_t)p.H * 4);
-    b.resid = take(n * 4);
-    b.rec = take(n * 4);
-    b.words = at;
+    b.body = c.take(body_bytes(p));
+    b.hist = c.take((size_t)kWebpSyms * 4);
+    b.codes = c.take((size_t)kWebpSyms * 4);
+    b.meta = c.take(16);
+    b.row_off = reinterpret_cast<uint64_t*>(c.take((size_t)p.H * 8));
+    b.row_bits = c.take((size_t)p.H * 4);
+    b.resid = c.take(n * 4);
+    b.rec = c.take(n * 4);
+    b.words = c.words;
     return b;
 }
 
 size_t webp_scratch_words(const WebpPlan& p) { return webp_carve(p, nullptr).words; }
-
-size_t webp_stream_bytes(const WebpPlan& p) { return 16 + up16(p.body_cap); }
 
 void webp_encode_device(const uint8_t* d_rgba, const WebpPlan& p, uint32_t* scratch, uint8_t* host_out,
                         hipStream_t st) {
@@ -441,9 +418,7 @@ void webp_encode_device(const uint8_t* d_rgba, const WebpPlan& p, uint32_t* scra
     k_webp_scan<<<1, kThreads, 0, st>>>(H, b.row_bits, b.row_off, b.meta);
     k_webp_zero<<<dim3((unsigned)((units + kThreads - 1) / kThreads)), kThreads, 0, st>>>(b.body, b.meta, units);
     k_webp_emit<<<rows, kThreads, 0, st>>>(b.resid, b.rec, b.codes, W, H, b.row_off, b.meta, b.body, words);
-    const size_t out_units = up16(p.body_cap) / 16;
-    k_webp_gather<<<dim3((unsigned)((out_units + kThreads - 1) / kThreads)), kThreads, 0, st>>>(
-        reinterpret_cast<const uint8_t*>(b.body), b.meta, p.body_cap, host_out);
+    body_gather(b.body, b.meta + 1, p.body_cap, host_out, st);  // meta[1]: the payload's bytes
     RR_HIP(hipGetLastError());
 }
 

@@ -41,10 +41,9 @@ struct WebpBufs {
 };
 WebpBufs webp_carve(const WebpPlan& p, uint32_t* base);  // base nullptr: only `words`
 size_t webp_scratch_words(const WebpPlan& p);
-size_t webp_stream_bytes(const WebpPlan& p);  // the pinned stream: 16 + the payload rounded up to 16
 
 // Enqueues the coder on st: host_out (device-visible pinned memory of
-// webp_stream_bytes) gets the stream. Reads d_rgba, writes scratch and host_out.
+// body_stream_bytes(p.body_cap)) gets the stream. Reads d_rgba, writes scratch and host_out.
 void webp_encode_device(const uint8_t* d_rgba, const WebpPlan& p, uint32_t* scratch, uint8_t* host_out,
                         hipStream_t st);
 

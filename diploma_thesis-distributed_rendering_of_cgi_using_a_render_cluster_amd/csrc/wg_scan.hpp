@@ -1,5 +1,5 @@
-// A workgroup's exclusive scan, for the run-length coders' offset kernels
-// (iris.hip; tga.hip and hdr.hip each keep their earlier private copy).
+// A workgroup's exclusive scan, for the body coders' offset kernels (tga.hip,
+// hdr.hip, iris.hip, webp.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -10,9 +10,11 @@
 //  - a plain decoder of the file returns quads, and they are the quads of an
 //    RGBE statement written here with frexp and ldexp in double;
 //  - every plane's packets obey the caps, and the file is within its bound;
-//  - the packets that follow from hdr_in_run / hdr_stretch_start on windows of
-//    eq bits, walked the way hdr.hip k_hdr_size does a lane at a time, are the
-//    same bytes.
+//  - the packets that follow from rle_in_run / rle_stretch_start with HdrRle's
+//    numbers on windows of eq bits, walked the way the device packer
+//    (rle_device.hpp) does a lane at a time (rle_check.h), are the same bytes.
+// And over all 256 windows the generic window functions equal the closed form
+// of hdr_rule.h's comment.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -23,6 +25,7 @@
 #include "grey.h"
 #include "hdr_rule.h"
 #include "image_io.hpp"
+#include "rle_check.h"
 
 using namespace rr;
 
@@ -94,29 +97,6 @@ static std::vector<float> make_image(int W, int H, int kind) {
     return img;
 }
 
-// One plane's packets from the eq bits and the rule's window functions, a byte
-// ("lane") at a time as k_hdr_size forms them.
-static void pack_by_windows(const std::vector<uint8_t>& p, std::vector<uint8_t>& out) {
-    const int W = (int)p.size();
-    auto eq = [&](int j) { return j > 0 && j < W && p[(size_t)j] == p[(size_t)j - 1]; };
-    int first = 0;
-    for (int i = 0; i < W; ++i) {
-        uint32_t win = 0;  // bit k: eq(i - 3 + k)
-        for (int k = 0; k < 8; ++k) win |= (uint32_t)eq(i - 3 + k) << k;
-        const bool run = hdr_in_run(win >> 1);
-        const bool start = i == 0 || hdr_stretch_start(win & 0x7Fu);
-        const bool next_starts = i + 1 >= W || hdr_stretch_start(win >> 1);
-        if (start) first = i;
-        const uint32_t cap = run ? kHdrRunPacket : kHdrLitPacket;
-        const uint32_t q = (uint32_t)(i - first) % cap;
-        if (q == cap - 1u || next_starts) {  // a packet's last byte knows its count
-            out.push_back((uint8_t)hdr_packet_header(run, q + 1u));
-            if (run) out.push_back(p[(size_t)i]);
-            else out.insert(out.end(), p.begin() + (i - (int)q), p.begin() + i + 1);
-        }
-    }
-}
-
 static void check_image(const std::vector<float>& img, int W, int H, int C, const char* what) {
     std::vector<uint8_t> file;
     CHECK(encode_hdr(img.data(), W, H, C, file), "%s %dx%d C=%d refused", what, W, H, C);
@@ -164,7 +144,7 @@ static void check_image(const std::vector<float>& img, int W, int H, int C, cons
             }
             CHECK(ok, "%s %dx%d C=%d row %d plane %d: a packet of count 0, over the plane or the file", what, W, H, C, y, k);
             CHECK(got == plane, "%s %dx%d C=%d row %d plane %d: decoded bytes differ", what, W, H, C, y, k);
-            pack_by_windows(plane, again);
+            pack_by_windows<HdrRle>(plane, again);
         }
     }
     CHECK(!ok || pos == file.size(), "%s %dx%d: %zu trailing bytes", what, W, H, file.size() - pos);
@@ -175,6 +155,12 @@ static void check_image(const std::vector<float>& img, int W, int H, int C, cons
 }
 
 int main() {
+    // the four windows of three consecutive eq bits that cover the byte
+    CHECK(window_mismatches<HdrRle>([](auto eq) {
+              return (eq(-2) & eq(-1) & eq(0)) | (eq(-1) & eq(0) & eq(1)) | (eq(0) & eq(1) & eq(2)) |
+                     (eq(1) & eq(2) & eq(3));
+          }) == 0,
+          "HdrRle: the window functions differ from the closed form");
     const int widths[] = {1, 7, 8, 9, 63, 64, 65, 127, 128, 129, 255, 256, 257, 513, 32767, 32768};
     for (int W : widths)
         for (int H = 1; H <= 3; ++H) {

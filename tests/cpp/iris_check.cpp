@@ -12,9 +12,11 @@
 //  - the tables are in the stated order and contiguous, the lengths are the
 //    bytes the row-planes take, the file ends with the last one and is within
 //    its bound;
-//  - the packets that follow from iris_in_run / iris_stretch_start on windows
-//    of eq bits, walked the way iris.hip k_iris_size does a lane at a time, are
-//    the same bytes.
+//  - the packets that follow from rle_in_run / rle_stretch_start with IrisRle's
+//    numbers on windows of eq bits, walked the way the device packer
+//    (rle_device.hpp) does a lane at a time (rle_check.h), are the same bytes.
+// And over all 256 windows the generic window functions equal the closed form
+// of iris_rule.h's comment.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -23,6 +25,7 @@
 #include "grey.h"
 #include "image_io.hpp"
 #include "iris_rule.h"
+#include "rle_check.h"
 
 using namespace rr;
 
@@ -72,29 +75,6 @@ static std::vector<uint8_t> make_image(int W, int H, int kind) {
         if (kind != 3 && rnd() % 7u == 0u) p[rnd() % 4u] ^= 0x55;  // a channel of its own
     }
     return img;
-}
-
-// One row-plane's packets from the eq bits and the rule's window functions, a
-// byte ("lane") at a time as k_iris_size forms them, and the terminator.
-static void pack_by_windows(const std::vector<uint8_t>& p, std::vector<uint8_t>& out) {
-    const int W = (int)p.size();
-    auto eq = [&](int j) { return j > 0 && j < W && p[(size_t)j] == p[(size_t)j - 1]; };
-    int first = 0;
-    for (int i = 0; i < W; ++i) {
-        uint32_t win = 0;  // bit k: eq(i - 3 + k)
-        for (int k = 0; k < 7; ++k) win |= (uint32_t)eq(i - 3 + k) << k;
-        const bool run = iris_in_run(win >> 1);
-        const bool start = i == 0 || iris_stretch_start(win & 0x3Fu);
-        const bool next_starts = i + 1 >= W || iris_stretch_start(win >> 1);
-        if (start) first = i;
-        const uint32_t q = (uint32_t)(i - first) % kIrisPacket;
-        if (q == kIrisPacket - 1u || next_starts) {  // a packet's last byte knows its count
-            out.push_back((uint8_t)iris_packet_header(run, q + 1u));
-            if (run) out.push_back(p[(size_t)i]);
-            else out.insert(out.end(), p.begin() + (i - (int)q), p.begin() + i + 1);
-        }
-    }
-    out.push_back(0);
 }
 
 static void check_image(const std::vector<uint8_t>& img, int W, int H, int C, const char* what) {
@@ -151,7 +131,8 @@ static void check_image(const std::vector<uint8_t>& img, int W, int H, int C, co
             CHECK(got == plane, "%s %dx%d C=%d row %d channel %d: decoded bytes differ", what, W, H, C, f, z);
             CHECK(len <= iris_plane_max_bytes((uint64_t)W), "%s %dx%d row %d channel %d: above the row's bound", what, W, H,
                   f, z);
-            pack_by_windows(plane, again);
+            pack_by_windows<IrisRle>(plane, again);
+            again.push_back(0);  // the terminator
         }
     CHECK(expect == file.size(), "%s %dx%d C=%d: %zu trailing bytes", what, W, H, C, file.size() - expect);
     CHECK(again.size() == file.size() - body0 - 8 * n &&
@@ -160,6 +141,8 @@ static void check_image(const std::vector<uint8_t>& img, int W, int H, int C, co
 }
 
 int main() {
+    CHECK(window_mismatches<IrisRle>([](auto eq) { return (eq(-1) & eq(0)) | (eq(0) & eq(1)) | (eq(1) & eq(2)); }) == 0,
+          "IrisRle: the window functions differ from the closed form");
     const int widths[] = {1, 2, 3, 4, 5, 63, 64, 65, 126, 127, 128, 129, 253, 254, 255, 256, 257, 381, 382, 513};
     const char* names[] = {"random", "short runs", "long runs", "one colour"};
     for (int W : widths)

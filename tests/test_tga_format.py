@@ -5,7 +5,9 @@ the reader rejects what it should."""
 import ctypes
 import io
 import os
+import shutil
 import struct
+import subprocess
 import types
 
 import numpy as np
@@ -13,7 +15,7 @@ import pytest
 from PIL import Image
 
 import tga as T
-from conftest import ROOT
+from conftest import PKG, ROOT
 
 MODES = {"BW": 1, "RGB": 3, "RGBA": 4}
 IMAGES = T.images()
@@ -134,6 +136,27 @@ def test_refusals(rr, tmp_path):
         rr.encode_image(wide[:, :4], str(tmp_path / "z"), "BMP")
     assert e.value.code == n.RR_ENOTSUP
     assert "TARGA" in str(e.value)
+
+
+def test_tga_check_program(tmp_path):
+    """tests/cpp/tga_check.cpp: the host coder and the rule functions alone (host code, no HIP
+    header), built with the system C++ compiler under AddressSanitizer and UBSan, run as a
+    child process, as tests/test_iris_format.py does."""
+    csrc = os.path.join(ROOT, PKG, "csrc")
+    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no system C++ compiler"
+    exe = str(tmp_path / "tga_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-ffp-contract=off",
+           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", csrc,
+           os.path.join(ROOT, "tests", "cpp", "tga_check.cpp"), os.path.join(csrc, "image_io.cpp"), "-o", exe, "-lz",
+           "-lpthread"]
+    build = subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True, text=True)
+    if build.returncode != 0:
+        build = subprocess.run(cmd, capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "tga_check: ok" in run.stdout
 
 
 def test_abi_and_naming(rr):
