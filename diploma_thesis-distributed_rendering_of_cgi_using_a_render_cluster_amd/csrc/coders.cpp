@@ -1,6 +1,6 @@
-// The coders of a frame's file: the dispatch to the device coders (jpeg.hip,
-// png.hip, png16.hip, exr.hip, tga.hip, hdr.hip, iris.hip, webp.hip), the host-built files around their streams, and
-// the host coders of an RGBA8 image. See frame.hpp.
+// The coders of a frame's file: the dispatch to the device coders (formats.hpp
+// lists them), the host-built files around their streams, and the host coders
+// of an RGBA8 image. See frame.hpp.
 #include <cerrno>
 #include <cstring>
 
@@ -33,42 +33,6 @@ void ensure_jpeg_table(rr_ctx* c, int quality) {
     c->jpeg_tab_quality = quality;
 }
 
-int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p) {
-    const bool ok = k == Coder::Png8    ? png_plan(W, H, C, p)
-                    : k == Coder::Png16 ? png16_plan(W, H, C, p)
-                    : k == Coder::Exr32 ? exr32_plan(W, H, C, p)
-                                        : exr_plan(W, H, C, p);
-    if (ok) return RR_OK;
-    const char* name = k == Coder::Png8    ? "PNG"
-                       : k == Coder::Png16 ? "16-bit PNG"
-                       : k == Coder::Exr32 ? "32-bit EXR"
-                                           : "EXR";
-    return fail(RR_EINVAL, std::string("image size outside the device ") + name + " encoder's range");
-}
-
-static const char* const kIrisRange =
-    "image size outside the IRIS format's range (65535 x 65535, a body bound below 2 GB)";
-static const char* const kWebpRange =
-    "image size outside the WEBP format's range (16384 x 16384, a payload bound below 2 GB)";
-
-int plan_or_refuse(const FrameOutput& fo, int W, int H, BodyOut& o) {
-    const int C = fo.color_mode;
-    switch (fo.coder) {
-    case Coder::Tga:
-        if (tga_plan(W, H, C, !fo.tga_raw, o.tga)) return RR_OK;
-        return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
-    case Coder::Hdr:
-        if (hdr_plan(W, H, C, o.hdr)) return RR_OK;
-        return fail(RR_EINVAL, "image size outside the HDR coder's range (a body bound below 2 GB)");
-    case Coder::Iris:
-        return iris_plan(W, H, C, o.iris) ? RR_OK : fail(RR_EINVAL, kIrisRange);
-    case Coder::Webp:
-        return webp_plan(W, H, C, o.webp) ? RR_OK : fail(RR_EINVAL, kWebpRange);
-    default:
-        return RR_OK;  // no body coder: nothing to plan
-    }
-}
-
 std::string webp_quality_warning(int quality) {
     if (quality >= 100) return "";
     return "WEBP at quality " + std::to_string(quality) +
@@ -77,81 +41,113 @@ std::string webp_quality_warning(int quality) {
 
 namespace {
 
-// Device encode by a body coder (TARGA, HDR, IRIS, WEBP) into o's pinned
-// stream, by the format's plan p: launch(scratch, host_out) enqueues it.
-template <class Plan, class Launch>
-void enqueue_body(const char* name, const Plan& p, size_t scratch_words, const CoderInput& in, DevFrame& f,
-                  hipStream_t st, BodyOut& o, Launch launch) {
-    if (p.W != in.W || p.H != in.H) throw std::runtime_error(std::string(name) + " plan of another image");
-    f.body_scratch.ensure(scratch_words);
-    o.stream.ensure(body_stream_bytes(p.body_cap));
-    void* dev_host = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
-    f.prof.begin(st, RR_K_PNG);
-    launch(f.body_scratch.ptr, static_cast<uint8_t*>(dev_host));
-    f.prof.end(st);
+// One body coder, every fact of it here. plan: the format's plan in o and its
+// BodyShape (scratch words; what a body holds at least); false: a size out of
+// range. launch: enqueues the coder. file: the file around a body of len bytes.
+struct BodyCoder {
+    bool (*plan)(const FrameOutput& fo, int W, int H, CodedOut& o);
+    void (*launch)(const CoderInput& in, const CodedOut& o, uint32_t* scratch, uint8_t* out, hipStream_t st);
+    void (*file)(const CodedOut& o, const uint8_t* body, size_t len, std::vector<uint8_t>& data);
+};
+
+template <class Plan>
+bool shaped(CodedOut& o, Coder k, const Plan& p, size_t scratch_words, uint64_t min_len) {
+    o.body = {k, p.W, p.H, p.body_cap, scratch_words, min_len};
+    return true;
 }
 
-void enqueue_body(Coder k, const CoderInput& in, DevFrame& f, hipStream_t st, BodyOut& o) {
-    if (k == Coder::Tga)
-        enqueue_body("TARGA", o.tga, tga_scratch_words(o.tga), in, f, st, o, [&](uint32_t* scratch, uint8_t* out) {
-            tga_encode_device(in.rgba8, o.tga, scratch, out, st);
-        });
-    else if (k == Coder::Hdr)
-        enqueue_body("HDR", o.hdr, hdr_scratch_words(o.hdr), in, f, st, o, [&](uint32_t* scratch, uint8_t* out) {
-            hdr_encode_device(in.film, in.inv_spp, o.hdr, scratch, out, st);
-        });
-    else if (k == Coder::Iris)
-        enqueue_body("IRIS", o.iris, iris_scratch_words(o.iris), in, f, st, o, [&](uint32_t* scratch, uint8_t* out) {
-            iris_encode_device(in.rgba8, o.iris, scratch, out, st);
-        });
-    else
-        enqueue_body("WEBP", o.webp, webp_scratch_words(o.webp), in, f, st, o, [&](uint32_t* scratch, uint8_t* out) {
-            webp_encode_device(in.rgba8, o.webp, scratch, out, st);
-        });
+const BodyCoder kTga = {
+    [](const FrameOutput& fo, int W, int H, CodedOut& o) {  // a raw body has its exact length
+        return tga_plan(W, H, fo.color_mode, !fo.tga_raw, o.tga) &&
+               shaped(o, fo.coder, o.tga, tga_scratch_words(o.tga), o.tga.rle ? 0 : o.tga.body_cap);
+    },
+    [](const CoderInput& in, const CodedOut& o, uint32_t* scratch, uint8_t* out, hipStream_t st) {
+        tga_encode_device(in.rgba8, o.tga, scratch, out, st);
+    },
+    [](const CodedOut& o, const uint8_t* body, size_t len, std::vector<uint8_t>& data) {
+        tga_header_bytes(o.tga.W, o.tga.H, o.tga.C, o.tga.rle, data);
+        data.insert(data.end(), body, body + len);
+    }};
+const BodyCoder kHdr = {
+    [](const FrameOutput& fo, int W, int H, CodedOut& o) {  // so has a flat one
+        return hdr_plan(W, H, fo.color_mode, o.hdr) &&
+               shaped(o, fo.coder, o.hdr, hdr_scratch_words(o.hdr), o.hdr.flat ? o.hdr.body_cap : 0);
+    },
+    [](const CoderInput& in, const CodedOut& o, uint32_t* scratch, uint8_t* out, hipStream_t st) {
+        hdr_encode_device(in.film, in.inv_spp, o.hdr, scratch, out, st);
+    },
+    [](const CodedOut& o, const uint8_t* body, size_t len, std::vector<uint8_t>& data) {
+        hdr_header_bytes(o.hdr.W, o.hdr.H, data);
+        data.insert(data.end(), body, body + len);
+    }};
+const BodyCoder kIris = {
+    [](const FrameOutput& fo, int W, int H, CodedOut& o) {  // the tables; of every row-plane a packet and its terminator
+        return iris_plan(W, H, fo.color_mode, o.iris) &&
+               shaped(o, fo.coder, o.iris, iris_scratch_words(o.iris), (8 + 3) * (uint64_t)o.iris.H * (uint64_t)o.iris.C);
+    },
+    [](const CoderInput& in, const CodedOut& o, uint32_t* scratch, uint8_t* out, hipStream_t st) {
+        iris_encode_device(in.rgba8, o.iris, scratch, out, st);
+    },
+    [](const CodedOut& o, const uint8_t* body, size_t len, std::vector<uint8_t>& data) {
+        iris_header_bytes(o.iris.W, o.iris.H, o.iris.C, data);
+        data.insert(data.end(), body, body + len);
+    }};
+const BodyCoder kWebp = {
+    [](const FrameOutput& fo, int W, int H, CodedOut& o) {  // the 5 bytes of signature and sizes
+        return webp_plan(W, H, fo.color_mode, o.webp) && shaped(o, fo.coder, o.webp, webp_scratch_words(o.webp), 5);
+    },
+    [](const CoderInput& in, const CodedOut& o, uint32_t* scratch, uint8_t* out, hipStream_t st) {
+        webp_encode_device(in.rgba8, o.webp, scratch, out, st);
+    },
+    [](const CodedOut&, const uint8_t* body, size_t len, std::vector<uint8_t>& data) {
+        webp_wrap_stream(body, len, data);  // the RIFF and chunk headers, and the pad byte
+    }};
+const BodyCoder& body_coder(Coder k) {
+    return k == Coder::Tga ? kTga : k == Coder::Hdr ? kHdr : k == Coder::Iris ? kIris : kWebp;
 }
 
-// The checked length of the body in o's stream: within the plan's bound
-// body_cap and the stream, and at least min_len (an exact length: body_cap).
-uint64_t body_stream_len(const BodyOut& o, const char* name, uint32_t body_cap, uint64_t min_len) {
+// The length at the head of o's stream, which `what` coded: over(len, cap) says
+// whether it is more than that coder can have left in a stream of cap bytes.
+template <class Over>
+uint64_t stream_len(const CodedOut& o, const std::string& what, Over over) {
     uint64_t len = 0;
     std::memcpy(&len, o.stream.ptr, sizeof len);
-    if (len > body_cap || len + 16 > o.stream.cap || len < min_len)
-        throw std::runtime_error(std::string("device ") + name + " stream overflow");
+    if (over(len, o.stream.cap)) throw std::runtime_error("device " + what + " stream overflow");
     return len;
 }
 
-// The file of a device-coded TARGA, HDR, IRIS or WEBP image: the host-built
-// header + the device body. What a body holds at least: a raw TARGA and a flat
-// HDR body their exact length; IRIS the tables and every coded row-plane a
-// packet and its terminator; WEBP the 5 bytes of signature and sizes, inside
-// the host-built RIFF and chunk headers.
-void body_file_bytes(const BodyOut& o, Coder k, std::vector<uint8_t>& data) {
-    const uint8_t* body = o.stream.ptr + 16;
-    if (k == Coder::Tga) {
-        const TgaPlan& p = o.tga;
-        const uint64_t len = body_stream_len(o, "TARGA", p.body_cap, p.rle ? 0 : p.body_cap);
-        tga_header_bytes(p.W, p.H, p.C, p.rle, data);
-        data.insert(data.end(), body, body + len);
-    } else if (k == Coder::Hdr) {
-        const HdrPlan& p = o.hdr;
-        const uint64_t len = body_stream_len(o, "HDR", p.body_cap, p.flat ? p.body_cap : 0);
-        hdr_header_bytes(p.W, p.H, data);
-        data.insert(data.end(), body, body + len);
-    } else if (k == Coder::Iris) {
-        const IrisPlan& p = o.iris;
-        const uint64_t planes = (uint64_t)p.H * (uint64_t)p.C;
-        const uint64_t len = body_stream_len(o, "IRIS", p.body_cap, 8 * planes + 3 * planes);
-        iris_header_bytes(p.W, p.H, p.C, data);
-        data.insert(data.end(), body, body + len);
-    } else {
-        webp_wrap_stream(body, (size_t)body_stream_len(o, "WEBP", o.webp.body_cap, 5), data);
-    }
+// The pinned memory p as the device addresses it.
+template <class T>
+T* device_pointer(const PinnedBuf& p) {
+    void* dev = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev, p.ptr, 0));
+    return static_cast<T*>(dev);
+}
+
+// Device encode by body coder k into o's pinned stream, by the plan in o.
+void enqueue_body(Coder k, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o) {
+    const BodyShape& b = o.body;
+    if (b.coder != k || b.W != in.W || b.H != in.H)
+        throw std::runtime_error(std::string(coder_info(k).name) + " plan of another image");
+    f.body_scratch.ensure(b.scratch_words);
+    o.stream.ensure(body_stream_bytes(b.body_cap));
+    f.prof.begin(st, RR_K_PNG);
+    body_coder(k).launch(in, o, f.body_scratch.ptr, device_pointer<uint8_t>(o.stream), st);
+    f.prof.end(st);
+}
+
+// The file of body coder k's image: a body within the plan's bound and the stream, no less than its least.
+void body_file_bytes(const CodedOut& o, Coder k, std::vector<uint8_t>& data) {
+    const BodyShape& b = o.body;
+    const uint64_t len = stream_len(o, coder_info(k).name, [&](uint64_t len, size_t cap) {
+        return len > b.body_cap || len + 16 > cap || len < b.min_len;
+    });
+    body_coder(k).file(o, o.stream.ptr + 16, (size_t)len, data);
 }
 
 // Device JPEG encode of an RGBA8 image (transform into f.jpeg_coeffs + Huffman
 // coding) into o's pinned stream. grey: a one-component file (RR_COLOR_BW).
-void enqueue_jpeg(rr_ctx* c, const CoderInput& in, bool grey, int quality, DevFrame& f, hipStream_t st, JpegOut& o) {
+void enqueue_jpeg(rr_ctx* c, const CoderInput& in, bool grey, int quality, DevFrame& f, hipStream_t st, CodedOut& o) {
     const int W = in.W, H = in.H;
     if (!c->jpeg_huff.ptr) {
         quiesce(c);
@@ -166,37 +162,30 @@ void enqueue_jpeg(rr_ctx* c, const CoderInput& in, bool grey, int quality, DevFr
     f.jpeg_blk.ensure(2 * nblocks + 2 * mcuy);
     f.jpeg_scratch.ensure(mcuy * jpeg_row_scratch_words(W, grey));
     o.stream.ensure(jpeg_stream_max_bytes(W, H, grey) + 16);
-    o.W = W;
-    o.H = H;
-    o.quality = quality;
-    o.grey = grey;
-    void* dev_host = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, o.stream.ptr, 0));
+    o.jpeg = {W, H, quality, grey};
     uint32_t* blk = f.jpeg_blk.ptr;
     JpegDevBufs b{blk, blk + nblocks, blk + 2 * nblocks, blk + 2 * nblocks + mcuy, f.jpeg_scratch.ptr};
     jpeg_encode_device(in.rgba8, W, H, grey, in.jpeg_tab, c->jpeg_huff.ptr, f.jpeg_coeffs.ptr, b,
-                       static_cast<uint8_t*>(dev_host), st);
+                       device_pointer<uint8_t>(o.stream), st);
 }
 
 // The file of a device-coded JPEG: host-built header + the device stream.
-void jpeg_file_bytes(const JpegOut& o, std::vector<uint8_t>& data) {
-    uint64_t len = 0;
-    std::memcpy(&len, o.stream.ptr, sizeof len);
-    if (len + 16 > o.stream.cap) throw std::runtime_error("device JPEG stream overflow");
-    jpeg_header_bytes(o.W, o.H, o.quality, data, o.grey);
+void jpeg_file_bytes(const CodedOut& o, std::vector<uint8_t>& data) {
+    const uint64_t len =
+        stream_len(o, coder_info(Coder::Jpeg).name, [](uint64_t len, size_t cap) { return len + 16 > cap; });
+    jpeg_header_bytes(o.jpeg.W, o.jpeg.H, o.jpeg.quality, data, o.jpeg.grey);
     data.insert(data.end(), o.stream.ptr + 16, o.stream.ptr + 16 + len);
 }
 
 // The file of a deflate-coded image: the host-built container of format k
 // around the device stream. C: the channels the stream was coded with.
-void deflate_file_bytes(const DeflateOut& o, Coder k, int C, std::vector<uint8_t>& data) {
-    const DeflatePlan& p = o.plan;
+void deflate_file_bytes(const CodedOut& o, Coder k, int C, std::vector<uint8_t>& data) {
+    const DeflatePlan& p = o.deflate;
     const uint32_t* tab = reinterpret_cast<const uint32_t*>(o.tab.ptr);
-    uint64_t len = 0;
-    std::memcpy(&len, o.stream.ptr, sizeof len);
     // one stream: its bound counts the 4 bytes of Adler-32 the host adds
-    if (len > o.stream.cap || len + 16 + (p.own_stream ? 0 : 4) > o.stream.cap)
-        throw std::runtime_error("device deflate stream overflow");
+    const uint64_t len = stream_len(o, "deflate", [&](uint64_t len, size_t cap) {
+        return len > cap || len + 16 + (p.own_stream ? 0 : 4) > cap;
+    });
     switch (k) {
     case Coder::Png8:
     case Coder::Png16:
@@ -216,11 +205,23 @@ void deflate_file_bytes(const DeflateOut& o, Coder k, int C, std::vector<uint8_t
 
 }  // namespace
 
+int plan_or_refuse(const FrameOutput& fo, int W, int H, CodedOut& o) {
+    const Coder k = fo.coder;
+    const int C = fo.color_mode;
+    DeflatePlan& p = o.deflate;
+    const bool ok = k == Coder::Png8    ? png_plan(W, H, C, p)
+                    : k == Coder::Png16 ? png16_plan(W, H, C, p)
+                    : k == Coder::Exr   ? exr_plan(W, H, C, p)
+                    : k == Coder::Exr32 ? exr32_plan(W, H, C, p)
+                                        : !device_body(k) || body_coder(k).plan(fo, W, H, o);
+    return ok ? RR_OK : fail(RR_EINVAL, coder_info(k).range);
+}
+
 void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o) {
     const Coder k = fo.coder;
     const int C = fo.color_mode;
-    if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o.jpeg);
-    if (device_body(k)) return enqueue_body(k, in, f, st, o.body);
+    if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o);
+    if (device_body(k)) return enqueue_body(k, in, f, st, o);
     if (!device_deflate(k)) throw std::runtime_error("no device coder for this output");
     // the front ends' own buffers. "PNG" at compression 0 .. 100: a filter type
     // per row of the H rows, and at 16 bits the raw scanlines, 2C W H bytes
@@ -238,17 +239,13 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
     if (adaptive) f.png_ftype.ensure((size_t)in.H);
     if (adaptive && k == Coder::Png16) f.png_raw.ensure((size_t)2 * (size_t)C * (size_t)in.W * (size_t)in.H);
     // the coder's scratch and its pinned outputs
-    DeflateOut& d = o.deflate;
-    const DeflatePlan& p = d.plan;
+    const DeflatePlan& p = o.deflate;
     f.deflate_scratch.ensure(deflate_scratch_words(p));
-    d.stream.ensure((p.own_stream ? exr_stream_max_bytes(p) : deflate_stream_max_bytes(p)) + 32);
-    d.tab.ensure((size_t)p.nbands * (p.own_stream ? 4 : 2) * sizeof(uint32_t));
-    void *dev_host = nullptr, *dev_tab = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev_host, d.stream.ptr, 0));
-    RR_HIP(hipHostGetDevicePointer(&dev_tab, d.tab.ptr, 0));
+    o.stream.ensure((p.own_stream ? exr_stream_max_bytes(p) : deflate_stream_max_bytes(p)) + 32);
+    o.tab.ensure((size_t)p.nbands * (p.own_stream ? 4 : 2) * sizeof(uint32_t));
     uint32_t* scratch = f.deflate_scratch.ptr;
-    uint8_t* out = static_cast<uint8_t*>(dev_host);
-    uint32_t* tab = static_cast<uint32_t*>(dev_tab);
+    uint8_t* out = device_pointer<uint8_t>(o.stream);
+    uint32_t* tab = device_pointer<uint32_t>(o.tab);
     f.prof.begin(st, RR_K_PNG);
     switch (k) {
     case Coder::Png8:
@@ -270,48 +267,32 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
 }
 
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data) {
-    if (fo.coder == Coder::Jpeg) jpeg_file_bytes(o.jpeg, data);
-    else if (device_body(fo.coder)) body_file_bytes(o.body, fo.coder, data);
-    else deflate_file_bytes(o.deflate, fo.coder, fo.color_mode, data);
+    if (fo.coder == Coder::Jpeg) jpeg_file_bytes(o, data);
+    else if (device_body(fo.coder)) body_file_bytes(o, fo.coder, data);
+    else deflate_file_bytes(o, fo.coder, fo.color_mode, data);
 }
 
 int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,
               uint64_t* bytes, int mode, int compression) {
     if (!out_path || !format) return fail(RR_EINVAL, "out_path and format are required");
-    const std::string fmt(format);
+    const Format* f = find_format(format);
+    if (!f || coder_info(f->coder).film) return fail(RR_ENOTSUP, unsupported_format(format, true));
+    const Coder k = f->coder;
+    const int C = resolve_color_mode(mode, f->no_alpha);
+    const bool adaptive = compression >= 0;  // "PNG"
     std::vector<uint8_t> data;
-    std::string ext;
-    if (fmt == "JPEG") {
+    if (k == Coder::Jpeg) {
         if (quality < 1 || quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
-        if (!encode_jpeg(rgba, W, H, quality, data, 0, resolve_color_mode(mode, true) == RR_COLOR_BW))
-            return fail(RR_EINVAL, "JPEG encode failed");
-        ext = ".jpg";
-    } else if (fmt == "PNG") {
-        const bool adaptive = compression >= 0;
-        if (!encode_png(rgba, W, H, data, adaptive ? png_zlib_level(compression) : 1, 0, resolve_color_mode(mode, false),
-                        adaptive))
+        if (!encode_jpeg(rgba, W, H, quality, data, 0, C == RR_COLOR_BW)) return fail(RR_EINVAL, "JPEG encode failed");
+    } else if (k == Coder::Png8) {
+        if (!encode_png(rgba, W, H, data, adaptive ? png_zlib_level(compression) : 1, 0, C, adaptive))
             return fail(RR_EIO, "PNG encode failed");
-        ext = ".png";
-    } else if (fmt == "TARGA" || fmt == "TARGA_RAW") {
-        if (!encode_tga(rgba, W, H, resolve_color_mode(mode, false), fmt == "TARGA", data))
-            return fail(RR_EINVAL, "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)");
-        ext = ".tga";
-    } else if (fmt == "IRIS") {
-        if (!encode_iris(rgba, W, H, resolve_color_mode(mode, false), data)) return fail(RR_EINVAL, kIrisRange);
-        ext = ".rgb";
-    } else if (fmt == "WEBP") {  // lossless at every quality: the caller flags one below 100
-        if (!encode_webp(rgba, W, H, resolve_color_mode(mode, false), data)) return fail(RR_EINVAL, kWebpRange);
-        ext = ".webp";
-    } else if (fmt == "OPEN_EXR" || fmt == "HDR") {
-        return fail(RR_ENOTSUP, "unsupported output format '" + fmt +
-                                    "' for an RGBA8 image: it needs the float film (JPEG, PNG, TARGA, TARGA_RAW, "
-                                    "IRIS and WEBP are supported here)");
-    } else {
-        return fail(RR_ENOTSUP, "unsupported output format '" + fmt +
-                                    "' (JPEG, PNG, TARGA, TARGA_RAW, IRIS and WEBP are supported here; OPEN_EXR and "
-                                    "HDR need the float film)");
+    } else if (!(k == Coder::Tga    ? encode_tga(rgba, W, H, C, !f->tga_raw, data)
+                 : k == Coder::Iris ? encode_iris(rgba, W, H, C, data)
+                                    : encode_webp(rgba, W, H, C, data))) {  // lossless: the caller flags a quality below 100
+        return fail(RR_EINVAL, coder_info(k).range);
     }
-    const std::string path = std::string(out_path) + ext;
+    const std::string path = std::string(out_path) + f->ext;
     if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
     if (bytes) *bytes = data.size();
     return RR_OK;

@@ -280,9 +280,8 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     DevFrame& f = sl.dev;
     DevBuild& build = sl.tiles ? sl.build : s->build;
     FrameSlot* prev = c->last_enqueued;
-    // (the deflate coder, the TARGA packer, the HDR, the IRIS and the WEBP coder read their
-    // slot's rgba8 / film and write slot buffers only, so the next frame waits
-    // for the image, ev[5], not for the coder)
+    // (a slot coder, formats.hpp, reads its slot's rgba8 / film and writes slot
+    // buffers only, so the next frame waits for the image, ev[5], not for the coder)
     if (prev && prev != &sl && !(sl.tiles && prev->tiles))
         RR_HIP(hipStreamWaitEvent(st, slot_coder(prev->out.coder) ? prev->ev[5] : prev->ev[2], 0));
     c->last_enqueued = &sl;
@@ -332,8 +331,8 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
         } else {
             RR_HIP(hipEventRecord(sl.ev[5], st));
             // Png16: the film again, through exposure and view transform, at 16
-            // bits; OPEN_EXR and HDR: the film's means, the product finish_frame
-            // forms, no view transform; TARGA, IRIS and WEBP read rgba8 and none of these
+            // bits; the other film coders: the film's means, the product
+            // finish_frame forms, no view transform; the rest read rgba8 and none of these
             in.inv_spp = k.inv_spp;
             in.exposure_scale = k.exposure_scale;
             in.view_transform = fs.view_transform;

@@ -45,35 +45,20 @@ struct PinnedBuf {
     }
 };
 
-// The pinned outputs of a deflate-coded image (deflate.hpp): the stream
-// [uint64 length][pad][bytes] and the bands' table, 2 or 4 words per band by
-// the plan's own_stream. The plan is made before the coder is enqueued
-// (plan_or_refuse).
-struct DeflateOut {
-    PinnedBuf stream, tab;
-    rr::DeflatePlan plan{};
-};
-
-// The pinned output of a device-coded JPEG, [uint64 length][pad][bytes], and
-// what it was coded with: the file's header is built from these.
+// What a device-coded JPEG was coded with: the file's header is built from these.
 struct JpegOut {
-    PinnedBuf stream;
     int W = 0, H = 0, quality = 0;
     bool grey = false;
 };
 
-// The pinned output of a device-coded TARGA, HDR or IRIS body or WEBP payload,
-// [uint64 length][8 B pad][bytes] (tga.hpp, hdr.hpp, iris.hpp, webp.hpp), of
-// body_stream_bytes. A frame writes one file, so the four share the stream. The
-// format's plan is made before the coder is enqueued (plan_or_refuse); the host
-// builds the file's header (WEBP: the RIFF and chunk headers and the pad byte)
-// from it.
-struct BodyOut {
-    PinnedBuf stream;
-    rr::TgaPlan tga{};
-    rr::HdrPlan hdr{};
-    rr::IrisPlan iris{};
-    rr::WebpPlan webp{};
+// What every body coder's plan says: whose it is, the image, the body's bound, the
+// slot scratch the coder takes and the least a body holds (an exact length: body_cap).
+struct BodyShape {
+    Coder coder = Coder::None;
+    int W = 0, H = 0;
+    uint32_t body_cap = 0;
+    size_t scratch_words = 0;
+    uint64_t min_len = 0;
 };
 
 // The pinned stream of a body of at most body_cap bytes: 16 + the body rounded
@@ -81,11 +66,20 @@ struct BodyOut {
 inline size_t body_stream_bytes(uint32_t body_cap) { return 16 + ((size_t)body_cap + 15) / 16 * 16; }
 
 // Where the device coders write: a frame slot has one, and the context one
-// more for the inspection entry points.
+// more for the inspection entry points. A frame writes one file, so every coder
+// writes the one pinned stream, [uint64 length][8 B pad][bytes]; a deflate
+// coder also the bands' table, 2 or 4 words per band by the plan's own_stream.
+// The rest is what the host builds the file's header or container from; the
+// plans are made before the coder is enqueued (plan_or_refuse).
 struct CodedOut {
+    PinnedBuf stream, tab;
     JpegOut jpeg;
-    DeflateOut deflate;
-    BodyOut body;
+    rr::DeflatePlan deflate{};
+    BodyShape body;  // of the plan below that the frame's format uses
+    rr::TgaPlan tga{};
+    rr::HdrPlan hdr{};
+    rr::IrisPlan iris{};
+    rr::WebpPlan webp{};
 };
 
 struct FrameRun {
@@ -107,8 +101,8 @@ struct FrameSlot {
     bool busy = false;
     uint64_t ticket = 0;
     // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
-    // work done, 3 outputs on the host (after their copies), 5 (device PNG,
-    // EXR, TARGA, HDR, IRIS and WEBP frames) before the slot's coder: the state shared between frames is free
+    // work done, 3 outputs on the host (after their copies), 5 (frames of a
+    // slot_coder) before the slot's coder: the state shared between frames is free
     hipEvent_t ev[6] = {};
     // The slot's frames run on its own stream and write only its own device
     // state, so a k_tiles frame runs on the GPU beside the other slots'
@@ -265,7 +259,7 @@ void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int
 
 // ---- the device coders (coders.cpp) ----------------------------------------
 
-// The image a coder reads. rgba8: Jpeg, Png8, Tga, Iris and Webp; film: Png16, Exr, Exr32 and Hdr,
+// The image a coder reads (formats.hpp CoderInfo::film): rgba8, or the film,
 // W x H float4 sums scaled by inv_spp. exposure_scale, view_transform, look
 // and gamma (resolved: resolve_view, or an inspection call's own check): Png16,
 // which takes the film through exposure and view transform again at 16 bits.
@@ -283,14 +277,11 @@ struct CoderInput {
     const float* jpeg_tab = nullptr;
 };
 
-// The plan of a deflate-coded image of C channels. A size outside the coder's
-// range is refused (RR_EINVAL), never rerouted: there is no other coder that
+// The plan of a W x H image for fo's deflate or body coder, into o (any other
+// coder has none: RR_OK). A size outside the coder's range is refused
+// (RR_EINVAL, CoderInfo::range), never rerouted: there is no other coder that
 // writes the same file.
-int plan_or_refuse(Coder k, int C, int W, int H, DeflatePlan& p);
-// The same for the image of a body coder (fo.coder: Tga, Hdr, Iris or Webp),
-// into that format's plan of o. Refused: a TARGA or IRIS side above 65535, a
-// WEBP side above 16384, and a body bound of 2 GB and more.
-int plan_or_refuse(const FrameOutput& fo, int W, int H, BodyOut& o);
+int plan_or_refuse(const FrameOutput& fo, int W, int H, CodedOut& o);
 // What a WEBP file of this quality is flagged with (rr_last_warning): "" at 100
 // and above, else that the file is lossless, as lossy WEBP is not built.
 std::string webp_quality_warning(int quality);
@@ -305,18 +296,17 @@ void ensure_jpeg_table(rr_ctx* c, int quality);
 // Enqueue the device coder that `fo` names (Jpeg ... Webp) on stream st, with
 // f's scratch and profiler, into o's pinned buffers. fo.color_mode: the file's
 // channels; fo.png_compression ("PNG"): LEGACY the Sub front end, 0 .. 100 the
-// adaptive one (the device coders have one effort level). A deflate format
-// codes by o.deflate.plan, a TARGA, HDR, IRIS or WEBP one by its plan in o.body
-// (plan_or_refuse).
+// adaptive one (the device coders have one effort level). A deflate or body
+// coder codes by its plan in o (plan_or_refuse).
 void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o);
 
 // The file of a device-coded image, once its stream is on the host: the
 // host-built header or container around it.
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data);
 
-// The host coders: an RGBA8 image as a "JPEG", "PNG", "TARGA", "TARGA_RAW", "IRIS" or "WEBP"
-// file at out_path + its extension ("OPEN_EXR" and "HDR" need the float film: RR_ENOTSUP). mode: a colour mode as rr_set_color_mode takes it, 0 the format's
-// own layout. compression ("PNG"): LEGACY, or 0 .. 100 (rr_set_png_compression).
+// The host coders: an RGBA8 image as a file of `format` at out_path + its
+// extension (a format that needs the float film: RR_ENOTSUP). mode: a colour
+// mode as rr_set_color_mode takes it, 0 the format's own layout. compression ("PNG"): LEGACY, or 0 .. 100 (rr_set_png_compression).
 int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,
               uint64_t* bytes, int mode = 0, int compression = RR_PNG_COMPRESSION_LEGACY);
 

@@ -41,7 +41,8 @@ void rr_render_params_default(rr_render_params* p) {
 
 // The warning of a host encode, which has no context: rr_last_warning(NULL).
 static void set_encode_warning(const char* format, int quality) {
-    g_warn = format && std::string(format) == "WEBP" ? webp_quality_warning(quality) : "";
+    const Format* f = find_format(format);
+    g_warn = f && f->coder == Coder::Webp ? webp_quality_warning(quality) : "";
 }
 
 int32_t rr_abi_version(void) { return RR_ABI_VERSION; }
@@ -188,9 +189,7 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
     if (!c || !s || !ticket) return fail(RR_EINVAL, "NULL ctx, scene or ticket");
     if (s->ctx && s->ctx != c) return fail(RR_EINVAL, "scene belongs to another context");
     if (out_path && !format) return fail(RR_EINVAL, "format is required when out_path is given");
-    if (format && !known_format(format))
-        return fail(RR_ENOTSUP, std::string("unsupported output format '") + format +
-                                    "' (JPEG, PNG, OPEN_EXR, TARGA, TARGA_RAW, HDR, IRIS and WEBP are supported)");
+    if (format && !known_format(format)) return fail(RR_ENOTSUP, unsupported_format(format));
     const FrameOutput fo = resolve_output(c->settings, s->desc.render, format, out_path != nullptr, jpeg_quality);
     if (fo.coder == Coder::Jpeg && (jpeg_quality < 1 || jpeg_quality > 100))
         return fail(RR_EINVAL, "jpeg_quality must be 1..100");
@@ -209,14 +208,7 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->scene = s;
         sl->out_path = out_path ? out_path : "";
         sl->out = fo;
-        if (device_deflate(fo.coder)) {
-            const int rc = plan_or_refuse(fo.coder, fo.color_mode, sl->fs.W, sl->fs.H, sl->coded.deflate.plan);
-            if (rc != RR_OK) return rc;
-        }
-        if (device_body(fo.coder)) {
-            const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded.body);
-            if (rc != RR_OK) return rc;
-        }
+        if (const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded)) return rc;
         sl->quality_warning.clear();
         if (fo.coder == Coder::Webp) sl->quality_warning = webp_quality_warning(fo.quality);
         if (fo.coder == Coder::Png16) {

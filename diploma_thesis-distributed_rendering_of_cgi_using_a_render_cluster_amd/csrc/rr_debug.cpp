@@ -32,8 +32,8 @@ int debug_view_settings(const rr_ctx* c, int view, int& look, float& gamma) {
     return RR_OK;
 }
 
-// The body of the coders' entry points: a w x h image of the caller's (RGBA8
-// for Jpeg, Png8, Tga, Iris and Webp, float RGBA means for the others) through coder k in C
+// The body of the coders' entry points: a w x h image of the caller's (RGBA8,
+// or float RGBA means for a coder of the film, CoderInfo::film) through coder k in C
 // channels, with the context's PNG compression; the file's bytes to `out` if
 // `cap` suffices. alpha_one, view_transform, exposure_scale: CoderInput's.
 int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, bool alpha_one, int view_transform,
@@ -46,18 +46,13 @@ int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, boo
     in.view_transform = view_transform;
     if (k == Coder::Png16)
         if (const int rc = debug_view_settings(c, view_transform, in.look, in.gamma)) return rc;
-    if (device_deflate(k))
-        if (const int rc = plan_or_refuse(k, C, w, h, c->home_coded.deflate.plan)) return rc;
     const FrameOutput fo{k, C, png_compression_of(c->settings), quality, tga_raw};
-    if (device_body(k))
-        if (const int rc = plan_or_refuse(fo, w, h, c->home_coded.body)) return rc;
+    if (const int rc = plan_or_refuse(fo, w, h, c->home_coded)) return rc;
     if (k == Coder::Webp) c->frame_warning = webp_quality_warning(quality);  // flagged as a frame's file is
     return guarded([&] {
         if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
         set_device(c);
-        const bool bytes8 = k == Coder::Jpeg || k == Coder::Png8 || k == Coder::Tga || k == Coder::Iris ||
-                            k == Coder::Webp;
-        const size_t bytes = (size_t)w * h * (bytes8 ? 4 : sizeof(float4));
+        const size_t bytes = (size_t)w * h * (coder_info(k).film ? sizeof(float4) : 4);
         DevBuf<uint8_t> img;
         img.ensure(bytes);
         RR_HIP(hipMemcpy(img.ptr, image, bytes, hipMemcpyHostToDevice));
@@ -119,38 +114,30 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
                            int32_t jpeg_quality, uint8_t* out, uint64_t cap, uint64_t* len) {
     if (!c || !format || !image || !len || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
     if (!valid_color_mode(color_mode)) return fail(RR_EINVAL, "bad colour mode");
-    const std::string fmt(format);
-    const bool jpeg = fmt == "JPEG", hdr = fmt == "HDR";
-    const int C = resolve_color_mode(color_mode, jpeg || hdr);
-    Coder k = Coder::None;
-    if (jpeg) {
-        if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "JPEG takes an RGBA8 image at depth 8");
-        if (w > 65535 || h > 65535) return fail(RR_EINVAL, "image size outside the JPEG format's range");
-        if (jpeg_quality < 1 || jpeg_quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
-        k = Coder::Jpeg;
-    } else if (fmt == "PNG" && (depth == 0 || depth == 8)) {
-        if (image_is_float) return fail(RR_EINVAL, "8-bit PNG takes an RGBA8 image");
-        k = Coder::Png8;
-    } else if (fmt == "TARGA" || fmt == "TARGA_RAW") {  // 8 bits a channel and no other depth
-        if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "TARGA takes an RGBA8 image at depth 8");
-        k = Coder::Tga;
-    } else if (fmt == "IRIS") {  // the same
-        if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "IRIS takes an RGBA8 image at depth 8");
-        k = Coder::Iris;
-    } else if (fmt == "WEBP") {  // the same; jpeg_quality below 100 is flagged (rr_last_warning), the file lossless
-        if (image_is_float || (depth != 0 && depth != 8)) return fail(RR_EINVAL, "WEBP takes an RGBA8 image at depth 8");
-        k = Coder::Webp;
-    } else if (hdr) {  // the film's floats and no other depth
-        if (!image_is_float || (depth != 0 && depth != 32)) return fail(RR_EINVAL, "HDR takes a float RGBA image at depth 32");
-        k = Coder::Hdr;
-    } else {
-        if (!image_is_float) return fail(RR_EINVAL, "16-bit PNG and OPEN_EXR take a float RGBA image");
-        if (fmt == "PNG" && depth == 16) k = Coder::Png16;
-        else if (fmt == "OPEN_EXR" && (depth == 0 || depth == 16 || depth == 32)) k = depth == 32 ? Coder::Exr32 : Coder::Exr;
-        else return fail(RR_EINVAL, "no such format and depth: '" + fmt + "' at " + std::to_string(depth));
+    const Format* f = find_format(format);
+    const int C = resolve_color_mode(color_mode, f && f->no_alpha);
+    // A format of one coder takes that coder's image at its depth. Where the depth chooses the coder, a depth
+    // that is no coder's names none, as an unknown format does: both are asked for a float image, then refused.
+    const bool fixed = f && !f->deep_depth;
+    Coder k = f ? format_coder(*f, depth) : Coder::None;
+    const bool depth_ok = depth == 0 || depth == coder_info(k).depth;
+    if (!fixed && !depth_ok) k = Coder::None;
+    const CoderInfo& ci = coder_info(k);
+    const bool film = k == Coder::None || ci.film;
+    if ((image_is_float != 0) != film || (fixed && !depth_ok)) {
+        const std::string image = film ? "a float RGBA image" : "an RGBA8 image";
+        if (fixed) return fail(RR_EINVAL, ci.name + (" takes " + image) + " at depth " + std::to_string(ci.depth));
+        return fail(RR_EINVAL, film ? "16-bit PNG and OPEN_EXR take " + image : "8-bit PNG takes " + image);
     }
+    if (k == Coder::None)
+        return fail(RR_EINVAL, std::string("no such format and depth: '") + format + "' at " + std::to_string(depth));
+    if (k == Coder::Jpeg) {
+        if (w > 65535 || h > 65535) return fail(RR_EINVAL, ci.range);
+        if (jpeg_quality < 1 || jpeg_quality > 100) return fail(RR_EINVAL, "jpeg_quality must be 1..100");
+    }
+    // (WEBP: a jpeg_quality below 100 is flagged, rr_last_warning, the file lossless)
     return debug_encode(c, k, C, image, w, h, true, view_transform, exposure_scale, jpeg_quality, out, cap, len,
-                        fmt == "TARGA_RAW");
+                        f->tga_raw);
 }
 
 int rr_debug_hdr_host(const float* rgba, int32_t w, int32_t h, int32_t color_mode, uint8_t* out, uint64_t cap,
@@ -160,7 +147,7 @@ int rr_debug_hdr_host(const float* rgba, int32_t w, int32_t h, int32_t color_mod
     return guarded([&] {
         std::vector<uint8_t> data;
         if (!encode_hdr(rgba, w, h, resolve_color_mode(color_mode, true), data))
-            return fail(RR_EINVAL, "image size outside the HDR coder's range (a body bound below 2 GB)");
+            return fail(RR_EINVAL, coder_info(Coder::Hdr).range);
         *bytes = data.size();
         if (out && cap >= *bytes) std::memcpy(out, data.data(), data.size());
         return RR_OK;

@@ -175,17 +175,31 @@ bool settings_from_env(OutputSettings& s, std::string& err) {
     return true;
 }
 
-bool known_format(const char* format) {
-    const std::string f(format ? format : "");
-    return f == "JPEG" || f == "PNG" || f == "OPEN_EXR" || f == "TARGA" || f == "TARGA_RAW" || f == "HDR" ||
-           f == "IRIS" || f == "WEBP";
+const char* coder_ext(Coder k) {
+    if (k == Coder::HostRgba) k = Coder::Png8;  // the host's file of the same format
+    for (const Format& f : kFormats)
+        if (f.coder == k || (f.deep_depth && f.deep == k)) return f.ext;
+    return "";
 }
 
-const char* coder_ext(Coder k) {
-    if (k == Coder::Hdr) return ".hdr";
-    if (k == Coder::Iris) return ".rgb";
-    if (k == Coder::Webp) return ".webp";
-    return k == Coder::Jpeg ? ".jpg" : (k == Coder::Exr || k == Coder::Exr32) ? ".exr" : k == Coder::Tga ? ".tga" : ".png";
+// kFormats' names as a refusal lists them, "A, B and C". film: 1 the formats
+// that need the float film, 0 those of an RGBA8 image, -1 all.
+static std::string format_names(int film) {
+    std::string s, last;
+    for (const Format& f : kFormats) {
+        if (film >= 0 && coder_info(f.coder).film != (film != 0)) continue;
+        if (!last.empty()) s += (s.empty() ? "" : ", ") + last;
+        last = f.name;
+    }
+    return s.empty() ? last : s + " and " + last;
+}
+
+std::string unsupported_format(const std::string& format, bool rgba8) {
+    const std::string head = "unsupported output format '" + format + "'";
+    if (!rgba8) return head + " (" + format_names(-1) + " are supported)";
+    if (known_format(format.c_str()))
+        return head + " for an RGBA8 image: it needs the float film (" + format_names(0) + " are supported here)";
+    return head + " (" + format_names(0) + " are supported here; " + format_names(1) + " need the float film)";
 }
 
 int resolve_color_mode(int mode, bool no_alpha) {
@@ -195,28 +209,19 @@ int resolve_color_mode(int mode, bool no_alpha) {
 
 FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const char* format, bool has_path,
                            int jpeg_quality) {
-    const bool jpeg = has_path && std::string(format) == "JPEG";
-    const bool exr = has_path && std::string(format) == "OPEN_EXR";
-    const bool tga_raw = has_path && std::string(format) == "TARGA_RAW";
-    const bool tga = tga_raw || (has_path && std::string(format) == "TARGA");
-    const bool hdr = has_path && std::string(format) == "HDR";
-    const bool iris = has_path && std::string(format) == "IRIS";
-    const bool webp = has_path && std::string(format) == "WEBP";
+    const Format* f = has_path ? find_format(format) : nullptr;
     FrameOutput o;
-    o.tga_raw = tga_raw;
-    if (!has_path) o.coder = Coder::None;
-    else if (jpeg) o.coder = Coder::Jpeg;
-    else if (tga) o.coder = Coder::Tga;  // 8 bits a channel: the depth settings do not apply
-    else if (hdr) o.coder = Coder::Hdr;  // RGBE quads of the film's means: nor do they here
-    else if (iris) o.coder = Coder::Iris;  // 8 bits a channel, as TARGA; it has alpha: RGBA stays RGBA
-    else if (webp) o.coder = Coder::Webp;  // the same; lossless at every quality
-    else if (exr)  // HALF unless the context, or at 0 the scene, asks for FLOAT channels
-        o.coder = (s.exr_depth ? s.exr_depth : r.exr_depth) == 32 ? Coder::Exr32 : Coder::Exr;
-    // "PNG". 16 bits per sample: always the device coder (there is no host one)
-    else if ((s.png_depth ? s.png_depth : r.color_depth) == 16) o.coder = Coder::Png16;
-    else o.coder = s.device_png ? Coder::Png8 : Coder::HostRgba;
+    if (f) {
+        // the context's depth, at 0 the scene's: HALF or FLOAT channels, 8 or 16 bits per sample
+        const int depth = f->coder == Coder::Exr ? (s.exr_depth ? s.exr_depth : r.exr_depth)
+                                                 : (s.png_depth ? s.png_depth : r.color_depth);
+        o.coder = format_coder(*f, depth);
+        // 8 bits: the host coder unless the context asks (16 has no host coder)
+        if (o.coder == Coder::Png8 && !s.device_png) o.coder = Coder::HostRgba;
+        o.tga_raw = f->tga_raw;
+    }
     // the context's mode, at 0 the scene's, at 0 again the format's own layout
-    o.color_mode = resolve_color_mode(s.color_mode ? s.color_mode : r.color_mode, jpeg || hdr);
+    o.color_mode = resolve_color_mode(s.color_mode ? s.color_mode : r.color_mode, f && f->no_alpha);
     // the context's setting, at SCENE the scene's (-1, legacy, where it has no field)
     o.png_compression = s.png_compression == RR_PNG_COMPRESSION_SCENE ? r.png_compression : s.png_compression;
     o.quality = jpeg_quality;

@@ -8,6 +8,7 @@
 
 #include <string>
 
+#include "formats.hpp"
 #include "rr.h"
 
 namespace rr {
@@ -56,45 +57,26 @@ bool setting_from_text(OutputSettings& s, const std::string& var, const char* te
 // Every variable that is set, in the order above. false + err: s is unchanged.
 bool settings_from_env(OutputSettings& s, std::string& err);
 
-// Who codes a frame's output. HostRgba: the 8-bit image comes back to the host
-// (rr_render_frame_to_memory; a "PNG" file from the host's zlib threads where a
-// path is given). Jpeg ... Exr32: coded on the device, the file written from the
-// slot's pinned stream. Png8: "PNG" with rr_set_device_png; Png16: "PNG" at 16
-// bits per sample, for which there is no host coder. Exr: "OPEN_EXR" with HALF
-// channels; Exr32: with FLOAT channels (rr_set_exr_depth). Tga: "TARGA" and
-// "TARGA_RAW" (FrameOutput::tga_raw), always 8 bits a channel. Hdr: "HDR",
-// Radiance RGBE quads of the film's means. Iris: "IRIS", a run-length coded
-// Silicon Graphics .rgb file of the 8-bit image. Webp: "WEBP", a lossless WebP
-// file (VP8L) of the 8-bit image.
-enum class Coder { None, HostRgba, Jpeg, Png8, Png16, Exr, Exr32, Tga, Hdr, Iris, Webp };
-
-// The formats behind the deflate coder (deflate.hip): their coder reads only
-// its slot's rgba8 / film and writes slot buffers only.
-inline bool device_deflate(Coder k) {
-    return k == Coder::Png8 || k == Coder::Png16 || k == Coder::Exr || k == Coder::Exr32;
-}
-
-// The body coders: the TARGA packer (tga.hip), the HDR coder (hdr.hip), the
-// IRIS coder (iris.hip) and the WEBP coder (webp.hip), which form a dense body
-// in the slot's scratch and gather it into the slot's pinned stream.
-inline bool device_body(Coder k) {
-    return k == Coder::Tga || k == Coder::Hdr || k == Coder::Iris || k == Coder::Webp;
-}
-
-// The coders that read only their slot's rgba8 / film and write slot buffers
-// only: the deflate formats and the body coders. The next frame waits for such
-// a frame's image, not for its coder.
+// The coders' families (formats.hpp). A slot coder reads only its slot's rgba8 /
+// film and writes slot buffers only: the next frame waits for such a frame's
+// image, not for its coder.
+inline bool device_deflate(Coder k) { return coder_info(k).family == Family::Deflate; }
+inline bool device_body(Coder k) { return coder_info(k).family == Family::Body; }
 inline bool slot_coder(Coder k) { return device_deflate(k) || device_body(k); }
 
-// The output formats a frame can be submitted with.
-bool known_format(const char* format);
-
+// The formats a frame can be submitted with (kFormats), and the extension of a coder's files.
+inline bool known_format(const char* format) { return find_format(format) != nullptr; }
 const char* coder_ext(Coder k);
+
+// What a format that is not written is refused with, listing those that are:
+// a frame's (rr_frame_submit), or with rgba8 an RGBA8 image's (do_encode), for
+// which the formats of the float film are not written either.
+std::string unsupported_format(const std::string& format, bool rgba8 = false);
 
 // The channels a frame's file holds (rr_set_color_mode), which is also the
 // resolved mode's value: RR_COLOR_BW 1, RR_COLOR_RGB 3, RR_COLOR_RGBA 4. mode 0:
-// the format's layout before there was a setting (JPEG three components, PNG
-// OPEN_EXR, TARGA, IRIS and WEBP four channels). JPEG and HDR have no alpha (no_alpha):
+// the format's layout before there was a setting (JPEG three components, the
+// others four channels). A format without alpha (Format::no_alpha):
 // RGBA resolves to RGB, as in Blender, and mode 0 is RGB.
 int resolve_color_mode(int mode, bool no_alpha);
 
@@ -104,14 +86,12 @@ struct FrameOutput {
     int color_mode = RR_COLOR_RGBA;                    // the file's channels (resolve_color_mode)
     int png_compression = RR_PNG_COMPRESSION_LEGACY;   // LEGACY, or 0 .. 100
     int quality = 0;                                   // JPEG
-    bool tga_raw = false;                              // Coder::Tga: "TARGA_RAW", no run-length packets
+    bool tga_raw = false;                              // Coder::Tga: no run-length packets (Format::tga_raw)
 };
 
 // What a frame of a scene with render settings r is written as on a context
-// with settings s. format: "JPEG", "PNG", "OPEN_EXR", "TARGA", "TARGA_RAW",
-// "HDR", "IRIS" or "WEBP" (known_format, checked by the caller); without a path
-// there is no file (Coder::None). A TARGA, an IRIS and a WEBP file are 8 bits a
-// channel and an HDR file RGBE quads whatever the depth settings.
+// with settings s. format: a name of kFormats (known_format, checked by the
+// caller); without a path there is no file (Coder::None).
 FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const char* format, bool has_path,
                            int jpeg_quality);
 

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "formats.hpp"
 #include "rr.h"
 
 namespace {
@@ -120,15 +121,8 @@ int main(int argc, char** argv) {
         return 1;
     }
     // the extension write_still appends; a format nobody writes is an error, as in the library
-    const std::string ext = fmt == "JPEG"                             ? ".jpg"
-                            : fmt == "PNG"                            ? ".png"
-                            : fmt == "OPEN_EXR"                       ? ".exr"
-                            : (fmt == "TARGA" || fmt == "TARGA_RAW") ? ".tga"
-                            : fmt == "HDR"                            ? ".hdr"
-                            : fmt == "IRIS"                           ? ".rgb"
-                            : fmt == "WEBP"                           ? ".webp"
-                                                                      : "";
-    if (ext.empty()) {
+    const rr::Format* known = rr::find_format(fmt.c_str());
+    if (!known) {
         std::fprintf(stderr, "rr-blender-shim: unsupported output format '%s'\n", fmt.c_str());
         std::printf("Error: unsupported output format '%s'\n", fmt.c_str());
         return 1;
@@ -165,7 +159,7 @@ int main(int argc, char** argv) {
     }
     std::printf("Fra:%ld Mem:0M | Rendered %d x %d, %d spp, %.3f ms device\n", frame, st.width, st.height, st.spp,
                 st.build_ms + st.trace_ms);
-    std::printf("Saved: '%s%s'\n", out_path.c_str(), ext.c_str());
+    std::printf("Saved: '%s%s'\n", out_path.c_str(), known->ext);
     std::printf(" Time: %s (Saving: %s)\n", blender_time(t.file_saving_finished_at - t.started_rendering_at).c_str(),
                 blender_time(t.file_saving_finished_at - t.file_saving_started_at).c_str());
     std::printf("\n");

@@ -1,5 +1,6 @@
 // Stand-alone checks of csrc/settings.cpp (no GPU, no HIP): the environment
-// spellings, the setters' ranges, and the file resolve_output gives a frame.
+// spellings, the setters' ranges, the file resolve_output gives a frame, and
+// the format table of csrc/formats.hpp with the refusal texts made from it.
 // Built with the system compiler and -fsanitize=address,undefined and run as a
 // child process by tests/test_settings.py. Exit status 0 and "settings_check:
 // ok" when every check holds; every failed check is printed.
@@ -322,10 +323,146 @@ static void check_resolve_output() {
           "extensions");
 }
 
-int main() {
+// ---- the format table (formats.hpp) ----------------------------------------
+
+static const Coder J = Coder::Jpeg, HOST = Coder::HostRgba, P8 = Coder::Png8, P16 = Coder::Png16, X16 = Coder::Exr,
+                   X32 = Coder::Exr32, TG = Coder::Tga, HD = Coder::Hdr, IR = Coder::Iris, WP = Coder::Webp;
+
+struct FormatRow {
+    const char* name;
+    const char* ext;
+    bool no_alpha, tga_raw;
+    // the coder of a frame with a path, by the depth levels above: [context level 0, 1, 2][scene level 1, 2]
+    // [device_png off, on]
+    Coder at[3][2][2];
+};
+// what a frame of each name has been written as since the format was added
+static const FormatRow kFormatRows[] = {
+    {"JPEG", ".jpg", true, false, {{{J, J}, {J, J}}, {{J, J}, {J, J}}, {{J, J}, {J, J}}}},
+    {"PNG", ".png", false, false,
+     {{{HOST, P8}, {P16, P16}}, {{HOST, P8}, {HOST, P8}}, {{P16, P16}, {P16, P16}}}},
+    {"OPEN_EXR", ".exr", false, false,
+     {{{X16, X16}, {X32, X32}}, {{X16, X16}, {X16, X16}}, {{X32, X32}, {X32, X32}}}},
+    {"TARGA", ".tga", false, false, {{{TG, TG}, {TG, TG}}, {{TG, TG}, {TG, TG}}, {{TG, TG}, {TG, TG}}}},
+    {"TARGA_RAW", ".tga", false, true, {{{TG, TG}, {TG, TG}}, {{TG, TG}, {TG, TG}}, {{TG, TG}, {TG, TG}}}},
+    {"HDR", ".hdr", true, false, {{{HD, HD}, {HD, HD}}, {{HD, HD}, {HD, HD}}, {{HD, HD}, {HD, HD}}}},
+    {"IRIS", ".rgb", false, false, {{{IR, IR}, {IR, IR}}, {{IR, IR}, {IR, IR}}, {{IR, IR}, {IR, IR}}}},
+    {"WEBP", ".webp", false, false, {{{WP, WP}, {WP, WP}}, {{WP, WP}, {WP, WP}}, {{WP, WP}, {WP, WP}}}},
+};
+
+struct CoderRowFacts {
+    Coder k;
+    Family family;
+    bool film;  // reads the float film, else the 8-bit image
+    const char* ext;
+    const char* range;
+};
+static const CoderRowFacts kCoderFacts[] = {
+    {Coder::None, Family::Host, false, "", ""},
+    {Coder::HostRgba, Family::Host, false, ".png", ""},
+    {Coder::Jpeg, Family::Jpeg, false, ".jpg", "image size outside the JPEG format's range"},
+    {Coder::Png8, Family::Deflate, false, ".png", "image size outside the device PNG encoder's range"},
+    {Coder::Png16, Family::Deflate, true, ".png", "image size outside the device 16-bit PNG encoder's range"},
+    {Coder::Exr, Family::Deflate, true, ".exr", "image size outside the device EXR encoder's range"},
+    {Coder::Exr32, Family::Deflate, true, ".exr", "image size outside the device 32-bit EXR encoder's range"},
+    {Coder::Tga, Family::Body, false, ".tga",
+     "image size outside the TARGA format's range (65535 x 65535, a body below 2 GB)"},
+    {Coder::Hdr, Family::Body, true, ".hdr", "image size outside the HDR coder's range (a body bound below 2 GB)"},
+    {Coder::Iris, Family::Body, false, ".rgb",
+     "image size outside the IRIS format's range (65535 x 65535, a body bound below 2 GB)"},
+    {Coder::Webp, Family::Body, false, ".webp",
+     "image size outside the WEBP format's range (16384 x 16384, a payload bound below 2 GB)"},
+};
+
+static void check_formats() {
+    CHECK(sizeof kFormats / sizeof kFormats[0] == 8, "eight formats");
+    size_t row = 0;
+    for (const FormatRow& w : kFormatRows) {
+        const Format* f = find_format(w.name);
+        CHECK(f && known_format(w.name), "%s is a format", w.name);
+        if (!f) continue;
+        CHECK(f == &kFormats[row++], "%s: the table's order is the refusals'", w.name);
+        CHECK(std::strcmp(f->ext, w.ext) == 0, "%s: extension %s, want %s", w.name, f->ext, w.ext);
+        CHECK(f->no_alpha == w.no_alpha, "%s: no_alpha %d", w.name, (int)f->no_alpha);
+        CHECK(f->tga_raw == w.tga_raw, "%s: tga_raw %d", w.name, (int)f->tga_raw);
+        for (int ctx = 0; ctx < 3; ++ctx)
+            for (int scene = 1; scene <= 2; ++scene)
+                for (int dev = 0; dev < 2; ++dev) {
+                    OutputSettings s;
+                    s.device_png = dev != 0;
+                    s.png_depth = kPngDepth[ctx];
+                    s.exr_depth = kExrDepth[ctx];
+                    RenderDesc r;
+                    r.color_depth = kPngDepth[scene];
+                    r.exr_depth = kExrDepth[scene];
+                    const FrameOutput o = resolve_output(s, r, w.name, true, 90);
+                    const Coder want = w.at[ctx][scene - 1][dev];
+                    CHECK(o.coder == want, "%s depth %d/%d device_png %d: coder %d, want %d", w.name, ctx, scene, dev,
+                          (int)o.coder, (int)want);
+                    CHECK(o.tga_raw == w.tga_raw, "%s: the frame's tga_raw %d", w.name, (int)o.tga_raw);
+                    // no setting: the format's own layout; RGBA asked of a format without alpha is RGB
+                    CHECK(o.color_mode == (w.no_alpha ? RR_COLOR_RGB : RR_COLOR_RGBA), "%s: layout %d", w.name,
+                          o.color_mode);
+                    s.color_mode = RR_COLOR_RGBA;
+                    CHECK(resolve_output(s, r, w.name, true, 90).color_mode == (w.no_alpha ? RR_COLOR_RGB : RR_COLOR_RGBA),
+                          "%s: RGBA", w.name);
+                    CHECK(resolve_output(s, r, w.name, false, 90).coder == Coder::None, "%s: no path, no coder", w.name);
+                }
+    }
+    for (const char* bad : {"TIFF", "BMP", "jpeg", "PNG ", "", "TARGA_"})
+        CHECK(!known_format(bad) && !find_format(bad), "'%s' is no format", bad);
+    CHECK(!known_format(nullptr), "NULL is no format");
+
+    CHECK(sizeof kCoders / sizeof kCoders[0] == 11, "a row for every Coder");
+    for (const CoderRowFacts& w : kCoderFacts) {
+        const CoderInfo& ci = coder_info(w.k);
+        CHECK(ci.family == w.family, "coder %d: family %d", (int)w.k, (int)ci.family);
+        CHECK(ci.film == w.film, "coder %d: film %d", (int)w.k, (int)ci.film);
+        CHECK(std::strcmp(coder_ext(w.k), w.ext) == 0, "coder %d: extension %s", (int)w.k, coder_ext(w.k));
+        CHECK(std::strcmp(ci.range, w.range) == 0, "coder %d: range refusal '%s'", (int)w.k, ci.range);
+        CHECK(device_deflate(w.k) == (w.family == Family::Deflate) && device_body(w.k) == (w.family == Family::Body) &&
+                  slot_coder(w.k) == (w.family == Family::Deflate || w.family == Family::Body),
+              "coder %d: the family predicates", (int)w.k);
+    }
+    // the depth rr_debug_encode_device takes for a coder besides 0, and the names its messages use
+    CHECK(coder_info(J).depth == 8 && coder_info(P8).depth == 8 && coder_info(TG).depth == 8 &&
+              coder_info(IR).depth == 8 && coder_info(WP).depth == 8 && coder_info(P16).depth == 16 &&
+              coder_info(X16).depth == 16 && coder_info(X32).depth == 32 && coder_info(HD).depth == 32,
+          "coder depths");
+    CHECK(std::string(coder_info(J).name) == "JPEG" && std::string(coder_info(TG).name) == "TARGA" &&
+              std::string(coder_info(HD).name) == "HDR" && std::string(coder_info(IR).name) == "IRIS" &&
+              std::string(coder_info(WP).name) == "WEBP",
+          "coder names");
+
+    // the refusals that list the formats, as rr_frame_submit and the host coders have worded them
+    CHECK(unsupported_format("TIFF") ==
+              "unsupported output format 'TIFF' (JPEG, PNG, OPEN_EXR, TARGA, TARGA_RAW, HDR, IRIS and WEBP are supported)",
+          "'%s'", unsupported_format("TIFF").c_str());
+    CHECK(unsupported_format("HDR", true) ==
+              "unsupported output format 'HDR' for an RGBA8 image: it needs the float film (JPEG, PNG, TARGA, "
+              "TARGA_RAW, IRIS and WEBP are supported here)",
+          "'%s'", unsupported_format("HDR", true).c_str());
+    CHECK(unsupported_format("OPEN_EXR", true) ==
+              "unsupported output format 'OPEN_EXR' for an RGBA8 image: it needs the float film (JPEG, PNG, TARGA, "
+              "TARGA_RAW, IRIS and WEBP are supported here)",
+          "'%s'", unsupported_format("OPEN_EXR", true).c_str());
+    CHECK(unsupported_format("TIFF", true) ==
+              "unsupported output format 'TIFF' (JPEG, PNG, TARGA, TARGA_RAW, IRIS and WEBP are supported here; "
+              "OPEN_EXR and HDR need the float film)",
+          "'%s'", unsupported_format("TIFF", true).c_str());
+}
+
+// `settings_check --formats`: the table's "name extension" lines, for tests/test_settings.py to hold the
+// package's Python copy (naming.py EXTENSIONS) to.
+int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "--formats") == 0) {
+        for (const Format& f : kFormats) std::printf("%s %s\n", f.name, f.ext);
+        return 0;
+    }
     check_env();
     check_setters();
     check_resolve_output();
+    check_formats();
     if (g_failed) {
         std::printf("settings_check: %d of %d checks FAILED\n", g_failed, g_checked);
         return 1;

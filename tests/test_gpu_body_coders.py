@@ -1,5 +1,5 @@
 """The TARGA, HDR, IRIS and WEBP device coders share one scratch buffer and one
-pinned stream per frame slot (device.hpp body_scratch, frame.hpp BodyOut): calls
+pinned stream per frame slot (device.hpp body_scratch, frame.hpp CodedOut): calls
 of the four on one context, the buffers growing and then reused below their
 capacity, each give the host coder's file."""
 import ctypes
