@@ -41,6 +41,14 @@ std::string webp_quality_warning(int quality) {
 
 namespace {
 
+// The pinned memory p as the device addresses it.
+template <class T>
+T* device_pointer(const PinnedBuf& p) {
+    void* dev = nullptr;
+    RR_HIP(hipHostGetDevicePointer(&dev, p.ptr, 0));
+    return static_cast<T*>(dev);
+}
+
 // One body coder, every fact of it here. plan: the format's plan in o and its
 // BodyShape (scratch words; what a body holds at least); false: a size out of
 // range. launch: enqueues the coder. file: the file around a body of len bytes.
@@ -102,7 +110,37 @@ const BodyCoder kWebp = {
     [](const CodedOut&, const uint8_t* body, size_t len, std::vector<uint8_t>& data) {
         webp_wrap_stream(body, len, data);  // the RIFF and chunk headers, and the pad byte
     }};
+// OPEN_EXR with a chunk per scanline (rr_set_exr_codec NONE, RLE): the body path's
+// scratch and stream under the format's own coder rows, Exr and Exr32. NONE has
+// its exact length, an RLE body a byte of every scanline at least.
+const BodyCoder kExrRows = {
+    [](const FrameOutput& fo, int W, int H, CodedOut& o) {
+        const bool rle = fo.exr_codec == RR_EXR_CODEC_RLE;
+        return exr_rows_plan(W, H, fo.color_mode, coder_info(fo.coder).depth, rle, o.exr_rows) &&
+               shaped(o, fo.coder, o.exr_rows, exr_rows_scratch_words(o.exr_rows),
+                      rle ? (uint64_t)o.exr_rows.H : o.exr_rows.body_cap);
+    },
+    [](const CoderInput& in, const CodedOut& o, uint32_t* scratch, uint8_t* out, hipStream_t st) {
+        uint32_t* tab = o.exr_rows.rle ? device_pointer<uint32_t>(o.tab) : nullptr;
+        exr_rows_encode_device(in.film, in.inv_spp, in.alpha_one, o.exr_rows, scratch, out, tab, st);
+    },
+    [](const CodedOut& o, const uint8_t* body, size_t len, std::vector<uint8_t>& data) {
+        const ExrRowsPlan& p = o.exr_rows;
+        const uint32_t* tab = p.rle ? reinterpret_cast<const uint32_t*>(o.tab.ptr) : nullptr;
+        if (!exr_wrap_rows(p.W, p.H, body, len, tab, data, p.full ? 2 : 1, p.C, p.rle ? 1 : 0))
+            throw std::runtime_error("device EXR scanline table does not match its body");
+    }};
+// Whether fo's file is an OPEN_EXR file coded by kExrRows.
+bool exr_rows(const FrameOutput& fo) {
+    if (fo.coder != Coder::Exr && fo.coder != Coder::Exr32) return false;
+    const int codec = exr_codec_written(fo);
+    return codec == RR_EXR_CODEC_NONE || codec == RR_EXR_CODEC_RLE;
+}
+bool exr_pxr24(const FrameOutput& fo) {
+    return (fo.coder == Coder::Exr || fo.coder == Coder::Exr32) && exr_codec_written(fo) == RR_EXR_CODEC_PXR24;
+}
 const BodyCoder& body_coder(Coder k) {
+    if (k == Coder::Exr || k == Coder::Exr32) return kExrRows;
     return k == Coder::Tga ? kTga : k == Coder::Hdr ? kHdr : k == Coder::Iris ? kIris : kWebp;
 }
 
@@ -116,14 +154,6 @@ uint64_t stream_len(const CodedOut& o, const std::string& what, Over over) {
     return len;
 }
 
-// The pinned memory p as the device addresses it.
-template <class T>
-T* device_pointer(const PinnedBuf& p) {
-    void* dev = nullptr;
-    RR_HIP(hipHostGetDevicePointer(&dev, p.ptr, 0));
-    return static_cast<T*>(dev);
-}
-
 // Device encode by body coder k into o's pinned stream, by the plan in o.
 void enqueue_body(Coder k, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o) {
     const BodyShape& b = o.body;
@@ -131,6 +161,7 @@ void enqueue_body(Coder k, const CoderInput& in, DevFrame& f, hipStream_t st, Co
         throw std::runtime_error(std::string(coder_info(k).name) + " plan of another image");
     f.body_scratch.ensure(b.scratch_words);
     o.stream.ensure(body_stream_bytes(b.body_cap));
+    if (device_deflate(k) && o.exr_rows.rle) o.tab.ensure((size_t)b.H * 2 * sizeof(uint32_t));  // the scanlines' table
     f.prof.begin(st, RR_K_PNG);
     body_coder(k).launch(in, o, f.body_scratch.ptr, device_pointer<uint8_t>(o.stream), st);
     f.prof.end(st);
@@ -179,7 +210,8 @@ void jpeg_file_bytes(const CodedOut& o, std::vector<uint8_t>& data) {
 
 // The file of a deflate-coded image: the host-built container of format k
 // around the device stream. C: the channels the stream was coded with.
-void deflate_file_bytes(const CodedOut& o, Coder k, int C, std::vector<uint8_t>& data) {
+// compression: an OPEN_EXR file's attribute, 3 ZIP or 5 PXR24.
+void deflate_file_bytes(const CodedOut& o, Coder k, int C, std::vector<uint8_t>& data, int compression = 3) {
     const DeflatePlan& p = o.deflate;
     const uint32_t* tab = reinterpret_cast<const uint32_t*>(o.tab.ptr);
     // one stream: its bound counts the 4 bytes of Adler-32 the host adds
@@ -195,7 +227,7 @@ void deflate_file_bytes(const CodedOut& o, Coder k, int C, std::vector<uint8_t>&
     case Coder::Exr:
     case Coder::Exr32:
         if (!exr_wrap_stream(p.W, p.H, o.stream.ptr + 16, (size_t)len, tab, p.nbands, data, k == Coder::Exr32 ? 2 : 1,
-                             C))
+                             C, compression))
             throw std::runtime_error("device EXR chunk table does not match its stream");
         break;
     default:
@@ -209,7 +241,9 @@ int plan_or_refuse(const FrameOutput& fo, int W, int H, CodedOut& o) {
     const Coder k = fo.coder;
     const int C = fo.color_mode;
     DeflatePlan& p = o.deflate;
-    const bool ok = k == Coder::Png8    ? png_plan(W, H, C, p)
+    const bool ok = exr_rows(fo)        ? kExrRows.plan(fo, W, H, o)
+                    : exr_pxr24(fo)     ? pxr24_plan(W, H, C, coder_info(k).depth, p)
+                    : k == Coder::Png8  ? png_plan(W, H, C, p)
                     : k == Coder::Png16 ? png16_plan(W, H, C, p)
                     : k == Coder::Exr   ? exr_plan(W, H, C, p)
                     : k == Coder::Exr32 ? exr32_plan(W, H, C, p)
@@ -221,7 +255,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
     const Coder k = fo.coder;
     const int C = fo.color_mode;
     if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o);
-    if (device_body(k)) return enqueue_body(k, in, f, st, o);
+    if (device_body(k) || exr_rows(fo)) return enqueue_body(k, in, f, st, o);
     if (!device_deflate(k)) throw std::runtime_error("no device coder for this output");
     // the front ends' own buffers. "PNG" at compression 0 .. 100: a filter type
     // per row of the H rows, and at 16 bits the raw scanlines, 2C W H bytes
@@ -257,10 +291,12 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
         else png16_encode_device(front, C, p, scratch, out, tab, st);
         break;
     case Coder::Exr:  // HALF channels
-        exr_encode_device(in.film, in.inv_spp, in.alpha_one, C, p, scratch, out, tab, st);
+        if (exr_pxr24(fo)) pxr24_encode_device(in.film, in.inv_spp, in.alpha_one, C, 16, p, scratch, out, tab, st);
+        else exr_encode_device(in.film, in.inv_spp, in.alpha_one, C, p, scratch, out, tab, st);
         break;
     default:  // Coder::Exr32: FLOAT channels
-        exr32_encode_device(in.film, in.inv_spp, in.alpha_one, C, p, scratch, out, tab, st);
+        if (exr_pxr24(fo)) pxr24_encode_device(in.film, in.inv_spp, in.alpha_one, C, 32, p, scratch, out, tab, st);
+        else exr32_encode_device(in.film, in.inv_spp, in.alpha_one, C, p, scratch, out, tab, st);
         break;
     }
     f.prof.end(st);
@@ -268,8 +304,8 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
 
 void coded_file_bytes(const CodedOut& o, const FrameOutput& fo, std::vector<uint8_t>& data) {
     if (fo.coder == Coder::Jpeg) jpeg_file_bytes(o, data);
-    else if (device_body(fo.coder)) body_file_bytes(o, fo.coder, data);
-    else deflate_file_bytes(o, fo.coder, fo.color_mode, data);
+    else if (device_body(fo.coder) || exr_rows(fo)) body_file_bytes(o, fo.coder, data);
+    else deflate_file_bytes(o, fo.coder, fo.color_mode, data, exr_pxr24(fo) ? 5 : 3);
 }
 
 int do_encode(const uint8_t* rgba, int W, int H, const char* out_path, const char* format, int quality,

@@ -432,7 +432,8 @@ __global__ __launch_bounds__(kThreads) void k_deflate_codes(DeflatePlan p, const
         const uint32_t total = eob + lens[256];
         const uint32_t dyn = bd.last ? (total + 7) / 8 : (total + 3 + 7) / 8 + 4;
         // own streams: against the band's raw bytes, less the 6 bytes of zlib framing the host adds
-        const uint32_t sto = p.own_stream ? (bd.n > 6u ? bd.n - 6u : 0u) : stored_bytes(bd.n);
+        const uint32_t raw_n = p.raw_stride * (uint32_t)bd.rows;  // bd.n but for PXR24 FLOAT chunks
+        const uint32_t sto = p.own_stream ? (raw_n > 6u ? raw_n - 6u : 0u) : stored_bytes(bd.n);
         const uint32_t mode = dyn < sto ? 0u : 1u;
         uint32_t s1 = 1, s2 = 0;  // Adler-32 of the band from the chunk sums
         for (uint32_t q = 0; q < nsub; ++q) {
@@ -443,7 +444,7 @@ __global__ __launch_bounds__(kThreads) void k_deflate_codes(DeflatePlan p, const
         }
         uint32_t* r = rec + 4 * (size_t)b;
         r[0] = mode;
-        r[1] = mode ? (p.own_stream ? bd.n : sto) : dyn;
+        r[1] = mode ? (p.own_stream ? raw_n : sto) : dyn;
         r[2] = (s2 << 16) | s1;
         r[3] = bd.n;
         if (mode == 0) {  // block header, end of block and trailer; the tokens come from k_deflate_emit
@@ -641,17 +642,19 @@ inline uint32_t host_stored_bytes(uint32_t n) { return n + 5u * ((n + 65534u) / 
 
 }  // namespace
 
-bool deflate_plan(int W, int H, uint32_t stride, DeflatePlan& p) {
+bool deflate_plan(int W, int H, uint32_t stride, DeflatePlan& p, uint32_t raw_stride) {
     p = DeflatePlan{};
     p.W = W;
     p.H = H;
     p.stride = stride;
+    p.raw_stride = raw_stride ? raw_stride : stride;
     p.nbands = (H + kDeflateBandRows - 1) / kDeflateBandRows;
     p.band_full = p.stride * (uint32_t)std::min(H, kDeflateBandRows);
     p.band_pos = (p.band_full + kTile - 1) / kTile * kTile;
     p.nsub = p.band_pos / kDeflateSub;
     p.nseg = p.band_pos / kSeg;
-    p.band_cap = (host_stored_bytes(p.band_full) + 15u) / 16u * 16u + 32u;
+    const uint32_t raw_full = p.raw_stride * (uint32_t)std::min(H, kDeflateBandRows);
+    p.band_cap = (std::max(host_stored_bytes(p.band_full), raw_full) + 15u) / 16u * 16u + 32u;
     return (uint64_t)p.nbands * p.band_cap < (1ull << 31);  // band offsets in the stream are 32-bit
 }
 

@@ -38,6 +38,10 @@ struct DeflatePlan {
     // table holds {mode (0 dynamic, 1 raw), bytes, Adler-32, front-end bytes}
     // per band, 4 words.
     int own_stream;
+    // own streams: the bytes of a row in a raw band, which the codes stage
+    // compares a band's stream with. The front end's own (stride) but for PXR24
+    // FLOAT chunks, which code 3 bytes of a sample's 4. band_cap holds either.
+    uint32_t raw_stride;
 };
 
 struct DeflateBufs {
@@ -59,8 +63,9 @@ inline void deflate_distinct(DeflatePlan& p) {
             if (p.dist[a] == p.dist[b]) p.dist[a] = 0u;
 }
 
-// Everything of the plan but dist and own_stream; false: a stream of 2 GB and more.
-bool deflate_plan(int W, int H, uint32_t stride, DeflatePlan& p);
+// Everything of the plan but dist and own_stream; false: a stream of 2 GB and
+// more. raw_stride 0: the stride.
+bool deflate_plan(int W, int H, uint32_t stride, DeflatePlan& p, uint32_t raw_stride = 0);
 DeflateBufs deflate_carve(const DeflatePlan& p, uint32_t* base);  // base nullptr: only `words`
 size_t deflate_scratch_words(const DeflatePlan& p);
 size_t deflate_stream_max_bytes(const DeflatePlan& p);  // one zlib stream with every band stored

@@ -212,8 +212,9 @@ struct DevFrame {
     // PNG frames with the adaptive filter (rr_set_png_compression): a filter type per image row, and at 16 bits
     // the raw big-endian scanlines (png16.hip k_png16_raw); grow-only, untouched by legacy frames
     DevBuf<uint8_t> png_ftype, png_raw;
-    // TARGA, HDR, IRIS and WEBP frames (tga.hip, hdr.hip, iris.hip, webp.hip): the dense body and the coder's
-    // records, carved by the coder's *_carve; grow-only. A frame writes one file, so the four share it
+    // TARGA, HDR, IRIS and WEBP frames, and OPEN_EXR frames of the codecs NONE and RLE (tga.hip, hdr.hip, iris.hip,
+    // webp.hip, exr_codec.hip): the dense body and the coder's records, carved by the coder's *_carve;
+    // grow-only. A frame writes one file, so they share it
     DevBuf<uint32_t> body_scratch;
     // written by render_frame_device, about the frame it enqueued
     int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
@@ -371,6 +372,14 @@ void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int 
 // as above. W <= 2^18 (a band has twice the bytes).
 bool exr32_plan(int W, int H, int C, DeflatePlan& p);
 void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+                         uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
+// The same files with PXR24 chunks (rr_set_exr_codec; exr.hip Pxr24Front): zlib
+// over 16 scanlines of byte planes of pixel differences, depth 16 the halfs'
+// own bits, 32 the floats' 24-bit form (pxr24_rule.h; 3 C W bytes a scanline in
+// the stream, DeflatePlan::raw_stride = 4 C W in a raw chunk). The ranges of
+// exr_plan / exr32_plan; exr_stream_max_bytes and the table as above.
+bool pxr24_plan(int W, int H, int C, int depth, DeflatePlan& p);
+void pxr24_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, int depth, const DeflatePlan& p,
                          uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 // The view settings of a frame as kernel arguments (view.hpp FilmicDev::args):

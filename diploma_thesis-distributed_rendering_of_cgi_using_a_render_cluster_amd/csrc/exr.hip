@@ -23,6 +23,10 @@
 //  - deflate.hip's scan + gather into pinned host memory.
 // Same film -> same bytes.
 //
+// PXR24 (rr_set_exr_codec) is a third front end: Pxr24Front and pxr24_plan
+// below; the raw kernels are the two here. NONE and RLE, a chunk per
+// scanline and no deflate, are exr_codec.hip.
+//
 // FLOAT channels (Blender's "Float (Full)", rr_set_exr_depth 32) are a second
 // front end of the same shape: ExrFloatFront, k_exr32_raw and exr32_plan below,
 // n = 16W * rows bytes a chunk, the means' own bits.
@@ -32,7 +36,8 @@
 
 #include "deflate.hpp"
 #include "device.hpp"
-#include "grey.h"
+#include "exr_samples.hpp"
+#include "pxr24_rule.h"
 
 namespace rr {
 
@@ -40,78 +45,12 @@ namespace {
 
 constexpr int kThreads = 256;
 
-// float -> half bits: clamped to +-65504, round to nearest even, subnormals kept.
-__device__ __forceinline__ uint32_t half_bits(float f) {
-    const uint32_t x = __float_as_uint(f);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    uint32_t a = x & 0x7FFFFFFFu;
-    if (a > 0x7F800000u) return sign | 0x7E00u;  // NaN
-    a = min(a, 0x477FE000u);                     // 65504
-    if (a >= 0x38800000u) {                      // >= 2^-14: a normal half
-        a -= 112u << 23;
-        a += 0xFFFu + ((a >> 13) & 1u);
-        return sign | (a >> 13);
-    }
-    const uint32_t e = a >> 23;
-    if (e < 102u) return sign;  // < 2^-25: below half of the smallest subnormal (and 0)
-    const uint32_t m = (a & 0x7FFFFFu) | 0x800000u;
-    const uint32_t s = 126u - e;  // 14 .. 24: m * 2^(e - 150) in units of 2^-24
-    uint32_t h = m >> s;
-    const uint32_t rem = m & ((1u << s) - 1u), mid = 1u << (s - 1u);
-    if (rem > mid || (rem == mid && (h & 1u))) h += 1u;
-    return sign | h;
-}
-
-struct Film {
-    const float4* px;
-    float inv_spp;
-    int alpha_one;
-};
-
-// Mean of sample k of a band: k counts scanline by scanline, plane by plane.
-// C = 4: planes A, B, G, R; C = 3: B, G, R; C = 1: Y, the Rec.709 luma of the
-// means (products and sums rounded one by one, left to right).
-template <int C>
-__device__ __forceinline__ float sample_mean(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
-    const uint32_t W = (uint32_t)p.W, row_samples = (uint32_t)C * W;
-    const uint32_t row = k / row_samples, rem = k - row * row_samples;
-    const uint32_t ch = rem / W, x = rem - ch * W;
-    const float4 v = fm.px[(size_t)(row0 + (int)row) * W + x];
-    if constexpr (C == 4) {
-        const float c = ch == 0 ? v.w : ch == 1 ? v.z : ch == 2 ? v.y : v.x;
-        return (ch == 0 && fm.alpha_one) ? 1.0f : __fmul_rn(c, fm.inv_spp);
-    } else if constexpr (C == 3) {
-        const float c = ch == 0 ? v.z : ch == 1 ? v.y : v.x;
-        return __fmul_rn(c, fm.inv_spp);
-    } else {
-        const float r = __fmul_rn(v.x, fm.inv_spp), g = __fmul_rn(v.y, fm.inv_spp), b = __fmul_rn(v.z, fm.inv_spp);
-        return luma709(r, g, b);
-    }
-}
-
-// Half of sample k of a band.
-template <int C>
-__device__ __forceinline__ uint32_t sample_half(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
-    return half_bits(sample_mean<C>(fm, p, row0, k));
-}
-
-// Byte j of a band after the reorder (before the predictor).
-template <int C>
-__device__ __forceinline__ uint32_t reordered_byte(const Film& fm, const DeflatePlan& p, int row0, uint32_t half_n,
-                                                   uint32_t j) {
-    const bool hi = j >= half_n;
-    const uint32_t h = sample_half<C>(fm, p, row0, hi ? j - half_n : j);
-    return hi ? h >> 8 : h & 0xFFu;
-}
-
-// Byte j of a chunk as the coder sees it: reordered, less its predecessor + 128.
+// Byte j of a chunk as the coder sees it (exr_samples.hpp exr_pred_byte).
 template <int C>
 struct ExrFront {
     Film fm;
     __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t n, uint32_t j) const {
-        uint32_t v = reordered_byte<C>(fm, p, row0, n / 2, j);
-        if (j > 0) v = (v - reordered_byte<C>(fm, p, row0, n / 2, j - 1) + 128u) & 0xFFu;
-        return v;
+        return exr_pred_byte<C, false>(fm, p.W, row0, n, j);
     }
 };
 
@@ -122,10 +61,10 @@ __global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, DeflatePlan p, co
     const int b = blockIdx.y;
     if (rec[4 * (size_t)b] == 0u) return;
     const int row0 = b * kDeflateBandRows;
-    const uint32_t n = p.stride * (uint32_t)min(kDeflateBandRows, p.H - row0);
+    const uint32_t n = p.raw_stride * (uint32_t)min(kDeflateBandRows, p.H - row0);
     const uint32_t k = blockIdx.x * kThreads + threadIdx.x;  // sample
     if (2u * k >= n) return;
-    const uint32_t h = sample_half<C>(fm, p, row0, k);
+    const uint32_t h = sample_half<C>(fm, p.W, row0, k);
     uint8_t* o = out + (size_t)b * p.band_cap + 2u * k;  // band_cap is a multiple of 16
     *reinterpret_cast<uint16_t*>(o) = (uint16_t)h;
 }
@@ -136,30 +75,12 @@ __global__ __launch_bounds__(kThreads) void k_exr_raw(Film fm, DeflatePlan p, co
 // first n / 2 positions alternate bytes 0 and 2 of consecutive samples, the
 // second n / 2 bytes 1 and 3: position q of a half belongs to sample q / 2.
 
-// Bits of sample k of a band: the mean itself, no clamp and no rounding.
-template <int C>
-__device__ __forceinline__ uint32_t sample_float(const Film& fm, const DeflatePlan& p, int row0, uint32_t k) {
-    return __float_as_uint(sample_mean<C>(fm, p, row0, k));
-}
-
-// Byte j of a band of floats after the reorder (before the predictor).
-template <int C>
-__device__ __forceinline__ uint32_t reordered_byte32(const Film& fm, const DeflatePlan& p, int row0, uint32_t half_n,
-                                                     uint32_t j) {
-    const bool hi = j >= half_n;
-    const uint32_t q = hi ? j - half_n : j;
-    const uint32_t bits = sample_float<C>(fm, p, row0, q >> 1);
-    return (bits >> (16u * (q & 1u) + (hi ? 8u : 0u))) & 0xFFu;
-}
-
-// Byte j of a FLOAT chunk as the coder sees it: reordered, less its predecessor + 128.
+// Byte j of a FLOAT chunk as the coder sees it (exr_samples.hpp exr_pred_byte).
 template <int C>
 struct ExrFloatFront {
     Film fm;
     __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t n, uint32_t j) const {
-        uint32_t v = reordered_byte32<C>(fm, p, row0, n / 2, j);
-        if (j > 0) v = (v - reordered_byte32<C>(fm, p, row0, n / 2, j - 1) + 128u) & 0xFFu;
-        return v;
+        return exr_pred_byte<C, true>(fm, p.W, row0, n, j);
     }
 };
 
@@ -170,12 +91,39 @@ __global__ __launch_bounds__(kThreads) void k_exr32_raw(Film fm, DeflatePlan p, 
     const int b = blockIdx.y;
     if (rec[4 * (size_t)b] == 0u) return;
     const int row0 = b * kDeflateBandRows;
-    const uint32_t n = p.stride * (uint32_t)min(kDeflateBandRows, p.H - row0);
+    const uint32_t n = p.raw_stride * (uint32_t)min(kDeflateBandRows, p.H - row0);
     const uint32_t k = blockIdx.x * kThreads + threadIdx.x;  // sample
     if (4u * k >= n) return;                                 // n = 16W * rows: whole samples
     uint8_t* o = out + (size_t)b * p.band_cap + 4u * k;      // band_cap is a multiple of 16, n <= band_cap
-    *reinterpret_cast<uint32_t*>(o) = sample_float<C>(fm, p, row0, k);
+    *reinterpret_cast<uint32_t*>(o) = sample_float<C>(fm, p.W, row0, k);
 }
+
+// ---- PXR24 (rr_set_exr_codec RR_EXR_CODEC_PXR24): a third front end ----
+// A chunk of `rows` scanlines holds per scanline and channel one run of W
+// pixels: with v the half's 16 bits (S = 2) or the float's 24-bit form
+// (pxr24_rule.h, S = 3) and p the value of the pixel before (0 at x = 0), the
+// difference d = v - p as S planes of W bytes, the most significant first. A
+// scanline takes S C W bytes. A raw chunk is the file's own halfs or floats
+// (k_exr_raw, k_exr32_raw; DeflatePlan::raw_stride).
+template <int C, bool Full>
+struct Pxr24Front {
+    Film fm;
+    __device__ __forceinline__ uint32_t value(int W, int row0, uint32_t k) const {
+        if constexpr (Full) return float24_bits(sample_float<C>(fm, W, row0, k));
+        else return sample_half<C>(fm, W, row0, k);
+    }
+    __device__ __forceinline__ uint32_t operator()(const DeflatePlan& p, int row0, uint32_t, uint32_t j) const {
+        constexpr uint32_t S = Full ? 3u : 2u;
+        const uint32_t W = (uint32_t)p.W, run = S * W;
+        const uint32_t row = j / p.stride, r = j - row * p.stride;
+        const uint32_t ch = r / run, q = r - ch * run;
+        const uint32_t plane = q / W, x = q - plane * W;
+        const uint32_t k = (row * (uint32_t)C + ch) * W + x;
+        uint32_t d = value(p.W, row0, k);
+        if (x > 0) d -= value(p.W, row0, k - 1u);
+        return (d >> (8u * (S - 1u - plane))) & 0xFFu;
+    }
+};
 
 }  // namespace
 
@@ -229,26 +177,46 @@ bool exr32_plan(int W, int H, int C, DeflatePlan& p) {
     return ok;
 }
 
-size_t exr_stream_max_bytes(const DeflatePlan& p) { return (size_t)p.stride * (size_t)p.H; }
+bool pxr24_plan(int W, int H, int C, int depth, DeflatePlan& p) {
+    // the ranges of the ZIP coder at the same depth
+    const bool full = depth == 32;
+    if (W <= 0 || H <= 0 || W > (full ? 1 << 18 : 1 << 19) || (C != 1 && C != 3 && C != 4)) return false;
+    const uint32_t w = (uint32_t)W, cw = (uint32_t)C * w;
+    const uint32_t stride = (full ? 3u : 2u) * cw;
+    const bool ok = deflate_plan(W, H, stride, p, (full ? 4u : 2u) * cw);
+    // 1; W: the next byte plane of the same run; the row's stride: the scanline above
+    p.dist[0] = 1u;
+    p.dist[1] = w <= 32768u ? w : 0u;
+    p.dist[2] = stride <= 32768u ? stride : 0u;
+    deflate_distinct(p);  // narrow images: W = 1
+    p.own_stream = 1;
+    return ok;
+}
+
+size_t exr_stream_max_bytes(const DeflatePlan& p) { return (size_t)p.raw_stride * (size_t)p.H; }
 
 namespace {
 
 template <int C>
-void exr_launch(const Film& fm, bool full, const DeflatePlan& p, const DeflateBufs& c, hipStream_t st) {
-    if (full) k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFloatFront<C>{fm}, p, c.filt, c.adler_part);
-    else k_deflate_front<<<dim3(p.nsub, p.nbands), 256, 0, st>>>(ExrFront<C>{fm}, p, c.filt, c.adler_part);
+void exr_launch(const Film& fm, bool full, bool pxr24, const DeflatePlan& p, const DeflateBufs& c, hipStream_t st) {
+    const dim3 front(p.nsub, p.nbands);
+    if (pxr24 && full) k_deflate_front<<<front, 256, 0, st>>>(Pxr24Front<C, true>{fm}, p, c.filt, c.adler_part);
+    else if (pxr24) k_deflate_front<<<front, 256, 0, st>>>(Pxr24Front<C, false>{fm}, p, c.filt, c.adler_part);
+    else if (full) k_deflate_front<<<front, 256, 0, st>>>(ExrFloatFront<C>{fm}, p, c.filt, c.adler_part);
+    else k_deflate_front<<<front, 256, 0, st>>>(ExrFront<C>{fm}, p, c.filt, c.adler_part);
     deflate_bands_device(p, c, st);
-    const dim3 grid((p.band_full / (full ? 4 : 2) + kThreads - 1) / kThreads, p.nbands);
+    const uint32_t raw_full = p.raw_stride * (uint32_t)std::min(p.H, kDeflateBandRows);  // band_full but for PXR24 FLOAT
+    const dim3 grid((raw_full / (full ? 4 : 2) + kThreads - 1) / kThreads, p.nbands);
     if (full) k_exr32_raw<C><<<grid, kThreads, 0, st>>>(fm, p, c.rec, c.out);
     else k_exr_raw<C><<<grid, kThreads, 0, st>>>(fm, p, c.rec, c.out);
 }
 
-void exr_encode(const Film& fm, bool full, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
-                uint32_t* host_tab, hipStream_t st) {
+void exr_encode(const Film& fm, bool full, bool pxr24, int C, const DeflatePlan& p, uint32_t* scratch,
+                uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
     const DeflateBufs c = deflate_carve(p, scratch);
-    if (C == 1) exr_launch<1>(fm, full, p, c, st);
-    else if (C == 3) exr_launch<3>(fm, full, p, c, st);
-    else exr_launch<4>(fm, full, p, c, st);
+    if (C == 1) exr_launch<1>(fm, full, pxr24, p, c, st);
+    else if (C == 3) exr_launch<3>(fm, full, pxr24, p, c, st);
+    else exr_launch<4>(fm, full, pxr24, p, c, st);
     deflate_gather_device(p, c, host_out, host_tab, st);
 }
 
@@ -256,12 +224,17 @@ void exr_encode(const Film& fm, bool full, int C, const DeflatePlan& p, uint32_t
 
 void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
                        uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
-    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, false, C, p, scratch, host_out, host_tab, st);
+    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, false, false, C, p, scratch, host_out, host_tab, st);
 }
 
 void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
                          uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
-    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, true, C, p, scratch, host_out, host_tab, st);
+    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, true, false, C, p, scratch, host_out, host_tab, st);
+}
+
+void pxr24_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, int depth, const DeflatePlan& p,
+                         uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
+    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, depth == 32, true, C, p, scratch, host_out, host_tab, st);
 }
 
 }  // namespace rr

@@ -14,6 +14,7 @@
 
 #include "deflate.hpp"
 #include "device.hpp"
+#include "exr_codec.hpp"
 #include "hdr.hpp"
 #include "iris.hpp"
 #include "rr.h"
@@ -76,6 +77,7 @@ struct CodedOut {
     JpegOut jpeg;
     rr::DeflatePlan deflate{};
     BodyShape body;  // of the plan below that the frame's format uses
+    rr::ExrRowsPlan exr_rows{};  // OPEN_EXR with the codec NONE or RLE: a body in the stream, RLE's row table in tab
     rr::TgaPlan tga{};
     rr::HdrPlan hdr{};
     rr::IrisPlan iris{};
@@ -120,7 +122,8 @@ struct FrameSlot {
     PinnedBuf host_rgba, host_counters, host_upload;
     CodedOut coded;  // the device-coded file's stream; a deflate frame's plan is made when the frame is submitted
     rr::FrameSetup fs;
-    std::string quality_warning;    // a WEBP frame below quality 100: lossless all the same
+    // a WEBP frame below quality 100: lossless all the same; an OPEN_EXR frame of a codec not built: ZIP
+    std::string quality_warning;
     bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
     std::string view_warning;
     double submit_at = 0.0;         // UNIX time when the device work was enqueued

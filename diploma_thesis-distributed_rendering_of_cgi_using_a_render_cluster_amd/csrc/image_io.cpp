@@ -8,6 +8,7 @@
 // encoded on parallel host threads and joined with RSTn markers.
 #include "image_io.hpp"
 
+#include "exr_rle_rule.h"
 #include "grey.h"
 #include "hdr_rule.h"
 #include "iris_rule.h"
@@ -613,12 +614,11 @@ void exr_attr(std::vector<uint8_t>& o, const char* name, const char* type, const
 }
 }  // namespace
 
-bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
-                     std::vector<uint8_t>& out, int pixel_type, int channels) {
+namespace {
+// The file's magic, version and header with the compression attribute `compression`.
+bool exr_header_bytes(int W, int H, int pixel_type, int channels, int compression, std::vector<uint8_t>& out) {
     if (channels != 1 && channels != 3 && channels != 4) return false;
-    const uint32_t row_bytes = (pixel_type == 2 ? 4u : 2u) * (uint32_t)channels * (uint32_t)W;  // planes of FLOAT or HALF
     out.clear();
-    out.reserve(n + 512 + (size_t)nchunks * 22);
     const uint8_t start[8] = {0x76, 0x2F, 0x31, 0x01, 2, 0, 0, 0};
     out.insert(out.end(), start, start + 8);
     std::vector<uint8_t> v;
@@ -632,7 +632,7 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
     }
     v.push_back(0);
     exr_attr(out, "channels", "chlist", v);
-    exr_attr(out, "compression", "compression", {3});  // ZIP, 16 scanlines
+    exr_attr(out, "compression", "compression", {(uint8_t)compression});  // 3: ZIP, 16 scanlines
     v.clear();
     put_le(v, 0, 4);
     put_le(v, 0, 4);
@@ -646,6 +646,20 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
     exr_attr(out, "screenWindowCenter", "v2f", std::vector<uint8_t>(8, 0));
     exr_attr(out, "screenWindowWidth", "float", one);
     out.push_back(0);
+    return true;
+}
+}  // namespace
+
+bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
+                     std::vector<uint8_t>& out, int pixel_type, int channels, int compression) {
+    const uint32_t row_bytes = (pixel_type == 2 ? 4u : 2u) * (uint32_t)channels * (uint32_t)W;  // planes of FLOAT or HALF
+    // the bytes of a scanline as the chunk's stream holds them: PXR24 (5) 3 of a float's 4
+    const uint32_t front_row_bytes = compression == 5 && pixel_type == 2 ? row_bytes / 4u * 3u : row_bytes;
+    std::vector<uint8_t> head;
+    if (!exr_header_bytes(W, H, pixel_type, channels, compression, head)) return false;
+    out.clear();
+    out.reserve(n + 512 + (size_t)nchunks * 22);
+    out = head;
     uint64_t at = out.size() + 8ull * (uint64_t)nchunks;
     for (int b = 0; b < nchunks; ++b) {
         put_le(out, at, 8);
@@ -656,8 +670,9 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
         const uint32_t mode = chunk_tab[4 * b], len = chunk_tab[4 * b + 1], adler = chunk_tab[4 * b + 2];
         if (src + len > n) return false;
         // a raw chunk is its scanlines' bytes, a coded one is smaller
-        const uint32_t raw = row_bytes * (uint32_t)std::min(16, H - b * 16);
-        if (chunk_tab[4 * b + 3] != raw || (mode == 0 ? len + 6 >= raw : len != raw)) return false;
+        const uint32_t rows = (uint32_t)std::min(16, H - b * 16);
+        const uint32_t raw = row_bytes * rows;
+        if (chunk_tab[4 * b + 3] != front_row_bytes * rows || (mode == 0 ? len + 6 >= raw : len != raw)) return false;
         put_le(out, (uint32_t)(b * 16), 4);
         put_le(out, mode == 0 ? len + 6 : len, 4);
         if (mode == 0) {
@@ -667,6 +682,29 @@ bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t
         out.insert(out.end(), data + src, data + src + len);
         if (mode == 0)
             for (int k = 3; k >= 0; --k) out.push_back((uint8_t)(adler >> (8 * k)));
+        src += len;
+    }
+    return src == n;
+}
+
+bool exr_wrap_rows(int W, int H, const uint8_t* data, size_t n, const uint32_t* row_tab, std::vector<uint8_t>& out,
+                   int pixel_type, int channels, int compression) {
+    const uint32_t row_bytes = (pixel_type == 2 ? 4u : 2u) * (uint32_t)channels * (uint32_t)W;
+    if (!exr_header_bytes(W, H, pixel_type, channels, compression, out)) return false;
+    out.reserve(out.size() + n + (size_t)H * 16);
+    uint64_t at = out.size() + 8ull * (uint64_t)H;
+    for (int y = 0; y < H; ++y) {
+        put_le(out, at, 8);
+        at += 8 + (row_tab ? row_tab[2 * y + 1] : row_bytes);
+    }
+    size_t src = 0;
+    for (int y = 0; y < H; ++y) {
+        const uint32_t mode = row_tab ? row_tab[2 * y] : 1u, len = row_tab ? row_tab[2 * y + 1] : row_bytes;
+        // a raw chunk is its scanline's bytes, a coded one is smaller and not empty
+        if (src + len > n || (mode == 0 ? len >= row_bytes || len == 0 : len != row_bytes)) return false;
+        put_le(out, (uint32_t)y, 4);
+        put_le(out, len, 4);
+        out.insert(out.end(), data + src, data + src + len);
         src += len;
     }
     return src == n;
@@ -707,6 +745,8 @@ void rle_pack_row(const uint8_t* row, size_t W, std::vector<uint8_t>& out) {
 }
 
 }  // namespace
+
+void exr_rle_pack(const uint8_t* bytes, size_t n, std::vector<uint8_t>& out) { rle_pack_row<ExrRle>(bytes, n, out); }
 
 // ------------------------------------------------------------- TARGA ------
 void tga_header_bytes(int W, int H, int C, bool rle, std::vector<uint8_t>& out) {

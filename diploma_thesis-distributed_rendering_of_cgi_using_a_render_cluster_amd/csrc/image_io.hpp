@@ -56,10 +56,22 @@ void png_wrap_stream(int W, int H, const uint8_t* z, size_t n, const uint32_t* b
 // bytes} per chunk. Mode 0: deflate data, wrapped here in 78 01 ... Adler-32;
 // mode 1: the raw chunk. pixel_type: 1 HALF (8W bytes a scanline) or 2 FLOAT
 // (16W), the type of all four channels; nothing else in the header depends on
-// it. channels: 4 the list A, B, G, R; 3: B, G, R; 1: Y. false: the pieces do
+// it. compression: the header's attribute, 3 ZIP or 5 PXR24 (whose FLOAT
+// chunks code 3 bytes a sample; a raw chunk is the full floats). channels: 4 the list A, B, G, R; 3: B, G, R; 1: Y. false: the pieces do
 // not add up to n, or a chunk's size is not what its scanlines allow.
 bool exr_wrap_stream(int W, int H, const uint8_t* data, size_t n, const uint32_t* chunk_tab, int nchunks,
-                     std::vector<uint8_t>& out, int pixel_type = 1, int channels = 4);
+                     std::vector<uint8_t>& out, int pixel_type = 1, int channels = 4, int compression = 3);
+// The same file with a chunk per scanline (compression 0 NONE, 1 RLE) around
+// the dense body coded on the device (exr_codec.hip): data = the scanlines'
+// chunks back to back, row_tab = {mode, bytes} per scanline, mode 0 packets
+// (fewer bytes than the scanline's), 1 the raw scanline; nullptr: every
+// scanline raw. false: the chunks do not add up to n, or a size is not what
+// its scanline allows.
+bool exr_wrap_rows(int W, int H, const uint8_t* data, size_t n, const uint32_t* row_tab, std::vector<uint8_t>& out,
+                   int pixel_type, int channels, int compression);
+// The packets of an RLE chunk for n bytes already reordered and differenced,
+// appended to out: the host statement of exr_rle_rule.h.
+void exr_rle_pack(const uint8_t* bytes, size_t n, std::vector<uint8_t>& out);
 // A TARGA file of the RGBA8 image (tga_rule.h): the 18-byte header (no id, no
 // colour map, type 2 true colour or 3 grey, + 8 run-length coded, bottom-left
 // origin, 8 C bits a pixel, 8 alpha bits for C = 4) and the body, rows bottom

@@ -211,6 +211,7 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         if (const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded)) return rc;
         sl->quality_warning.clear();
         if (fo.coder == Coder::Webp) sl->quality_warning = webp_quality_warning(fo.quality);
+        else sl->quality_warning = exr_codec_warning(fo);
         if (fo.coder == Coder::Png16) {
             set_device(c);
             ensure_srgb16(c);
@@ -366,6 +367,12 @@ int rr_set_exr_depth(rr_ctx* c, int32_t depth) {
     if (!c) return fail(RR_EINVAL, "NULL ctx");
     std::string err;
     return setter_result(set_exr_depth(c->settings, depth, err), err);
+}
+
+int rr_set_exr_codec(rr_ctx* c, int32_t codec) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_exr_codec(c->settings, codec, err), err);
 }
 
 int rr_set_color_mode(rr_ctx* c, int32_t mode) {

@@ -10,6 +10,7 @@
 #include "frame.hpp"
 #include "image_io.hpp"
 #include "png_filter.h"
+#include "pxr24_rule.h"
 
 using namespace rr;
 
@@ -36,8 +37,10 @@ int debug_view_settings(const rr_ctx* c, int view, int& look, float& gamma) {
 // or float RGBA means for a coder of the film, CoderInfo::film) through coder k in C
 // channels, with the context's PNG compression; the file's bytes to `out` if
 // `cap` suffices. alpha_one, view_transform, exposure_scale: CoderInput's.
+// exr_codec: FrameOutput's (rr_debug_encode_device: the context's).
 int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, bool alpha_one, int view_transform,
-                 float exposure_scale, int quality, uint8_t* out, uint64_t cap, uint64_t* len, bool tga_raw = false) {
+                 float exposure_scale, int quality, uint8_t* out, uint64_t cap, uint64_t* len, bool tga_raw = false,
+                 int exr_codec = RR_EXR_CODEC_ZIP) {
     CoderInput in;
     in.W = w;
     in.H = h;
@@ -46,9 +49,10 @@ int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, boo
     in.view_transform = view_transform;
     if (k == Coder::Png16)
         if (const int rc = debug_view_settings(c, view_transform, in.look, in.gamma)) return rc;
-    const FrameOutput fo{k, C, png_compression_of(c->settings), quality, tga_raw};
+    const FrameOutput fo{k, C, png_compression_of(c->settings), quality, tga_raw, exr_codec};
     if (const int rc = plan_or_refuse(fo, w, h, c->home_coded)) return rc;
     if (k == Coder::Webp) c->frame_warning = webp_quality_warning(quality);  // flagged as a frame's file is
+    if ((k == Coder::Exr || k == Coder::Exr32) && exr_codec != RR_EXR_CODEC_ZIP) c->frame_warning = exr_codec_warning(fo);
     return guarded([&] {
         if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
         set_device(c);
@@ -137,7 +141,7 @@ int rr_debug_encode_device(rr_ctx* c, const char* format, int32_t depth, int32_t
     }
     // (WEBP: a jpeg_quality below 100 is flagged, rr_last_warning, the file lossless)
     return debug_encode(c, k, C, image, w, h, true, view_transform, exposure_scale, jpeg_quality, out, cap, len,
-                        f->tga_raw);
+                        f->tga_raw, exr_codec_of(c->settings));
 }
 
 int rr_debug_hdr_host(const float* rgba, int32_t w, int32_t h, int32_t color_mode, uint8_t* out, uint64_t cap,
@@ -167,6 +171,33 @@ int rr_debug_scene_png_compression(rr_scene* s, int32_t* compression) {
     if (!s || !compression) return fail(RR_EINVAL, "NULL argument");
     *compression = s->desc.render.png_compression;
     return RR_OK;
+}
+
+int rr_debug_scene_exr_codec(rr_scene* s, int32_t* codec) {
+    if (!s || !codec) return fail(RR_EINVAL, "NULL argument");
+    *codec = s->desc.render.exr_codec;
+    return RR_OK;
+}
+
+int rr_debug_float24(const float* in, uint64_t n, uint32_t* out) {
+    if ((!in || !out) && n) return fail(RR_EINVAL, "NULL array");
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t bits;
+        std::memcpy(&bits, in + i, 4);
+        out[i] = float24_bits(bits);
+    }
+    return RR_OK;
+}
+
+int rr_debug_exr_rle(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len) {
+    if (!in || !len || !n) return fail(RR_EINVAL, "bad arguments");
+    return guarded([&] {
+        std::vector<uint8_t> data;
+        exr_rle_pack(in, (size_t)n, data);
+        *len = data.size();
+        if (out && cap >= *len) std::memcpy(out, data.data(), data.size());
+        return RR_OK;
+    });
 }
 
 int rr_debug_sin_fixed(const float* in, uint64_t n, float* out) {

@@ -12,6 +12,7 @@
 
 #include "json.hpp"
 #include "looks.hpp"
+#include "settings.hpp"
 
 namespace rr {
 
@@ -660,6 +661,16 @@ SceneDesc load_scene(const std::string& path) {
         if (exr_depth != 16.0 && exr_depth != 32.0)
             throw std::runtime_error("render.exr_depth must be 16 or 32, got " + std::to_string(exr_depth));
         d.exr_depth = (int)exr_depth;
+        // Blender's image_settings.exr_codec by its enum name; no field: ZIP (rr_set_exr_codec SCENE takes it)
+        if (r.has("exr_codec")) {
+            const Json& v = r["exr_codec"];
+            const int codec = v.type == Json::String ? exr_codec_of_name(v.str) : -1;
+            if (codec < 0)
+                throw std::runtime_error(
+                    "render.exr_codec must be \"NONE\", \"RLE\", \"ZIPS\", \"ZIP\", \"PIZ\", \"PXR24\", \"B44\", "
+                    "\"B44A\", \"DWAA\" or \"DWAB\"");
+            d.exr_codec = codec;
+        }
         // Blender's image_settings.color_mode; no field: each format's own layout (rr_set_color_mode)
         const std::string color_mode = r.get_str("color_mode", "");
         if (color_mode == "BW") d.color_mode = RR_COLOR_BW;

@@ -118,6 +118,7 @@ struct RenderDesc {
     int look = 0;        // looks.hpp kLooks id of render.look (0 None; rr_set_look NULL takes it)
     double gamma = 1.0;  // render.gamma, in (0, 5] (rr_set_display_gamma 0 takes it)
     double dither_intensity = 0.0;  // render.dither_intensity, in [0, 2] (rr_set_dither RR_DITHER_SCENE takes it)
+    int exr_codec = RR_EXR_CODEC_ZIP;  // render.exr_codec, an RR_EXR_CODEC_* value; no field: ZIP (rr_set_exr_codec SCENE takes it)
     int png_compression = -1;  // render.png_compression, 0 .. 100; -1: no field (rr_set_png_compression SCENE takes it)
     // What of the scene's colour management no frame can apply, for the
     // frame's warning ("" when there is nothing): a view transform this

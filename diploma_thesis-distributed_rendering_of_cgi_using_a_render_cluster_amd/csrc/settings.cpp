@@ -27,6 +27,15 @@ bool set_exr_depth(OutputSettings& s, int depth, std::string& err) {
     return true;
 }
 
+bool set_exr_codec(OutputSettings& s, int codec, std::string& err) {
+    if (codec < RR_EXR_CODEC_SCENE || codec > RR_EXR_CODEC_DWAB) {
+        err = "EXR codec must be RR_EXR_CODEC_SCENE (0) or one of RR_EXR_CODEC_NONE (1) .. RR_EXR_CODEC_DWAB (10)";
+        return false;
+    }
+    s.exr_codec = codec;
+    return true;
+}
+
 bool valid_color_mode(int mode) {
     return mode == RR_COLOR_SCENE || mode == RR_COLOR_BW || mode == RR_COLOR_RGB || mode == RR_COLOR_RGBA;
 }
@@ -115,6 +124,15 @@ bool apply_text(OutputSettings& s, const std::string& var, const char* t, std::s
         const int d = n == (long)(int)n ? (int)n : -1;
         return var == "RR_PNG_DEPTH" ? set_png_depth(s, d, err) : set_exr_depth(s, d, err);
     }
+    if (var == "RR_EXR_CODEC") {
+        if (v.empty()) return set_exr_codec(s, RR_EXR_CODEC_SCENE, err);
+        const int k = exr_codec_of_name(t);
+        if (k < 0) {
+            err = "EXR codec must be NONE, RLE, ZIPS, ZIP, PIZ, PXR24, B44, B44A, DWAA or DWAB";
+            return false;
+        }
+        return set_exr_codec(s, k, err);
+    }
     if (var == "RR_COLOR_MODE") {
         if (v.empty()) return set_color_mode(s, RR_COLOR_SCENE, err);
         if (v == "BW") return set_color_mode(s, RR_COLOR_BW, err);
@@ -154,8 +172,8 @@ bool apply_text(OutputSettings& s, const std::string& var, const char* t, std::s
     return false;
 }
 
-constexpr const char* kEnvVars[] = {"RR_PNG_DEPTH",     "RR_EXR_DEPTH",       "RR_COLOR_MODE", "RR_LOOK",
-                                    "RR_DISPLAY_GAMMA", "RR_PNG_COMPRESSION", "RR_DITHER",     "RR_DEVICE_PNG"};
+constexpr const char* kEnvVars[] = {"RR_PNG_DEPTH",     "RR_EXR_DEPTH",       "RR_EXR_CODEC", "RR_COLOR_MODE", "RR_LOOK",
+                                    "RR_DISPLAY_GAMMA", "RR_PNG_COMPRESSION", "RR_DITHER",    "RR_DEVICE_PNG"};
 
 }  // namespace
 
@@ -224,12 +242,24 @@ FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const c
     o.color_mode = resolve_color_mode(s.color_mode ? s.color_mode : r.color_mode, f && f->no_alpha);
     // the context's setting, at SCENE the scene's (-1, legacy, where it has no field)
     o.png_compression = s.png_compression == RR_PNG_COMPRESSION_SCENE ? r.png_compression : s.png_compression;
+    // the context's codec, at SCENE the scene's (ZIP where it has no field)
+    o.exr_codec = s.exr_codec != RR_EXR_CODEC_SCENE ? s.exr_codec : r.exr_codec;
     o.quality = jpeg_quality;
     return o;
 }
 
 int png_compression_of(const OutputSettings& s) {
     return s.png_compression >= 0 ? s.png_compression : RR_PNG_COMPRESSION_LEGACY;
+}
+
+int exr_codec_of(const OutputSettings& s) {
+    return s.exr_codec != RR_EXR_CODEC_SCENE ? s.exr_codec : RR_EXR_CODEC_ZIP;
+}
+
+std::string exr_codec_warning(const FrameOutput& fo) {
+    if ((fo.coder != Coder::Exr && fo.coder != Coder::Exr32) || exr_codec_built(fo.exr_codec)) return "";
+    return std::string("OPEN_EXR with codec ") + exr_codec_name(fo.exr_codec) +
+           ": that codec is not built, the file is ZIP (lossless, 16 scanlines a chunk)";
 }
 
 float dither_of(const OutputSettings& s) { return s.dither > 0.f ? s.dither : 0.f; }

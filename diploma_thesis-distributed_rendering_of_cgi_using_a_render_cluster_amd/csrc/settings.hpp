@@ -22,6 +22,8 @@ struct OutputSettings {
     int png_depth = 0;
     // channel type of "OPEN_EXR" frames (rr_set_exr_depth / RR_EXR_DEPTH): 0 the scene's, 16 HALF, 32 FLOAT
     int exr_depth = 0;
+    // compression of "OPEN_EXR" frames (rr_set_exr_codec / RR_EXR_CODEC): an RR_EXR_CODEC_* value, SCENE the scene's
+    int exr_codec = RR_EXR_CODEC_SCENE;
     // colour mode of the files (rr_set_color_mode / RR_COLOR_MODE): 0 the scene's, else RR_COLOR_BW / RGB / RGBA
     int color_mode = 0;
     // look of Filmic frames (rr_set_look / RR_LOOK): a looks.hpp kLooks id, -1 the scene's
@@ -40,6 +42,7 @@ struct OutputSettings {
 inline void set_device_png(OutputSettings& s, bool on) { s.device_png = on; }
 bool set_png_depth(OutputSettings& s, int depth, std::string& err);
 bool set_exr_depth(OutputSettings& s, int depth, std::string& err);
+bool set_exr_codec(OutputSettings& s, int codec, std::string& err);
 bool set_color_mode(OutputSettings& s, int mode, std::string& err);
 bool set_look(OutputSettings& s, const char* name, std::string& err);  // NULL or "": the scene's
 bool set_display_gamma(OutputSettings& s, double gamma, std::string& err);
@@ -47,10 +50,29 @@ bool set_dither(OutputSettings& s, double intensity, std::string& err);
 bool set_png_compression(OutputSettings& s, int percent, std::string& err);
 
 bool valid_color_mode(int mode);
+
+// Blender's names of the OpenEXR codecs, by RR_EXR_CODEC_* value ("" for SCENE
+// and anything else), and the value of a name (-1: no codec's name).
+inline const char* exr_codec_name(int codec) {
+    constexpr const char* names[] = {"", "NONE", "RLE", "ZIPS", "ZIP", "PIZ", "PXR24", "B44", "B44A", "DWAA", "DWAB"};
+    static_assert(sizeof names / sizeof *names == RR_EXR_CODEC_DWAB + 1, "a name for every value");
+    return codec > RR_EXR_CODEC_SCENE && codec <= RR_EXR_CODEC_DWAB ? names[codec] : "";
+}
+inline int exr_codec_of_name(const std::string& name) {
+    for (int k = RR_EXR_CODEC_SCENE + 1; k <= RR_EXR_CODEC_DWAB; ++k)
+        if (name == exr_codec_name(k)) return k;
+    return -1;
+}
+// The codecs that are built: a frame that asks for another is written as ZIP
+// and flagged (exr_codec_warning).
+inline bool exr_codec_built(int codec) {
+    return codec == RR_EXR_CODEC_NONE || codec == RR_EXR_CODEC_RLE || codec == RR_EXR_CODEC_ZIP ||
+           codec == RR_EXR_CODEC_PXR24;
+}
 // rr_set_png_compression's values: LEGACY, SCENE or a percentage.
 bool valid_png_compression(int v);
 
-// One variable's text (RR_PNG_DEPTH, RR_EXR_DEPTH, RR_COLOR_MODE, RR_LOOK,
+// One variable's text (RR_PNG_DEPTH, RR_EXR_DEPTH, RR_EXR_CODEC, RR_COLOR_MODE, RR_LOOK,
 // RR_DISPLAY_GAMMA, RR_PNG_COMPRESSION, RR_DITHER, RR_DEVICE_PNG) through its
 // setter. A refusal's err names the variable and quotes the text.
 bool setting_from_text(OutputSettings& s, const std::string& var, const char* text, std::string& err);
@@ -87,7 +109,14 @@ struct FrameOutput {
     int png_compression = RR_PNG_COMPRESSION_LEGACY;   // LEGACY, or 0 .. 100
     int quality = 0;                                   // JPEG
     bool tga_raw = false;                              // Coder::Tga: no run-length packets (Format::tga_raw)
+    int exr_codec = RR_EXR_CODEC_ZIP;                  // Coder::Exr, Exr32: the codec asked for, never SCENE
 };
+
+// The codec fo's OPEN_EXR file is written with: the one asked for where it is
+// built, else ZIP. And what rr_last_warning says of such a file ("" for a file
+// of another format or of a codec that is built).
+inline int exr_codec_written(const FrameOutput& fo) { return exr_codec_built(fo.exr_codec) ? fo.exr_codec : RR_EXR_CODEC_ZIP; }
+std::string exr_codec_warning(const FrameOutput& fo);
 
 // What a frame of a scene with render settings r is written as on a context
 // with settings s. format: a name of kFormats (known_format, checked by the
@@ -98,6 +127,8 @@ FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const c
 // The PNG compression of an image that comes with no scene (the inspection
 // entry points): the context's, SCENE meaning legacy.
 int png_compression_of(const OutputSettings& s);
+// The OpenEXR codec of such an image: the context's, SCENE meaning ZIP.
+int exr_codec_of(const OutputSettings& s);
 // The dither of such an image: the context's; none where it leaves the
 // intensity to a scene.
 float dither_of(const OutputSettings& s);

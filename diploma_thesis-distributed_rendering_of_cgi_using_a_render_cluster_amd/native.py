@@ -99,7 +99,27 @@ EXPORTS = [
     "rr_set_dither", "rr_debug_dither_noise", "rr_debug_sin_fixed",
     "rr_set_png_compression", "rr_encode_image_png", "rr_debug_png_filters", "rr_debug_scene_png_compression",
     "rr_debug_hdr_host",
+    "rr_set_exr_codec", "rr_debug_scene_exr_codec", "rr_debug_float24", "rr_debug_exr_rle",
 ]
+
+# rr_set_exr_codec's values (include/rr.h), by Blender's names of the codecs
+EXR_CODECS = {"": 0, "NONE": 1, "RLE": 2, "ZIPS": 3, "ZIP": 4, "PIZ": 5, "PXR24": 6, "B44": 7, "B44A": 8,
+              "DWAA": 9, "DWAB": 10}
+RR_EXR_CODEC_SCENE, RR_EXR_CODEC_NONE, RR_EXR_CODEC_RLE, RR_EXR_CODEC_ZIPS, RR_EXR_CODEC_ZIP = 0, 1, 2, 3, 4
+RR_EXR_CODEC_PIZ, RR_EXR_CODEC_PXR24, RR_EXR_CODEC_B44, RR_EXR_CODEC_B44A = 5, 6, 7, 8
+RR_EXR_CODEC_DWAA, RR_EXR_CODEC_DWAB = 9, 10
+
+
+def exr_codec_value(codec) -> int:
+    """One of Blender's codec names, "" / None (the scene's), or an RR_EXR_CODEC_* value, as an int."""
+    if codec is None:
+        return RR_EXR_CODEC_SCENE
+    if isinstance(codec, str):
+        if codec not in EXR_CODECS:
+            raise ValueError(f"EXR codec must be one of {', '.join(k for k in EXR_CODECS if k)}, got {codec!r}")
+        return EXR_CODECS[codec]
+    return int(codec)
+
 
 # rr_set_png_compression's values beside 0 .. 100 (include/rr.h)
 RR_PNG_COMPRESSION_LEGACY, RR_PNG_COMPRESSION_SCENE = -1, -2
@@ -212,6 +232,11 @@ def lib() -> ctypes.CDLL:
         "rr_encode_image_png": (c_int, [u8p, i32, i32, ctypes.c_char_p, i32, i32, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_png_filters": (c_int, [u8p, i32, i32, i32, u8p]),
         "rr_debug_scene_png_compression": (c_int, [P, i32p]),
+        "rr_set_exr_codec": (c_int, [P, i32]),
+        "rr_debug_scene_exr_codec": (c_int, [P, i32p]),
+        "rr_debug_float24": (c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+        "rr_debug_exr_rle": (c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                     ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_hdr_host": (c_int, [f32p, i32, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
@@ -340,6 +365,13 @@ class Scene:
         _check(lib().rr_debug_scene_png_compression(self.handle, ctypes.byref(v)))
         return v.value
 
+    def exr_codec(self) -> int:
+        """rr_debug_scene_exr_codec: the scene file's render.exr_codec as an
+        RR_EXR_CODEC_* value, RR_EXR_CODEC_ZIP where it has none (host only)."""
+        v = ctypes.c_int32()
+        _check(lib().rr_debug_scene_exr_codec(self.handle, ctypes.byref(v)))
+        return v.value
+
     def object_matrix(self, obj: int, frame: float) -> np.ndarray:
         m = (ctypes.c_double * 16)()
         _check(lib().rr_debug_object_matrix(self.handle, obj, float(frame), m))
@@ -350,8 +382,11 @@ class RenderContext:
     """One HIP device (rr_ctx). Not thread-safe; one frame in flight at a time."""
 
     def __init__(self, device: int = 0, png_depth: int = 0, exr_depth: int = 0, color_mode=0,
-                 look: str | None = None, display_gamma: float = 0.0, dither=None, png_compression=None):
-        """dither: the dither of the 8-bit images (set_dither): an intensity in [0, 2] or
+                 look: str | None = None, display_gamma: float = 0.0, dither=None, png_compression=None,
+                 exr_codec=None):
+        """exr_codec: the compression of "OPEN_EXR" frames (set_exr_codec): one of Blender's names
+        or an RR_EXR_CODEC_* value; None: the context's own (the scene's, or what RR_EXR_CODEC says).
+        dither: the dither of the 8-bit images (set_dither): an intensity in [0, 2] or
         "scene"; None: the context's own (0, or what RR_DITHER says).
         png_compression: the compression of "PNG" files (set_png_compression): 0 .. 100,
         "scene" or "legacy"; None: the context's own (legacy, or what RR_PNG_COMPRESSION says).
@@ -377,6 +412,8 @@ class RenderContext:
             self.set_dither(dither)
         if png_compression is not None:
             self.set_png_compression(png_compression)
+        if exr_codec is not None:
+            self.set_exr_codec(exr_codec)
         self.device = device
 
     def close(self):
@@ -562,6 +599,14 @@ class RenderContext:
         if n.value > out.size:
             raise RRError(RR_EINVAL, f"device EXR of {n.value} bytes exceeds the {out.size}-byte buffer")
         return out[:n.value].tobytes()
+
+    def set_exr_codec(self, codec=RR_EXR_CODEC_SCENE):
+        """rr_set_exr_codec: Blender's image_settings.exr_codec for this context's
+        "OPEN_EXR" frames: "NONE", "RLE", "ZIP" or "PXR24" (coded on the device), ""
+        / None for each scene's render.exr_codec (ZIP without one), or one of the
+        codecs that are not built ("ZIPS", "PIZ", "B44", "B44A", "DWAA", "DWAB"):
+        such a frame is written as ZIP and last_warning says so."""
+        _check(lib().rr_set_exr_codec(self.handle, exr_codec_value(codec)), self.handle)
 
     def set_exr_depth(self, depth: int = 0):
         """rr_set_exr_depth: channel type of "OPEN_EXR" frames of this context, 0
@@ -796,3 +841,23 @@ def png_filters(raw: np.ndarray, bpp: int) -> np.ndarray:
     _check(lib().rr_debug_png_filters(_ptr(raw.reshape(-1), ctypes.c_uint8), row_bytes, rows, int(bpp),
                                       _ptr(out, ctypes.c_uint8)))
     return out
+
+
+def float24(values) -> np.ndarray:
+    """rr_debug_float24: the 24-bit form PXR24 files hold of float32 values
+    (host only), as uint32."""
+    a = np.ascontiguousarray(values, dtype=np.float32).ravel()
+    out = np.zeros(a.size, np.uint32)
+    _check(lib().rr_debug_float24(a.ctypes.data, a.size, out.ctypes.data))
+    return out
+
+
+def exr_rle(data) -> bytes:
+    """rr_debug_exr_rle: the packets an RLE chunk holds for bytes that are
+    already reordered and differenced (host only)."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
+    cap = a.size + a.size // 127 + 2
+    out = np.zeros(cap, np.uint8)
+    n = ctypes.c_uint64()
+    _check(lib().rr_debug_exr_rle(a.ctypes.data, a.size, out.ctypes.data, cap, ctypes.byref(n)))
+    return out[: n.value].tobytes()

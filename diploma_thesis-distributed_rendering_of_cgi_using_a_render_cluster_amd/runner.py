@@ -42,7 +42,7 @@ class BackendRunner:
     def __init__(self, base_directory_path: str | os.PathLike, tracer: WorkerTraceBuilder | None = None,
                  device: int = 0, params: RenderParams | None = None, ctx=None, device_png: bool = False,
                  png_depth: int = 0, exr_depth: int = 0, color_mode=0, look: str | None = None,
-                 display_gamma: float = 0.0, dither=None, png_compression=None):
+                 display_gamma: float = 0.0, dither=None, png_compression=None, exr_codec=None):
         """ctx: a RenderContext on `device` is created here; tests of the host
         logic alone pass a stand-in with the same methods (no rendering).
         device_png: "PNG" jobs are coded on the device (rr_set_device_png).
@@ -65,6 +65,10 @@ class BackendRunner:
         dither: the dither of every job's 8-bit images (rr_set_dither): an
         intensity in [0, 2], "scene" for each scene's own
         render.dither_intensity, or None for the context's own (0, or RR_DITHER).
+        exr_codec: Blender's codec of every job's "OPEN_EXR" files
+        (rr_set_exr_codec): "NONE", "RLE", "ZIP", "PXR24", "" for each scene's own
+        render.exr_codec, or None for the context's own (the scene's, or what
+        RR_EXR_CODEC says). A codec that is not built is written as ZIP and flagged.
         png_compression: Blender's compression of every job's "PNG" files
         (rr_set_png_compression): 0 .. 100, "scene" for each scene's own
         render.png_compression, "legacy", or None for the context's own (legacy,
@@ -92,6 +96,8 @@ class BackendRunner:
             self.ctx.set_dither(dither)
         if png_compression is not None:
             self.ctx.set_png_compression(png_compression)
+        if exr_codec is not None:
+            self.ctx.set_exr_codec(exr_codec)
         self._scenes: dict[str, Scene] = {}
         self._lock = threading.Lock()  # one caller at a time per context (queue.rs:79-118)
         self.last_stats = None

@@ -621,6 +621,80 @@ int rr_debug_png_filters(const uint8_t* raw, int32_t row_bytes, int32_t rows,
  * RR_PNG_COMPRESSION_LEGACY for a scene without render.png_compression. */
 int rr_debug_scene_png_compression(rr_scene* scene, int32_t* compression);
 
+/* Compression of ctx's "OPEN_EXR" files: Blender's image_settings.exr_codec
+ * behind write_still (render-timing-script.py:83-92).
+ *  - RR_EXR_CODEC_SCENE (the default): the scene's render.exr_codec (one of
+ *    Blender's names "NONE", "RLE", "ZIPS", "ZIP", "PIZ", "PXR24", "B44",
+ *    "B44A", "DWAA", "DWAB"), and ZIP where the scene has none: the files as
+ *    they were before there was a setting, byte for byte.
+ *  - RR_EXR_CODEC_ZIP: zlib over chunks of 16 scanlines (exr.hip).
+ *  - RR_EXR_CODEC_NONE: a chunk per scanline, its planes (A, B, G, R / B, G, R
+ *    / Y) as little-endian halfs or floats, unprocessed.
+ *  - RR_EXR_CODEC_RLE: a chunk per scanline; its n bytes reordered (even-
+ *    indexed bytes first) and differenced as for ZIP, then run-length packets:
+ *    the byte count - 1 (0 .. 127) and a value for a run of count bytes, the
+ *    byte -count (as a signed char, count 1 .. 127) and count bytes for a
+ *    literal. Runs start from 3 equal bytes. A scanline whose packets are not
+ *    shorter than n is stored as its n unprocessed bytes.
+ *  - RR_EXR_CODEC_PXR24: zlib over chunks of 16 scanlines of byte planes of
+ *    differences between neighbouring pixels: HALF channels their 16 bits
+ *    (lossless), FLOAT channels rounded to 24 bits (sign, exponent, 15
+ *    mantissa bits; lossy, as in OpenEXR). A chunk whose stream is not smaller
+ *    than its unprocessed scanlines is stored as those: full floats at FLOAT.
+ *  - RR_EXR_CODEC_ZIPS, _PIZ, _B44, _B44A, _DWAA, _DWAB: not built. The file
+ *    is written as ZIP, which is lossless and which every reader reads, and
+ *    rr_last_warning names the codec asked for. The frame never fails.
+ * NONE, RLE and PXR24 are coded on the device (exr_codec.hip, exr.hip), at
+ * both depths and in every colour mode; the sizes refused are those of ZIP at
+ * the same depth. Pinned: the file structure, OpenEXR's decoder contract (a
+ * negative count copies -count bytes, otherwise count + 1 copies of the next
+ * byte; a chunk of the raw size is raw) and the bytes against a numpy
+ * restatement. Not pinned (no OpenEXR library was at hand): which bytes go
+ * into which RLE packet (the project's own rule, exr_rle_rule.h; any decoder
+ * returns the same bytes), the 24-bit rounding (pxr24_rule.h, restated from
+ * OpenEXR's floatToFloat24 from memory), and the numbers of Blender's DNA
+ * that tools/blend_export.py maps to the names.
+ * rr_create reads RR_EXR_CODEC (one of the names above; empty: the scene's)
+ * from the environment the same way; any other text fails rr_create with
+ * RR_EINVAL. Applies to frames submitted after the call and to
+ * rr_debug_encode_device("OPEN_EXR", 16 | 32, ...), where RR_EXR_CODEC_SCENE
+ * means ZIP; frames in flight keep the codec of their submit. PNG, JPEG and
+ * the other formats are unaffected. RR_EINVAL for a NULL ctx or any other
+ * value. */
+#define RR_EXR_CODEC_SCENE 0
+#define RR_EXR_CODEC_NONE 1
+#define RR_EXR_CODEC_RLE 2
+#define RR_EXR_CODEC_ZIPS 3
+#define RR_EXR_CODEC_ZIP 4
+#define RR_EXR_CODEC_PIZ 5
+#define RR_EXR_CODEC_PXR24 6
+#define RR_EXR_CODEC_B44 7
+#define RR_EXR_CODEC_B44A 8
+#define RR_EXR_CODEC_DWAA 9
+#define RR_EXR_CODEC_DWAB 10
+int rr_set_exr_codec(rr_ctx* ctx, int32_t codec);
+
+/* The codec a scene file asks for (host only; write_still's
+ * image_settings.exr_codec, render-timing-script.py:83-92): an
+ * RR_EXR_CODEC_* value, RR_EXR_CODEC_ZIP for a scene without
+ * render.exr_codec. */
+int rr_debug_scene_exr_codec(rr_scene* scene, int32_t* codec);
+
+/* The 24-bit form PXR24 files hold of FLOAT samples (write_still's OPEN_EXR
+ * files, render-timing-script.py:83-92), evaluated on the host by the rule the
+ * device coder uses (pxr24_rule.h): out[i] = the 24 bits of in[i]; a reader
+ * returns out[i] << 8 as the float's bits. Exported so that tests tie the C
+ * statement to numpy. RR_EINVAL for a NULL array with n > 0. */
+int rr_debug_float24(const float* in, uint64_t n, uint32_t* out);
+
+/* The run-length packets an RLE chunk holds for n bytes that are already
+ * reordered and differenced (write_still's OPEN_EXR files,
+ * render-timing-script.py:83-92), by the host statement of exr_rle_rule.h.
+ * *len receives the packets' length; they are copied to out if cap >= *len.
+ * Exported so that tests tie the C statement to numpy. RR_EINVAL for a NULL
+ * array or n = 0. */
+int rr_debug_exr_rle(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len);
+
 /* Run the 8-bit view pass (the one frames of the Filmic family and frames
  * with a display gamma or a dither take after rendering) on a float RGBA image
  * of the caller's (width * height * 4 floats, taken as means: spp = 1): value *

@@ -175,6 +175,11 @@ def export_action(bf, act_blk):
 COLOR_MODE_OF_PLANES = {8: "BW", 24: "RGB", 32: "RGBA"}
 
 
+# ImageFormatData.exr_codec (R_IMF_EXR_CODEC_*) -> Blender's enum name, which render.exr_codec holds
+EXR_CODEC_OF_DNA = {0: "NONE", 1: "PXR24", 2: "ZIP", 3: "PIZ", 4: "RLE", 5: "ZIPS", 6: "B44", 7: "B44A", 8: "DWAA",
+                    9: "DWAB"}
+
+
 def export(path: str, args) -> dict:
     bf = BlendFile(path)
     sc = bf.blocks_with_code(b"SC")[0]
@@ -215,6 +220,12 @@ def export(path: str, args) -> dict:
         out["render"]["color_depth"] = color_depth
     if exr_depth != 16:  # likewise: 16 is what a scene without the field means
         out["render"]["exr_depth"] = exr_depth
+    # image_settings.exr_codec: ImageFormatData.exr_codec holds R_IMF_EXR_CODEC_*. The numbers
+    # are restated from memory and not pinned against a Blender; a number outside the list
+    # exports as ZIP. ZIP is what a scene without the field means
+    exr_codec = EXR_CODEC_OF_DNA.get(bf.read_struct_at(rd("im_format"), "ImageFormatData", "exr_codec"), "ZIP")
+    if exr_codec != "ZIP":
+        out["render"]["exr_codec"] = exr_codec
     # image_settings.color_mode: ImageFormatData.planes holds the bits of a pixel
     # (R_IMF_PLANES_BW 8, _RGB 24, _RGBA 32). Written only with --color-mode
     # project: a scene without the field keeps each format's own layout, and
