@@ -19,18 +19,21 @@ void ensure_srgb16(rr_ctx* c) {
     RR_HIP(hipMemcpy(c->srgb16_lut.ptr, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
-void ensure_jpeg_table(rr_ctx* c, int quality) {
-    if (c->jpeg_tab_quality == quality) return;
-    quiesce(c);
+const float* jpeg_table(rr_ctx* c, int quality) {
+    if (quality < 1 || quality > 100) throw std::runtime_error("jpeg_quality must be 1..100");
+    DevBuf<float>& d = c->jpeg_tab[quality];
+    if (d.ptr) return d.ptr;
     JpegTables t;
     jpeg_tables(quality, t);
     float tab[192];  // dct | qinv luma | qinv chroma
     std::memcpy(tab, t.dct, sizeof t.dct);
     std::memcpy(tab + 64, t.qinv_l, sizeof t.qinv_l);
     std::memcpy(tab + 128, t.qinv_c, sizeof t.qinv_c);
-    c->jpeg_tab.ensure(192);
-    RR_HIP(hipMemcpy(c->jpeg_tab.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
-    c->jpeg_tab_quality = quality;
+    DevBuf<float> fresh;  // a buffer no kernel reads yet: nothing to wait for
+    fresh.ensure(192);
+    RR_HIP(hipMemcpy(fresh.ptr, tab, sizeof tab, hipMemcpyHostToDevice));
+    d = std::move(fresh);
+    return d.ptr;
 }
 
 std::string webp_quality_warning(int quality) {
@@ -154,14 +157,18 @@ uint64_t stream_len(const CodedOut& o, const std::string& what, Over over) {
     return len;
 }
 
-// Device encode by body coder k into o's pinned stream, by the plan in o.
-void enqueue_body(Coder k, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o) {
+// What body coder k's plan in o takes of f's scratch and o's pinned buffers.
+void reserve_body(Coder k, int W, int H, DevFrame& f, CodedOut& o) {
     const BodyShape& b = o.body;
-    if (b.coder != k || b.W != in.W || b.H != in.H)
+    if (b.coder != k || b.W != W || b.H != H)
         throw std::runtime_error(std::string(coder_info(k).name) + " plan of another image");
     f.body_scratch.ensure(b.scratch_words);
     o.stream.ensure(body_stream_bytes(b.body_cap));
     if (device_deflate(k) && o.exr_rows.rle) o.tab.ensure((size_t)b.H * 2 * sizeof(uint32_t));  // the scanlines' table
+}
+
+// Device encode by body coder k into o's pinned stream, by the plan in o.
+void enqueue_body(Coder k, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o) {
     f.prof.begin(st, RR_K_PNG);
     body_coder(k).launch(in, o, f.body_scratch.ptr, device_pointer<uint8_t>(o.stream), st);
     f.prof.end(st);
@@ -178,8 +185,7 @@ void body_file_bytes(const CodedOut& o, Coder k, std::vector<uint8_t>& data) {
 
 // Device JPEG encode of an RGBA8 image (transform into f.jpeg_coeffs + Huffman
 // coding) into o's pinned stream. grey: a one-component file (RR_COLOR_BW).
-void enqueue_jpeg(rr_ctx* c, const CoderInput& in, bool grey, int quality, DevFrame& f, hipStream_t st, CodedOut& o) {
-    const int W = in.W, H = in.H;
+void reserve_jpeg(rr_ctx* c, int W, int H, bool grey, DevFrame& f, CodedOut& o) {
     if (!c->jpeg_huff.ptr) {
         quiesce(c);
         uint32_t h[4 * 256];
@@ -193,6 +199,12 @@ void enqueue_jpeg(rr_ctx* c, const CoderInput& in, bool grey, int quality, DevFr
     f.jpeg_blk.ensure(2 * nblocks + 2 * mcuy);
     f.jpeg_scratch.ensure(mcuy * jpeg_row_scratch_words(W, grey));
     o.stream.ensure(jpeg_stream_max_bytes(W, H, grey) + 16);
+}
+
+void enqueue_jpeg(rr_ctx* c, const CoderInput& in, bool grey, int quality, DevFrame& f, hipStream_t st, CodedOut& o) {
+    const int W = in.W, H = in.H;
+    const size_t mcuy = jpeg_mcu_rows(H, grey);
+    const size_t nblocks = jpeg_block_count(W, H, grey);
     o.jpeg = {W, H, quality, grey};
     uint32_t* blk = f.jpeg_blk.ptr;
     JpegDevBufs b{blk, blk + nblocks, blk + 2 * nblocks, blk + 2 * nblocks + mcuy, f.jpeg_scratch.ptr};
@@ -251,32 +263,44 @@ int plan_or_refuse(const FrameOutput& fo, int W, int H, CodedOut& o) {
     return ok ? RR_OK : fail(RR_EINVAL, coder_info(k).range);
 }
 
-void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o) {
+void reserve_coder(rr_ctx* c, const FrameOutput& fo, int W, int H, DevFrame& f, CodedOut& o) {
     const Coder k = fo.coder;
     const int C = fo.color_mode;
-    if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o);
-    if (device_body(k) || exr_rows(fo)) return enqueue_body(k, in, f, st, o);
+    if (k == Coder::Jpeg) return reserve_jpeg(c, W, H, C == RR_COLOR_BW, f, o);
+    if (device_body(k) || exr_rows(fo)) return reserve_body(k, W, H, f, o);
     if (!device_deflate(k)) throw std::runtime_error("no device coder for this output");
     // the front ends' own buffers. "PNG" at compression 0 .. 100: a filter type
     // per row of the H rows, and at 16 bits the raw scanlines, 2C W H bytes
     // (less than the plan's stream, which is below 2 GB)
     const bool png = k == Coder::Png8 || k == Coder::Png16;
     const bool adaptive = png && fo.png_compression >= 0;
+    if (k == Coder::Png16) ensure_srgb16(c);
+    if (adaptive) f.png_ftype.ensure((size_t)H);
+    if (adaptive && k == Coder::Png16) f.png_raw.ensure((size_t)2 * (size_t)C * (size_t)W * (size_t)H);
+    // the coder's scratch and its pinned outputs
+    const DeflatePlan& p = o.deflate;
+    if (p.W != W || p.H != H) throw std::runtime_error(std::string(coder_info(k).name) + " plan of another image");
+    f.deflate_scratch.ensure(deflate_scratch_words(p));
+    o.stream.ensure((p.own_stream ? exr_stream_max_bytes(p) : deflate_stream_max_bytes(p)) + 32);
+    o.tab.ensure((size_t)p.nbands * (p.own_stream ? 4 : 2) * sizeof(uint32_t));
+}
+
+void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o) {
+    const Coder k = fo.coder;
+    const int C = fo.color_mode;
+    reserve_coder(c, fo, in.W, in.H, f, o);
+    if (k == Coder::Jpeg) return enqueue_jpeg(c, in, C == RR_COLOR_BW, fo.quality, f, st, o);
+    if (device_body(k) || exr_rows(fo)) return enqueue_body(k, in, f, st, o);
+    const bool png = k == Coder::Png8 || k == Coder::Png16;
+    const bool adaptive = png && fo.png_compression >= 0;
     Png16Front front{};
     if (k == Coder::Png16) {
         if (in.view_transform >= VIEW_FILMIC && !c->filmic.ready)
             throw std::runtime_error("Filmic view transform without LUTs");
-        ensure_srgb16(c);
         front = Png16Front{in.film, in.inv_spp, in.exposure_scale, in.view_transform, c->srgb16_lut.ptr,
                            view_args(c, in.view_transform, in.look, in.gamma)};
     }
-    if (adaptive) f.png_ftype.ensure((size_t)in.H);
-    if (adaptive && k == Coder::Png16) f.png_raw.ensure((size_t)2 * (size_t)C * (size_t)in.W * (size_t)in.H);
-    // the coder's scratch and its pinned outputs
     const DeflatePlan& p = o.deflate;
-    f.deflate_scratch.ensure(deflate_scratch_words(p));
-    o.stream.ensure((p.own_stream ? exr_stream_max_bytes(p) : deflate_stream_max_bytes(p)) + 32);
-    o.tab.ensure((size_t)p.nbands * (p.own_stream ? 4 : 2) * sizeof(uint32_t));
     uint32_t* scratch = f.deflate_scratch.ptr;
     uint8_t* out = device_pointer<uint8_t>(o.stream);
     uint32_t* tab = device_pointer<uint32_t>(o.tab);

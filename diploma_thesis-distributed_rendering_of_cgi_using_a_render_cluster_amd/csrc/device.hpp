@@ -214,8 +214,16 @@ struct DevFrame {
     DevBuf<uint8_t> png_ftype, png_raw;
     // TARGA, HDR, IRIS and WEBP frames, and OPEN_EXR frames of the codecs NONE and RLE (tga.hip, hdr.hip, iris.hip,
     // webp.hip, exr_codec.hip): the dense body and the coder's records, carved by the coder's *_carve;
-    // grow-only. A frame writes one file, so they share it
+    // grow-only. The coders of a frame's files run one after another on its stream, so they share it
+    // (and the scratch above), sized for the largest before the first is enqueued (frame.hpp reserve_coder)
     DevBuf<uint32_t> body_scratch;
+    // Reduced outputs (rr_frame_output.reduce; reduce.hip): per factor 2, 4, 8 the reduced film, sums as
+    // `film` holds, and the 8-bit image the view pass makes of it; allocated at the first frame that needs them
+    struct Reduced {
+        DevBuf<float4> film;
+        DevBuf<uint8_t> rgba8;
+    } reduced[3];
+    static int reduced_slot(int k) { return k == 2 ? 0 : k == 4 ? 1 : 2; }
     // written by render_frame_device, about the frame it enqueued
     int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log (trav_counts)

@@ -283,7 +283,7 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     // (a slot coder, formats.hpp, reads its slot's rgba8 / film and writes slot
     // buffers only, so the next frame waits for the image, ev[5], not for the coder)
     if (prev && prev != &sl && !(sl.tiles && prev->tiles))
-        RR_HIP(hipStreamWaitEvent(st, slot_coder(prev->out.coder) ? prev->ev[5] : prev->ev[2], 0));
+        RR_HIP(hipStreamWaitEvent(st, prev->slot_coders_only ? prev->ev[5] : prev->ev[2], 0));
     c->last_enqueued = &sl;
     // a k_tiles frame enqueued while another k_tiles frame is pending overlaps
     // it: whole-tile work units (render_frame_device); a frame rendered alone
@@ -318,18 +318,58 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
     }
     RR_HIP(hipEventRecord(sl.ev[4], st));
     const size_t npix = (size_t)fs.W * fs.H;
-    const Coder coder = sl.out.coder;
-    if (coder == Coder::Jpeg || slot_coder(coder)) {
+    // The frame's files, in output order, each by its own coder on this stream.
+    // First everything they allocate (reserve_coder says why), and the reduced
+    // films and 8-bit images of the factors in use.
+    bool want8[3] = {}, wanted[3] = {};
+    for (int i = 0; i < sl.n_outs; ++i) {
+        SlotOutput& o = sl.outs[i];
+        const Coder coder = o.out.coder;
+        if (o.reduce > 1) {
+            const int r = DevFrame::reduced_slot(o.reduce);
+            wanted[r] = true;
+            f.reduced[r].film.ensure((size_t)o.W * o.H);
+            if (!coder_info(coder).film) {
+                want8[r] = true;
+                f.reduced[r].rgba8.ensure((size_t)o.W * o.H * 4);
+            }
+        }
+        if (coder == Coder::Jpeg || slot_coder(coder)) reserve_coder(c, o.out, o.W, o.H, f, o.coded);
+        if (coder == Coder::HostRgba) o.host_rgba.ensure((size_t)o.W * o.H * 4);
+    }
+    // (set by the entry point: no file of this frame is coded by the JPEG coder)
+    if (sl.slot_coders_only) RR_HIP(hipEventRecord(sl.ev[5], st));
+    // a factor's film, and where an 8-bit output reads it the view pass over it: the frame's exposure, view
+    // transform, look and gamma, the dither keyed on the reduced image's own pixels. Once per factor
+    for (int r = 0; r < 3; ++r) {
+        if (!wanted[r]) continue;
+        const int K = 2 << r, RW = reduced_size(fs.W, K), RH = reduced_size(fs.H, K);
+        f.prof.begin(st, RR_K_ACCUM);
+        film_reduce_device(f.film.ptr, fs.W, fs.H, K, f.reduced[r].film.ptr, st);
+        if (want8[r]) {
+            FrameConsts rk = k;
+            rk.W = RW;
+            rk.H = RH;
+            rk.npix = RW * RH;
+            rk.div_w = FastDiv::make((uint32_t)RW);
+            view_device(view_args(c, fs.view_transform, fs.look, fs.gamma, fs.dither), rk, c->paths.srgb_lut.ptr,
+                        f.reduced[r].film.ptr, reinterpret_cast<uchar4*>(f.reduced[r].rgba8.ptr), st);
+        }
+        f.prof.end(st);
+    }
+    for (int i = 0; i < sl.n_outs; ++i) {
+        SlotOutput& o = sl.outs[i];
+        const Coder coder = o.out.coder;
+        if (coder != Coder::Jpeg && !slot_coder(coder)) continue;
+        const DevFrame::Reduced* red = o.reduce > 1 ? &f.reduced[DevFrame::reduced_slot(o.reduce)] : nullptr;
         CoderInput in;
-        in.rgba8 = f.rgba8.ptr;
-        in.film = f.film.ptr;
-        in.W = fs.W;
-        in.H = fs.H;
+        in.rgba8 = red ? red->rgba8.ptr : f.rgba8.ptr;
+        in.film = red ? red->film.ptr : f.film.ptr;
+        in.W = o.W;
+        in.H = o.H;
         if (coder == Coder::Jpeg) {
-            ensure_jpeg_table(c, sl.out.quality);
-            in.jpeg_tab = c->jpeg_tab.ptr;
+            in.jpeg_tab = jpeg_table(c, o.out.quality);
         } else {
-            RR_HIP(hipEventRecord(sl.ev[5], st));
             // Png16: the film again, through exposure and view transform, at 16
             // bits; the other film coders: the film's means, the product
             // finish_frame forms, no view transform; the rest read rgba8 and none of these
@@ -339,14 +379,16 @@ void enqueue_frame(rr_ctx* c, FrameSlot& sl) {
             in.look = fs.look;
             in.gamma = fs.gamma;
         }
-        enqueue_coder(c, sl.out, in, f, st, sl.coded);
+        enqueue_coder(c, o.out, in, f, st, o.coded);
     }
     RR_HIP(hipEventRecord(sl.ev[2], st));
     // the outputs' device-to-host copies follow on the slot's own stream: the
     // next frames run on the other slots' streams, so nothing waits for them
-    if (coder == Coder::HostRgba) {
-        sl.host_rgba.ensure(npix * 4);
-        RR_HIP(hipMemcpyAsync(sl.host_rgba.ptr, f.rgba8.ptr, npix * 4, hipMemcpyDeviceToHost, st));
+    for (int i = 0; i < sl.n_outs; ++i) {
+        SlotOutput& o = sl.outs[i];
+        if (o.out.coder != Coder::HostRgba) continue;
+        const uint8_t* src = o.reduce > 1 ? f.reduced[DevFrame::reduced_slot(o.reduce)].rgba8.ptr : f.rgba8.ptr;
+        RR_HIP(hipMemcpyAsync(o.host_rgba.ptr, src, (size_t)o.W * o.H * 4, hipMemcpyDeviceToHost, st));
     }
     const int cpc = counters_per_chunk(fs.max_bounces);
     const size_t nctr = (size_t)cpc * r.chunks;

@@ -17,6 +17,7 @@
 #include "exr_codec.hpp"
 #include "hdr.hpp"
 #include "iris.hpp"
+#include "reduce.hpp"
 #include "rr.h"
 #include "scene.hpp"
 #include "settings.hpp"
@@ -66,9 +67,9 @@ struct BodyShape {
 // up to 16.
 inline size_t body_stream_bytes(uint32_t body_cap) { return 16 + ((size_t)body_cap + 15) / 16 * 16; }
 
-// Where the device coders write: a frame slot has one, and the context one
-// more for the inspection entry points. A frame writes one file, so every coder
-// writes the one pinned stream, [uint64 length][8 B pad][bytes]; a deflate
+// Where a device coder writes: a frame slot has one for each of its outputs, and
+// the context one more for the inspection entry points. An output is one file,
+// so its coder writes the one pinned stream, [uint64 length][8 B pad][bytes]; a deflate
 // coder also the bands' table, 2 or 4 words per band by the plan's own_stream.
 // The rest is what the host builds the file's header or container from; the
 // plans are made before the coder is enqueued (plan_or_refuse).
@@ -82,6 +83,19 @@ struct CodedOut {
     rr::HdrPlan hdr{};
     rr::IrisPlan iris{};
     rr::WebpPlan webp{};
+};
+
+// One file of a frame (rr_frame_output), resolved when the frame is submitted.
+// Pinned memory grows on demand: an output a context never uses holds none.
+struct SlotOutput {
+    FrameOutput out;      // resolve_output
+    CodedOut coded;       // the device-coded file's stream; its plan is made when the frame is submitted
+    std::string path;     // without the extension
+    std::string warning;  // a WEBP file below quality 100: lossless all the same; OPEN_EXR of a codec not built: ZIP
+    int reduce = 1;       // the factor its image is reduced by
+    int W = 0, H = 0;     // the image's size: the frame's, reduced
+    PinnedBuf host_rgba;  // Coder::HostRgba: the 8-bit image, for the host coder
+    uint64_t bytes = 0;   // the file's size, once written
 };
 
 struct FrameRun {
@@ -103,8 +117,9 @@ struct FrameSlot {
     bool busy = false;
     uint64_t ticket = 0;
     // 0 start, 1 built, 4 image done (before the device JPEG coder), 2 stream
-    // work done, 3 outputs on the host (after their copies), 5 (frames of a
-    // slot_coder) before the slot's coder: the state shared between frames is free
+    // work done (every output's coder), 3 outputs on the host (after their
+    // copies), 5 (frames whose files all come from slot coders) before the
+    // slot's reductions and coders: the state shared between frames is free
     hipEvent_t ev[6] = {};
     // The slot's frames run on its own stream and write only its own device
     // state, so a k_tiles frame runs on the GPU beside the other slots'
@@ -119,18 +134,18 @@ struct FrameSlot {
     rr::DevBuild build;
     const rr_scene* build_scene = nullptr;
     bool tiles = false;  // this frame renders with k_tiles (may overlap its neighbours)
-    PinnedBuf host_rgba, host_counters, host_upload;
-    CodedOut coded;  // the device-coded file's stream; a deflate frame's plan is made when the frame is submitted
+    PinnedBuf host_counters, host_upload;
+    // The frame's files, outs[0 .. n_outs): none for a frame without a path. rr_render_frame_to_memory has
+    // one of Coder::HostRgba without a path: the 8-bit image to the host.
+    SlotOutput outs[RR_MAX_FRAME_OUTPUTS];
+    int n_outs = 0;
+    bool slot_coders_only = false;  // every output is coded by a slot coder (enqueue_frame: what the next frame waits for)
     rr::FrameSetup fs;
-    // a WEBP frame below quality 100: lossless all the same; an OPEN_EXR frame of a codec not built: ZIP
-    std::string quality_warning;
     bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
     std::string view_warning;
     double submit_at = 0.0;         // UNIX time when the device work was enqueued
     bool anchor = false;            // submitted to an idle context: its device start is submit_at
     rr_scene* scene = nullptr;
-    std::string out_path;
-    rr::FrameOutput out;  // the frame's file, resolved when the frame is submitted (resolve_output)
     float* film_out = nullptr;
     FrameRun r{};
     rr_frame_timing tm{};
@@ -149,9 +164,10 @@ struct rr_ctx {
     rr::DevFrame home;   // the inspection entry points' frame state (a frame uses its slot's)
     rr::CodedOut home_coded;  // and their coders' outputs: an inspection call touches no frame slot
     // tables of the device JPEG coder (jpeg.hip), read by every slot's frames:
-    // the transform's for the last quality, the entropy coder's Huffman codes
-    rr::DevBuf<float> jpeg_tab;
-    int jpeg_tab_quality = -1;
+    // the transform's by quality, each written once when first asked for and
+    // never again (so two JPEG outputs of one frame may differ in quality, and
+    // a change of quality waits for nobody); the entropy coder's Huffman codes
+    rr::DevBuf<float> jpeg_tab[101];
     rr::DevBuf<uint32_t> jpeg_huff;
     rr::OutputSettings settings;  // rr_set_* / RR_* (settings.hpp)
     rr::DevBuf<float> srgb16_lut;  // the 16-bit path's sRGB table (build_srgb16_lut), uploaded at its first frame
@@ -169,6 +185,9 @@ struct rr_ctx {
     // rr_last_warning = the context's warning (a broken RR_OCIO_DIR, kept for
     // the context's lifetime) + the last completed frame's
     std::string ctx_warning, frame_warning, warning;
+    // the files of the frame completed last (rr_last_output_bytes)
+    uint64_t last_output_bytes[RR_MAX_FRAME_OUTPUTS] = {};
+    int last_outputs = 0;
     // Device start times of completed frames (rr_frame_complete): every frame
     // also records its start on start_ring[ticket % kStartRing], which outlives
     // the frame slot's own events by a few frames, so the next frame's start is
@@ -268,7 +287,7 @@ void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int
 // which takes the film through exposure and view transform again at 16 bits.
 // alpha_one (Exr, Exr32): A = 1, as in a rendered frame's file; else the
 // image's own alpha. jpeg_tab: the transform's table for the file's quality
-// (ensure_jpeg_table).
+// (jpeg_table).
 struct CoderInput {
     const uint8_t* rgba8 = nullptr;
     const float4* film = nullptr;
@@ -292,15 +311,24 @@ std::string webp_quality_warning(int quality);
 // The 16-bit path's sRGB table on the device. Written once, before the first
 // kernel that reads it is enqueued, and never again.
 void ensure_srgb16(rr_ctx* c);
-// The device JPEG transform's table for `quality` in c->jpeg_tab, rewritten
-// with every stream idle when the quality changes.
-void ensure_jpeg_table(rr_ctx* c, int quality);
+// The device JPEG transform's table for `quality` (1 .. 100), uploaded when
+// first asked for into a buffer nothing reads yet.
+const float* jpeg_table(rr_ctx* c, int quality);
+
+// Everything enqueue_coder(fo, a W x H image) allocates, in f's scratch and o's
+// pinned buffers, and the tables it uploads. A frame reserves for all its
+// outputs before it enqueues the first coder: the coders of one frame run one
+// after another on the slot's stream and share f's scratch, and a buffer that
+// grew (DevBuf::ensure frees and allocates) under a coder still queued would be
+// freed under it. Grow-only, so the scratch ends at the largest plan's size.
+void reserve_coder(rr_ctx* c, const FrameOutput& fo, int W, int H, DevFrame& f, CodedOut& o);
 
 // Enqueue the device coder that `fo` names (Jpeg ... Webp) on stream st, with
 // f's scratch and profiler, into o's pinned buffers. fo.color_mode: the file's
 // channels; fo.png_compression ("PNG"): LEGACY the Sub front end, 0 .. 100 the
 // adaptive one (the device coders have one effort level). A deflate or body
-// coder codes by its plan in o (plan_or_refuse).
+// coder codes by its plan in o (plan_or_refuse). Reserves first (reserve_coder:
+// nothing new for a frame that has reserved already).
 void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFrame& f, hipStream_t st, CodedOut& o);
 
 // The file of a device-coded image, once its stream is on the host: the

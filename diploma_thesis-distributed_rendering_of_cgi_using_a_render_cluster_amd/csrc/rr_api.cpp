@@ -118,7 +118,7 @@ void rr_destroy(rr_ctx* c) {
     c->paths.release();
     c->home.release();
     c->filmic.release();
-    c->jpeg_tab.release();
+    for (auto& t : c->jpeg_tab) t.release();
     c->jpeg_huff.release();
     c->srgb16_lut.release();
     for (auto& sl : c->slots)
@@ -134,6 +134,10 @@ void rr_destroy(rr_ctx* c) {
     for (auto& sl : c->slots) {
         if (sl.stream) (void)hipStreamDestroy(sl.stream);  // c->stream is slot 0's
         sl.dev.release();
+        for (auto& r : sl.dev.reduced) {
+            r.film.release();
+            r.rgba8.release();
+        }
         sl.build.release();
     }
     delete c;
@@ -184,15 +188,21 @@ int rr_scene_resolution(rr_scene* s, const rr_render_params* p, int32_t* w, int3
     return RR_OK;
 }
 
-int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* params, const char* out_path,
-                    const char* format, int32_t jpeg_quality, uint64_t* ticket) {
-    if (!c || !s || !ticket) return fail(RR_EINVAL, "NULL ctx, scene or ticket");
+}  // extern "C"
+
+namespace {
+
+// A frame's submission, with the files it was asked for (none: a frame without
+// a path). What the context and the scene add comes on top; the whole list is
+// checked, resolved and planned before anything is enqueued.
+int submit_frame(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* params,
+                 std::vector<OutputRequest> list, uint64_t* ticket) {
     if (s->ctx && s->ctx != c) return fail(RR_EINVAL, "scene belongs to another context");
-    if (out_path && !format) return fail(RR_EINVAL, "format is required when out_path is given");
-    if (format && !known_format(format)) return fail(RR_ENOTSUP, unsupported_format(format));
-    const FrameOutput fo = resolve_output(c->settings, s->desc.render, format, out_path != nullptr, jpeg_quality);
-    if (fo.coder == Coder::Jpeg && (jpeg_quality < 1 || jpeg_quality > 100))
-        return fail(RR_EINVAL, "jpeg_quality must be 1..100");
+    add_extra_outputs(c->settings, s->desc.render, list);
+    if (!list.empty()) {
+        std::string err;
+        if (const int rc = check_outputs(list, err)) return fail(rc, err);
+    }
     FrameSlot* sl = slot_for(c, c->next_ticket);
     if (sl->busy) return fail(RR_EBUSY, "too many frames in flight (complete the oldest first)");
     return guarded([&] {
@@ -206,16 +216,28 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
         sl->anim_ms = ms_since(t_anim);
         sl->tm.started_rendering_at = unix_now();
         sl->scene = s;
-        sl->out_path = out_path ? out_path : "";
-        sl->out = fo;
-        if (const int rc = plan_or_refuse(fo, sl->fs.W, sl->fs.H, sl->coded)) return rc;
-        sl->quality_warning.clear();
-        if (fo.coder == Coder::Webp) sl->quality_warning = webp_quality_warning(fo.quality);
-        else sl->quality_warning = exr_codec_warning(fo);
-        if (fo.coder == Coder::Png16) {
-            set_device(c);
-            ensure_srgb16(c);
+        sl->n_outs = 0;  // (a refusal below leaves the slot without a frame)
+        bool slot_only = !list.empty();
+        for (size_t i = 0; i < list.size(); ++i) {
+            const OutputRequest& q = list[i];
+            SlotOutput& o = sl->outs[i];
+            o.out = resolve_output(c->settings, s->desc.render, q.format.c_str(), true, q.quality);
+            o.path = q.path;
+            o.reduce = q.reduce;
+            o.W = reduced_size(sl->fs.W, q.reduce);
+            o.H = reduced_size(sl->fs.H, q.reduce);
+            o.bytes = 0;
+            if (const int rc = plan_or_refuse(o.out, o.W, o.H, o.coded)) return rc;
+            o.warning = o.out.coder == Coder::Webp ? webp_quality_warning(o.out.quality) : exr_codec_warning(o.out);
+            if (!slot_coder(o.out.coder)) slot_only = false;
         }
+        sl->n_outs = (int)list.size();
+        sl->slot_coders_only = slot_only;
+        for (int i = 0; i < sl->n_outs; ++i)
+            if (sl->outs[i].out.coder == Coder::Png16) {
+                set_device(c);
+                ensure_srgb16(c);
+            }
         sl->film_out = nullptr;
         sl->anchor = idle(c);
         sl->submit_at = unix_now();
@@ -228,6 +250,33 @@ int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
     });
 }
 
+}  // namespace
+
+extern "C" {
+
+int rr_frame_submit(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* params, const char* out_path,
+                    const char* format, int32_t jpeg_quality, uint64_t* ticket) {
+    if (!c || !s || !ticket) return fail(RR_EINVAL, "NULL ctx, scene or ticket");
+    if (out_path && !format) return fail(RR_EINVAL, "format is required when out_path is given");
+    std::vector<OutputRequest> list;
+    if (out_path) list.push_back({out_path, format, jpeg_quality, 1});
+    return submit_frame(c, s, frame, params, std::move(list), ticket);
+}
+
+int rr_frame_submit_outputs(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* params,
+                            const rr_frame_output* outs, int32_t n, uint64_t* ticket) {
+    if (!c || !s || !ticket) return fail(RR_EINVAL, "NULL ctx, scene or ticket");
+    if (n < 1 || n > RR_MAX_FRAME_OUTPUTS || !outs)
+        return fail(RR_EINVAL, "a frame writes 1 .. " + std::to_string(RR_MAX_FRAME_OUTPUTS) + " files, not " +
+                                   std::to_string(n));
+    std::vector<OutputRequest> list;
+    for (int32_t i = 0; i < n; ++i) {
+        if (!outs[i].out_path || !outs[i].format) return fail(RR_EINVAL, "every output needs out_path and format");
+        list.push_back({outs[i].out_path, outs[i].format, outs[i].jpeg_quality, outs[i].reduce});
+    }
+    return submit_frame(c, s, frame, params, std::move(list), ticket);
+}
+
 int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_frame_stats* stats) {
     if (!c) return fail(RR_EINVAL, "NULL ctx");
     if (ticket != c->next_complete) return fail(RR_EINVAL, "frames must be completed in submission order");
@@ -236,27 +285,44 @@ int rr_frame_complete(rr_ctx* c, uint64_t ticket, rr_frame_timing* timing, rr_fr
     const int rc = guarded([&] {
         finish_frame(c, *sl);
         const FrameSetup& fs = sl->fs;
-        const FrameOutput& fo = sl->out;
         set_render_span(c, *sl, unix_now());
-        uint64_t bytes = 0;
         const auto t_enc = std::chrono::steady_clock::now();
-        if (fo.coder == Coder::Jpeg || slot_coder(fo.coder)) {  // the host's container + the device-coded stream
-            std::vector<uint8_t> data;
-            coded_file_bytes(sl->coded, fo, data);
-            const std::string path = sl->out_path + coder_ext(fo.coder);
-            bytes = data.size();
-            if (!write_file(path, data)) return fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
-        } else if (fo.coder == Coder::HostRgba) {  // a submitted frame's: "PNG" by the host coder
-            const int e = do_encode(sl->host_rgba.ptr, fs.W, fs.H, sl->out_path.c_str(), "PNG", fo.quality, &bytes,
-                                    fo.color_mode, fo.png_compression);
-            if (e != RR_OK) return e;
+        // Every file is built and written, also behind one that failed: the
+        // first failure's code is the frame's, and its text names every file
+        // that was not written.
+        int failed = RR_OK;
+        std::string failures;
+        c->last_outputs = sl->n_outs;
+        for (int i = 0; i < sl->n_outs; ++i) {
+            SlotOutput& o = sl->outs[i];
+            const FrameOutput& fo = o.out;
+            o.bytes = 0;
+            int e = RR_OK;
+            if (fo.coder == Coder::Jpeg || slot_coder(fo.coder)) {  // the host's container + the device-coded stream
+                std::vector<uint8_t> data;
+                coded_file_bytes(o.coded, fo, data);
+                const std::string path = o.path + coder_ext(fo.coder);
+                if (write_file(path, data)) o.bytes = data.size();
+                else e = fail(RR_EIO, "cannot write " + path + ": " + std::strerror(errno));
+            } else if (fo.coder == Coder::HostRgba) {  // a submitted frame's: "PNG" by the host coder
+                e = do_encode(o.host_rgba.ptr, o.W, o.H, o.path.c_str(), "PNG", fo.quality, &o.bytes, fo.color_mode,
+                              fo.png_compression);
+            }
+            c->last_output_bytes[i] = o.bytes;
+            if (e != RR_OK) {
+                if (failed == RR_OK) failed = e;
+                failures += (failures.empty() ? "" : "; ") + g_err;
+            }
         }
+        if (failed != RR_OK) return fail(failed, failures);
+        const uint64_t bytes = sl->n_outs ? sl->outs[0].bytes : 0;
         const double enc_ms = ms_since(t_enc);
         sl->tm.file_saving_finished_at = unix_now();
         if (timing) *timing = sl->tm;
         c->frame_warning = sl->view_warning;
-        if (!sl->quality_warning.empty())
-            c->frame_warning += (c->frame_warning.empty() ? "" : "; ") + sl->quality_warning;
+        for (int i = 0; i < sl->n_outs; ++i)
+            if (!sl->outs[i].warning.empty())
+                c->frame_warning += (c->frame_warning.empty() ? "" : "; ") + sl->outs[i].warning;
         if (stats) {
             fill_stats(stats, fs, sl->r, sl->scene->mesh.n_tris);
             stats->view_transform_substituted = sl->view_substituted ? 1 : 0;
@@ -282,6 +348,30 @@ int rr_render_frame(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_param
     return rr_frame_complete(c, t, timing, stats);
 }
 
+int rr_render_frame_outputs(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* params,
+                            const rr_frame_output* outs, int32_t n, rr_frame_timing* timing, rr_frame_stats* stats) {
+    if (c && c->next_complete != c->next_ticket)
+        return fail(RR_EBUSY, "rr_render_frame_outputs while submitted frames are pending");
+    uint64_t t = 0;
+    const int rc = rr_frame_submit_outputs(c, s, frame, params, outs, n, &t);
+    if (rc != RR_OK) return rc;
+    return rr_frame_complete(c, t, timing, stats);
+}
+
+int rr_last_output_bytes(rr_ctx* c, int32_t index, uint64_t* bytes) {
+    if (!c || !bytes) return fail(RR_EINVAL, "NULL argument");
+    if (index < 0 || index >= c->last_outputs)
+        return fail(RR_EINVAL, "the frame completed last wrote " + std::to_string(c->last_outputs) + " files");
+    *bytes = c->last_output_bytes[index];
+    return RR_OK;
+}
+
+int rr_set_extra_outputs(rr_ctx* c, const char* spec) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_extra_outputs(c->settings, spec, err), err);
+}
+
 int rr_synchronize(rr_ctx* c) {
     if (!c) return fail(RR_EINVAL, "NULL ctx");
     return guarded([&] {
@@ -303,17 +393,23 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         sl->view_warning = resolve_view(c, sl->fs);
         sl->view_substituted = !sl->view_warning.empty();
         sl->scene = s;
-        sl->out_path.clear();
-        sl->quality_warning.clear();
-        sl->out = FrameOutput{};
-        sl->out.coder = Coder::HostRgba;  // the 8-bit image to the host; no file
+        SlotOutput& o = sl->outs[0];  // the 8-bit image to the host; no file
+        o.out = FrameOutput{};
+        o.out.coder = Coder::HostRgba;
+        o.path.clear();
+        o.warning.clear();
+        o.reduce = 1;
+        o.W = sl->fs.W;
+        o.H = sl->fs.H;
+        sl->n_outs = 1;
+        sl->slot_coders_only = false;
         sl->film_out = film;
         sl->ticket = c->next_ticket;
         enqueue_frame(c, *sl);
         finish_frame(c, *sl);
         sl->film_out = nullptr;
         const FrameSetup& fs = sl->fs;
-        if (rgba8) std::memcpy(rgba8, sl->host_rgba.ptr, (size_t)fs.W * fs.H * 4);
+        if (rgba8) std::memcpy(rgba8, sl->outs[0].host_rgba.ptr, (size_t)fs.W * fs.H * 4);
         c->frame_warning = sl->view_warning;
         if (stats) {
             fill_stats(stats, fs, sl->r, s->mesh.n_tris);

@@ -62,10 +62,7 @@ int debug_encode(rr_ctx* c, Coder k, int C, const void* image, int w, int h, boo
         RR_HIP(hipMemcpy(img.ptr, image, bytes, hipMemcpyHostToDevice));
         in.rgba8 = img.ptr;
         in.film = reinterpret_cast<const float4*>(img.ptr);
-        if (k == Coder::Jpeg) {
-            ensure_jpeg_table(c, quality);
-            in.jpeg_tab = c->jpeg_tab.ptr;
-        }
+        if (k == Coder::Jpeg) in.jpeg_tab = jpeg_table(c, quality);
         enqueue_coder(c, fo, in, c->home, c->stream, c->home_coded);
         RR_HIP(hipStreamSynchronize(c->stream));
         std::vector<uint8_t> data;
@@ -542,6 +539,29 @@ int rr_debug_bsdf_sample(rr_ctx* c, const float* mat12, const float* n3, const f
             RR_HIP(hipMemcpyAsync(pdf, dp.ptr, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
             RR_HIP(hipMemcpyAsync(ok, dk.ptr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         }
+        RR_HIP(hipStreamSynchronize(st));
+        return RR_OK;
+    });
+}
+
+int rr_debug_film_reduce(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int32_t reduce, float* out) {
+    if (!rgba || !out || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    if (!reduce_factor_valid(reduce)) return fail(RR_EINVAL, "reduce must be 1, 2, 4 or 8");
+    return guarded([&] {
+        if (!c) {  // the rule as the host states it
+            film_reduce_host(rgba, w, h, reduce, out);
+            return RR_OK;
+        }
+        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
+        set_device(c);
+        hipStream_t st = c->stream;
+        const size_t n_in = (size_t)w * h, n_out = (size_t)reduced_size(w, reduce) * reduced_size(h, reduce);
+        DevBuf<float4> in, red;
+        in.ensure(n_in);
+        red.ensure(n_out);
+        RR_HIP(hipMemcpyAsync(in.ptr, rgba, n_in * sizeof(float4), hipMemcpyHostToDevice, st));
+        film_reduce_device(in.ptr, w, h, reduce, red.ptr, st);
+        RR_HIP(hipMemcpyAsync(out, red.ptr, n_out * sizeof(float4), hipMemcpyDeviceToHost, st));
         RR_HIP(hipStreamSynchronize(st));
         return RR_OK;
     });

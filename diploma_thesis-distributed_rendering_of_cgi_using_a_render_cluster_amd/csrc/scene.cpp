@@ -726,6 +726,12 @@ SceneDesc load_scene(const std::string& path) {
                 throw std::runtime_error("render.png_compression must be in 0 .. 100, got " + std::to_string(v.num));
             d.png_compression = (int)v.num;
         }
+        // Blender's image_settings.use_preview: a JPEG beside every OPEN_EXR frame
+        if (r.has("use_preview")) {
+            const Json& v = r["use_preview"];
+            if (v.type != Json::Bool) throw std::runtime_error("render.use_preview must be true or false");
+            d.use_preview = v.b;
+        }
     }
     if (s.render.resx <= 0 || s.render.resy <= 0 || s.render.percent <= 0)
         throw std::runtime_error("invalid resolution");

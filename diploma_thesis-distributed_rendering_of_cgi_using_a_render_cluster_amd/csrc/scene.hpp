@@ -120,6 +120,7 @@ struct RenderDesc {
     double dither_intensity = 0.0;  // render.dither_intensity, in [0, 2] (rr_set_dither RR_DITHER_SCENE takes it)
     int exr_codec = RR_EXR_CODEC_ZIP;  // render.exr_codec, an RR_EXR_CODEC_* value; no field: ZIP (rr_set_exr_codec SCENE takes it)
     int png_compression = -1;  // render.png_compression, 0 .. 100; -1: no field (rr_set_png_compression SCENE takes it)
+    bool use_preview = false;  // render.use_preview: an "OPEN_EXR" frame also writes a JPEG (settings.hpp add_extra_outputs)
     // What of the scene's colour management no frame can apply, for the
     // frame's warning ("" when there is nothing): a view transform this
     // renderer does not know (rendered as Standard), a look it does not know

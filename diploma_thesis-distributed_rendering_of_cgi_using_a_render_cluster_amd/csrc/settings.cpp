@@ -2,6 +2,7 @@
 // frame gets from them. See settings.hpp.
 #include "settings.hpp"
 
+#include <algorithm>
 #include <cstdlib>
 
 #include "looks.hpp"
@@ -88,6 +89,42 @@ bool set_png_compression(OutputSettings& s, int percent, std::string& err) {
     return true;
 }
 
+bool set_extra_outputs(OutputSettings& s, const char* spec, std::string& err) {
+    std::vector<ExtraOutput> list;
+    const std::string text(spec ? spec : "");
+    for (size_t at = 0; !text.empty() && at <= text.size();) {
+        const size_t end = std::min(text.find(',', at), text.size());
+        const std::string entry = text.substr(at, end - at);
+        at = end + 1;
+        const size_t colon = entry.find(':');
+        const std::string name = entry.substr(0, colon), factor = colon == std::string::npos ? "1" : entry.substr(colon + 1);
+        ExtraOutput e;
+        e.format = find_format(name.c_str());
+        if (!e.format) {
+            err = "extra output '" + entry + "': " + unsupported_format(name);
+            return false;
+        }
+        if (factor != "1" && factor != "2" && factor != "4" && factor != "8") {
+            err = "extra output '" + entry + "': the factor must be 1, 2, 4 or 8";
+            return false;
+        }
+        e.reduce = factor[0] - '0';
+        for (const ExtraOutput& o : list)
+            if (o.reduce == e.reduce && std::string(o.format->ext) == e.format->ext) {
+                err = "extra output '" + entry + "' would write the same file as '" + o.format->name + "'";
+                return false;
+            }
+        if ((int)list.size() == RR_MAX_FRAME_OUTPUTS - 1) {
+            err = "at most " + std::to_string(RR_MAX_FRAME_OUTPUTS - 1) + " extra outputs (a frame writes " +
+                  std::to_string(RR_MAX_FRAME_OUTPUTS) + " files at most)";
+            return false;
+        }
+        list.push_back(e);
+    }
+    s.extra_outputs = list;
+    return true;
+}
+
 namespace {
 
 // A whole text as one number, as strtol / strtod read it.
@@ -168,12 +205,14 @@ bool apply_text(OutputSettings& s, const std::string& var, const char* t, std::s
         }
         return set_png_compression(s, (int)n, err);
     }
+    if (var == "RR_EXTRA_OUTPUTS") return set_extra_outputs(s, t, err);
     err = "not an output setting";
     return false;
 }
 
 constexpr const char* kEnvVars[] = {"RR_PNG_DEPTH",     "RR_EXR_DEPTH",       "RR_EXR_CODEC", "RR_COLOR_MODE", "RR_LOOK",
-                                    "RR_DISPLAY_GAMMA", "RR_PNG_COMPRESSION", "RR_DITHER",    "RR_DEVICE_PNG"};
+                                    "RR_DISPLAY_GAMMA", "RR_PNG_COMPRESSION", "RR_DITHER",    "RR_DEVICE_PNG",
+                                    "RR_EXTRA_OUTPUTS"};
 
 }  // namespace
 
@@ -246,6 +285,50 @@ FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const c
     o.exr_codec = s.exr_codec != RR_EXR_CODEC_SCENE ? s.exr_codec : r.exr_codec;
     o.quality = jpeg_quality;
     return o;
+}
+
+std::string extra_output_path(const std::string& path, int reduce) {
+    return reduce == 1 ? path : path + ".r" + std::to_string(reduce);
+}
+
+void add_extra_outputs(const OutputSettings& s, const RenderDesc& r, std::vector<OutputRequest>& list) {
+    if (list.empty()) return;
+    const OutputRequest own = list[0];
+    for (const ExtraOutput& e : s.extra_outputs)
+        list.push_back({extra_output_path(own.path, e.reduce), e.format->name, own.quality, e.reduce});
+    if (s.extra_outputs.empty() && r.use_preview && own.format == "OPEN_EXR")
+        list.push_back({own.path, "JPEG", own.quality, 1});
+}
+
+int check_outputs(const std::vector<OutputRequest>& list, std::string& err) {
+    if (list.empty() || (int)list.size() > RR_MAX_FRAME_OUTPUTS) {
+        err = "a frame writes 1 .. " + std::to_string(RR_MAX_FRAME_OUTPUTS) + " files, not " + std::to_string(list.size());
+        return RR_EINVAL;
+    }
+    std::vector<std::string> files;
+    for (const OutputRequest& o : list) {
+        if (!(o.reduce == 1 || o.reduce == 2 || o.reduce == 4 || o.reduce == 8)) {
+            err = "output reduce must be 1, 2, 4 or 8, got " + std::to_string(o.reduce);
+            return RR_EINVAL;
+        }
+        const Format* f = find_format(o.format.c_str());
+        if (!f) {
+            err = unsupported_format(o.format);
+            return RR_ENOTSUP;
+        }
+        if (f->coder == Coder::Jpeg && (o.quality < 1 || o.quality > 100)) {
+            err = "jpeg_quality must be 1..100";
+            return RR_EINVAL;
+        }
+        files.push_back(o.path + f->ext);
+    }
+    for (size_t i = 0; i < files.size(); ++i)
+        for (size_t j = 0; j < i; ++j)
+            if (files[i] == files[j]) {
+                err = "two outputs of one frame would write " + files[i];
+                return RR_EINVAL;
+            }
+    return RR_OK;
 }
 
 int png_compression_of(const OutputSettings& s) {

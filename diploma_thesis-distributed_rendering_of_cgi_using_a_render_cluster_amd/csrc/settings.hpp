@@ -7,6 +7,7 @@
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include "formats.hpp"
 #include "rr.h"
@@ -14,6 +15,13 @@
 namespace rr {
 
 struct RenderDesc;  // scene.hpp
+
+// One entry of rr_set_extra_outputs' list: a format of kFormats and the factor
+// its file is reduced by (1, 2, 4 or 8).
+struct ExtraOutput {
+    const Format* format = nullptr;
+    int reduce = 1;
+};
 
 struct OutputSettings {
     // 8-bit "PNG" frames are coded on the device (rr_set_device_png / RR_DEVICE_PNG)
@@ -34,6 +42,8 @@ struct OutputSettings {
     float gamma = 0.f;
     // dither of the 8-bit image (rr_set_dither / RR_DITHER): an intensity in [0, 2], RR_DITHER_SCENE the scene's
     float dither = 0.f;
+    // files every frame with a path writes beside its own (rr_set_extra_outputs / RR_EXTRA_OUTPUTS)
+    std::vector<ExtraOutput> extra_outputs;
 };
 
 // The setters. false + err for a value outside the setting's range, which
@@ -48,6 +58,11 @@ bool set_look(OutputSettings& s, const char* name, std::string& err);  // NULL o
 bool set_display_gamma(OutputSettings& s, double gamma, std::string& err);
 bool set_dither(OutputSettings& s, double intensity, std::string& err);
 bool set_png_compression(OutputSettings& s, int percent, std::string& err);
+// spec: "FORMAT[:K]" entries joined by commas, e.g. "JPEG:4,PNG": a name of
+// kFormats and a factor 1 (also when left out), 2, 4 or 8; at most
+// RR_MAX_FRAME_OUTPUTS - 1 entries, no two of which would write the same file.
+// NULL or "": none.
+bool set_extra_outputs(OutputSettings& s, const char* spec, std::string& err);
 
 bool valid_color_mode(int mode);
 
@@ -123,6 +138,30 @@ std::string exr_codec_warning(const FrameOutput& fo);
 // caller); without a path there is no file (Coder::None).
 FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const char* format, bool has_path,
                            int jpeg_quality);
+
+// One file a frame is asked to write: rr_frame_output with its strings owned.
+struct OutputRequest {
+    std::string path, format;
+    int quality = 0, reduce = 1;
+};
+
+// Where an entry of rr_set_extra_outputs writes for a frame submitted with
+// `path`: "<path>" at factor 1, "<path>.r<K>" at K > 1 (the extension follows).
+std::string extra_output_path(const std::string& path, int reduce);
+
+// Appends what the context and the scene add to a frame's own files, list[0]
+// giving the path and the quality: the context's extra outputs; with none of
+// those, a scene with render.use_preview whose frame is "OPEN_EXR" adds
+// "<path>.jpg", JPEG at factor 1 (Blender's image_settings.use_preview). An
+// empty list (a frame without a file) stays empty.
+void add_extra_outputs(const OutputSettings& s, const RenderDesc& r, std::vector<OutputRequest>& list);
+
+// What a list of 1 or more files is refused for, before anything is planned:
+// RR_OK, or RR_EINVAL (more than RR_MAX_FRAME_OUTPUTS files; no path or format;
+// a factor that is not 1, 2, 4 or 8; a JPEG quality outside 1 .. 100; two
+// files of one name, which err names) or RR_ENOTSUP (a format nobody writes:
+// unsupported_format's text) with err.
+int check_outputs(const std::vector<OutputRequest>& list, std::string& err);
 
 // The PNG compression of an image that comes with no scene (the inspection
 // entry points): the context's, SCENE meaning legacy.

@@ -20,6 +20,7 @@ SHIM_PATH = os.path.join(_HERE, "lib", "rr-blender-shim")
 RR_OK, RR_ENOENT, RR_EIO, RR_ENOMEM, RR_ENODEV, RR_EINVAL, RR_ENOTSUP = 0, -2, -5, -12, -19, -22, -95
 RR_EBUSY = -16
 RR_MAX_FRAMES_IN_FLIGHT = 3
+RR_MAX_FRAME_OUTPUTS = 4
 RR_VIEW_SCENE, RR_VIEW_STANDARD, RR_VIEW_RAW, RR_VIEW_FILMIC = -1, 0, 1, 2
 RR_VIEW_FILMIC_LOG, RR_VIEW_FALSE_COLOR = 3, 4
 # rr_set_look's names (include/rr.h), each also with Blender's "Filmic - " prefix
@@ -43,6 +44,12 @@ class RenderParams(ctypes.Structure):
                 ("height", ctypes.c_int32), ("view_transform", ctypes.c_int32),
                 ("spp_per_chunk", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("max_diffuse_bounces", ctypes.c_int32), ("max_glossy_bounces", ctypes.c_int32)]
+
+
+class FrameOutput(ctypes.Structure):
+    """rr_frame_output: one file of a frame (submit_frame_outputs)."""
+    _fields_ = [("out_path", ctypes.c_char_p), ("format", ctypes.c_char_p),
+                ("jpeg_quality", ctypes.c_int32), ("reduce", ctypes.c_int32)]
 
 
 class FrameTiming(ctypes.Structure):
@@ -100,6 +107,8 @@ EXPORTS = [
     "rr_set_png_compression", "rr_encode_image_png", "rr_debug_png_filters", "rr_debug_scene_png_compression",
     "rr_debug_hdr_host",
     "rr_set_exr_codec", "rr_debug_scene_exr_codec", "rr_debug_float24", "rr_debug_exr_rle",
+    "rr_frame_submit_outputs", "rr_render_frame_outputs", "rr_last_output_bytes", "rr_set_extra_outputs",
+    "rr_debug_film_reduce",
 ]
 
 # rr_set_exr_codec's values (include/rr.h), by Blender's names of the codecs
@@ -237,6 +246,13 @@ def lib() -> ctypes.CDLL:
         "rr_debug_float24": (c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
         "rr_debug_exr_rle": (c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                      ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_frame_submit_outputs": (c_int, [P, P, i32, ctypes.POINTER(RenderParams), ctypes.POINTER(FrameOutput), i32,
+                                            ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_render_frame_outputs": (c_int, [P, P, i32, ctypes.POINTER(RenderParams), ctypes.POINTER(FrameOutput), i32,
+                                            ctypes.POINTER(FrameTiming), ctypes.POINTER(FrameStats)]),
+        "rr_last_output_bytes": (c_int, [P, i32, ctypes.POINTER(ctypes.c_uint64)]),
+        "rr_set_extra_outputs": (c_int, [P, ctypes.c_char_p]),
+        "rr_debug_film_reduce": (c_int, [P, f32p, i32, i32, i32, f32p]),
         "rr_debug_hdr_host": (c_int, [f32p, i32, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
@@ -462,6 +478,50 @@ class RenderContext:
                                      fmt.encode() if (fmt is not None and out_path is not None) else None,
                                      int(quality), ctypes.byref(t)), self.handle)
         return int(t.value)
+
+    @staticmethod
+    def _outputs(outputs):
+        """(path, fmt[, quality[, reduce]]) tuples as an rr_frame_output array (quality 90, reduce 1)."""
+        arr = (FrameOutput * max(len(outputs), 1))()
+        for a, o in zip(arr, outputs):
+            path, fmt, quality, reduce = tuple(o) + (90, 1)[len(o) - 2:]
+            a.out_path = os.fspath(path).encode() if path is not None else None
+            a.format = fmt.encode() if fmt is not None else None
+            a.jpeg_quality, a.reduce = int(quality), int(reduce)
+        return arr
+
+    def submit_frame_outputs(self, scene: Scene, frame: int, params: RenderParams | None, outputs) -> int:
+        """rr_frame_submit_outputs: one frame, several files. outputs: (path, fmt, quality, reduce)
+        tuples, path without extension, reduce 1, 2, 4 or 8 (a proxy reduced by that factor)."""
+        t = ctypes.c_uint64()
+        _check(lib().rr_frame_submit_outputs(self.handle, scene.handle, int(frame),
+                                             ctypes.byref(params) if params else None,
+                                             self._outputs(outputs), len(outputs), ctypes.byref(t)), self.handle)
+        return int(t.value)
+
+    def render_frame_outputs(self, scene: Scene, frame: int, params: RenderParams | None, outputs):
+        """rr_render_frame_outputs: submit_frame_outputs + complete_frame; (timing, stats)."""
+        t, s = FrameTiming(), FrameStats()
+        _check(lib().rr_render_frame_outputs(self.handle, scene.handle, int(frame),
+                                             ctypes.byref(params) if params else None,
+                                             self._outputs(outputs), len(outputs), ctypes.byref(t),
+                                             ctypes.byref(s)), self.handle)
+        return t, s
+
+    def last_output_bytes(self, index: int = 0) -> int:
+        """rr_last_output_bytes: the size of file `index` of the frame completed last."""
+        n = ctypes.c_uint64()
+        _check(lib().rr_last_output_bytes(self.handle, int(index), ctypes.byref(n)), self.handle)
+        return int(n.value)
+
+    def set_extra_outputs(self, spec: str | None = None):
+        """rr_set_extra_outputs: files every frame with a path also writes, "FORMAT[:K],..."
+        ("JPEG:4,PNG": <path>.r4.jpg and <path>.png); None / "": none."""
+        _check(lib().rr_set_extra_outputs(self.handle, spec.encode() if spec else None), self.handle)
+
+    def film_reduce(self, rgba: np.ndarray, reduce: int) -> np.ndarray:
+        """rr_debug_film_reduce on the device: the box mean of an (H, W, 4) float32 image."""
+        return film_reduce(rgba, reduce, self)
 
     def complete_frame(self, ticket: int):
         """rr_frame_complete: wait, encode + write; (timing, stats)."""
@@ -840,6 +900,18 @@ def png_filters(raw: np.ndarray, bpp: int) -> np.ndarray:
     out = np.zeros(rows, np.uint8)
     _check(lib().rr_debug_png_filters(_ptr(raw.reshape(-1), ctypes.c_uint8), row_bytes, rows, int(bpp),
                                       _ptr(out, ctypes.c_uint8)))
+    return out
+
+
+def film_reduce(rgba: np.ndarray, reduce: int, ctx: "RenderContext | None" = None) -> np.ndarray:
+    """rr_debug_film_reduce: the (ceil(H / reduce), ceil(W / reduce), 4) box mean of an (H, W, 4)
+    float32 image by csrc/reduce_rule.h, on ctx's device, or on the host without a context."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+    h, w = rgba.shape[:2]
+    k = max(int(reduce), 1)
+    out = np.zeros((-(-h // k), -(-w // k), 4), np.float32)
+    _check(lib().rr_debug_film_reduce(ctx.handle if ctx else None, _ptr(rgba, ctypes.c_float), w, h, int(reduce),
+                                      _ptr(out, ctypes.c_float)), ctx.handle if ctx else None)
     return out
 
 

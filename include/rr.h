@@ -300,6 +300,80 @@ int rr_frame_submit(rr_ctx* ctx, rr_scene* scene, int32_t frame_index,
 int rr_frame_complete(rr_ctx* ctx, uint64_t ticket, rr_frame_timing* timing,
                       rr_frame_stats* stats);
 
+/* Several files from one rendered frame: the frame is traced once, its film
+ * stays on the device, and every output is coded from it. An output is what
+ * rr_frame_submit's (out_path, format, jpeg_quality) name, and goes through
+ * the context's and the scene's depth, colour mode, codec, PNG compression and
+ * dither settings on its own (JPEG beside an RGBA PNG: three components beside
+ * four). reduce: 1, or 2, 4 or 8 for a proxy: the file then holds the frame
+ * reduced by that factor, ceil(W / reduce) x ceil(H / reduce) pixels, each the
+ * box mean of its block of the film (partial blocks at the right and bottom
+ * edges average the pixels they have; float32 sums in row order, so the
+ * result is reproducible bit for bit). An 8-bit output of a factor is the
+ * view pass (exposure, view transform, look, gamma, dither keyed on its own
+ * pixel coordinates) over the reduced film; "OPEN_EXR", "HDR" and 16-bit "PNG"
+ * read the reduced film itself. Outputs of one factor share its film.
+ *
+ * rr_frame_submit(path, format, q) is rr_frame_submit_outputs with the one
+ * output {path, format, q, 1}, and rr_frame_complete completes a frame of
+ * several outputs as any other; a file that cannot be written is RR_EIO naming
+ * it, and the frame's other files are written all the same. rr_frame_timing
+ * and rr_frame_stats keep their meaning; stats.output_bytes is outs[0]'s, and
+ * rr_last_output_bytes gives every file's size of the frame completed last
+ * (RR_EINVAL for an index that frame did not have).
+ *
+ * Refused before anything is launched or written: n outside 1 ..
+ * RR_MAX_FRAME_OUTPUTS, a reduce other than 1, 2, 4, 8, or two outputs of one
+ * file name (RR_EINVAL, naming the file); a format nobody writes (RR_ENOTSUP,
+ * rr_frame_submit's text); a size outside a coder's range, judged at the
+ * output's reduced size (RR_EINVAL, the coder's text: a proxy can bring a
+ * frame into a coder's range). Two JPEG outputs may differ in quality: the
+ * context keeps the transform's table of every quality it has been asked for.
+ * rr_last_warning joins the outputs' warnings in output order.
+ *
+ * What a context adds (rr_set_extra_outputs) or a scene (render.use_preview)
+ * counts towards RR_MAX_FRAME_OUTPUTS. */
+#define RR_MAX_FRAME_OUTPUTS 4
+typedef struct rr_frame_output {
+    const char* out_path;   /* without extension, as rr_frame_submit takes it */
+    const char* format;     /* "JPEG", "PNG", ...: a format rr_render_frame writes */
+    int32_t jpeg_quality;   /* as rr_frame_submit's */
+    int32_t reduce;         /* 1, 2, 4 or 8 */
+} rr_frame_output;
+int rr_frame_submit_outputs(rr_ctx* ctx, rr_scene* scene, int32_t frame_index,
+                            const rr_render_params* params, const rr_frame_output* outs,
+                            int32_t n, uint64_t* ticket);
+/* submit + complete, as rr_render_frame is */
+int rr_render_frame_outputs(rr_ctx* ctx, rr_scene* scene, int32_t frame_index,
+                            const rr_render_params* params, const rr_frame_output* outs,
+                            int32_t n, rr_frame_timing* timing, rr_frame_stats* stats);
+int rr_last_output_bytes(rr_ctx* ctx, int32_t index, uint64_t* bytes);
+
+/* Files every frame of ctx that is submitted with a path writes beside its
+ * own, for callers that cannot be changed (the Blender-CLI shim under the
+ * reference worker). spec: "FORMAT[:K]" entries joined by commas, e.g.
+ * "JPEG:4,PNG": a format name and a factor 1 (also when left out), 2, 4 or 8,
+ * at most RR_MAX_FRAME_OUTPUTS - 1 entries. An entry of factor 1 writes
+ * <out_path><ext>, one of factor K <out_path>.r<K><ext>, with the frame's
+ * jpeg_quality. NULL or "": none. RR_EINVAL for a spec that does not parse,
+ * which changes nothing; a frame whose own file an entry would overwrite is
+ * refused when it is submitted (RR_EINVAL, as above). Also read from
+ * RR_EXTRA_OUTPUTS by rr_create, like the other RR_* output settings.
+ *
+ * A scene may carry render.use_preview (Blender's image_settings.use_preview,
+ * exported only when set): on a context without extra outputs an "OPEN_EXR"
+ * frame of it also writes <out_path>.jpg, a JPEG of the frame's quality at
+ * factor 1. Not pinned: what Blender writes for that setting, and where, is
+ * recalled from memory. */
+int rr_set_extra_outputs(rr_ctx* ctx, const char* spec);
+
+/* The box mean of a reduced output (csrc/reduce_rule.h) of a w x h image of 4
+ * floats a pixel, into out: ceil(w / reduce) x ceil(h / reduce) pixels. With
+ * a context the device kernel runs (k_film_reduce), with ctx NULL the host's
+ * statement of the same rule; reduce 1, 2, 4 or 8. */
+int rr_debug_film_reduce(rr_ctx* ctx, const float* rgba, int32_t w, int32_t h, int32_t reduce,
+                         float* out /* ceil(w/reduce) * ceil(h/reduce) * 4 */);
+
 /* Wait until every piece of device work ctx has enqueued (frames in flight
  * included) has finished; their tickets still have to be completed. */
 int rr_synchronize(rr_ctx* ctx);

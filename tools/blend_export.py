@@ -180,6 +180,10 @@ EXR_CODEC_OF_DNA = {0: "NONE", 1: "PXR24", 2: "ZIP", 3: "PIZ", 4: "RLE", 5: "ZIP
                     9: "DWAB"}
 
 
+# ImageFormatData.flag: "save a JPEG beside the frame" (image_settings.use_preview)
+R_IMF_FLAG_PREVIEW_JPG = 1 << 1
+
+
 def export(path: str, args) -> dict:
     bf = BlendFile(path)
     sc = bf.blocks_with_code(b"SC")[0]
@@ -226,6 +230,10 @@ def export(path: str, args) -> dict:
     exr_codec = EXR_CODEC_OF_DNA.get(bf.read_struct_at(rd("im_format"), "ImageFormatData", "exr_codec"), "ZIP")
     if exr_codec != "ZIP":
         out["render"]["exr_codec"] = exr_codec
+    # image_settings.use_preview: a bit of ImageFormatData.flag (recalled from memory, not pinned
+    # against a Blender). Written only when set: a scene without the field writes no preview
+    if int(bf.read_struct_at(rd("im_format"), "ImageFormatData", "flag")) & R_IMF_FLAG_PREVIEW_JPG:
+        out["render"]["use_preview"] = True
     # image_settings.color_mode: ImageFormatData.planes holds the bits of a pixel
     # (R_IMF_PLANES_BW 8, _RGB 24, _RGBA 32). Written only with --color-mode
     # project: a scene without the field keeps each format's own layout, and
