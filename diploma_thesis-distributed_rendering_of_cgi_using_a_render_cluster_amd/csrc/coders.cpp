@@ -125,7 +125,7 @@ const BodyCoder kExrRows = {
     },
     [](const CoderInput& in, const CodedOut& o, uint32_t* scratch, uint8_t* out, hipStream_t st) {
         uint32_t* tab = o.exr_rows.rle ? device_pointer<uint32_t>(o.tab) : nullptr;
-        exr_rows_encode_device(in.film, in.inv_spp, in.alpha_one, o.exr_rows, scratch, out, tab, st);
+        exr_rows_encode_device(in.film, in.inv_spp, (in.alpha_mask ? 2 : in.alpha_one ? 1 : 0), o.exr_rows, scratch, out, tab, st);
     },
     [](const CodedOut& o, const uint8_t* body, size_t len, std::vector<uint8_t>& data) {
         const ExrRowsPlan& p = o.exr_rows;
@@ -299,6 +299,7 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
             throw std::runtime_error("Filmic view transform without LUTs");
         front = Png16Front{in.film, in.inv_spp, in.exposure_scale, in.view_transform, c->srgb16_lut.ptr,
                            view_args(c, in.view_transform, in.look, in.gamma)};
+        front.alpha_mask = in.alpha_mask ? 1 : 0;
     }
     const DeflatePlan& p = o.deflate;
     uint32_t* scratch = f.deflate_scratch.ptr;
@@ -315,12 +316,12 @@ void enqueue_coder(rr_ctx* c, const FrameOutput& fo, const CoderInput& in, DevFr
         else png16_encode_device(front, C, p, scratch, out, tab, st);
         break;
     case Coder::Exr:  // HALF channels
-        if (exr_pxr24(fo)) pxr24_encode_device(in.film, in.inv_spp, in.alpha_one, C, 16, p, scratch, out, tab, st);
-        else exr_encode_device(in.film, in.inv_spp, in.alpha_one, C, p, scratch, out, tab, st);
+        if (exr_pxr24(fo)) pxr24_encode_device(in.film, in.inv_spp, (in.alpha_mask ? 2 : in.alpha_one ? 1 : 0), C, 16, p, scratch, out, tab, st);
+        else exr_encode_device(in.film, in.inv_spp, (in.alpha_mask ? 2 : in.alpha_one ? 1 : 0), C, p, scratch, out, tab, st);
         break;
     default:  // Coder::Exr32: FLOAT channels
-        if (exr_pxr24(fo)) pxr24_encode_device(in.film, in.inv_spp, in.alpha_one, C, 32, p, scratch, out, tab, st);
-        else exr32_encode_device(in.film, in.inv_spp, in.alpha_one, C, p, scratch, out, tab, st);
+        if (exr_pxr24(fo)) pxr24_encode_device(in.film, in.inv_spp, (in.alpha_mask ? 2 : in.alpha_one ? 1 : 0), C, 32, p, scratch, out, tab, st);
+        else exr32_encode_device(in.film, in.inv_spp, (in.alpha_mask ? 2 : in.alpha_one ? 1 : 0), C, p, scratch, out, tab, st);
         break;
     }
     f.prof.end(st);

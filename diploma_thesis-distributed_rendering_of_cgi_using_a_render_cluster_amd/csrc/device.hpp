@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "region_rule.h"
 #include "rr.h"
 #include "rr_device.h"
 
@@ -224,6 +225,10 @@ struct DevFrame {
         DevBuf<uint8_t> rgba8;
     } reduced[3];
     static int reduced_slot(int k) { return k == 2 ? 0 : k == 4 ? 1 : 2; }
+    // A region frame (rr_set_region; region.hip): the windowed film, sums as `film` holds, and the 8-bit image
+    // the view pass makes of it; what the reductions and the coders of such a frame read instead of film / rgba8
+    DevBuf<float4> window_film;
+    DevBuf<uint8_t> window_rgba8;
     // written by render_frame_device, about the frame it enqueued
     int tile_slices = 0;       // k_tiles units per box tile (0: not k_tiles)
     bool unit_logged = false;  // its k_tiles launch wrote the unit log (trav_counts)
@@ -236,6 +241,11 @@ struct FrameOpts {
     bool count_traversal = false;  // RR_FLAG_COUNT_TRAVERSAL
     bool force_wavefront = false;  // RR_FLAG_WAVEFRONT: LDS-resident scenes take the split path, not k_tiles
     bool tile_whole = false;       // k_tiles: one work unit per tile (the frame overlaps a pending one)
+    // a region frame (rr_set_region): the split path traces and accumulates the region's pixels alone, the tile
+    // path runs the 8 x 8 tiles that meet the region alone (partial tiles whole); either leaves the film outside
+    // unwritten. Inside the frame, not empty.
+    bool region_on = false;
+    RegionRect region;
 };
 
 // Frame constants passed by value to the path kernels.
@@ -258,6 +268,15 @@ struct FrameConsts {
     // bound on |subpixel offset| of a camera sample (filter support + 1 px of
     // rounding slack): k_tiles' whole-tile culling test
     float filter_reach;
+};
+
+// The split path's constants: the frame's, and the pixels it enumerates. Its path index is p = dense pixel *
+// spp_chunk + sample with the dense pixel in [0, npix); a region frame (rw > 0) counts the region's pixels
+// row-major, npix = rw * region rows, and region_pix maps a dense pixel to the full-frame pixel that the camera
+// ray, the RNG key and the film use, so a region's samples are the full frame's. rw = 0: dense = full.
+struct SplitConsts : FrameConsts {
+    int rx0 = 0, ry0 = 0, rw = 0;
+    FastDiv div_rw;
 };
 
 // LBVH build for the current obj_xform (uploaded by the caller).
@@ -299,6 +318,9 @@ bool scene_in_lds(int n_tris, int n_mats, int n_lights);
 // all samples; LDS-resident scene). Such a frame touches only per-frame-slot
 // buffers and read-only tables, so it may run beside the other slot's frame.
 bool frame_uses_tiles(const FrameConsts& base, bool force_wavefront);
+// The pixels a tile-path frame runs: the frame's, or of a region frame those of the tiles that meet the region
+// (partial tiles count whole, cut only at the frame's edges).
+long long tiles_pixels_run(int W, int H, bool region_on, const RegionRect& r);
 
 // Render all chunks of one frame: film accumulate + tonemap to rgba8.
 // counters_per_chunk receives the device counter layout for stats.
@@ -372,14 +394,15 @@ void png_encode_device_adaptive(const uint8_t* d_rgba, int C, const DeflatePlan&
 // C: 4 the planes A, B, G, R; 3: B, G, R; 1: Y, the Rec.709 luma of the means; 2C W bytes a scanline.
 bool exr_plan(int W, int H, int C, DeflatePlan& p);
 size_t exr_stream_max_bytes(const DeflatePlan& p);  // every chunk raw
-// film: W x H float4 sums, scaled by inv_spp; alpha_one: A = 1.0 (rendered frames), else film.w * inv_spp.
-void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+// film: W x H float4 sums, scaled by inv_spp; alpha_one: 1 A = 1.0 (rendered frames), 0 film.w * inv_spp, 2 a mask:
+// A = 1.0 where film.w != 0 and 0 elsewhere (an uncropped region frame's windowed film).
+void exr_encode_device(const float4* d_film, float inv_spp, int alpha_one, int C, const DeflatePlan& p,
                        uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 // The same file with FLOAT channels: the means' own bits (no clamp, no
 // rounding), chunks of 16W bytes a scanline; exr_stream_max_bytes and the table
 // as above. W <= 2^18 (a band has twice the bytes).
 bool exr32_plan(int W, int H, int C, DeflatePlan& p);
-void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+void exr32_encode_device(const float4* d_film, float inv_spp, int alpha_one, int C, const DeflatePlan& p,
                          uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 // The same files with PXR24 chunks (rr_set_exr_codec; exr.hip Pxr24Front): zlib
 // over 16 scanlines of byte planes of pixel differences, depth 16 the halfs'
@@ -387,7 +410,7 @@ void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, in
 // the stream, DeflatePlan::raw_stride = 4 C W in a raw chunk). The ranges of
 // exr_plan / exr32_plan; exr_stream_max_bytes and the table as above.
 bool pxr24_plan(int W, int H, int C, int depth, DeflatePlan& p);
-void pxr24_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, int depth, const DeflatePlan& p,
+void pxr24_encode_device(const float4* d_film, float inv_spp, int alpha_one, int C, int depth, const DeflatePlan& p,
                          uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 // The view settings of a frame as kernel arguments (view.hpp FilmicDev::args):
@@ -423,6 +446,9 @@ struct Png16Front {
     int view_transform;  // RR_VIEW_STANDARD / RAW, or one of the Filmic family (`filmic` holds the LUTs)
     const float* srgb16;  // kSrgb16LutSize + 2 floats (scene.hpp build_srgb16_lut)
     FilmicArgs filmic;    // the LUTs, and for every view the display gamma
+    // an uncropped region frame's windowed film: a pixel with film.w == 0 lies outside the region and is written
+    // (0, 0, 0, 0), any other as usual with A = 65535 (the extended front end alone reads it)
+    int alpha_mask = 0;
 };
 void png16_encode_device(const Png16Front& f, int C, const DeflatePlan& p, uint32_t* scratch, uint8_t* host_out,
                          uint32_t* host_tab, hipStream_t st);

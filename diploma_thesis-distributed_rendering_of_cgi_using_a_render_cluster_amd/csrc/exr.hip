@@ -222,19 +222,19 @@ void exr_encode(const Film& fm, bool full, bool pxr24, int C, const DeflatePlan&
 
 }  // namespace
 
-void exr_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+void exr_encode_device(const float4* d_film, float inv_spp, int alpha_one, int C, const DeflatePlan& p,
                        uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
-    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, false, false, C, p, scratch, host_out, host_tab, st);
+    exr_encode(Film{d_film, inv_spp, alpha_one}, false, false, C, p, scratch, host_out, host_tab, st);
 }
 
-void exr32_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, const DeflatePlan& p,
+void exr32_encode_device(const float4* d_film, float inv_spp, int alpha_one, int C, const DeflatePlan& p,
                          uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
-    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, true, false, C, p, scratch, host_out, host_tab, st);
+    exr_encode(Film{d_film, inv_spp, alpha_one}, true, false, C, p, scratch, host_out, host_tab, st);
 }
 
-void pxr24_encode_device(const float4* d_film, float inv_spp, bool alpha_one, int C, int depth, const DeflatePlan& p,
+void pxr24_encode_device(const float4* d_film, float inv_spp, int alpha_one, int C, int depth, const DeflatePlan& p,
                          uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
-    exr_encode(Film{d_film, inv_spp, alpha_one ? 1 : 0}, depth == 32, true, C, p, scratch, host_out, host_tab, st);
+    exr_encode(Film{d_film, inv_spp, alpha_one}, depth == 32, true, C, p, scratch, host_out, host_tab, st);
 }
 
 }  // namespace rr

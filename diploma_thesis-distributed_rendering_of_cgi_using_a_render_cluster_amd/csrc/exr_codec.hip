@@ -175,10 +175,10 @@ ExrRowsBufs exr_rows_carve(const ExrRowsPlan& p, uint32_t* base) {
 
 size_t exr_rows_scratch_words(const ExrRowsPlan& p) { return exr_rows_carve(p, nullptr).words; }
 
-void exr_rows_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const ExrRowsPlan& p,
+void exr_rows_encode_device(const float4* d_film, float inv_spp, int alpha_one, const ExrRowsPlan& p,
                             uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st) {
     const ExrRowsBufs b = exr_rows_carve(p, scratch);
-    const Film fm{d_film, inv_spp, alpha_one ? 1 : 0};
+    const Film fm{d_film, inv_spp, alpha_one};
     if (p.full) launch_c<true>(fm, p, b, host_tab, st);
     else launch_c<false>(fm, p, b, host_tab, st);
     body_gather(b.body, b.total, p.body_cap, host_out, st);

@@ -41,7 +41,7 @@ ExrRowsBufs exr_rows_carve(const ExrRowsPlan& p, uint32_t* base);  // base nullp
 size_t exr_rows_scratch_words(const ExrRowsPlan& p);
 // film: W x H float4 sums, scaled by inv_spp; alpha_one: A = 1.0 (rendered
 // frames), else film.w * inv_spp. host_tab (RLE): 2 H words of pinned memory.
-void exr_rows_encode_device(const float4* d_film, float inv_spp, bool alpha_one, const ExrRowsPlan& p,
+void exr_rows_encode_device(const float4* d_film, float inv_spp, int alpha_one, const ExrRowsPlan& p,
                             uint32_t* scratch, uint8_t* host_out, uint32_t* host_tab, hipStream_t st);
 
 }  // namespace rr

@@ -58,7 +58,9 @@ __device__ __forceinline__ float sample_mean(const Film& fm, int width, int row0
     const float4 v = fm.px[(size_t)(row0 + (int)row) * W + x];
     if constexpr (C == 4) {
         const float c = ch == 0 ? v.w : ch == 1 ? v.z : ch == 2 ? v.y : v.x;
-        return (ch == 0 && fm.alpha_one) ? 1.0f : __fmul_rn(c, fm.inv_spp);
+        // alpha_one: 0 the film's alpha mean, 1 A = 1, 2 a mask: A = 1 where film.w != 0, else 0
+        if (ch == 0 && fm.alpha_one) return (fm.alpha_one == 2 && c == 0.0f) ? 0.0f : 1.0f;
+        return __fmul_rn(c, fm.inv_spp);
     } else if constexpr (C == 3) {
         const float c = ch == 0 ? v.z : ch == 1 ? v.y : v.x;
         return __fmul_rn(c, fm.inv_spp);

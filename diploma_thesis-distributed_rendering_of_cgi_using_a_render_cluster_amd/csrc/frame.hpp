@@ -18,6 +18,7 @@
 #include "hdr.hpp"
 #include "iris.hpp"
 #include "reduce.hpp"
+#include "region.hpp"
 #include "rr.h"
 #include "scene.hpp"
 #include "settings.hpp"
@@ -100,6 +101,7 @@ struct SlotOutput {
 
 struct FrameRun {
     int W, H, chunks, spp_chunk, tile_slices;
+    long long pixels_run;  // the pixels whose camera rays ran: the frame's, or on the split path a region's
     bool rebuilt;
     float build_ms, trace_ms, readback_ms;
     float render_ms, device_ms;  // ev0 -> ev4 (build + trace + view transform), ev0 -> ev2 (+ device JPEG)
@@ -141,6 +143,7 @@ struct FrameSlot {
     int n_outs = 0;
     bool slot_coders_only = false;  // every output is coded by a slot coder (enqueue_frame: what the next frame waits for)
     rr::FrameSetup fs;
+    rr::FrameRegion region;  // resolve_region at submit: what of the frame is rendered and written
     bool view_substituted = false;  // the scene's view settings not applied in full (view_warning says what)
     std::string view_warning;
     double submit_at = 0.0;         // UNIX time when the device work was enqueued
@@ -239,7 +242,8 @@ int frame_hier(const FrameSetup& fs, int n_tris);
 // The samples a chunk of the split path takes: by the frame's size alone, and
 // lowered to what the device's free memory holds.
 int choose_spp_chunk(const FrameSetup& fs);
-int fit_spp_chunk(const FrameSetup& fs, const DevPaths& p);
+// npix: the pixels the split path enumerates (a region's; 0: the frame's).
+int fit_spp_chunk(const FrameSetup& fs, const DevPaths& p, long long npix = 0);
 
 // The view transform, look and display gamma a frame on ctx is rendered with
 // (fs.view_transform, fs.look, fs.gamma). The context's look and gamma come
@@ -277,6 +281,7 @@ void finish_frame(rr_ctx* c, FrameSlot& sl);
 // The frame's render span in the worker's record (sl.tm), from the device's
 // own clock, once finish_frame has returned. t_sync: the UNIX time then.
 void set_render_span(rr_ctx* c, FrameSlot& sl, double t_sync);
+// width, height: the frame's; camera_rays: of the pixels that ran (FrameRun::pixels_run).
 void fill_stats(rr_frame_stats* st, const FrameSetup& fs, const FrameRun& r, int n_tris);
 
 // ---- the device coders (coders.cpp) ----------------------------------------
@@ -296,6 +301,9 @@ struct CoderInput {
     int view_transform = VIEW_STANDARD, look = 0;
     float gamma = 1.0f;
     bool alpha_one = true;
+    // the film is an uncropped region frame's windowed film: film.w != 0 marks the region. Exr, Exr32: A = 1
+    // there and 0 outside; Png16: A = 65535 there, (0, 0, 0, 0) outside. Comes before alpha_one.
+    bool alpha_mask = false;
     const float* jpeg_tab = nullptr;
 };
 

@@ -91,6 +91,7 @@ __device__ __forceinline__ float display1g(const Png16Front& f, float a) {
 // The 16-bit sample of channel ch (0 R, 1 G, 2 B) of a film sum.
 template <bool X>
 __device__ __forceinline__ uint32_t sample16(const Png16Front& f, float4 acc, uint32_t ch) {
+    if (X && f.alpha_mask && acc.w == 0.0f) return 0u;  // outside an uncropped region: black, whatever the view
     if (f.view_transform >= RR_VIEW_FILMIC) {  // the Filmic family
         float d[3];
         display_filmic<X>(f, acc, d);
@@ -103,6 +104,7 @@ __device__ __forceinline__ uint32_t sample16(const Png16Front& f, float4 acc, ui
 // of the three display-referred values, products and sums rounded one by one.
 template <bool X>
 __device__ __forceinline__ uint32_t grey16(const Png16Front& f, float4 acc) {
+    if (X && f.alpha_mask && acc.w == 0.0f) return 0u;
     float d[3];
     if (f.view_transform >= RR_VIEW_FILMIC) {  // the Filmic family
         display_filmic<X>(f, acc, d);
@@ -121,7 +123,7 @@ __device__ __forceinline__ uint32_t row_byte(const Png16Front& f, const float4* 
     uint32_t s;
     if constexpr (C == 4) {
         const uint32_t ch = (q >> 1) & 3u;
-        if (ch == 3u) return 0xFFu;  // A = 65535
+        if (ch == 3u) return (X && f.alpha_mask && row[q >> 3].w == 0.0f) ? 0u : 0xFFu;  // A = 65535, or the mask's 0
         s = sample16<X>(f, row[q >> 3], ch);
     } else if constexpr (C == 3) {
         const uint32_t k = q >> 1, px = k / 3u;
@@ -164,14 +166,14 @@ __global__ __launch_bounds__(256) void k_png16_raw(Png16Front f, size_t npix, ui
             o[1] = (uint16_t)g;
             o[2] = (uint16_t)b;
         } else {
-            reinterpret_cast<uint2*>(raw)[i] = make_uint2(r | (g << 16), b | 0xFFFF0000u);  // A = 65535
+            reinterpret_cast<uint2*>(raw)[i] = make_uint2(r | (g << 16), b | ((X && f.alpha_mask && acc.w == 0.0f) ? 0u : 0xFFFF0000u));  // A = 65535, or the mask's 0
         }
     }
 }
 
 // Whether a frame's settings need the extended front end.
 bool png16_extended(const Png16Front& f) {
-    return f.view_transform > RR_VIEW_FILMIC || f.filmic.inv_gamma != 0.0f;
+    return f.view_transform > RR_VIEW_FILMIC || f.filmic.inv_gamma != 0.0f || f.alpha_mask != 0;
 }
 
 }  // namespace

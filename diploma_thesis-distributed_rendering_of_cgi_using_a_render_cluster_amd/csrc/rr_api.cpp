@@ -188,6 +188,36 @@ int rr_scene_resolution(rr_scene* s, const rr_render_params* p, int32_t* w, int3
     return RR_OK;
 }
 
+int rr_region_resolution(rr_ctx* c, rr_scene* s, const rr_render_params* p, int32_t* w, int32_t* h) {
+    if (!c || !s) return fail(RR_EINVAL, "NULL ctx or scene");
+    int32_t W = 0, H = 0;
+    rr_scene_resolution(s, p, &W, &H);
+    FrameRegion rg;
+    std::string err;
+    if (!resolve_region(c->settings, s->desc.render, W, H, rg, err)) return fail(RR_EINVAL, err);
+    if (w) *w = rg.out_w(W);
+    if (h) *h = rg.out_h(H);
+    return RR_OK;
+}
+
+int rr_set_region(rr_ctx* c, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t crop) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    std::string err;
+    return setter_result(set_region(c->settings, x0, y0, x1, y1, crop != 0, err), err);
+}
+
+int rr_set_region_off(rr_ctx* c) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    set_region_off(c->settings);
+    return RR_OK;
+}
+
+int rr_set_region_from_scene(rr_ctx* c, int32_t on) {
+    if (!c) return fail(RR_EINVAL, "NULL ctx");
+    set_region_from_scene(c->settings, on != 0);
+    return RR_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -217,6 +247,12 @@ int submit_frame(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* 
         sl->tm.started_rendering_at = unix_now();
         sl->scene = s;
         sl->n_outs = 0;  // (a refusal below leaves the slot without a frame)
+        {
+            std::string err;
+            if (!resolve_region(c->settings, s->desc.render, sl->fs.W, sl->fs.H, sl->region, err))
+                return fail(RR_EINVAL, err);
+        }
+        const int OW = sl->region.out_w(sl->fs.W), OH = sl->region.out_h(sl->fs.H);
         bool slot_only = !list.empty();
         for (size_t i = 0; i < list.size(); ++i) {
             const OutputRequest& q = list[i];
@@ -224,8 +260,8 @@ int submit_frame(rr_ctx* c, rr_scene* s, int32_t frame, const rr_render_params* 
             o.out = resolve_output(c->settings, s->desc.render, q.format.c_str(), true, q.quality);
             o.path = q.path;
             o.reduce = q.reduce;
-            o.W = reduced_size(sl->fs.W, q.reduce);
-            o.H = reduced_size(sl->fs.H, q.reduce);
+            o.W = reduced_size(OW, q.reduce);
+            o.H = reduced_size(OH, q.reduce);
             o.bytes = 0;
             if (const int rc = plan_or_refuse(o.out, o.W, o.H, o.coded)) return rc;
             o.warning = o.out.coder == Coder::Webp ? webp_quality_warning(o.out.quality) : exr_codec_warning(o.out);
@@ -393,14 +429,20 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         sl->view_warning = resolve_view(c, sl->fs);
         sl->view_substituted = !sl->view_warning.empty();
         sl->scene = s;
+        {
+            std::string err;
+            if (!resolve_region(c->settings, s->desc.render, sl->fs.W, sl->fs.H, sl->region, err))
+                return fail(RR_EINVAL, err);
+        }
+        const int OW = sl->region.out_w(sl->fs.W), OH = sl->region.out_h(sl->fs.H);
         SlotOutput& o = sl->outs[0];  // the 8-bit image to the host; no file
         o.out = FrameOutput{};
         o.out.coder = Coder::HostRgba;
         o.path.clear();
         o.warning.clear();
         o.reduce = 1;
-        o.W = sl->fs.W;
-        o.H = sl->fs.H;
+        o.W = OW;
+        o.H = OH;
         sl->n_outs = 1;
         sl->slot_coders_only = false;
         sl->film_out = film;
@@ -409,7 +451,7 @@ int rr_render_frame_to_memory(rr_ctx* c, rr_scene* s, int32_t frame, const rr_re
         finish_frame(c, *sl);
         sl->film_out = nullptr;
         const FrameSetup& fs = sl->fs;
-        if (rgba8) std::memcpy(rgba8, sl->outs[0].host_rgba.ptr, (size_t)fs.W * fs.H * 4);
+        if (rgba8) std::memcpy(rgba8, sl->outs[0].host_rgba.ptr, (size_t)OW * OH * 4);
         c->frame_warning = sl->view_warning;
         if (stats) {
             fill_stats(stats, fs, sl->r, s->mesh.n_tris);

@@ -567,6 +567,28 @@ int rr_debug_film_reduce(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int
     });
 }
 
+int rr_debug_film_window(rr_ctx* c, const float* rgba, int32_t w, int32_t h, int32_t x0, int32_t y0, int32_t x1,
+                         int32_t y1, int32_t crop, float alpha_sum, float* out) {
+    if (!c || !rgba || !out || w <= 0 || h <= 0) return fail(RR_EINVAL, "bad arguments");
+    const RegionRect r{x0, y0, x1, y1};
+    if (r.empty() || x0 < 0 || y0 < 0 || x1 > w || y1 > h)
+        return fail(RR_EINVAL, "the region must lie inside the image and hold a pixel");
+    return guarded([&] {
+        if (!idle(c)) return fail(RR_EBUSY, "submitted frames are pending");
+        set_device(c);
+        hipStream_t st = c->stream;
+        const size_t n_in = (size_t)w * h, n_out = crop ? (size_t)r.w() * r.h() : n_in;
+        DevBuf<float4> in, win;
+        in.ensure(n_in);
+        win.ensure(n_out);
+        RR_HIP(hipMemcpyAsync(in.ptr, rgba, n_in * sizeof(float4), hipMemcpyHostToDevice, st));
+        film_window_device(in.ptr, w, h, r, crop != 0, alpha_sum, win.ptr, st);
+        RR_HIP(hipMemcpyAsync(out, win.ptr, n_out * sizeof(float4), hipMemcpyDeviceToHost, st));
+        RR_HIP(hipStreamSynchronize(st));
+        return RR_OK;
+    });
+}
+
 int rr_debug_object_matrix(rr_scene* s, int32_t obj, double frame, double* m16) {
     if (!s || !m16) return fail(RR_EINVAL, "NULL argument");
     return guarded([&] {

@@ -732,6 +732,24 @@ SceneDesc load_scene(const std::string& path) {
             if (v.type != Json::Bool) throw std::runtime_error("render.use_preview must be true or false");
             d.use_preview = v.b;
         }
+        // Blender's render border (use_border): fractions of the frame, y from the bottom; crop = use_crop_to_border
+        if (r.has("border")) {
+            const Json& b = r["border"];
+            if (b.type != Json::Object) throw std::runtime_error("render.border must be an object");
+            double* const dst[4] = {&d.border_min_x, &d.border_max_x, &d.border_min_y, &d.border_max_y};
+            const char* const names[4] = {"min_x", "max_x", "min_y", "max_y"};
+            for (int k = 0; k < 4; ++k) {
+                if (!b.has(names[k]) || b[names[k]].type != Json::Number || !(b[names[k]].num >= 0.0) ||
+                    b[names[k]].num > 1.0)
+                    throw std::runtime_error(std::string("render.border.") + names[k] + " must be a number in [0, 1]");
+                *dst[k] = b[names[k]].num;
+            }
+            if (b.has("crop")) {
+                if (b["crop"].type != Json::Bool) throw std::runtime_error("render.border.crop must be true or false");
+                d.border_crop = b["crop"].b;
+            }
+            d.has_border = true;
+        }
     }
     if (s.render.resx <= 0 || s.render.resy <= 0 || s.render.percent <= 0)
         throw std::runtime_error("invalid resolution");

@@ -120,6 +120,10 @@ struct RenderDesc {
     double dither_intensity = 0.0;  // render.dither_intensity, in [0, 2] (rr_set_dither RR_DITHER_SCENE takes it)
     int exr_codec = RR_EXR_CODEC_ZIP;  // render.exr_codec, an RR_EXR_CODEC_* value; no field: ZIP (rr_set_exr_codec SCENE takes it)
     int png_compression = -1;  // render.png_compression, 0 .. 100; -1: no field (rr_set_png_compression SCENE takes it)
+    // render.border {min_x, max_x, min_y, max_y, crop}: Blender's render border as fractions of the frame, y from
+    // the bottom (region_rule.h); honoured only where the context asks (rr_set_region_from_scene)
+    bool has_border = false, border_crop = false;
+    double border_min_x = 0.0, border_max_x = 1.0, border_min_y = 0.0, border_max_y = 1.0;
     bool use_preview = false;  // render.use_preview: an "OPEN_EXR" frame also writes a JPEG (settings.hpp add_extra_outputs)
     // What of the scene's colour management no frame can apply, for the
     // frame's warning ("" when there is nothing): a view transform this

@@ -125,6 +125,43 @@ bool set_extra_outputs(OutputSettings& s, const char* spec, std::string& err) {
     return true;
 }
 
+bool set_region(OutputSettings& s, int x0, int y0, int x1, int y1, bool crop, std::string& err) {
+    constexpr int kMax = 1 << 30;
+    const bool in_range = x0 >= -kMax && y0 >= -kMax && x1 <= kMax && y1 <= kMax;
+    if (!in_range || x0 >= x1 || y0 >= y1) {
+        err = "region (" + std::to_string(x0) + ", " + std::to_string(y0) + ", " + std::to_string(x1) + ", " +
+              std::to_string(y1) + ") must have x0 < x1 and y0 < y1, each within +-2^30";
+        return false;
+    }
+    s.region_on = true;
+    s.region = RegionRect{x0, y0, x1, y1};
+    s.region_crop = crop;
+    return true;
+}
+
+bool resolve_region(const OutputSettings& s, const RenderDesc& r, int W, int H, FrameRegion& out, std::string& err) {
+    out = FrameRegion{};
+    RegionRect asked;
+    if (s.region_from_scene && r.has_border) {
+        asked = region_of_border(r.border_min_x, r.border_max_x, r.border_min_y, r.border_max_y, W, H);
+        out.crop = r.border_crop;
+    } else if (s.region_on) {
+        asked = s.region;
+        out.crop = s.region_crop;
+    } else {
+        return true;
+    }
+    out.r = region_clamp(asked, W, H);
+    if (out.r.empty()) {
+        err = "region (" + std::to_string(asked.x0) + ", " + std::to_string(asked.y0) + ", " +
+              std::to_string(asked.x1) + ", " + std::to_string(asked.y1) + ") is empty inside the " +
+              std::to_string(W) + " x " + std::to_string(H) + " frame";
+        return false;
+    }
+    out.on = !(out.r.w() == W && out.r.h() == H);
+    return true;
+}
+
 namespace {
 
 // A whole text as one number, as strtol / strtod read it.
@@ -206,13 +243,41 @@ bool apply_text(OutputSettings& s, const std::string& var, const char* t, std::s
         return set_png_compression(s, (int)n, err);
     }
     if (var == "RR_EXTRA_OUTPUTS") return set_extra_outputs(s, t, err);
+    if (var == "RR_REGION") {
+        if (v.empty()) {
+            set_region_off(s);
+            set_region_from_scene(s, false);
+            return true;
+        }
+        if (v == "scene") {
+            set_region_from_scene(s, true);
+            return true;
+        }
+        long f[5] = {0, 0, 0, 0, 0};
+        int nf = 0;
+        for (size_t at = 0; at <= v.size(); ++nf) {
+            const size_t end = std::min(v.find(',', at), v.size());
+            const std::string field = v.substr(at, end - at);
+            at = end + 1;
+            if (nf == 5 || !whole_long(field.c_str(), f[nf]) || std::to_string(f[nf]) != field ||
+                f[nf] != (long)(int)f[nf]) {
+                nf = -1;
+                break;
+            }
+        }
+        if (nf < 4 || (nf == 5 && f[4] != 0 && f[4] != 1)) {
+            err = "not 'x0,y0,x1,y1[,crop]' (whole numbers, crop 0 or 1) or 'scene'";
+            return false;
+        }
+        return set_region(s, (int)f[0], (int)f[1], (int)f[2], (int)f[3], f[4] == 1, err);
+    }
     err = "not an output setting";
     return false;
 }
 
 constexpr const char* kEnvVars[] = {"RR_PNG_DEPTH",     "RR_EXR_DEPTH",       "RR_EXR_CODEC", "RR_COLOR_MODE", "RR_LOOK",
                                     "RR_DISPLAY_GAMMA", "RR_PNG_COMPRESSION", "RR_DITHER",    "RR_DEVICE_PNG",
-                                    "RR_EXTRA_OUTPUTS"};
+                                    "RR_EXTRA_OUTPUTS", "RR_REGION"};
 
 }  // namespace
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "formats.hpp"
+#include "region_rule.h"
 #include "rr.h"
 
 namespace rr {
@@ -44,6 +45,12 @@ struct OutputSettings {
     float dither = 0.f;
     // files every frame with a path writes beside its own (rr_set_extra_outputs / RR_EXTRA_OUTPUTS)
     std::vector<ExtraOutput> extra_outputs;
+    // the render region (rr_set_region / rr_set_region_off / RR_REGION): off on a new context
+    bool region_on = false;
+    RegionRect region;         // full-frame pixels, rows top first, half open; clamped when a frame is resolved
+    bool region_crop = false;  // the outputs are the region's pixels alone; else the full frame, (0, 0, 0, 0) outside
+    // a scene's render.border gives the region (rr_set_region_from_scene / RR_REGION=scene); comes before `region`
+    bool region_from_scene = false;
 };
 
 // The setters. false + err for a value outside the setting's range, which
@@ -63,6 +70,11 @@ bool set_png_compression(OutputSettings& s, int percent, std::string& err);
 // RR_MAX_FRAME_OUTPUTS - 1 entries, no two of which would write the same file.
 // NULL or "": none.
 bool set_extra_outputs(OutputSettings& s, const char* spec, std::string& err);
+// The region: x0 < x1 and y0 < y1 (an inverted or empty rectangle is refused), each within +-2^30; beyond
+// the frame is allowed and clamped when a frame is resolved.
+bool set_region(OutputSettings& s, int x0, int y0, int x1, int y1, bool crop, std::string& err);
+inline void set_region_off(OutputSettings& s) { s.region_on = false; }
+inline void set_region_from_scene(OutputSettings& s, bool on) { s.region_from_scene = on; }
 
 bool valid_color_mode(int mode);
 
@@ -88,8 +100,8 @@ inline bool exr_codec_built(int codec) {
 bool valid_png_compression(int v);
 
 // One variable's text (RR_PNG_DEPTH, RR_EXR_DEPTH, RR_EXR_CODEC, RR_COLOR_MODE, RR_LOOK,
-// RR_DISPLAY_GAMMA, RR_PNG_COMPRESSION, RR_DITHER, RR_DEVICE_PNG) through its
-// setter. A refusal's err names the variable and quotes the text.
+// RR_DISPLAY_GAMMA, RR_PNG_COMPRESSION, RR_DITHER, RR_DEVICE_PNG, RR_EXTRA_OUTPUTS, RR_REGION) through its
+// setter. RR_REGION: "x0,y0,x1,y1[,crop]" (crop 0 or 1), "scene" (the scene's border), "" off. A refusal's err names the variable and quotes the text.
 bool setting_from_text(OutputSettings& s, const std::string& var, const char* text, std::string& err);
 // Every variable that is set, in the order above. false + err: s is unchanged.
 bool settings_from_env(OutputSettings& s, std::string& err);
@@ -138,6 +150,20 @@ std::string exr_codec_warning(const FrameOutput& fo);
 // caller); without a path there is no file (Coder::None).
 FrameOutput resolve_output(const OutputSettings& s, const RenderDesc& r, const char* format, bool has_path,
                            int jpeg_quality);
+
+// The region a W x H frame of a scene with render settings r renders on a context with settings s.
+struct FrameRegion {
+    bool on = false;    // false: the whole frame, and nothing of the region code runs
+    bool crop = false;
+    RegionRect r;       // clamped to the frame, never empty when on
+    // the size of the frame's files and of rr_render_frame_to_memory's image
+    int out_w(int W) const { return on && crop ? r.w() : W; }
+    int out_h(int H) const { return on && crop ? r.h() : H; }
+};
+// The scene's border where the context asks for it and the scene has one, else the context's own region,
+// clamped. A region that covers the whole frame resolves to off: such a frame is the frame without a region.
+// false + err (naming the region and the frame size): nothing of the region lies inside the frame.
+bool resolve_region(const OutputSettings& s, const RenderDesc& r, int W, int H, FrameRegion& out, std::string& err);
 
 // One file a frame is asked to write: rr_frame_output with its strings owned.
 struct OutputRequest {

@@ -395,6 +395,21 @@ RR_D void path_of(const FrameConsts& fc, uint32_t p, int& pix, int& sl) {
     sl = (int)p - pix * fc.spp_chunk;
 }
 
+// The full-frame pixel of a dense pixel of the split path (SplitConsts): itself, or on a region frame the
+// region's pixel in row-major order. Wave-uniform branch on a kernel argument.
+// RR_SPLIT_CONSTS: the constants these kernels take. tiles.hip, which compiles them only for their effect on
+// k_tiles' code and never launches them, sets FrameConsts: with it the mapping is the identity and that unit's
+// code is what it was before there were regions.
+#ifndef RR_SPLIT_CONSTS
+#define RR_SPLIT_CONSTS SplitConsts
+#endif
+RR_D int region_pix(const FrameConsts&, int dense) { return dense; }
+RR_D int region_pix(const SplitConsts& fc, int dense) {
+    if (fc.rw == 0) return dense;
+    const int ry = (int)fc.div_rw.div((uint32_t)dense);
+    return (fc.ry0 + ry) * fc.W + fc.rx0 + (dense - ry * fc.rw);
+}
+
 // Packet traversal with per-lane box tests: the camera kernel's walk until
 // the beam (packet_trace_beam below) replaced it there. It stays because
 // rr_debug_trace width 5 and its tests run it over arbitrary rays
@@ -648,7 +663,7 @@ RR_D void packet_trace_beam(const QNode6* __restrict__ nodes, const TriPack* __r
 // 02 / 03 frame slice against 12.5 / 14.1.
 template <bool kCount>
 __global__ __launch_bounds__(kBlock, kTraceWaves) void k_trace_primary_packet(
-    FrameConsts fc, SceneArgs sa, int np, float2* __restrict__ hits, uint32_t* __restrict__ deal,
+    RR_SPLIT_CONSTS fc, SceneArgs sa, int np, float2* __restrict__ hits, uint32_t* __restrict__ deal,
     int32_t* __restrict__ spill, unsigned long long* __restrict__ tc, uint32_t* __restrict__ tail) {
     __shared__ int stack_all[kWavesPerBlock * kPacketStack];
     lds_int* stk = lds_slot(stack_all) + (threadIdx.x >> 6) * kPacketStack;
@@ -666,6 +681,7 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_trace_primary_packet(
         const bool valid = p < np;
         int pix, sl;
         path_of(fc, (uint32_t)(valid ? p : 0), pix, sl);
+        pix = region_pix(fc, pix);
         const int py = (int)fc.div_w.div((uint32_t)pix), px = pix - py * fc.W;
         float3 o = mk3(0.0f, 0.0f, 0.0f), d = o;
         float tmin = 0.0f, tmax = -1.0f;
@@ -691,7 +707,7 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_trace_primary_packet(
 // and the bounce-0 shadow queue.
 // In path-index order (pixel-major), so the bounce-0 shadow rays and the
 // bounce-1 paths are queued with the samples of one pixel side by side.
-__global__ __launch_bounds__(kBlock, kShadeWaves) void k_shade_primary(FrameConsts fc, SceneArgs sa, int np,
+__global__ __launch_bounds__(kBlock, kShadeWaves) void k_shade_primary(RR_SPLIT_CONSTS fc, SceneArgs sa, int np,
                                                           const float2* __restrict__ hits, Rad rad,
                                                           PathQueue out, ShadowQueue sq, QueueOut qo,
                                                           const float4* __restrict__ tnrm) {
@@ -705,6 +721,7 @@ __global__ __launch_bounds__(kBlock, kShadeWaves) void k_shade_primary(FrameCons
         if (p < np) {
             int pix, sl;
             path_of(fc, (uint32_t)p, pix, sl);
+            pix = region_pix(fc, pix);
             const uint32_t key = path_key(fc.seed, (uint32_t)pix, (uint32_t)(fc.first_sample + sl));
             float3 o, d;
             float tmin, tmax;
@@ -747,7 +764,7 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_trace_extend(Scene
 
 // Bounce b: shade from hits[slot], in the queue's time order (slot_t); appends
 // the next path queue and this bounce's shadow queue.
-__global__ __launch_bounds__(kBlock, kShadeWaves) void k_shade_extend(FrameConsts fc, int bounce, SceneArgs sa, PathQueue in,
+__global__ __launch_bounds__(kBlock, kShadeWaves) void k_shade_extend(RR_SPLIT_CONSTS fc, int bounce, SceneArgs sa, PathQueue in,
                                                          QueueIn qi, const float2* __restrict__ hits,
                                                          Rad rad, PathQueue out, ShadowQueue sq,
                                                          QueueOut qo, const float4* __restrict__ tnrm) {
@@ -769,6 +786,7 @@ __global__ __launch_bounds__(kBlock, kShadeWaves) void k_shade_extend(FrameConst
             const Hit h = unpack_hit(hits[i]);
             int pix, sl;
             path_of(fc, (uint32_t)pid, pix, sl);
+            pix = region_pix(fc, pix);
             const uint32_t key = path_key(fc.seed, (uint32_t)pix, (uint32_t)(fc.first_sample + sl));
             float3 L = rad.get(pid);
             shade(fc, bounce, v, xyz(a), xyz(b), xyz(c), (uint32_t)f2i(b.w), h, key, L, so);
@@ -820,14 +838,15 @@ __global__ __launch_bounds__(kTraceBlock, kTraceWaves) void k_shadow_refill(Scen
 // Film sum in the grouped order (kFilmGroup, rr_device.h): the open group's
 // partial sum crosses chunk boundaries in `part` (touched only by frames of
 // several chunks).
-__global__ __launch_bounds__(kBlock) void k_accumulate(FrameConsts fc, Rad rad,
+__global__ __launch_bounds__(kBlock) void k_accumulate(RR_SPLIT_CONSTS fc, Rad rad,
                                                        float4* __restrict__ film, float4* __restrict__ part,
                                                        int first_chunk, int last_chunk, const float* __restrict__ srgb,
                                                        uchar4* __restrict__ out) {
     for (int pix = blockIdx.x * kBlock + threadIdx.x; pix < fc.npix; pix += gridDim.x * kBlock) {
+        const int fpix = region_pix(fc, pix);  // the film's pixel; the records and `part` are dense
         float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f), P = acc;
         if (!first_chunk) {
-            acc = film[pix];
+            acc = film[fpix];
             P = part[pix];
         }
         // the pixel's records are contiguous (path index pixel-major): read
@@ -864,11 +883,11 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(FrameConsts fc, Rad rad,
             acc.x = acc.x + P.x;
             acc.y = acc.y + P.y;
             acc.z = acc.z + P.z;
-            out[pix] = tonemap(fc, acc, srgb);
+            out[fpix] = tonemap(fc, acc, srgb);
         } else {
             part[pix] = P;
         }
-        film[pix] = acc;
+        film[fpix] = acc;
     }
 }
 

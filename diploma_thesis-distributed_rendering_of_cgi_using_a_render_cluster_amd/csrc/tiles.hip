@@ -23,6 +23,9 @@
 // this include is a change of k_tiles' code and wants its own measurement.
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // those kernels, unused here
+// with the frame's own constants: a region frame's pixel mapping (SplitConsts) is wavefront.hip's alone, and
+// these copies stay the kernels k_tiles was measured beside
+#define RR_SPLIT_CONSTS FrameConsts
 #include "split_kernels.hpp"
 #pragma clang diagnostic pop
 
@@ -518,6 +521,29 @@ RR_D TileOrder tile_order(const FrameConsts& fc, const ScreenCull& sc) {
     return to;
 }
 
+// A region frame (rr_set_region): the tiles that meet the region, in tile coordinates. Only they are work
+// units: region_order is the frame's order cut to that rectangle, its tile indices and its box relative to
+// the rectangle's corner (TileOrder::at then gives rectangle coordinates; the caller adds x0, y0). Partial
+// tiles run whole; the film window (region.hip) drops their pixels outside the region.
+struct TileRect {
+    int x0, y0, w, h;
+};
+RR_D TileOrder region_order(const TileOrder& to, const TileRect& rt) {
+    TileOrder r;
+    r.tx = rt.w;
+    r.n = rt.w * rt.h;
+    r.bx0 = r.by0 = r.bw = r.bh = 0;
+    const int bx0 = max(to.bx0, rt.x0), by0 = max(to.by0, rt.y0);
+    const int bx1 = min(to.bx0 + to.bw, rt.x0 + rt.w), by1 = min(to.by0 + to.bh, rt.y0 + rt.h);
+    if (to.bw > 0 && to.bh > 0 && bx0 < bx1 && by0 < by1) {
+        r.bx0 = bx0 - rt.x0;
+        r.by0 = by0 - rt.y0;
+        r.bw = bx1 - bx0;
+        r.bh = by1 - by0;
+    }
+    return r;
+}
+
 // Whether no sample of tile (tx, ty) can land inside the screen rectangle:
 // every subpixel position is px + 0.5 + offset with |offset| < filter_reach
 // (which includes a pixel of rounding slack), so each sample's own test in
@@ -733,11 +759,12 @@ struct TileSlices {
 };
 namespace {
 
-template <bool kCount, bool kWhole>
+template <bool kCount, bool kWhole, bool kRegion = false>
 RR_D void tiles_body(const FrameConsts& fc, const LdsView& v, uint32_t* __restrict__ tile_ctr, float4* __restrict__ film,
                      const float* __restrict__ srgb, uchar4* __restrict__ out, uint32_t* __restrict__ tot,
                      int32_t* __restrict__ spill, unsigned long long* __restrict__ tc, lds_int* stack,
-                     const TileSlices sl, unsigned long long rt_entry, lds_uint* cont_ctr) {
+                     const TileSlices sl, unsigned long long rt_entry, lds_uint* cont_ctr,
+                     const TileRect rt = TileRect{0, 0, 0, 0}) {
     const int stride = gridDim.x * kBlock;
     // counting instantiation only: the wave's shader-clock and real-time
     // counters at start and end give the clock the kernel ran at (read-only
@@ -755,7 +782,9 @@ RR_D void tiles_body(const FrameConsts& fc, const LdsView& v, uint32_t* __restri
     // spill) them in VGPRs for the whole kernel: every lane holds the same
     // values, lane 0's copy goes to SGPRs.
     const ScreenCull cull = uniform_cull(screen_cull(fc, v.nodes));
-    const TileOrder to = uniform_order(tile_order(fc, cull));
+    const TileOrder fto = uniform_order(tile_order(fc, cull));
+    // kRegion: the units are the region's tiles alone; the costs stay indexed by the frame's screen tiles
+    const TileOrder to = kRegion ? region_order(fto, rt) : fto;
     const int lane = threadIdx.x & 63;
     // Work units: each tile of the screen-rectangle box is cut into sl.n slices,
     // one per sample group; every other tile is one unit whose samples are all
@@ -805,6 +834,10 @@ RR_D void tiles_body(const FrameConsts& fc, const LdsView& v, uint32_t* __restri
         const unsigned long long u_start = __builtin_amdgcn_s_memrealtime();
         int tx, ty;
         to.at(t, tx, ty);
+        if (kRegion) {
+            tx += rt.x0;
+            ty += rt.y0;
+        }
         const int px = tx * kTile + (lane & (kTile - 1)), py = ty * kTile + (lane >> 3);
         const bool valid = px < fc.W && py < fc.H;
         const int pix = py * fc.W + px;
@@ -929,7 +962,7 @@ RR_D void tiles_body(const FrameConsts& fc, const LdsView& v, uint32_t* __restri
             s_gen = s_lo;
             // counting launches: the samples this body ran, per tile, in the second half of the cost buffer
             // (rr_debug_tile_costs hands out the whole buffer; tests/test_gpu_tile_covered.py reads it)
-            if (kCount && lane == 0) atomicAdd(&sl.cost[to.n + ty * to.tx + tx], (uint32_t)(s_hi - s_lo));
+            if (kCount && lane == 0) atomicAdd(&sl.cost[fto.n + ty * fto.tx + tx], (uint32_t)(s_hi - s_lo));
         }
         for (int s = s_lo; s < s_gen; ++s) {
             const uint32_t key = sample_key(pk, (uint32_t)s);
@@ -977,7 +1010,7 @@ RR_D void tiles_body(const FrameConsts& fc, const LdsView& v, uint32_t* __restri
         }
         if (lane == 0) {  // this unit's time, for the next launch's hand-out order (k_tile_order)
             const unsigned long long u_end = __builtin_amdgcn_s_memrealtime();
-            atomicAdd(&sl.cost[ty * to.tx + tx], (uint32_t)(u_end - u_start));
+            atomicAdd(&sl.cost[ty * fto.tx + tx], (uint32_t)(u_end - u_start));
             if ((kCount || RR_TILES_LOG_ALWAYS) && u < kUnitLog) {  // the counting launch's unit log (device.hpp kUnitLog)
                 tc[kTravWords + 2 * u] = u_start;
                 tc[kTravWords + 2 * u + 1] = u_end;
@@ -1066,14 +1099,15 @@ RR_D int cost_bucket(uint32_t c) {
     const int e = 31 - __builtin_clz(c);
     return min(kOrderBuckets - 1, 4 * e + (int)((c >> (e - 2)) & 3u));
 }
-__global__ __launch_bounds__(kOrderThreads) void k_tile_order(FrameConsts fc, const BvhNode* __restrict__ nodes,
-                                                              uint32_t* __restrict__ cost, int32_t* __restrict__ order,
-                                                              uint32_t* __restrict__ tile_ctr,
-                                                              uint32_t* __restrict__ ray_ctr, int n_ray_ctr) {
+template <bool kRegion>
+RR_D void tile_order_body(const FrameConsts& fc, const BvhNode* __restrict__ nodes, uint32_t* __restrict__ cost,
+                          int32_t* __restrict__ order, uint32_t* __restrict__ tile_ctr,
+                          uint32_t* __restrict__ ray_ctr, int n_ray_ctr, const TileRect rt) {
     __shared__ uint32_t cnt[kOrderBuckets];
     const int tid = threadIdx.x;
     const ScreenCull cull = screen_cull(fc, nodes);
-    const TileOrder to = tile_order(fc, cull);
+    const TileOrder fto = tile_order(fc, cull);
+    const TileOrder to = kRegion ? region_order(fto, rt) : fto;
     const int nb = to.bw * to.bh;
     for (int i = tid; i < kOrderBuckets; i += kOrderThreads) cnt[i] = 0u;
     for (int i = tid; i < kTileShards * kTileCtrStride; i += kOrderThreads) tile_ctr[i] = 0u;
@@ -1082,7 +1116,11 @@ __global__ __launch_bounds__(kOrderThreads) void k_tile_order(FrameConsts fc, co
     for (int t = tid; t < nb; t += kOrderThreads) {
         int x, y;
         to.at(t, x, y);
-        atomicAdd(&cnt[cost_bucket(cost[y * to.tx + x])], 1u);
+        if (kRegion) {
+            x += rt.x0;
+            y += rt.y0;
+        }
+        atomicAdd(&cnt[cost_bucket(cost[y * fto.tx + x])], 1u);
     }
     __syncthreads();
     if (tid == 0) {  // bucket starts, the heaviest bucket first
@@ -1097,26 +1135,41 @@ __global__ __launch_bounds__(kOrderThreads) void k_tile_order(FrameConsts fc, co
     for (int t = tid; t < nb; t += kOrderThreads) {
         int x, y;
         to.at(t, x, y);
-        order[atomicAdd(&cnt[cost_bucket(cost[y * to.tx + x])], 1u)] = t;
+        if (kRegion) {
+            x += rt.x0;
+            y += rt.y0;
+        }
+        order[atomicAdd(&cnt[cost_bucket(cost[y * fto.tx + x])], 1u)] = t;
     }
     __syncthreads();
-    for (int i = tid; i < to.n; i += kOrderThreads) cost[i] = 0u;
+    for (int i = tid; i < fto.n; i += kOrderThreads) cost[i] = 0u;
+}
+__global__ __launch_bounds__(kOrderThreads) void k_tile_order(FrameConsts fc, const BvhNode* __restrict__ nodes,
+                                                              uint32_t* __restrict__ cost, int32_t* __restrict__ order,
+                                                              uint32_t* __restrict__ tile_ctr,
+                                                              uint32_t* __restrict__ ray_ctr, int n_ray_ctr) {
+    tile_order_body<false>(fc, nodes, cost, order, tile_ctr, ray_ctr, n_ray_ctr, TileRect{0, 0, 0, 0});
 }
 
 // Film of the sliced tiles: the group sums of each box tile that is not
 // culled, added in group order (the same box and culling test as k_tiles,
 // from the same root node), then tonemapped. One wave per tile.
-__global__ __launch_bounds__(kBlock) void k_tiles_fold(FrameConsts fc, const BvhNode* __restrict__ nodes,
-                                                       TileSlices sl, float4* __restrict__ film,
-                                                       const float* __restrict__ srgb, uchar4* __restrict__ out) {
+template <bool kRegion>
+RR_D void tiles_fold_body(const FrameConsts& fc, const BvhNode* __restrict__ nodes, const TileSlices& sl,
+                          float4* __restrict__ film, const float* __restrict__ srgb, uchar4* __restrict__ out,
+                          const TileRect rt) {
     const ScreenCull cull = screen_cull(fc, nodes);
-    const TileOrder to = tile_order(fc, cull);
+    const TileOrder to = kRegion ? region_order(tile_order(fc, cull), rt) : tile_order(fc, cull);
     const int nb = to.bw * to.bh;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     for (int t = wave; t < nb; t += gridDim.x * kWavesPerBlock) {
         int tx, ty;
         to.at(t, tx, ty);
+        if (kRegion) {
+            tx += rt.x0;
+            ty += rt.y0;
+        }
         if (tile_culled(fc, cull, tx, ty)) continue;
         const int px = tx * kTile + (lane & (kTile - 1)), py = ty * kTile + (lane >> 3);
         if (px >= fc.W || py >= fc.H) continue;
@@ -1131,6 +1184,44 @@ __global__ __launch_bounds__(kBlock) void k_tiles_fold(FrameConsts fc, const Bvh
         film[pix] = acc;
         out[pix] = tonemap(fc, acc, srgb);
     }
+}
+__global__ __launch_bounds__(kBlock) void k_tiles_fold(FrameConsts fc, const BvhNode* __restrict__ nodes,
+                                                       TileSlices sl, float4* __restrict__ film,
+                                                       const float* __restrict__ srgb, uchar4* __restrict__ out) {
+    tiles_fold_body<false>(fc, nodes, sl, film, srgb, out, TileRect{0, 0, 0, 0});
+}
+
+// The three kernels of a region frame: the same bodies over the region's tiles (TileRect). Kernels of their
+// own, so that a frame without a region launches what it always did.
+template <bool kCount, bool kWhole>
+__global__ __launch_bounds__(kBlock, kWhole ? RR_TILES_WAVES_WHOLE : RR_TILES_WAVES) void k_tiles_region(
+    FrameConsts fc, SceneArgs sa, uint32_t* __restrict__ tile_ctr, float4* __restrict__ film,
+    const float* __restrict__ srgb, uchar4* __restrict__ out, uint32_t* __restrict__ tot, int32_t* __restrict__ spill,
+    unsigned long long* __restrict__ tc, TileSlices sl, TileRect rt) {
+    const unsigned long long rt_entry = kCount ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    __shared__ int lds_stack[kLdsStack * kBlock];
+    __shared__ uint32_t cont_ctr[kWctr * kWavesPerBlock];
+    extern __shared__ float4 dyn4[];
+    lds_int* stack = lds_slot(lds_stack);
+    if (threadIdx.x < kWctr * kWavesPerBlock) cont_ctr[threadIdx.x] = 0u;
+    int used;
+    const LdsView v = stage_scene<true>((lds_f4w*)dyn4, sa, true, used, &fc);
+    tiles_body<kCount, kWhole, true>(fc, v, tile_ctr, film, srgb, out, tot, spill, tc, stack, sl, rt_entry,
+                                     (lds_uint*)cont_ctr, rt);
+}
+__global__ __launch_bounds__(kOrderThreads) void k_tile_order_region(FrameConsts fc, const BvhNode* __restrict__ nodes,
+                                                                     uint32_t* __restrict__ cost,
+                                                                     int32_t* __restrict__ order,
+                                                                     uint32_t* __restrict__ tile_ctr,
+                                                                     uint32_t* __restrict__ ray_ctr, int n_ray_ctr,
+                                                                     TileRect rt) {
+    tile_order_body<true>(fc, nodes, cost, order, tile_ctr, ray_ctr, n_ray_ctr, rt);
+}
+__global__ __launch_bounds__(kBlock) void k_tiles_fold_region(FrameConsts fc, const BvhNode* __restrict__ nodes,
+                                                              TileSlices sl, float4* __restrict__ film,
+                                                              const float* __restrict__ srgb, uchar4* __restrict__ out,
+                                                              TileRect rt) {
+    tiles_fold_body<true>(fc, nodes, sl, film, srgb, out, rt);
 }
 
 // LDS-resident scenes render through k_tiles (RR_FLAG_WAVEFRONT: through the
@@ -1193,18 +1284,38 @@ bool frame_uses_tiles(const FrameConsts& base, bool force_wavefront) {
            tile_slab_bytes(base.spp_total, n_tiles) <= kTileSlabMax;
 }
 
+long long tiles_pixels_run(int W, int H, bool region_on, const RegionRect& r) {
+    if (!region_on) return (long long)W * H;
+    const int x0 = r.x0 / kTile * kTile, y0 = r.y0 / kTile * kTile;
+    const int x1 = std::min(W, (r.x1 + kTile - 1) / kTile * kTile), y1 = std::min(H, (r.y1 + kTile - 1) / kTile * kTile);
+    return (long long)(x1 - x0) * (y1 - y0);
+}
+
 namespace {
+// The tiles that meet a region of pixels (inside the frame, not empty; an unset one gives an empty rectangle).
+TileRect region_tiles(const RegionRect& r) {
+    if (r.empty()) return TileRect{0, 0, 0, 0};
+    const int x0 = r.x0 / kTile, y0 = r.y0 / kTile;
+    return TileRect{x0, y0, (r.x1 + kTile - 1) / kTile - x0, (r.y1 + kTile - 1) / kTile - y0};
+}
 // Launch geometry of k_tiles: the scene and the camera data staged in dynamic
 // LDS (stage_scene, stage_camera), the resident grid for it.
 struct TileGrid {
     decltype(&k_tiles<false, false>) kx;
+    decltype(&k_tiles_region<false, false>) kxr = nullptr;  // a region frame's
     size_t dyn;
     int grid;
-    TileGrid(const FrameConsts& fc, bool count, bool whole) {
+    TileGrid(const FrameConsts& fc, bool count, bool whole, bool region) {
         dyn = tiles_dyn_lds_bytes(fc);  // what scene_in_lds counted
         kx = count ? (whole ? k_tiles<true, true> : k_tiles<true, false>)
                    : (whole ? k_tiles<false, true> : k_tiles<false, false>);
-        grid = grid_for(kx, dyn);
+        if (region) {
+            kxr = count ? (whole ? k_tiles_region<true, true> : k_tiles_region<true, false>)
+                        : (whole ? k_tiles_region<false, true> : k_tiles_region<false, false>);
+            grid = grid_for(kxr, dyn);
+        } else {
+            grid = grid_for(kx, dyn);
+        }
     }
 };
 }  // namespace
@@ -1212,7 +1323,7 @@ struct TileGrid {
 void render_tiles_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f, const FrameConsts& base, int n_chunks,
                          FrameOpts o, hipStream_t st) {
     const int npix = base.npix;
-    const TileGrid G(base, o.count_traversal, o.tile_whole);
+    const TileGrid G(base, o.count_traversal, o.tile_whole, o.region_on);
     if (p.grid_blocks == 0) p.grid_blocks = device_cu_count() * kMaxBlocksPerCu;
     f.ensure_spill(p.grid_blocks);  // k_tiles: only the traversal stack spill area
     f.film.ensure((size_t)npix);
@@ -1249,19 +1360,36 @@ void render_tiles_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f
     TileSlices sl{o.tile_whole ? 1 : film_groups(base.spp_total), (size_t)192 * film_groups(base.spp_total), nullptr,
                   f.tile_order.ptr, f.tile_cost.ptr};
     f.tile_slices = sl.n;
+    // a region frame: only the tiles that meet the region are units, and the slab holds those alone
+    const TileRect rt = region_tiles(o.region);
+    const long tiles_run = o.region_on ? (long)rt.w * rt.h : tiles;
     if (sl.n > 1) {
-        f.tile_slab.ensure(sl.floats * (size_t)tiles);
+        f.tile_slab.ensure(sl.floats * (size_t)tiles_run);
         sl.slab = f.tile_slab.ptr;
     }
-    const int g = clamp_grid(tiles * 64, G.grid);
+    const int g = clamp_grid(tiles_run * 64, G.grid);
     f.prof.begin(st, RR_K_TILES);
     f.tile_ctrs.ensure((size_t)kTileShards * kTileCtrStride);
+    const int g_fold = (int)std::min<long>((tiles_run + kWavesPerBlock - 1) / kWavesPerBlock, 2048);
+    if (o.region_on) {
+        k_tile_order_region<<<1, kOrderThreads, 0, st>>>(fc, s.nodes.ptr, f.tile_cost.ptr, f.tile_order.ptr,
+                                                         f.tile_ctrs.ptr, reinterpret_cast<uint32_t*>(f.counters.ptr),
+                                                         (int)n_ctr, rt);
+        G.kxr<<<g, kBlock, G.dyn, st>>>(fc, sa, f.tile_ctrs.ptr, f.film.ptr, p.srgb_lut.ptr,
+                                        reinterpret_cast<uchar4*>(f.rgba8.ptr), tot, f.spill.ptr, tc, sl, rt);
+        if (sl.n > 1)
+            k_tiles_fold_region<<<g_fold, kBlock, 0, st>>>(fc, s.nodes.ptr, sl, f.film.ptr, p.srgb_lut.ptr,
+                                                           reinterpret_cast<uchar4*>(f.rgba8.ptr), rt);
+        f.prof.end(st);
+        RR_HIP(hipGetLastError());
+        return;
+    }
     k_tile_order<<<1, kOrderThreads, 0, st>>>(fc, s.nodes.ptr, f.tile_cost.ptr, f.tile_order.ptr, f.tile_ctrs.ptr,
                                               reinterpret_cast<uint32_t*>(f.counters.ptr), (int)n_ctr);
     G.kx<<<g, kBlock, G.dyn, st>>>(fc, sa, f.tile_ctrs.ptr, f.film.ptr, p.srgb_lut.ptr,
                                            reinterpret_cast<uchar4*>(f.rgba8.ptr), tot, f.spill.ptr, tc, sl);
     if (sl.n > 1)
-        k_tiles_fold<<<(int)std::min<long>((tiles + kWavesPerBlock - 1) / kWavesPerBlock, 2048), kBlock, 0, st>>>(
+        k_tiles_fold<<<g_fold, kBlock, 0, st>>>(
             fc, s.nodes.ptr, sl, f.film.ptr, p.srgb_lut.ptr, reinterpret_cast<uchar4*>(f.rgba8.ptr));
     f.prof.end(st);
     RR_HIP(hipGetLastError());

@@ -67,7 +67,7 @@ struct SplitGrids {
     int trace_e, shadow, shade_p, shade_e, packet;
     void (*kte)(SceneArgs, PathQueue, QueueIn, float2*, int32_t*, unsigned long long*, uint32_t*);
     void (*kts)(SceneArgs, ShadowQueue, QueueIn, Rad, int32_t*, unsigned long long*, uint32_t*);
-    void (*ktpk)(FrameConsts, SceneArgs, int, float2*, uint32_t*, int32_t*, unsigned long long*, uint32_t*);  // packets
+    void (*ktpk)(SplitConsts, SceneArgs, int, float2*, uint32_t*, int32_t*, unsigned long long*, uint32_t*);  // packets
     explicit SplitGrids(bool count) {
         kte = count ? k_trace_extend<true> : k_trace_extend<false>;
         kts = count ? k_shadow_refill<true> : k_shadow_refill<false>;
@@ -130,6 +130,7 @@ void DevFrame::release() {
     jpeg_coeffs.release(); jpeg_blk.release(); jpeg_scratch.release(); deflate_scratch.release();
     png_ftype.release(); png_raw.release();
     body_scratch.release();
+    window_film.release(); window_rgba8.release();
 }
 
 namespace {
@@ -144,7 +145,7 @@ namespace {
 // three (before the beam, packet_trace_beam). The per-lane camera kernel
 // (k_trace_primary) and the round-3 rule "packets only where a triangle covers
 // two pixels" were removed with their A/B switch.
-void render_split(DevPaths& p, DevFrame& f, const FrameConsts& base, int n_chunks, hipStream_t st, const SceneArgs& sa,
+void render_split(DevPaths& p, DevFrame& f, const SplitConsts& base, int n_chunks, hipStream_t st, const SceneArgs& sa,
                   unsigned long long* tc, PathQueue pq[2], const ShadowQueue& sq, const float4* tnrm) {
     KernelProfiler& pr = f.prof;
     const SplitGrids G(tc != nullptr);
@@ -156,7 +157,7 @@ void render_split(DevPaths& p, DevFrame& f, const FrameConsts& base, int n_chunk
     p.qctr.ensure(per_chunk * n_chunks);
     RR_HIP(hipMemsetAsync(p.qctr.ptr, 0, per_chunk * n_chunks * sizeof(uint32_t), st));
     for (int c = 0; c < n_chunks; ++c) {
-        FrameConsts fc = base;
+        SplitConsts fc = base;
         fc.first_sample = c * base.spp_chunk;
         fc.spp_chunk = base.spp_chunk;
         if (fc.first_sample + fc.spp_chunk > base.spp_total) fc.spp_chunk = base.spp_total - fc.first_sample;
@@ -212,7 +213,18 @@ void render_split(DevPaths& p, DevFrame& f, const FrameConsts& base, int n_chunk
 void render_frame_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f, const FrameConsts& base, int n_chunks,
                          FrameOpts o, hipStream_t st) {
     const int npix = base.npix;
-    const size_t npaths = (size_t)npix * base.spp_chunk;
+    // the pixels the split path enumerates: the frame's, or a region's alone
+    SplitConsts sc;
+    static_cast<FrameConsts&>(sc) = base;
+    sc.div_rw = FastDiv::make(1u);
+    if (o.region_on) {
+        sc.rx0 = o.region.x0;
+        sc.ry0 = o.region.y0;
+        sc.rw = o.region.w();
+        sc.div_rw = FastDiv::make((uint32_t)sc.rw);
+        sc.npix = o.region.w() * o.region.h();
+    }
+    const size_t npaths = (size_t)sc.npix * base.spp_chunk;
     f.tile_slices = 0;
     f.unit_logged = false;
     if (frame_uses_tiles(base, o.force_wavefront)) {  // one launch: all samples of every tile
@@ -234,7 +246,7 @@ void render_frame_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f
     }
     p.ensure_paths(npaths);
     f.ensure_spill(p.grid_blocks);
-    if (n_chunks > 1) p.film_part.ensure((size_t)npix);
+    if (n_chunks > 1) p.film_part.ensure((size_t)sc.npix);
     unsigned long long* tc = nullptr;
     if (o.count_traversal) {
         f.trav_counts.ensure(kTravWords);
@@ -245,7 +257,7 @@ void render_frame_device(const DevMesh& m, DevBuild& s, DevPaths& p, DevFrame& f
     ShadowQueue sq{p.sh_o.ptr, p.sh_d.ptr, p.sh_c.ptr};
     const SceneArgs sa{s.nodes.ptr, s.qnodes.ptr, s.tris.ptr, f.materials.ptr, f.lights.ptr, p.filter_table.ptr,
                        f.mat_lut.ptr, std::max(m.n_tris - 1, 1), m.n_tris, base.n_mats, base.n_lights, s.nq};
-    render_split(p, f, base, n_chunks, st, sa, tc, pq, sq, s.has4 ? s.tnrm.ptr : nullptr);
+    render_split(p, f, sc, n_chunks, st, sa, tc, pq, sq, s.has4 ? s.tnrm.ptr : nullptr);
     RR_HIP(hipGetLastError());
 }
 

@@ -109,6 +109,7 @@ EXPORTS = [
     "rr_set_exr_codec", "rr_debug_scene_exr_codec", "rr_debug_float24", "rr_debug_exr_rle",
     "rr_frame_submit_outputs", "rr_render_frame_outputs", "rr_last_output_bytes", "rr_set_extra_outputs",
     "rr_debug_film_reduce",
+    "rr_set_region", "rr_set_region_off", "rr_set_region_from_scene", "rr_region_resolution", "rr_debug_film_window",
 ]
 
 # rr_set_exr_codec's values (include/rr.h), by Blender's names of the codecs
@@ -253,6 +254,11 @@ def lib() -> ctypes.CDLL:
         "rr_last_output_bytes": (c_int, [P, i32, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_set_extra_outputs": (c_int, [P, ctypes.c_char_p]),
         "rr_debug_film_reduce": (c_int, [P, f32p, i32, i32, i32, f32p]),
+        "rr_set_region": (c_int, [P, i32, i32, i32, i32, i32]),
+        "rr_set_region_off": (c_int, [P]),
+        "rr_set_region_from_scene": (c_int, [P, i32]),
+        "rr_region_resolution": (c_int, [P, P, P, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "rr_debug_film_window": (c_int, [P, f32p, i32, i32, i32, i32, i32, i32, i32, ctypes.c_float, f32p]),
         "rr_debug_hdr_host": (c_int, [f32p, i32, i32, i32, u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         "rr_debug_object_matrix": (c_int, [P, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
         "rr_debug_bsdf_sample": (c_int, [P, f32p, f32p, f32p, i32, f32p, f32p, f32p, f32p, i32p]),
@@ -519,6 +525,40 @@ class RenderContext:
         ("JPEG:4,PNG": <path>.r4.jpg and <path>.png); None / "": none."""
         _check(lib().rr_set_extra_outputs(self.handle, spec.encode() if spec else None), self.handle)
 
+    def set_region(self, region=None, crop: bool = False, from_scene: bool | None = None):
+        """rr_set_region: frames render the rectangle (x0, y0, x1, y1) of full-frame pixels, rows top first, half
+        open; crop: the outputs are the region's pixels alone, else the full frame with (0, 0, 0, 0) outside.
+        None: rr_set_region_off. from_scene (when given): rr_set_region_from_scene, a scene's render.border
+        comes before this region."""
+        if region is None:
+            _check(lib().rr_set_region_off(self.handle), self.handle)
+        else:
+            x0, y0, x1, y1 = (int(v) for v in region)
+            _check(lib().rr_set_region(self.handle, x0, y0, x1, y1, 1 if crop else 0), self.handle)
+        if from_scene is not None:
+            _check(lib().rr_set_region_from_scene(self.handle, 1 if from_scene else 0), self.handle)
+
+    def set_region_from_scene(self, on: bool = True):
+        """rr_set_region_from_scene: a scene's render.border gives the region of its frames."""
+        _check(lib().rr_set_region_from_scene(self.handle, 1 if on else 0), self.handle)
+
+    def region_resolution(self, scene: Scene, params: RenderParams | None = None):
+        """rr_region_resolution: (width, height) of the files and of render_to_memory's images."""
+        w, h = ctypes.c_int32(), ctypes.c_int32()
+        _check(lib().rr_region_resolution(self.handle, scene.handle, ctypes.byref(params) if params else None,
+                                          ctypes.byref(w), ctypes.byref(h)), self.handle)
+        return int(w.value), int(h.value)
+
+    def film_window(self, rgba: np.ndarray, region, crop: bool, alpha_sum: float = 1.0) -> np.ndarray:
+        """rr_debug_film_window: k_film_window over an (H, W, 4) float32 image."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+        h, w = rgba.shape[:2]
+        x0, y0, x1, y1 = (int(v) for v in region)
+        out = np.zeros((y1 - y0, x1 - x0, 4) if crop else (h, w, 4), np.float32)
+        _check(lib().rr_debug_film_window(self.handle, _ptr(rgba, ctypes.c_float), w, h, x0, y0, x1, y1,
+                                          1 if crop else 0, float(alpha_sum), _ptr(out, ctypes.c_float)), self.handle)
+        return out
+
     def film_reduce(self, rgba: np.ndarray, reduce: int) -> np.ndarray:
         """rr_debug_film_reduce on the device: the box mean of an (H, W, 4) float32 image."""
         return film_reduce(rgba, reduce, self)
@@ -532,7 +572,7 @@ class RenderContext:
 
     def render_to_memory(self, scene: Scene, frame: int, params: RenderParams | None = None,
                          film: bool = True, rgba: bool = True):
-        w, h = scene.resolution(params)
+        w, h = self.region_resolution(scene, params)  # the frame's, or with a cropped region that region's
         f = np.zeros((h, w, 4), np.float32) if film else None
         r = np.zeros((h, w, 4), np.uint8) if rgba else None
         s = FrameStats()

@@ -42,7 +42,8 @@ class BackendRunner:
     def __init__(self, base_directory_path: str | os.PathLike, tracer: WorkerTraceBuilder | None = None,
                  device: int = 0, params: RenderParams | None = None, ctx=None, device_png: bool = False,
                  png_depth: int = 0, exr_depth: int = 0, color_mode=0, look: str | None = None,
-                 display_gamma: float = 0.0, dither=None, png_compression=None, exr_codec=None):
+                 display_gamma: float = 0.0, dither=None, png_compression=None, exr_codec=None,
+                 region=None, region_crop: bool = False, region_from_scene: bool = False):
         """ctx: a RenderContext on `device` is created here; tests of the host
         logic alone pass a stand-in with the same methods (no rendering).
         device_png: "PNG" jobs are coded on the device (rr_set_device_png).
@@ -72,7 +73,12 @@ class BackendRunner:
         png_compression: Blender's compression of every job's "PNG" files
         (rr_set_png_compression): 0 .. 100, "scene" for each scene's own
         render.png_compression, "legacy", or None for the context's own (legacy,
-        or RR_PNG_COMPRESSION)."""
+        or RR_PNG_COMPRESSION).
+        region: the render region of every job's frames (rr_set_region): (x0, y0,
+        x1, y1) in full-frame pixels, rows top first, half open, or None for the
+        context's own (none, or RR_REGION); region_crop: the files are the
+        region's pixels alone. region_from_scene: a scene's render.border gives
+        the region of its frames (rr_set_region_from_scene)."""
         base = Path(base_directory_path)
         if not base.is_dir():
             raise RenderError("Provided base directory path is not a directory.")
@@ -98,6 +104,10 @@ class BackendRunner:
             self.ctx.set_png_compression(png_compression)
         if exr_codec is not None:
             self.ctx.set_exr_codec(exr_codec)
+        if region is not None:
+            self.ctx.set_region(region, crop=region_crop)
+        if region_from_scene:
+            self.ctx.set_region_from_scene(True)
         self._scenes: dict[str, Scene] = {}
         self._lock = threading.Lock()  # one caller at a time per context (queue.rs:79-118)
         self.last_stats = None

@@ -374,6 +374,64 @@ int rr_set_extra_outputs(rr_ctx* ctx, const char* spec);
 int rr_debug_film_reduce(rr_ctx* ctx, const float* rgba, int32_t w, int32_t h, int32_t reduce,
                          float* out /* ceil(w/reduce) * ceil(h/reduce) * 4 */);
 
+/* The render region: Blender's render border. Frames of ctx render and write
+ * a rectangle of the frame instead of all of it. Off on a new context.
+ *
+ * rr_set_region: x0 <= x < x1, y0 <= y < y1 (half open) in pixels of the full
+ * frame, rows top first. x0 < x1 and y0 < y1, each within +-2^30, else RR_EINVAL, which
+ * changes nothing. The rectangle is clamped to the frame when a frame is
+ * submitted; one that lies outside it altogether refuses that frame
+ * (RR_EINVAL, naming the region and the frame's size) before anything is
+ * launched. A region that covers the whole frame is the frame without a
+ * region, byte for byte. rr_set_region_off turns it off. Read when a frame is
+ * submitted, as the other settings are; frames in flight keep theirs.
+ *
+ * crop != 0: every output (each file, a reduced one before its reduction, the
+ * images of rr_render_frame_to_memory) is the region's w x h pixels. crop 0:
+ * the full frame, (0, 0, 0, 0) outside the region: RGB 0 in every format, and
+ * A = 0 outside and opaque inside in the files that carry alpha (RGBA TARGA,
+ * IRIS, WEBP, PNG at 8 and 16 bits, OPEN_EXR A), black in those that do not
+ * (JPEG, HDR).
+ *
+ * Inside the region every value of every format and depth is the bits the
+ * same frame has there when rendered whole: each pixel's samples are keyed on
+ * its full-frame coordinates. The exception is the dither (rr_set_dither),
+ * Blender's noise keyed on the OUTPUT image's own pixel coordinates as for the
+ * reduced proxies, so a cropped 8-bit file with dither on is not a window of
+ * the full frame's file. `reduce` and the extra outputs apply to the windowed
+ * image.
+ *
+ * The split path (large scenes, RR_FLAG_WAVEFRONT) traces the region's pixels
+ * alone; the tile path (k_tiles) runs the 8 x 8 tiles that meet the region,
+ * partial tiles whole, and drops their pixels outside it. rr_frame_stats
+ * describes what ran: camera_rays and the ray counters are the region's on
+ * the split path, and on the tile path those of the tiles that ran (partial
+ * tiles count whole); width and height stay the frame's.
+ *
+ * rr_set_region_from_scene(ctx, 1): a scene's render.border {min_x, max_x,
+ * min_y, max_y, crop} (Blender's fractions, y from the bottom; exported only
+ * with use_border set) gives the region of its frames and comes before
+ * rr_set_region's; a scene without one leaves that in force. The pixel rule
+ * (csrc/region_rule.h) is recalled, not pinned against a Blender.
+ *
+ * RR_REGION, read by rr_create: "x0,y0,x1,y1[,crop]", "scene", or "" (off).
+ *
+ * rr_region_resolution: the size of the files and of
+ * rr_render_frame_to_memory's images for a frame of scene with params on ctx:
+ * the region's with crop, else the frame's (rr_scene_resolution, unchanged). */
+int rr_set_region(rr_ctx* ctx, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t crop);
+int rr_set_region_off(rr_ctx* ctx);
+int rr_set_region_from_scene(rr_ctx* ctx, int32_t on);
+int rr_region_resolution(rr_ctx* ctx, rr_scene* scene, const rr_render_params* params,
+                         int32_t* width, int32_t* height);
+
+/* k_film_window (csrc/region.hip) on a w x h image of 4 floats a pixel: with
+ * crop the (x1 - x0) x (y1 - y0) window, else the w x h image with zeros
+ * outside it; inside, the image's x, y, z and w = alpha_sum. The region must
+ * lie inside the image and hold a pixel (RR_EINVAL). */
+int rr_debug_film_window(rr_ctx* ctx, const float* rgba, int32_t w, int32_t h, int32_t x0, int32_t y0,
+                         int32_t x1, int32_t y1, int32_t crop, float alpha_sum, float* out);
+
 /* Wait until every piece of device work ctx has enqueued (frames in flight
  * included) has finished; their tickets still have to be completed. */
 int rr_synchronize(rr_ctx* ctx);

@@ -182,6 +182,9 @@ EXR_CODEC_OF_DNA = {0: "NONE", 1: "PXR24", 2: "ZIP", 3: "PIZ", 4: "RLE", 5: "ZIP
 
 # ImageFormatData.flag: "save a JPEG beside the frame" (image_settings.use_preview)
 R_IMF_FLAG_PREVIEW_JPG = 1 << 1
+# RenderData.mode: render.use_border and render.use_crop_to_border
+R_BORDER = 1 << 9
+R_CROP = 1 << 11
 
 
 def export(path: str, args) -> dict:
@@ -234,6 +237,16 @@ def export(path: str, args) -> dict:
     # against a Blender). Written only when set: a scene without the field writes no preview
     if int(bf.read_struct_at(rd("im_format"), "ImageFormatData", "flag")) & R_IMF_FLAG_PREVIEW_JPG:
         out["render"]["use_preview"] = True
+    # render.use_border / use_crop_to_border: bits of RenderData.mode; border_min_x .. border_max_y: the rctf
+    # RenderData.border, fractions of the frame with y from the bottom (the bits recalled from memory, not
+    # pinned against a Blender). Written only with use_border set: a scene without the field renders whole
+    if int(rd("mode")) & R_BORDER:
+        b = rd("border")
+        out["render"]["border"] = {"min_x": bf.read_struct_at(b, "rctf", "xmin"),
+                                   "max_x": bf.read_struct_at(b, "rctf", "xmax"),
+                                   "min_y": bf.read_struct_at(b, "rctf", "ymin"),
+                                   "max_y": bf.read_struct_at(b, "rctf", "ymax"),
+                                   "crop": bool(int(rd("mode")) & R_CROP)}
     # image_settings.color_mode: ImageFormatData.planes holds the bits of a pixel
     # (R_IMF_PLANES_BW 8, _RGB 24, _RGBA 32). Written only with --color-mode
     # project: a scene without the field keeps each format's own layout, and
